@@ -2,7 +2,7 @@
 """bench.py -- forward throughput of the CheckerPose hot path on MI355X (BASELINE.json metric).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32] [--npoint 512]
-                  [--workload lmo_ape|ycbv_rr21|lm13_n4096] [--no-extras] [--dry-run]
+                  [--workload lmo_ape|ycbv_rr21|lm13_n4096] [--dump-outputs DIR] [--full [--no-extras]] [--dry-run]
   N>1: either way works -- under the driver's launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N
        --master-addr 127.0.0.1 ... bench.py --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE come from the environment), or plain
        `python bench.py --gpus N`: with no WORLD_SIZE in the environment the process makes no GPU call, starts exactly that
@@ -12,9 +12,14 @@ A "step" = one forward of PoseNet_GNNskip (HRNet-W18 + decoder + 3 progressive G
 hr18GNN2_res6_gnn3Skip_mlpQuery, LM-O `ape` keypoints, npt=512) over one batch of B synthetic 256x256 crops
 already resident in HBM; every rank runs its own replica on its own batch shard (pure data parallel: the
 forward has no collective), so scaling is weak and value = N*B*K / max-over-ranks(time).
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` (dominant kernel = the
-MFMA implicit-GEMM conv) and `cpu_baseline` (oracle restatement timed on the host cores).  Extra keys of the default
-N=1 run (`--no-extras` skips them): `fp32_exact` (the path north_star's 1e-4 applies to, at its best
+Prints ONE JSON line on rank 0: `metric`, `value` (crops/s), `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed
+step) and the configuration.  A plain run does nothing else: set-up, `--warmup` untimed steps, exactly `--steps` timed steps, the
+line.  `--dump-outputs DIR` writes what the last timed step returned (rank 0's crops) as DIR/<name>.npy (dump_outputs); the
+inputs are seeded, so two builds can be compared array for array.
+
+`--full` adds the measurements that take runs of their own: `roofline` (dominant kernel = the MFMA implicit-GEMM conv;
+`--no-breakdown` skips it) and `cpu_baseline` (oracle restatement timed on the host cores; `--no-cpu-baseline` skips it).  Extra
+keys of a `--full` N=1 run (`--no-extras` skips them): `fp32_exact` (the path north_star's 1e-4 applies to, at its best
 batch), `by_batch` (bf16 at B = 1 / 8 / 32 / 64 / 128: the reference's test.py:198 runs batch 1, its configs train at 32),
 `b1_latency_ms`, `bf16_agreement` (the bf16 path's accuracy contract, checkerpose_amd/agreement.py, measured against the
 fp32 HIP path on the same crops) and `host_u8` (crops start as uint8 in pinned HOST memory and are double-buffered over
@@ -197,6 +202,31 @@ def timed_steps(step, steps, warmup):
         step()
     torch.cuda.synchronize()
     return time.perf_counter() - t0
+
+
+OUTPUT_NAMES = ("roi_bit", "x_bits", "y_bits", "seg", "x_id", "y_id")     # the forward's 6-tuple, named as test.py:290 names it
+DUMP_BUDGET_BYTES = 60 * 10 ** 6        # array bytes: the files stay under 64 MB in all, .npy headers included
+
+
+def dump_outputs(outs, path, budget=DUMP_BUDGET_BYTES):
+    """`--dump-outputs`: the arrays one step returned, as <path>/<name>.npy -- floating point as float32 (float64 stays float64),
+    integer ids as float64 (exact).  When they exceed `budget` bytes in all, every array keeps the same fixed, seeded sample of
+    crops (dim 0, ascending).  Returns {name: shape written}."""
+    import numpy as np
+    assert len(outs) == len(OUTPUT_NAMES), len(outs)
+    arrs = {}
+    for name, t in zip(OUTPUT_NAMES, outs):
+        t = t.detach().cpu()
+        arrs[name] = (t.float() if t.is_floating_point() and t.dtype != torch.float64 else t.double()).numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    if total > budget:
+        B = arrs[OUTPUT_NAMES[0]].shape[0]
+        rows = np.sort(np.random.default_rng(0).choice(B, max(1, B * budget // total), replace=False))
+        arrs = {k: a[rows] for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrs.items()}
 
 
 def side_measurements(net_bf16, npoint, dev, B_main, img_main):
@@ -782,16 +812,23 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="crops per GPU per step")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
     ap.add_argument("--npoint", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true")
-    ap.add_argument("--dump-convs", default=None, help="write per-conv-launch timings (json) to this path")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements that take runs of their own: roofline / per-kernel breakdown, the extras (N=1 lmo_ape "
+                         "bf16) and the CPU baseline; a plain run times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the arrays the last timed step returned (rank 0) as DIR/<name>.npy, float32 / float64, <= 64 MB in all")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-breakdown", action="store_true", help="--full: skip the roofline / per-kernel breakdown")
+    ap.add_argument("--dump-convs", default=None, help="--full: write per-conv-launch timings (json) to this path")
     ap.add_argument("--workload", default="lmo_ape", choices=["lmo_ape", "ycbv_rr21", "lm13_n4096"])
     ap.add_argument("--backbone", default="hrnet_w18", choices=["hrnet_w18", "hrnet_w18_small", "hrnet_w30", "resnet34"],
                     help="lmo_ape only: another of the reference's backbone names (not BASELINE's config; --no-extras --no-breakdown implied)")
-    ap.add_argument("--no-extras", action="store_true", help="skip fp32_exact / by_batch / bf16_agreement / host_u8 / the sub-configs")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip fp32_exact / by_batch / bf16_agreement / host_u8 / the sub-configs")
     ap.add_argument("--streams", type=int, default=1, help="ycbv_rr21: HIP streams the independent per-object networks' steps rotate over")
     ap.add_argument("--dry-run", action="store_true", help="launcher / rendezvous / timing collectives only, no GPU call (CPU test of --gpus N)")
     a = ap.parse_args()
+    if a.dump_convs and not a.full:
+        ap.error("--dump-convs is part of the breakdown: add --full")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:      # not under torchrun: launch the N ranks ourselves
         sys.exit(self_launch(__file__, a.gpus))
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != a.gpus:
@@ -816,7 +853,15 @@ def main():
     net, step, img = wl["net"], wl["step"], wl["img"]
     for _ in range(max(a.warmup, 2)):    # >= 2: eager run, then hipGraph capture
         step()
-    el, seen, per_rank = rk.timed(step, a.steps, torch.cuda.synchronize)
+    last = [None]
+
+    def timed_step():                    # keeps what the step returned (ycbv_rr21: each step another network's buffers)
+        last[0] = step()
+    el, seen, per_rank = rk.timed(timed_step, a.steps, torch.cuda.synchronize)
+    if a.dump_outputs and rank == 0:     # before any --full measurement runs the network again
+        print("bench: outputs of the last timed step -> %s: %s" % (a.dump_outputs, dump_outputs(last[0], a.dump_outputs)),
+              file=sys.stderr, flush=True)
+    last = None
     ms_per_step = el / a.steps * 1e3
     value = world * B * a.steps / el
 
@@ -833,7 +878,7 @@ def main():
            "cpu_affinity": rk.cpu_affinity}
     if a.workload == "ycbv_rr21":
         out["config"]["streams"] = max(a.streams, 1)
-    if rank == 0:
+    if rank == 0 and a.full:
         if not a.no_breakdown:
             roofline_report(out, net, B, a.dtype, a.workload, a.npoint, min(a.steps, 5), a.dump_convs)
         if world == 1 and not a.no_extras and a.workload == "lmo_ape" and a.dtype == "bf16":
@@ -843,6 +888,7 @@ def main():
             out["configs"] = sub_configs(a.dtype, dev)
         if world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.npoint)
+    if rank == 0:
         print(json.dumps(out), flush=True)
     rk.close()
 

@@ -153,6 +153,32 @@ def test_bench_prices_a_multi_launch_call_as_the_set(tmp_path, monkeypatch):
     assert bench.committed_profile("other", "unit")[:2] == (None, 10.0)
 
 
+def test_bench_dump_outputs_dtypes_and_seeded_sample(tmp_path):
+    """bench.dump_outputs (`--dump-outputs`): one float32 / float64 file per output of the forward's 6-tuple (integer ids exact in
+    float64); above the byte budget every array keeps the same crops, in ascending order, and the same ones on every call."""
+    import bench
+    g = torch.Generator().manual_seed(0)
+    B = 16
+    outs = (torch.randn(B, 1, 32, generator=g), torch.randn(B, 6, 32, generator=g).to(torch.bfloat16),
+            torch.randn(B, 6, 32, generator=g).double(), torch.rand(B, 1, 8, 8, generator=g),
+            torch.randint(0, 64, (B, 32), generator=g), torch.randint(0, 64, (B, 32), generator=g).int())
+    names = bench.OUTPUT_NAMES
+    assert bench.dump_outputs(outs, str(tmp_path / "all")) == {n: list(t.shape) for n, t in zip(names, outs)}
+    full = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in names}
+    assert [full[n].dtype for n in names] == [np.float32, np.float32, np.float64, np.float32, np.float64, np.float64]
+    for n, t in zip(names, outs):
+        assert np.array_equal(full[n], t.double().numpy()), n
+    budget = sum(a.nbytes for a in full.values()) // 4
+    bench.dump_outputs(outs, str(tmp_path / "s1"), budget=budget)
+    bench.dump_outputs(outs, str(tmp_path / "s2"), budget=budget)
+    s1 = {n: np.load(tmp_path / "s1" / (n + ".npy")) for n in names}
+    assert sum(a.nbytes for a in s1.values()) <= budget
+    rows = [int(np.flatnonzero((full["roi_bit"] == r).all(axis=(1, 2)))[0]) for r in s1["roi_bit"]]
+    assert 1 <= len(rows) < B and rows == sorted(set(rows))
+    for n in names:
+        assert np.array_equal(s1[n], full[n][rows]) and np.array_equal(s1[n], np.load(tmp_path / "s2" / (n + ".npy"))), n
+
+
 def test_kernel_log_collects_every_symbol_since_begin():
     """cp_kernel_log: "" after begin (no launch on the CPU box); cp_last_kernel is untouched by begin"""
     from checkerpose_amd import _abi
