@@ -139,6 +139,8 @@ SIGNATURES = {
     "cp_mlp_query_fused_supported": (_I, [_I, _I, _I, _I]),
     "cp_mlp_query_fused": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _L, _L, _L, _L]),
     "cp_mlp_query_fused_t": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _F, _P, _P, _P, _L, _L, _L, _L]),
+    "cp_mlp_query_fused_n": (_I, [_P, _I, _P, _I, _I, _I, _I, _P, _P, _P, _F, _P, _P, _P, _F, _P, _P, _I, _P, _L, _L, _L, _L,
+                                  _P, _P, _P, _P]),
     "cp_mlp_pair_fused_supported": (_I, [_I, _I, _I]),
     "cp_mlp_pair_fused": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _F, _P, _I, _I]),
     "cp_mlp_pair_fused_t": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _F, _P, _P, _F, _P, _I, _I]),
@@ -193,6 +195,7 @@ SIGNATURES = {
     "cp_index2feat_conv_t": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I]),
     "cp_index2feat_gather": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),
     "cp_bits_decode": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I]),
+    "cp_code_decode": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I]),
     "cp_correspondences": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "cp_correspondences_bbox": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "cp_pnp_ransac_scratch_bytes": (C.c_size_t, [_I, _I]),

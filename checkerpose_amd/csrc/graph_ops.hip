@@ -208,6 +208,33 @@ extern "C" int cp_bits_decode(cp_stream_t stream, const float* bits, int stage, 
   return cp_check_launch();
 }
 
+__global__ void code_decode_kernel(const float* __restrict__ bits, int rows, int r, int64_t* __restrict__ x64,
+                                   int64_t* __restrict__ y64, int32_t* __restrict__ x32, int32_t* __restrict__ y32, int N,
+                                   size_t total) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // over B*N
+  if (i >= total) return;
+  const size_t b = i / N;
+  const int n = (int)(i - b * N);
+  const float* z = bits + b * rows * N + n;
+  int x = 0, y = 0;
+  for (int j = 0; j < r; ++j) {
+    x = 2 * x + cp_sigmoid_gt_half(z[(size_t)(1 + j) * N]);
+    y = 2 * y + cp_sigmoid_gt_half(z[(size_t)(1 + r + j) * N]);
+  }
+  x64[i] = x; y64[i] = y;
+  if (x32) x32[i] = x;
+  if (y32) y32[i] = y;
+}
+
+extern "C" int cp_code_decode(cp_stream_t stream, const float* bits, int rows, int r, int64_t* x_id64, int64_t* y_id64,
+                              int32_t* x_id32, int32_t* y_id32, int B, int N) {
+  if (!bits || !x_id64 || !y_id64 || B <= 0 || N <= 0 || r < 1 || r > 30 || 1 + 2 * r > rows) return CP_ERR_INVALID;
+  const size_t total = (size_t)B * N;
+  CP_LAUNCH(code_decode_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bits, rows, r,
+            x_id64, y_id64, x_id32, y_id32, N, total);
+  return cp_check_launch();
+}
+
 // ------------------------------------------------------------------------------------------------
 // Post-forward decode on the device: what reference test.py:294-329 +
 // test_network_with_test_data.py:from_id_to_pose :50-66 do on the host with six .cpu().numpy() round trips per image

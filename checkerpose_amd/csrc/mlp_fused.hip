@@ -10,8 +10,11 @@
 //     tile's loads in flight under the MFMAs) and writes its 64 hidden channels of the tile -- LeakyReLU, bf16 -- into an LDS tile
 //     in MFMA operand order ([16-byte channel piece][row][16 B], double-buffered);
 //   waves 4-7 (layers 2 + 3): wave v owns rows 16 v .. 16 v + 15 of the PREVIOUS tile: 256 -> 64 from the hidden tile with W2
-//     resident in registers (128 VGPRs), LeakyReLU in fp32 (never rounded to bf16), then the 64 -> 2 head as per-lane partial dot
-//     products met by two cross-lane adds; 8 bytes per row leave, in the caller's (row, channel) strides (the logit block).
+//     resident in registers (128 VGPRs), LeakyReLU in fp32 (never rounded to bf16), then the 64 -> NOUT head as per-lane partial dot
+//     products met by two cross-lane adds; 4 * NOUT bytes per row leave, in the caller's (row, channel) strides (the logit block).
+// NOUT = 2: the refinement stages' query head (pipeline.py:168-180).  NOUT = 1 + 2r (r = 4..6): the woProg ablation's single head
+// (pipeline_lm.py:475-517), whose epilogue also decodes the x / y codes (rows 1..r, r+1..2r, MSB first) into the pixel ids with the
+// threshold cp_bits_decode uses (graph_ops.hip), so the head and the decode are one launch.
 // One barrier per tile.  The layer-1 image is cp_pack_gemm_weight's (gemm_lds.hip), as is the layer-2 image.
 #include "common.h"
 
@@ -20,13 +23,15 @@ namespace {
 constexpr int MQ_ROWS = 64;
 constexpr int MQ_PITCH = MQ_ROWS * 16 + 16;                  // plane [row][16 B]; +16: consecutive planes shift one bank slot
 constexpr int MQ_BUF = 32 * MQ_PITCH;                        // 32 pieces of 8 channels = 256 channels: 33 280 B
-constexpr int MQ_LDS = 4 * MQ_BUF + 512 + 2560;              // x tile x 2, hidden tile x 2, layer-3 weights, folded-BN vectors of layers 1 / 2
+// x tile x 2, hidden tile x 2, layer-3 weights (NOUT x 64 fp32), folded-BN vectors of layers 1 / 2
+template <int NOUT> constexpr int mq_lds() { return 4 * MQ_BUF + NOUT * 256 + 2560; }
 
 struct MlpQueryParams {
   const void* in; const void* w1; const float* s1; const float* t1;
   const void* w2; const float* s2; const float* t2;
-  const float* w3; const float* b3;                          // (2, 64) fp32 row-major, (2,)
+  const float* w3; const float* b3;                          // (NOUT, 64) fp32 row-major, (NOUT,)
   float* out;
+  int64_t* x64; int64_t* y64; int32_t* x32; int32_t* y32;    // NOUT = 1 + 2r: decoded ids (B, N) (x64 / y64 null: no decode)
   int M, Nrow, in_cs, in_coff, n_rt;
   uint32_t in_bytes;
   float slope1, slope2;
@@ -35,8 +40,10 @@ struct MlpQueryParams {
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-template <bool H>                                              // H: rows, weights and hidden rows in IEEE half (CP_F16; common.h cp_mma16)
+// H: rows, weights and hidden rows in IEEE half (CP_F16; common.h cp_mma16); NOUT: logits per row
+template <bool H, int NOUT>
 __global__ __launch_bounds__(512) void mlp_query_fused_kernel(const MlpQueryParams p) {
+  static_assert(NOUT == 2 || (NOUT >= 9 && NOUT <= 13 && (NOUT & 1)), "NOUT: 2 or 1 + 2r, r = 4..6");
   if constexpr (H) cp_f16_saturate_on();                     // half packs saturate at +-65504 (common.h)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* const sX = smem;                             // 2 x MQ_BUF
@@ -58,15 +65,17 @@ __global__ __launch_bounds__(512) void mlp_query_fused_kernel(const MlpQueryPara
 #pragma unroll
       for (int t = 0; t < 4; ++t) W[kc][t] = wsrc[((size_t)((g0 + (t >> 1)) * 8 + kc) * 2 + (t & 1)) * 64 + lane];
   }
-  float* const sW3 = (float*)(smem + 4 * MQ_BUF);            // [2][64]: layer-3 rows (kept out of the layer-1 waves' registers)
+  float* const sW3 = (float*)(smem + 4 * MQ_BUF);            // [NOUT][64]: layer-3 rows (kept out of the layer-1 waves' registers)
   // folded-BN scale / shift of layers 1 and 2 in LDS: read from global memory in the tile loop, the layer-2 waves' loads queued behind
   // the eight tile-prefetch loads they had just issued (vmcnt is in order: waiting for the vectors meant waiting for the prefetch)
-  float* const sA1 = sW3 + 128;                               // s1 | t1 [256 each]
+  float* const sA1 = sW3 + NOUT * 64;                         // s1 | t1 [256 each]
   float* const sA2 = sA1 + 512;                               // s2 | t2 [64 each]
-  if (tid < 128) sW3[tid] = p.w3[tid];
+  for (int i = tid; i < NOUT * 64; i += 512) sW3[i] = p.w3[i];
   if (tid < 256) { sA1[tid] = p.s1[tid]; sA1[256 + tid] = p.t1[tid]; }
   if (tid >= 256 && tid < 320) { sA2[tid - 256] = p.s2[tid - 256]; sA2[64 + tid - 256] = p.t2[tid - 256]; }
-  const float b3a = p.b3[0], b3b = p.b3[1];
+  float b3[NOUT];
+#pragma unroll
+  for (int c = 0; c < NOUT; ++c) b3[c] = p.b3[c];
 
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.in), 0, p.in_bytes, 0x00020000);
   // staging by the 256 threads of the layer-2 waves (they carry a quarter of the MFMA work; the layer-1 waves have no registers
@@ -151,29 +160,63 @@ __global__ __launch_bounds__(512) void mlp_query_fused_kernel(const MlpQueryPara
           acc[t] = cp_mma16<H>(W[kc][t], a, acc[t]);
       }
       // lane (x, q): row 16 v4 + x, hidden-2 channels 32 h + 8 q + {0..7}; layer 3 on the fp32 values
-      float d0 = 0.f, d1 = 0.f;
+      float d[NOUT];
+#pragma unroll
+      for (int c = 0; c < NOUT; ++c) d[c] = 0.f;
 #pragma unroll
       for (int h = 0; h < 2; ++h) {
         const int ch = h * 32 + q * 8;
         const f32x4 s0 = *(const f32x4*)(sA2 + ch), t0 = *(const f32x4*)(sA2 + 64 + ch);
         const f32x4 s1 = *(const f32x4*)(sA2 + ch + 4), t1 = *(const f32x4*)(sA2 + 64 + ch + 4);
-        const f32x4 a0 = *(const f32x4*)(sW3 + ch), a1 = *(const f32x4*)(sW3 + ch + 4);
-        const f32x4 c0 = *(const f32x4*)(sW3 + 64 + ch), c1 = *(const f32x4*)(sW3 + 64 + ch + 4);
+        float u0[4], u1[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          const float u0 = leaky(acc[2 * h][j] * s0[j] + t0[j], p.slope2), u1 = leaky(acc[2 * h + 1][j] * s1[j] + t1[j], p.slope2);
-          d0 += u0 * a0[j] + u1 * a1[j];
-          d1 += u0 * c0[j] + u1 * c1[j];
+          u0[j] = leaky(acc[2 * h][j] * s0[j] + t0[j], p.slope2);
+          u1[j] = leaky(acc[2 * h + 1][j] * s1[j] + t1[j], p.slope2);
+        }
+#pragma unroll
+        for (int c = 0; c < NOUT; ++c) {
+          const f32x4 a0 = *(const f32x4*)(sW3 + c * 64 + ch), a1 = *(const f32x4*)(sW3 + c * 64 + ch + 4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) d[c] += u0[j] * a0[j] + u1[j] * a1[j];
         }
       }
-      d0 += __shfl_xor(d0, 16); d1 += __shfl_xor(d1, 16);
-      d0 += __shfl_xor(d0, 32); d1 += __shfl_xor(d1, 32);
+      // every lane ends with the same sums: (a + b) + (c + d) in each of the four q lanes, fp32 addition being commutative
+#pragma unroll
+      for (int c = 0; c < NOUT; ++c) d[c] += __shfl_xor(d[c], 16);
+#pragma unroll
+      for (int c = 0; c < NOUT; ++c) d[c] += __shfl_xor(d[c], 32);
       const int m = (rt - step) * MQ_ROWS + v4 * 16 + x;
-      if (q == 0 && m < p.M) {
+      if (m < p.M) {
         const int b = m / p.Nrow, n = m - b * p.Nrow;
         float* o = p.out + p.o_base + (long long)b * p.o_sb + (long long)n * p.o_sn;
-        o[0] = d0 + b3a;
-        o[p.o_sc] = d1 + b3b;
+        if constexpr (NOUT == 2) {
+          if (q == 0) {
+            o[0] = d[0] + b3[0];
+            o[p.o_sc] = d[1] + b3[1];
+          }
+        } else {
+#pragma unroll
+          for (int c = 0; c < NOUT; ++c) {
+            d[c] += b3[c];
+            if ((c & 3) == q) o[c * p.o_sc] = d[c];             // the four q lanes share the row's stores
+          }
+          if (p.x64) {
+            // from_code_prob_to_id (pipeline.py:72-92): bit = [sigmoid(z) > 0.5] = [z > CP_SIGMOID_HALF_Z0], MSB first
+            constexpr int R = (NOUT - 1) / 2;
+            const float z0 = __uint_as_float(CP_SIGMOID_HALF_Z0_BITS);
+            int xi = 0, yi = 0;
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+              xi = 2 * xi + (d[1 + j] > z0 ? 1 : 0);
+              yi = 2 * yi + (d[1 + R + j] > z0 ? 1 : 0);
+            }
+            if (q == 0) p.x64[m] = xi;
+            else if (q == 1) p.y64[m] = yi;
+            else if (q == 2) { if (p.x32) p.x32[m] = xi; }
+            else if (p.y32) p.y32[m] = yi;
+          }
+        }
       }
       }
       stage_write(sv, (it + 1) & 1);                          // sX[(it + 1) & 1]: its readers (layer 1, iteration it - 1) passed the last barrier
@@ -184,16 +227,42 @@ __global__ __launch_bounds__(512) void mlp_query_fused_kernel(const MlpQueryPara
 
 }  // namespace
 
-extern "C" int cp_mlp_query_fused_supported(int C0, int C1, int C2, int C3) { return (C0 == 256 && C1 == 256 && C2 == 64 && C3 == 2) ? 1 : 0; }
+namespace {
+template <int NOUT>
+int mq_set_lds(int dev) {
+  static CpDeviceOnce once;
+  CP_LDS_ATTR_ONCE(once, dev, cp_set_max_lds((const void*)mlp_query_fused_kernel<false, NOUT>, mq_lds<NOUT>()) &&
+                                  cp_set_max_lds((const void*)mlp_query_fused_kernel<true, NOUT>, mq_lds<NOUT>()));
+  return CP_OK;
+}
 
-extern "C" int cp_mlp_query_fused_t(cp_stream_t stream, int dtype, const void* in, int in_cstride, int in_coff, int B, int N,
-                                  const void* packed_w1, const float* scale1, const float* shift1, float slope1,
-                                  const void* packed_w2, const float* scale2, const float* shift2, float slope2,
-                                  const float* w3, const float* b3, float* out, long long o_base, long long o_sb, long long o_sn,
-                                  long long o_sc) {
+template <int NOUT>
+int mq_launch(hipStream_t stream, int dtype, int grid, const MlpQueryParams& p) {
+  const int rc = mq_set_lds<NOUT>(cp_current_device());
+  if (rc != CP_OK) return rc;
+  if (dtype == CP_F16) CP_LAUNCH((mlp_query_fused_kernel<true, NOUT>), dim3((unsigned)grid), dim3(512), mq_lds<NOUT>(), stream, p);
+  else CP_LAUNCH((mlp_query_fused_kernel<false, NOUT>), dim3((unsigned)grid), dim3(512), mq_lds<NOUT>(), stream, p);
+  return cp_check_launch();
+}
+}  // namespace
+
+static bool mq_nout_ok(int nout) { return nout == 2 || nout == 9 || nout == 11 || nout == 13; }
+
+extern "C" int cp_mlp_query_fused_supported(int C0, int C1, int C2, int C3) {
+  return (C0 == 256 && C1 == 256 && C2 == 64 && mq_nout_ok(C3)) ? 1 : 0;
+}
+
+extern "C" int cp_mlp_query_fused_n(cp_stream_t stream, int dtype, const void* in, int in_cstride, int in_coff, int B, int N,
+                                    const void* packed_w1, const float* scale1, const float* shift1, float slope1,
+                                    const void* packed_w2, const float* scale2, const float* shift2, float slope2,
+                                    const float* w3, const float* b3, int nout, float* out, long long o_base, long long o_sb,
+                                    long long o_sn, long long o_sc, int64_t* x_id64, int64_t* y_id64, int32_t* x_id32,
+                                    int32_t* y_id32) {
   if (!in || !packed_w1 || !scale1 || !shift1 || !packed_w2 || !scale2 || !shift2 || !w3 || !b3 || !out || B <= 0 || N <= 0 ||
-      (dtype != CP_BF16 && dtype != CP_F16))
+      (dtype != CP_BF16 && dtype != CP_F16) || !mq_nout_ok(nout))
     return CP_ERR_INVALID;
+  // ids: both 64-bit outputs or neither, only behind a code head (nout = 1 + 2r); the 32-bit ones only beside them
+  if ((!x_id64) != (!y_id64) || ((x_id32 || y_id32) && !x_id64) || (x_id64 && nout == 2)) return CP_ERR_INVALID;
   if (in_cstride % 8 || in_coff % 8 || in_coff + 256 > in_cstride) return CP_ERR_ALIGN;
   if (!cp_aligned16(in) || !cp_aligned16(packed_w1) || !cp_aligned16(packed_w2) || !cp_aligned16(scale1) || !cp_aligned16(shift1) ||
       !cp_aligned16(scale2) || !cp_aligned16(shift2))
@@ -201,21 +270,31 @@ extern "C" int cp_mlp_query_fused_t(cp_stream_t stream, int dtype, const void* i
   const long long M = (long long)B * N;
   const long long in_bytes = M * in_cstride * 2;
   if (in_bytes >= (1LL << 32) || M >= (1LL << 31)) return CP_ERR_RANGE;
-  static CpDeviceOnce once;
-  const int dev = cp_current_device();
-  CP_LDS_ATTR_ONCE(once, dev, cp_set_max_lds((const void*)mlp_query_fused_kernel<false>, MQ_LDS) &&
-                                  cp_set_max_lds((const void*)mlp_query_fused_kernel<true>, MQ_LDS));
   const int n_cu = cp_num_cus();
   if (n_cu <= 0) return CP_ERR_HIP;
   MlpQueryParams p;
   p.in = in; p.w1 = packed_w1; p.s1 = scale1; p.t1 = shift1; p.w2 = packed_w2; p.s2 = scale2; p.t2 = shift2; p.w3 = w3; p.b3 = b3; p.out = out;
+  p.x64 = x_id64; p.y64 = y_id64; p.x32 = x_id32; p.y32 = y_id32;
   p.M = (int)M; p.Nrow = N; p.in_cs = in_cstride; p.in_coff = in_coff; p.n_rt = (int)((M + MQ_ROWS - 1) / MQ_ROWS);
   p.in_bytes = (uint32_t)in_bytes; p.slope1 = slope1; p.slope2 = slope2;
   p.o_base = o_base; p.o_sb = o_sb; p.o_sn = o_sn; p.o_sc = o_sc;
   const int grid = p.n_rt < n_cu ? p.n_rt : n_cu;
-  if (dtype == CP_F16) CP_LAUNCH((mlp_query_fused_kernel<true>), dim3((unsigned)grid), dim3(512), MQ_LDS, (hipStream_t)stream, p);
-  else CP_LAUNCH((mlp_query_fused_kernel<false>), dim3((unsigned)grid), dim3(512), MQ_LDS, (hipStream_t)stream, p);
-  return cp_check_launch();
+  const hipStream_t st = (hipStream_t)stream;
+  switch (nout) {
+    case 2: return mq_launch<2>(st, dtype, grid, p);
+    case 9: return mq_launch<9>(st, dtype, grid, p);
+    case 11: return mq_launch<11>(st, dtype, grid, p);
+    default: return mq_launch<13>(st, dtype, grid, p);
+  }
+}
+
+extern "C" int cp_mlp_query_fused_t(cp_stream_t stream, int dtype, const void* in, int in_cstride, int in_coff, int B, int N,
+                                  const void* packed_w1, const float* scale1, const float* shift1, float slope1,
+                                  const void* packed_w2, const float* scale2, const float* shift2, float slope2,
+                                  const float* w3, const float* b3, float* out, long long o_base, long long o_sb, long long o_sn,
+                                  long long o_sc) {
+  return cp_mlp_query_fused_n(stream, dtype, in, in_cstride, in_coff, B, N, packed_w1, scale1, shift1, slope1, packed_w2, scale2, shift2,
+                              slope2, w3, b3, 2, out, o_base, o_sb, o_sn, o_sc, nullptr, nullptr, nullptr, nullptr);
 }
 
 extern "C" int cp_mlp_query_fused(cp_stream_t stream, const void* in, int in_cstride, int in_coff, int B, int N,

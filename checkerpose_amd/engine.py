@@ -1043,6 +1043,39 @@ class Program:
         self.flops += fl
         self.conv_log.append((keys[0], M, 256 + 64 + 2, 256, fl, "mlp_fused", M * (256 * self.es + 8) + (256 * 256 + 64 * 256) * self.es))
 
+    def mlp_query_head(self, x: Act, keys, ws, bs, slope, out_tbuf, ostr, ids):
+        """the woProg ablation's MLP_QueryNet (pipeline_lm.py:475-517) in one launch: nout = ws[2].shape[0] = 1 + 2r logits of row
+        (b, n) to out_tbuf[ostr[0] + b * ostr[1] + n * ostr[3] + c * ostr[4]] (fp32) and, in the same epilogue, the x / y codes
+        decoded into ids = (x64, y64) (B, N) int64 torch tensors (cp_mlp_query_fused_n)"""
+        N = x.W
+        gdt = self.gdt
+        nout = int(ws[2].shape[0])
+        pw1 = self.ws.pack_gemm(keys[0], ws[0].reshape(ws[0].shape[0], ws[0].shape[1], 1, 1), 256, 256, 256, dtype=gdt)
+        pw2 = self.ws.pack_gemm(keys[1], ws[1].reshape(ws[1].shape[0], ws[1].shape[1], 1, 1), 64, 256, 256, dtype=gdt)
+        ck = ("mlp_query", keys[0])
+        if ck not in self.ws.cache:
+            dev = self.device
+            self.ws.cache[ck] = (torch.ones(256, dtype=torch.float32, device=dev), bs[0].float().contiguous(),
+                                 torch.ones(64, dtype=torch.float32, device=dev), bs[1].float().contiguous(),
+                                 ws[2].float().reshape(nout, 64).contiguous(), bs[2].float().contiguous())
+        s1, t1, s2, t2, w3, b3 = self.ws.cache[ck]
+        self.keep += [pw1, pw2, s1, t1, s2, t2, w3, b3]
+        xt = x.tbuf
+        a1 = (pw1.data_ptr(), s1.data_ptr(), t1.data_ptr(), float(slope), pw2.data_ptr(), s2.data_ptr(), t2.data_ptr(), float(slope),
+              w3.data_ptr(), b3.data_ptr(), nout)
+        o = (int(ostr[0]), int(ostr[1]), int(ostr[3]), int(ostr[4]), ids[0].data_ptr(), ids[1].data_ptr(), None, None)
+        self._add(self.lib.cp_mlp_query_fused_n, lambda P: (gdt, P(xt), x.cstride, x.coff, self.B, N) + a1 + (P(out_tbuf),) + o,
+                  "mlp_fused:" + keys[0], [xt], [out_tbuf, self.raw(ids[0]), self.raw(ids[1])])
+        M = self.B * N
+        fl = 2 * M * (256 * 256 + 256 * 64 + 64 * nout)
+        self.flops += fl
+        self.conv_log.append((keys[0], M, 256 + 64 + nout, 256, fl, "mlp_fused", M * (256 * self.es + 4 * nout + 16) + (256 * 256 + 64 * 256) * self.es))
+
+    def code_decode(self, bits_t, rows, r, x64_t, y64_t, N):
+        """x / y codes of a packed logit block (rows 1..r, r+1..2r) -> int64 ids (cp_code_decode)"""
+        a = (bits_t.data_ptr(), rows, r, x64_t.data_ptr(), y64_t.data_ptr(), None, None, self.B, N)
+        self._add(self.lib.cp_code_decode, lambda P: a, "code_decode", [self.raw(bits_t)], [self.raw(x64_t), self.raw(y64_t)])
+
     def can_fuse_mlp_pair(self, x: Act, w1, w2):
         return (USE_MLP_FUSED and self.dtype == CP_BF16 and x.H == 1 and self.B * x.W >= self.mlp_min_rows and x.C == w1.shape[1]
                 and x.C == x.Cphys and bool(self.lib.cp_mlp_pair_fused_supported(int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0])))

@@ -10,7 +10,7 @@ import torch
 
 from .. import _abi
 from ..engine import DTYPES, Program, ProgramGroup, WeightStore
-from ..netbuilder import NetEmitter, emit_init_net, emit_posenet
+from ..netbuilder import NetEmitter, emit_init_net, emit_posenet, emit_posenet_woprog
 
 
 _VERSION_OF = operator.attrgetter("_version")
@@ -367,7 +367,7 @@ class HipForwardMixin:
                 feats, g = emit_init_net(em, cfg, sio, "")
             else:
                 sio["seg_tb"] = prog.fixed(sio["seg"])
-                feats, _ = emit_posenet(em, cfg, sio)
+                feats, _ = (emit_posenet_woprog if cfg["kind"] == "woprog" else emit_posenet)(em, cfg, sio)
                 g = None
             if ext is not None:
                 prog.permute_cols(sio["bits"], ext["bits"], tiled["perm"], sio["gids"], 13, N, scatter=True)
@@ -448,7 +448,7 @@ class HipForwardMixin:
             emit_init_net(em, cfg, io, "")
         else:
             io["seg_tb"] = prog.fixed(io["seg"])
-            emit_posenet(em, cfg, io)
+            (emit_posenet_woprog if cfg["kind"] == "woprog" else emit_posenet)(em, cfg, io)
         prog.mark_forward_end()
         nb = pgrad.numel() * 4
         prog._add(lib.cp_memset_zero, lambda P: (pgrad.data_ptr(), nb), "pgrad_zero", [], [])

@@ -563,10 +563,11 @@ class NetEmitter:
         return self.p.edge_gather(pq, graph["idx"], graph["gids"], out, graph["K"], Co, graph["G"], slope)
 
 
-def emit_init_net(em: NetEmitter, cfg, io, pfx="", graph_out: Act = None, feat_outs=None, defer_head=False):
+def emit_init_net(em: NetEmitter, cfg, io, pfx="", graph_out: Act = None, feat_outs=None, defer_head=False, with_logits=True):
     """InitNet_GNN.forward init.py:109-128.  Returns (feats [Act], graph_feats Act).  defer_head: only the backbone is emitted
     now and the second return value is a callable that emits the head (conv1x1 -> EdgeConv layers -> Linear) and returns the
-    graph features -- PoseNet runs it on the refinement lane, beside the decoder's first stage (which needs the backbone only)."""
+    graph features -- PoseNet runs it on the refinement lane, beside the decoder's first stage (which needs the backbone only).
+    with_logits=False: the head stops at the graph features (the woProg ablation discards InitNet's logits: pipeline_lm.py:497)."""
     p = em.p
     N = cfg["npoint"]
     tp = em.tp
@@ -584,8 +585,8 @@ def emit_init_net(em: NetEmitter, cfg, io, pfx="", graph_out: Act = None, feat_o
                 a = p.fuse_sum([a], [0], feat_outs[i], relu=False)
             feats.append(a)
         if defer_head:
-            return feats, (lambda: _emit_init_head(em, cfg, io, pfx, graph_out, feats))
-        return feats, _emit_init_head(em, cfg, io, pfx, graph_out, feats)
+            return feats, (lambda: _emit_init_head(em, cfg, io, pfx, graph_out, feats, with_logits))
+        return feats, _emit_init_head(em, cfg, io, pfx, graph_out, feats, with_logits)
     fused_stem = (tp is None and cfg["backbone"] in HRNET_CFGS and not cfg.get("uint8_input") and p.can_fuse_stem(cfg["img_size"]))    # stem_width 64 in all of them
     if fused_stem:                 # layout change + conv1 + conv2 of the HRNet stem in one launch, straight from the NCHW image
         s1, t1 = em.ws.bn_fold(bb + "bn1")
@@ -599,11 +600,11 @@ def emit_init_net(em: NetEmitter, cfg, io, pfx="", graph_out: Act = None, feat_o
         tp.nograd.add(id(x.tbuf))                           # the image needs no gradient
     feats = em.hrnet(bb, x, feat_outs=feat_outs, stem_done=fused_stem, name=cfg["backbone"]) if cfg["backbone"] in HRNET_CFGS else em.resnet34(bb, x)
     if defer_head:
-        return feats, (lambda: _emit_init_head(em, cfg, io, pfx, graph_out, feats))
-    return feats, _emit_init_head(em, cfg, io, pfx, graph_out, feats)
+        return feats, (lambda: _emit_init_head(em, cfg, io, pfx, graph_out, feats, with_logits))
+    return feats, _emit_init_head(em, cfg, io, pfx, graph_out, feats, with_logits)
 
 
-def _emit_init_head(em: NetEmitter, cfg, io, pfx, graph_out, feats):
+def _emit_init_head(em: NetEmitter, cfg, io, pfx, graph_out, feats, with_logits=True):
     p, tp, N = em.p, em.tp, cfg["npoint"]
     f = feats[-1]                                           # (B, 8, 8, Cb)
     # conv1x1 Cb -> N, then `view(-1, N, 64).permute(0,2,1)` (init.py:112-114): keypoint n's 8x8 response map is its
@@ -652,6 +653,8 @@ def _emit_init_head(em: NetEmitter, cfg, io, pfx, graph_out, feats):
                         out=graph_out if (last and graph_out is not None) else None)
     if ng == 0 and graph_out is not None and not direct:
         raise RuntimeError("init_network_num_graph_module == 0 with more than 512 keypoints (patch-ordered rows) is not supported")
+    if not with_logits:
+        return g
     # Linear(64 -> 1 + 2r) (init.py:107,120-122) into the (B,13,N) logit block: r = 3 -> rows [roi | x2 x1 x0 | . . . | y2 y1 y0]
     # (the layout PoseNet appends its refinement bits to); an InitNet used alone with another res_log2 writes rows [0, 1 + 2r)
     wl = em.W(pfx + "mlp.weight")
@@ -929,4 +932,150 @@ def emit_posenet(em: NetEmitter, cfg, io):
         em._out_layer_bwd("seg_block", wseg, f, sd_, io["dseg"], 0, sd_ * f.H * f.W, 1, f.H * f.W)
     if active > 0:
         p.par_end()
+    return feats, f
+
+
+def emit_posenet_woprog(em: NetEmitter, cfg, io):
+    """PoseNet_GNNskip_ABwoProg.forward pipeline_lm.py:480-517 (the woProg ablation).  Two independent lanes behind the backbone:
+    the keypoint lane (1) runs InitNet's head up to its graph feature (its Linear(64 -> 7) logits are discarded by the reference and
+    not launched), refine_net[0..k) as pair MLP + EdgeConvs, then query_block -> the 1 + 2r logits packed into rows [0, 1 + 2r) of
+    the (B, 13, N) block and the decoded ids (one launch where the fused head applies); the decoder lane (0, with 2-5 for the skip
+    upsamples and the transposed-conv phases) runs up_net[0..k) -> seg_block.  No op of one lane waits for the other."""
+    p = em.p
+    N = cfg["npoint"]
+    r = cfg["res_log2"]
+    nref = r - 3
+    active = cfg["stage"] if cfg.get("stage") is not None else nref
+    assert 1 <= active <= nref
+    ngs = cfg["num_graph_module"]
+    ngs = (ngs,) * nref if isinstance(ngs, int) else tuple(ngs)
+    nf = cfg["num_filters"]
+    slope = cfg["leaky_slope"]
+    tp = em.tp
+    # decoder concat buffers filled in place by the backbone's incre modules (as in emit_posenet)
+    lowcats, feat_outs = {}, None
+    if tp is None and cfg["backbone"] in HRNET_CFGS:
+        feat_outs = [None] * 4
+        for i in range(1, active):
+            j = 3 - i
+            Cs = em.W("init_net.img_backbone.incre_modules.%d.0.conv3.weight" % j).shape[0]
+            Hs = cfg["img_size"] // (4 << j)
+            if p.can_conv_up2x(Hs, Hs, nf) and not (DECODER_SPLITK and p.would_splitk(p.B * 4 * Hs * Hs, 9 * (_rup(nf, p.E) + _rup(Cs, p.E)), nf)):
+                lowcats[i] = p.act(Hs, Hs, nf + Cs)
+                feat_outs[j] = lowcats[i].slice(_rup(nf, p.E), Cs)
+    head_later = tp is None
+    feats, g = emit_init_net(em, cfg, io, "init_net.", feat_outs=feat_outs, defer_head=head_later, with_logits=False)
+    p.par_begin(6 if tp is None else 2)      # 0 decoder, 1 keypoints, 2 skip upsamples, 3-5 transposed-conv phases
+
+    # ---- keypoint lane
+    p.set_lane(1)
+    if head_later:
+        g = g()
+    for i in range(active):
+        rp = "refine_net.%d" % i
+        pkeys = [rp + ".pre_graph_module.0", rp + ".pre_graph_module.2"]
+        pws = [em.W(k_ + ".weight") for k_ in pkeys]
+        if tp is None and p.can_fuse_mlp_pair(g, pws[0], pws[1]):
+            g = p.mlp_pair_fused(g, pkeys, pws, [em.W(k_ + ".bias") for k_ in pkeys], slope)     # csrc/mlp_fused.hip
+        else:
+            hk = {"in_half": True} if (tp is None and p.gnn_half) else {}
+            g = em.linear(g, pkeys[0], ACT_LEAKY, slope, **hk)
+            g = em.linear(g, pkeys[1], ACT_LEAKY, slope, **hk)
+        for gi in range(ngs[i]):
+            g = em.edgeconv("%s.pre_query_block.%d" % (rp, gi), g, io["graph"], cfg["graph_slope"])
+    qkeys = ["query_block.mlps.%d" % j for j in (0, 2, 4)]
+    qws = [em.W(k_ + ".weight") for k_ in qkeys]
+    nout = qws[2].shape[0]
+    ostr = (0, 13 * N, 0, 1, N)            # logit c of (b, n) -> row c of the (B, 13, N) block: [roi | x code | y code]
+    if tp is None and p.can_fuse_query_mlp(g, [qws[0].shape[1], qws[0].shape[0], qws[1].shape[0], nout]):
+        p.mlp_query_head(g, qkeys, qws, [em.W(k_ + ".bias") for k_ in qkeys], slope, io["bits_tb"], ostr, (io["x64"], io["y64"]))
+    else:
+        hk = {"in_half": True} if (tp is None and p.gnn_half) else {}
+        q = em.linear(g, qkeys[0], ACT_LEAKY, slope, **hk)
+        q = em.linear(q, qkeys[1], ACT_LEAKY, slope, **hk)
+        if tp is None:
+            em.linear(q, qkeys[2], ACT_NONE, 0.0, out_f32=True, ostr=ostr, out_tbuf=io["bits_tb"], in_half=p.gnn_half)
+        else:
+            wq4 = qws[2].view(nout, qws[2].shape[1], 1, 1)
+            p.conv(q, qkeys[2], wq4, tp.const_vec(nout, True), em._bias_vec(qkeys[2], nout), 1, 1, 1, 0, nout, out_f32=True,
+                   ostr=ostr, out_tbuf=io["bits_tb"])
+            em._out_layer_bwd(qkeys[2], wq4, q, nout, io["dbits"], 0, 13 * N, 1, N)
+        p.code_decode(io["bits"], 13, r, io["x64"], io["y64"], N)
+
+    # ---- decoder lane: up_net[0..k) -> seg_block (pipeline_lm.py:498-505), as emit_posenet runs it
+    p.set_lane(0)
+    cats = {}
+    if tp is None:
+        for i in range(1, active):
+            if i in lowcats:
+                continue
+            sk = feats[-i - 1]
+            cats[i] = p.act(2 * sk.H, 2 * sk.W, nf + sk.C)
+            p.set_lane(2)
+            p.upsample2x(sk, cats[i].slice(_rup(nf, p.E), sk.C))
+    wseg = em.W("seg_block.weight")
+    seg_fused = False
+    f = feats[-1]
+
+    def tail_conv(x, ck, bk, last, out=None):
+        nonlocal seg_fused
+        if (last and tp is None and out is None and p.can_conv_halo_seg(x, em.W(ck + ".weight").shape[0], wseg.shape[0])
+                and not (DECODER_SPLITK and p.would_splitk(x.B * x.H * x.W, 9 * x.Cphys, em.W(ck + ".weight").shape[0]))):
+            s_, t_ = em.ws.bn_fold(bk)
+            seg_fused = True
+            return p.conv_halo_seg(x, ck, em.W(ck + ".weight"), s_, t_, ACT_RELU, "seg_block", wseg, em.W("seg_block.bias"), io["seg_tb"])
+        return em.conv_bn(x, ck, bk, 3, 1, 1, out=out)
+
+    for i in range(active):
+        p.set_lane(0)
+        up = "up_net.%d" % i
+        last = i == active - 1
+        nxt = lowcats[i + 1].slice(0, nf) if (i + 1) in lowcats else None
+        if i == 0:
+            wt = em.W(up + ".0.weight")
+            s, t = em.ws.bn_fold(up + ".1") if tp is None else (tp.const_vec(nf, True), tp.const_vec(nf, False))
+            o = p.act(2 * f.H, 2 * f.W, nf)
+            for ph in range(4):
+                a, b = ph >> 1, ph & 1
+                if tp is None and ph > 0:
+                    p.set_lane(2 + ph)
+                p.conv(f, up + ".0", wt, s, t, 1 + a, 1 + b, 1, 0, nf, ACT_RELU if tp is None else ACT_NONE, transposed=1, phase=ph,
+                       ostr=((a * o.W + b) * o.cstride, o.H * o.W * o.cstride, 2 * o.W * o.cstride, 2 * o.cstride, 1),
+                       out_tbuf=o.tbuf, out_hw=(f.H, f.W))
+            if tp is None:
+                p.set_lane(0)
+                for ph in range(1, 4):
+                    p.sync(2 + ph, 0)
+            else:
+                o = _convt_train_tail(em, up, wt, f, o, nf)
+            f = em.conv_bn(o, up + ".3", up + ".4", 3, 1, 1)
+            f = tail_conv(f, up + ".6", up + ".7", last, out=nxt)
+        elif i in lowcats:
+            s1, t1 = em.ws.bn_fold(up + ".2")
+            f = p.conv_up2x(lowcats[i], up + ".1", em.W(up + ".1.weight"), s1, t1, ACT_RELU)
+            f = tail_conv(f, up + ".4", up + ".5", last, out=nxt)
+        else:
+            sk = feats[-i - 1]
+            cat = cats[i] if i in cats else p.act(2 * f.H, 2 * f.W, f.C + sk.C)
+            if i == 1 and i in cats:
+                p.sync(2, 0)
+            p.upsample2x(f, cat.slice(0, f.C))
+            if i not in cats:
+                p.upsample2x(sk, cat.slice(f.Cphys, sk.C))
+            if tp is not None:
+                _upsample_tape(tp, f, cat.slice(0, f.C))
+                _upsample_tape(tp, sk, cat.slice(f.Cphys, sk.C))
+            f = em.conv_bn(cat, up + ".1", up + ".2", 3, 1, 1)
+            f = tail_conv(f, up + ".4", up + ".5", last, out=nxt)
+    sd_ = wseg.shape[0]
+    if seg_fused:
+        pass
+    elif tp is None:
+        p.conv(f, "seg_block", wseg, em._unit(sd_), em.W("seg_block.bias"), 1, 1, 1, 0, sd_, out_f32=True,
+               ostr=(0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), out_tbuf=io["seg_tb"])
+    else:
+        p.conv(f, "seg_block", wseg, tp.const_vec(sd_, True), em._bias_vec("seg_block", sd_), 1, 1, 1, 0, sd_, out_f32=True,
+               ostr=(0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), out_tbuf=io["seg_tb"])
+        em._out_layer_bwd("seg_block", wseg, f, sd_, io["dseg"], 0, sd_ * f.H * f.W, 1, f.H * f.W)
+    p.par_end()
     return feats, f

@@ -79,3 +79,19 @@ def build_net(npoint=512, p3d=None, seed=0, lm=False, backbone="hrnet_w18", full
     fill_state_dict_(net.state_dict(), seed=seed)
     apply_overrides(net.state_dict(), overrides)
     return net.eval()
+
+
+def build_woprog(seed=0, overrides=None, npoint=512, res_log2=6, n_graph=3):
+    """The LM woProg ablation PoseNet_GNNskip_ABwoProg with the values of config/lm/hr18GNN2_res6_gnn3Skip_mlpQuery_lm_woProg.txt
+    (train_lm.py:198-203), deterministic weights (+ a fixture's recorded parameter overrides)."""
+    from .model.init_lm import InitNet_GNN
+    from .model.pipeline_lm import PoseNet_GNNskip_ABwoProg
+    p3d = lm_p3d(npoint)
+    init_net = InitNet_GNN(npoint=npoint, p3d_normed=p3d, res_log2=3, backbone_name="hrnet_w18", pretrain_backbone=False,
+                           max_batch_size=8, num_graph_module=2, graph_k=20, graph_leaky_slope=0.2)
+    net = PoseNet_GNNskip_ABwoProg(init_net=init_net, npoint=npoint, p3d_normed=p3d, res_log2=res_log2, num_filters=256,
+                                   max_batch_size=8, query_dims=None, local_k=2, leaky_slope=0.01, num_graph_module=n_graph,
+                                   graph_k=20, graph_leaky_slope=0.2, query_type="mlp")
+    fill_state_dict_(net.state_dict(), seed=seed)
+    apply_overrides(net.state_dict(), overrides)
+    return net.eval()

@@ -253,6 +253,16 @@ int cp_mlp_query_fused_t(cp_stream_t stream, int dtype, const void* in, int in_c
                          const void* packed_w1, const float* scale1, const float* shift1, float slope1,
                          const void* packed_w2, const float* scale2, const float* shift2, float slope2,
                          const float* w3, const float* b3, float* out, long long o_base, long long o_sb, long long o_sn, long long o_sc);
+/* the same with `nout` logits per row: 2 (the above) or 1 + 2r, r = 4..6 -- the woProg ablation's single head
+ * (pipeline_lm.py:475-517); cp_mlp_query_fused_supported(256, 256, 64, nout) says which.  w3 fp32 (nout, 64), b3 fp32 (nout).
+ * With x_id64 / y_id64 (both or neither; nout = 1 + 2r only) the same launch decodes the x / y codes -- logit rows 1..r and
+ * r+1..2r, MSB first, bit = [z > CP_SIGMOID_HALF_Z0] exactly as cp_bits_decode -- into ids (B, N) int64 (from_code_prob_to_id,
+ * pipeline.py:84-92), and into x_id32 / y_id32 (B, N) int32 where given. */
+int cp_mlp_query_fused_n(cp_stream_t stream, int dtype, const void* in, int in_cstride, int in_coff, int B, int N,
+                         const void* packed_w1, const float* scale1, const float* shift1, float slope1,
+                         const void* packed_w2, const float* scale2, const float* shift2, float slope2,
+                         const float* w3, const float* b3, int nout, float* out, long long o_base, long long o_sb, long long o_sn,
+                         long long o_sc, int64_t* x_id64, int64_t* y_id64, int32_t* x_id32, int32_t* y_id32);
 
 /* Refine_moduleGNN.pre_graph_module (pipeline.py:237-240, applied at :283-286: Linear(Cin -> 256) + LeakyReLU, Linear(256 -> 256) +
  * LeakyReLU over the concatenated [local | previous graph] feature rows) as ONE launch, bf16: the hidden rows stay in LDS.
@@ -504,6 +514,11 @@ int cp_index2feat_conv_t(cp_stream_t stream, int out_dtype, const void* f, int i
 #define CP_SIGMOID_HALF_Z0_BITS 0x33C00000u   /* largest fp32 z with sigmoidf(z) == 0.5f: 8.940696716e-08 */
 int cp_bits_decode(cp_stream_t stream, const float* bits, int stage, float* mask, int32_t* x_id,
                    int32_t* y_id, int64_t* x_id64, int64_t* y_id64, int B, int N);
+/* Code decode of a block that holds one head's rows packed (the woProg ablation, pipeline_lm.py:511-516): rows 1..r of
+ * bits (B, rows, N) are the x code, rows r+1..2r the y code, MSB first; x_id64 / y_id64 (B, N) int64 required, x_id32 / y_id32
+ * optional; 1 <= r, 1 + 2r <= rows.  The same bit predicate as cp_bits_decode (and cp_mlp_query_fused_n's epilogue). */
+int cp_code_decode(cp_stream_t stream, const float* bits, int rows, int r, int64_t* x_id64, int64_t* y_id64, int32_t* x_id32,
+                   int32_t* y_id32, int B, int N);
 
 /* Post-forward decode on the device (next-row N2; reference test.py:294-329 + test_network_with_test_data.py:50-66):
  * bits (B,13,N) fp32 logits, seg (B,2,H,W) fp32 logits (0 = visible, 1 = full), ids int64 (B,N), roi_xy_ori (B,2,H,W)
