@@ -84,10 +84,6 @@ class CpFuseBwdItem(C.Structure):
                 ("shift", C.c_int32), ("relu", C.c_int32), ("accumulate", C.c_int32), ("total", C.c_uint64)]
 
 
-class CpConvGroupItem(C.Structure):   # one layer of a grouped small-Cout conv launch (cp_conv3x3_halo_item fills it; params is opaque)
-    _fields_ = [("NT", C.c_int32), ("blocks", C.c_uint32), ("lds_bytes", C.c_uint32), ("pad", C.c_uint32), ("params", C.c_uint64 * 25)]
-
-
 class CpWgradDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("Ho", C.c_int32),
                 ("Wo", C.c_int32), ("Cout", C.c_int32), ("dy_cstride", C.c_int32), ("dy_coff", C.c_int32),
@@ -115,13 +111,10 @@ SIGNATURES = {
     "cp_packed_halo_weight_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_pack_conv3x3_halo_weight": (_I, [_P, _I, _P, _I, _I, _I, _P]),
     "cp_conv3x3_halo": (_I, [_P, C.POINTER(CpConvDesc), _P, _P, _P, _P, _P, _P]),
-    "cp_conv3x3_halo_group_supported": (_I, [_I, _I, _I, _I]),
     "cp_conv2x2_halo_supported": (_I, [_I, _I, _I, _I]),
     "cp_packed_conv2x2_halo_weight_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_pack_conv2x2_halo_weight": (_I, [_P, _I, _P, _I, _I, _I, _P]),
     "cp_conv2x2_halo": (_I, [_P, C.POINTER(CpConvDesc), _P, _P, _P, _P, _P, _P]),
-    "cp_conv3x3_halo_item": (_I, [C.POINTER(CpConvDesc), _P, _P, _P, _P, _P, _P, C.POINTER(CpConvGroupItem)]),
-    "cp_conv3x3_halo_group": (_I, [_P, _I, _P, _P, _I, C.c_uint32, C.c_uint32]),
     "cp_conv3x3_s2_small_supported": (_I, [_I, _I, _I, _I]),
     "cp_conv3x3_s2_small_weight_bytes": (C.c_size_t, [_I, _I]),
     "cp_pack_conv3x3_s2_small_weight": (_I, [_P, _P, _I, _I, _I, _I, _P]),
@@ -246,9 +239,6 @@ SIGNATURES = {
     "cp_bn_item_bwd_apply": (_I, [_I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _I, _P, _I, _I,
                                   _I, _P, _P, C.POINTER(CpBnItem)]),
     "cp_bn_group": (_I, [_P, _I, _I, _P, _P, _I, C.c_uint32, C.c_uint32]),
-    "cp_bn_train_fused": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _P, _P]),
-    "cp_bn_bwd_fused": (_I, [_P, _I, _P, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _I, _I, _P, _I, _I,
-                             _I, _P, _P]),
     "cp_edge_train_workspace_bytes": (C.c_size_t, [_I, _I]),
     "cp_edgeconv_train_fwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _F, _F, _P, _I, _I, _P, _P, _P, _P, _P, _P,
                                    _I, _I, _I, _I, _I, _F]),
@@ -270,8 +260,6 @@ SIGNATURES = {
     "cp_nhwc_to_nchw_f32": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I]),
     "cp_graph_begin_capture": (_I, [_P]),
     "cp_graph_end_capture": (_I, [_P, C.POINTER(_P)]),
-    "cp_graph_capture_set_deps": (_I, [_P, C.POINTER(_P), _I]),
-    "cp_graph_capture_tail": (_I, [_P, C.POINTER(_P), _I, C.POINTER(_I)]),
     "cp_graph_launch": (_I, [_P, _P]),
     "cp_graph_destroy": (_I, [_P]),
 }

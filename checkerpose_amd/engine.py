@@ -12,7 +12,7 @@ import os
 import torch
 
 from . import _abi
-from ._abi import ACT_LEAKY, ACT_NONE, ACT_RELU, CP_BF16, CP_F16, CP_F32, CpChainTail, CpChainTailConv, CpConvDesc, CpConvGroupItem, CpFuseConv
+from ._abi import ACT_LEAKY, ACT_NONE, ACT_RELU, CP_BF16, CP_F16, CP_F32, CpChainTail, CpChainTailConv, CpConvDesc, CpFuseConv
 
 _TORCH_DT = {CP_F32: torch.float32, CP_BF16: torch.bfloat16}
 USE_HALO = os.environ.get("CHECKERPOSE_AMD_HALO", "1") != "0"   # LDS-halo 3x3 kernel (A/B switch for kernel work)
@@ -34,8 +34,6 @@ USE_MLP_FUSED = os.environ.get("CHECKERPOSE_AMD_MLP_FUSED", "1") != "0"   # MLP_
 #  B = 8 1.84 vs 1.94, B = 32 3.11 vs 3.17 -- below 64 crops a forward is bound by its ~350 dependent graph nodes, and the stacks are 9 fewer)
 MLP_FUSED_MIN_ROWS = int(os.environ.get("CHECKERPOSE_AMD_MLP_FUSED_MIN_ROWS", "1"))
 EDGE_SCHED = os.environ.get("CHECKERPOSE_AMD_EDGE_SCHED", "1") != "0"   # A/B: bank-conflict-aware neighbour order for edge_fused
-USE_CONV_GROUP = os.environ.get("CHECKERPOSE_AMD_CONV_GROUP", "0") == "1"    # training: independent small 3x3 convs in one launch (measured: no gain)
-CONV_GROUP_MAX_C = int(os.environ.get("CHECKERPOSE_AMD_CONV_GROUP_MAXC", "48"))
 USE_SPLITK = os.environ.get("CHECKERPOSE_AMD_SPLITK", "1") != "0"     # small-batch split-K routing (cp_conv2d_igemm_splitk)
 GEMM_WS_SMALL_K = os.environ.get("CHECKERPOSE_AMD_GEMM_WS_SMALL_K", "1") != "0"   # A/B: weight-stationary GEMM from K = 64
 USE_MLP_GATHER = os.environ.get("CHECKERPOSE_AMD_MLP_GATHER", "1") != "0"   # Index2Feat's 4-tap gather inside the fused MLP pair's loader (A/B switch)
@@ -227,7 +225,7 @@ class Program:
         self._open = None
         self.flops = 0         # dense MACs*2 issued through cp_conv2d_igemm (algorithmic, unpadded)
         self.conv_log = _ConvLog(self)     # (name, M, Cout, K, flops, family, bytes) per MFMA launch -- bench roofline uses it
-        self._rw = {}          # op index -> (reads, writes): dead-launch elimination in finalize(dce=True), hazards of run_dag
+        self._rw = {}          # op index -> (reads, writes): dead-launch elimination in finalize(dce=True)
         # launch selection by batch size (module globals = the measured crossovers); HipForwardMixin.set_kernel_selection pins one
         # selection for every batch size, so a crop's bf16 bits do not depend on the size of the batch it arrives in
         self.chain_min, self.stem_min, self.edge_min, self.splitk = CHAIN_MIN_BATCH, STEM_MIN_BATCH, EDGE_FUSED_MIN_BATCH, USE_SPLITK
@@ -265,7 +263,7 @@ class Program:
 
     def raw(self, torch_tensor):
         """The TBuf standing for a caller-owned tensor an op touches through a raw pointer (index / mask / logits buffers):
-        listed in the op's reads / writes so the dataflow capture (run_dag) orders its producer and consumers."""
+        listed in the op's reads / writes (a launch that writes one is caller-visible: dead-launch elimination keeps it)."""
         key = (torch_tensor.data_ptr(), torch_tensor.numel() * torch_tensor.element_size())
         if key not in self._raw:
             t = TBuf(key[1])
@@ -439,73 +437,6 @@ class Program:
                   + R * S * wCin * wCout * self.es)          # algorithmic: input + output (+ residual) + weights, unpadded
         self.conv_log.append((wkey, x.B * Ho * Wo, wCout, R * S * wCin, fl, fam, nbytes))
         return out
-
-    def conv3x3_group(self, members):
-        """INDEPENDENT 3x3 / stride 1 / pad 1 convs (the branches of an HRNet module at equal depth) -> one cp_conv3x3_halo_group launch
-        for those the grouped kernel supports (<= 80 output channels, map >= 8 x 16), plain conv() launches for the rest.
-        members: [(x, wkey, w, scale, shift, act, slope, residual, out)]; no two members may write the same tensor.  -> [out Act]"""
-        lib = self.lib
-        outs, grp = [None] * len(members), []
-        for i, (x, wkey, w, scale, shift, act, slope, residual, out) in enumerate(members):
-            wCout, wCin = w.shape[0], w.shape[1]
-            if wCin != x.C:
-                raise RuntimeError("conv %s: weight expects %d input channels, activation has %d" % (wkey, wCin, x.C))
-            if USE_CONV_GROUP and _rup(wCout, self.E) <= CONV_GROUP_MAX_C and lib.cp_conv3x3_halo_group_supported(self.dtype, x.H, x.W, _rup(wCout, self.E)):
-                grp.append(i)
-            else:
-                outs[i] = self.conv(x, wkey, w, scale, shift, 3, 3, 1, 1, wCout, act, slope, residual=residual, out=out)
-        if len(grp) == 1:
-            x, wkey, w, scale, shift, act, slope, residual, out = members[grp[0]]
-            outs[grp[0]] = self.conv(x, wkey, w, scale, shift, 3, 3, 1, 1, w.shape[0], act, slope, residual=residual, out=out)
-            grp = []
-        if not grp:
-            return outs
-        builders, reads, writes, names = [], [], [], []
-        for i in grp:
-            x, wkey, w, scale, shift, act, slope, residual, out = members[i]
-            wCout, wCin = w.shape[0], w.shape[1]
-            packed = self.ws.pack_halo(wkey, w, wCout, wCin, x.Cphys)
-            sc, sh = self.ws.affine(wkey + "#0", scale, shift, wCout)
-            if out is None:
-                out = self.act(x.H, x.W, wCout)
-            d = CpConvDesc()
-            d.dtype, d.out_f32 = self.dtype, 0
-            d.B, d.H, d.W = x.B, x.H, x.W
-            d.Cin, d.in_cstride, d.in_coff = x.Cphys, x.cstride, x.coff
-            d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = 3, 3, 1, 1, x.H, x.W
-            d.act, d.slope, d.ksplit = act, slope, -1
-            d.Cout = out.Cphys
-            d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1
-            if residual is not None:
-                assert (residual.cstride, residual.coff, residual.H, residual.W) == (out.cstride, out.coff, out.H, out.W), \
-                    "residual must share the output layout"
-            self.keep += [d, packed, sc, sh]
-            rtb = residual.tbuf if residual is not None else None
-
-            def build(P, d=d, xtb=x.tbuf, rtb=rtb, otb=out.tbuf, pw=packed.data_ptr(), ps=sc.data_ptr(), pt=sh.data_ptr(), wkey=wkey):
-                it = CpConvGroupItem()
-                _abi.check(lib.cp_conv3x3_halo_item(C.byref(d), P(xtb), pw, ps, pt, P(rtb) if rtb is not None else None, P(otb), C.byref(it)),
-                           "cp_conv3x3_halo_item(%s)" % wkey)
-                return it
-            builders.append(build)
-            reads += [x.tbuf] + ([rtb] if rtb is not None else [])
-            writes.append(out.tbuf)
-            names.append(wkey)
-            outs[i] = out
-            fl = 2 * x.B * x.H * x.W * 9 * wCin * wCout
-            self.flops += fl
-            nbytes = (x.B * x.H * x.W * (wCin + wCout * (2 if residual is not None else 1)) + 9 * wCin * wCout) * self.es
-            self.conv_log.append((wkey, x.B * x.H * x.W, wCout, 9 * wCin, fl, "conv3x3_halo_group", nbytes))
-        assert len(set(id(t) for t in writes)) == len(writes), "conv3x3_group: two members write the same tensor"
-        dt = self.dtype
-
-        def argb(P):
-            items = [b(P) for b in builders]
-            raw, prefix, total = _abi.device_table(items, [it.blocks for it in items], self.device)
-            self.keep += [raw, prefix]
-            return (dt, raw.data_ptr(), prefix.data_ptr(), len(items), total, max(int(it.lds_bytes) for it in items))
-        self._add(lib.cp_conv3x3_halo_group, argb, "conv3x3_halo_group:" + names[0] + "+%d" % (len(names) - 1), reads, writes)
-        return outs
 
     def would_splitk(self, M, K, Cout):
         """small-batch regime: cp_conv2d_igemm would run this conv as its split-K variant (M output pixels, K = R*S*Cin physical)"""
@@ -1326,12 +1257,6 @@ class Program:
 
         self.calls = []       # kernel launches only: (fn, (None, args...), name)
         self.sched = []       # launches + fork/sync/join markers: ("op", call_index, lane) | ("fork", n) | ...
-        acc = []              # per launch: (reads, writes) as (lo, hi, tbuf id) byte intervals -- hazards of run_dag
-        for oi, op in enumerate(self.ops):
-            if op[0] not in ("__fork__", "__sync__", "__join__", "__mark__", "__wait__", "__dead__"):
-                rd, wr = self._rw.get(oi, ([], []))
-                acc.append(tuple([(P(t), P(t) + t.nbytes, id(t)) for t in lst] for lst in (rd, wr)))
-        self._acc, self._dag = acc, None      # hazards are derived on first use (dag property): quadratic in the launch count
         for op in self.ops:
             if op[0] == "__fork__":
                 self.sched.append(("fork", op[1]))
@@ -1350,63 +1275,6 @@ class Program:
                 self.sched.append(("op", len(self.calls), lane))
                 self.calls.append((fn, (None,) + tuple(argb(P)), name))
         return self
-
-    @property
-    def dag(self):
-        if self._dag is None:
-            self._dag = self._hazards(self._acc)
-        return self._dag
-
-    @staticmethod
-    def _hazards(acc):
-        """Per launch, the earlier launches it must wait for (transitively reduced): read-after-write, write-after-read and
-        write-after-write on overlapping BYTES (the planner recycles workspace bytes, so two tensors can share them) --
-        except that two launches writing the SAME tensor do not order each other: they fill disjoint channel slices of a
-        concatenation buffer (an in-place update lists the tensor in its reads and is ordered by that)."""
-        def hit(a, b, same_ok):
-            for lo, hi, ia in a:
-                for lo2, hi2, ib in b:
-                    if lo < hi2 and lo2 < hi and not (same_ok and ia == ib):
-                        return True
-            return False
-        deps, anc = [], []
-        for k, (rd, wr) in enumerate(acc):
-            d = set()
-            for j in range(k - 1, -1, -1):
-                rj, wj = acc[j]
-                if hit(wj, rd, False) or hit(rj, wr, False) or hit(wj, wr, True):
-                    d.add(j)
-            a = set(d)
-            for j in d:
-                a |= anc[j]
-            anc.append(a)
-            deps.append(sorted(j for j in d if not any(j in anc[i] for i in d if i != j)))
-        return deps
-
-    def run_dag(self, stream_ptr):
-        """Replay on ONE stream that is being captured into a hipGraph, each launch depending on exactly the launches
-        whose bytes it reads or overwrites (self.dag) -- the graph is the dataflow DAG of the program: a branch of the next
-        HRNet module starts as soon as ITS fuse terms are there, the tail of the slow stride-2 fuse chains runs under it."""
-        lib = self.lib
-        tails = []                                   # per launch: its last graph node
-        cap = 8
-        buf, n = (C.c_void_p * cap)(), C.c_int(0)
-        used = set()
-        for k, (fn, args, name) in enumerate(self.calls):
-            nodes = [tails[j] for j in self.dag[k]]
-            used.update(self.dag[k])
-            arr = (C.c_void_p * max(len(nodes), 1))(*nodes)
-            _abi.check(lib.cp_graph_capture_set_deps(stream_ptr, arr, len(nodes)), "capture deps")
-            rc = fn(stream_ptr, *args[1:])
-            if rc != 0:
-                _abi.check(rc, name)
-            _abi.check(lib.cp_graph_capture_tail(stream_ptr, buf, cap, C.byref(n)), "capture tail")
-            if n.value != 1:
-                raise RuntimeError("checkerpose_amd: launch %s left %d capture tail nodes (expected 1)" % (name, n.value))
-            tails.append(buf[0])
-        sinks = [tails[k] for k in range(len(tails)) if k not in used]
-        arr = (C.c_void_p * max(len(sinks), 1))(*sinks)
-        _abi.check(lib.cp_graph_capture_set_deps(stream_ptr, arr, len(sinks)), "capture deps")   # join: the capture ends on every sink
 
     def run(self, stream_ptr):
         """Sequential replay on one stream (program order)."""

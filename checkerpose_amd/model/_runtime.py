@@ -67,9 +67,7 @@ def _version_sum(tensors):
         return sum(map(_VERSION_OF, tensors))
     except RuntimeError:        # inference-mode tensors (built / loaded under torch.inference_mode) track no version: they cannot be
         return sum(0 if t.is_inference() else t._version for t in tensors)   # edited in place outside inference mode either
-TRAIN_GRAPH = os.environ.get("CHECKERPOSE_AMD_TRAIN_GRAPH", "fwd,bwd").split(",")
-# stream priority per graph lane of the eval programs (torch: -1 = high, 0 = default); A/B knob CHECKERPOSE_AMD_LANE_PRIO="-1,0,0"
-LANE_PRIO = [int(v) for v in os.environ.get("CHECKERPOSE_AMD_LANE_PRIO", "0").split(",") if v.strip()]   # which halves replay as hipGraphs (A/B + debugging)
+TRAIN_GRAPH = os.environ.get("CHECKERPOSE_AMD_TRAIN_GRAPH", "fwd,bwd").split(",")   # which halves replay as hipGraphs (A/B + debugging)
 
 
 def _replay_half(mod, pr, which, lo, hi, device):
@@ -88,18 +86,11 @@ def _replay_half(mod, pr, which, lo, hi, device):
         pr["warm"][which] = True
         return
     if g is None:
-        nl = prog.nlanes if (mod.use_lanes and mod.train_lanes and which == "fwd") else 1
-        lanes = [torch.cuda.Stream(device) for _ in range(nl)]
+        lanes = [torch.cuda.Stream(device)]
         lanes[0].wait_stream(cur)
         _abi.check(lib.cp_graph_begin_capture(lanes[0].cuda_stream), "graph capture begin")
         try:
-            if nl > 1:
-                pr["keep_streams"].append(prog.run_lanes_range(lanes, lo, hi))
-            elif mod.train_prep_lane:
-                lanes.append(torch.cuda.Stream(device))
-                pr["keep_streams"].append(prog.run_prep_range(lanes[0], lanes[1], lo, hi))
-            else:
-                prog.run_range(lanes[0].cuda_stream, lo, hi)
+            prog.run_range(lanes[0].cuda_stream, lo, hi)
         finally:
             gx = C.c_void_p()
             rc = lib.cp_graph_end_capture(lanes[0].cuda_stream, C.byref(gx))
@@ -179,15 +170,10 @@ class HipForwardMixin:
         self._idx_dev = None
         self._stale_eval = False          # a train step changed the weights / running stats the eval programs folded
         self.dp_allreduce = True          # all-reduce the flat gradient buffer when torch.distributed is initialised
-        self.train_prep_lane = os.environ.get("CHECKERPOSE_AMD_TRAIN_PREP_LANE", "0") == "1"   # weight prep on a side stream
-        #                                   under capture: measured -3 % at B=32 (46.5 vs 45.0 ms) -> off
-        self.train_lanes = os.environ.get("CHECKERPOSE_AMD_TRAIN_LANES", "0") == "1"   # parallel graph branches in the training
-        #                                   forward: measured +-0 % at B=32 (the step is bandwidth-, not latency-bound) -> off
         self.compute_dtype = os.environ.get("CHECKERPOSE_AMD_DTYPE", "fp32")
         self.use_graph = os.environ.get("CHECKERPOSE_AMD_GRAPH", "1") != "0"
         self.use_lanes = os.environ.get("CHECKERPOSE_AMD_LANES", "1") != "0"   # parallel graph branches
         self.max_lanes = int(os.environ.get("CHECKERPOSE_AMD_MAX_LANES", "0"))    # 0 = as many streams as the program has lanes (A/B knob)
-        self.use_dag = os.environ.get("CHECKERPOSE_AMD_DAG", "0") == "1"       # dataflow capture (Program.run_dag) instead of fork/join lanes
         self.batch_splits = int(os.environ.get("CHECKERPOSE_AMD_SPLITS", "1"))   # concurrent batch slices per forward (measured: 1 is fastest; 2 and 4 lose 8 % / 30 % at B=128)
         self.clone_outputs = True
         self.kernel_selection = os.environ.get("CHECKERPOSE_AMD_SELECTION", "auto")
@@ -609,18 +595,14 @@ class HipForwardMixin:
                     # launched concurrently on separate streams, forked from / joined to the caller's stream
                     graphs, keep = [], []
                     for sub in prog.progs:
-                        nl_ = sub.nlanes if self.use_lanes and not self.use_dag else 1
-                        # lane priorities (they carry into the captured graph): lane 0 = the 64x64 HRNet branch, whose launch is the
-                        # longest of a module AND has the longest dependent tail (its 2nd / 3rd stride-2 fuse convs); see LANE_PRIO
-                        lanes = [torch.cuda.Stream(device, priority=(LANE_PRIO[k] if k < len(LANE_PRIO) else 0)) for k in range(nl_)]
+                        nl_ = sub.nlanes if self.use_lanes else 1
+                        lanes = [torch.cuda.Stream(device) for _ in range(nl_)]
                         if self.max_lanes and len(lanes) > self.max_lanes:      # lane k -> stream k mod max_lanes (fewer queues in the graph)
                             lanes = [lanes[k % self.max_lanes] for k in range(len(lanes))]
                         lanes[0].wait_stream(cur)
                         _abi.check(lib.cp_graph_begin_capture(lanes[0].cuda_stream), "graph capture begin")
                         try:
-                            if self.use_dag:
-                                sub.run_dag(lanes[0].cuda_stream)
-                            elif len(lanes) > 1:
+                            if len(lanes) > 1:
                                 keep.append(sub.run_lanes(lanes))
                             else:
                                 sub.run(lanes[0].cuda_stream)

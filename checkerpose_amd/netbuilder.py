@@ -20,19 +20,7 @@ FUSE_OUT_DEEP = os.environ.get("CHECKERPOSE_AMD_FUSE_OUT_DEEP", "1") != "0"   # 
 
 DECODER_SPLITK = os.environ.get("CHECKERPOSE_AMD_DECODER_SPLITK", "1") != "0"   # A/B: decoder convs as split-K convs at batch 1-4
 HEAD_ON_REFINE_LANE = os.environ.get("CHECKERPOSE_AMD_HEAD_LANE", "1") != "0"   # A/B: InitNet head beside up_net[0]
-# opt-in (measured +-0: 11.02 / 11.02 vs 11.09 / 10.73 ms at B = 256, alternating on one box): the 2nd / 3rd convs of the long stride-2
-# fuse chains run in the NEXT module's region, on their target's lane, instead of behind the 64 x 64 branch's lane in front of the join
-FUSE_DEFER = os.environ.get("CHECKERPOSE_AMD_FUSE_DEFER", "0") == "1"
 FUSE_SAME_LANE = os.environ.get("CHECKERPOSE_AMD_FUSE_SAME_LANE", "1") != "0"   # A/B: a fuse chain's later convs on its source's lane (no second region)
-
-
-class _PendingTerm:
-    """A fuse term whose stride-2 chain is only started: `act` = the output of its first conv, `convs` = [(conv key, bn key, relu)]
-    still to run.  The next module resolves it on the lane of the branch that consumes it (NetEmitter._resolve)."""
-    __slots__ = ("act", "convs")
-
-    def __init__(self, act, convs):
-        self.act, self.convs = act, convs
 
 
 class NetEmitter:
@@ -95,12 +83,8 @@ class NetEmitter:
         tp = self.tp
         members, recs = [], []
         ws = [self.W(conv + ".weight") for _, conv, *_ in specs]
-        if all((k, stride, pad) == (3, 1, 1) for _, _, _, k, stride, pad, _, _ in specs):        # the convs themselves grouped too
-            raws = tp.conv3x3_group([(x, conv, w, tp.const_vec(w.shape[0], True), tp.const_vec(w.shape[0], False), ACT_NONE, 0.0, None, None)
-                                     for (x, conv, *_), w in zip(specs, ws)])
-        else:
-            raws = [tp.conv(x, conv, w, tp.const_vec(w.shape[0], True), tp.const_vec(w.shape[0], False), k, k, stride, pad, w.shape[0])
-                    for (x, conv, _, k, stride, pad, _, _), w in zip(specs, ws)]
+        raws = [tp.conv(x, conv, w, tp.const_vec(w.shape[0], True), tp.const_vec(w.shape[0], False), k, k, stride, pad, w.shape[0])
+                for (x, conv, _, k, stride, pad, _, _), w in zip(specs, ws)]
         for (x, conv, bn, k, stride, pad, relu, residual), w, raw in zip(specs, ws, raws):
             recs.append((x, conv, bn, w, k, stride, pad, ACT_RELU if relu else ACT_NONE, residual, raw))
         ys = []
@@ -261,12 +245,9 @@ class NetEmitter:
         return self.conv_bn(y, pfx + ".conv3", pfx + ".bn3", 1, 1, 0, relu=True, residual=sc, out=out)
 
     # ---- HRNet-W18 features (timm HighResolutionNetFeatures)
-    def _resolve(self, t):
-        """run what is left of a deferred fuse chain (on the CURRENT lane) -> its Act"""
-        if not isinstance(t, _PendingTerm):
-            return t
-        a = t.act
-        for ck, bk, relu in t.convs:
+    def _fuse_chain_rest(self, a, convs):
+        """the 2nd / 3rd convs of a stride-2 fuse chain (on the CURRENT lane): convs = [(conv key, bn key, relu)] -> its Act"""
+        for ck, bk, relu in convs:
             if FUSE_OUT_DEEP and self.p.can_fuse_out(a, [self.W(ck + ".weight").shape[0]]):
                 a = self.p.hr_fuse_out(a, [(ck, self.W(ck + ".weight")) + tuple(self.ws.bn_fold(bk)) + (3, relu)])[0]
             else:
@@ -280,7 +261,6 @@ class NetEmitter:
             assert out is None
             return x
         terms, shifts = x
-        terms = [self._resolve(t) for t in terms]
         if out is None:
             out = self.p.act(terms[0].H << shifts[0], terms[0].W << shifts[0], terms[0].C)
         return self.p.fuse_sum(terms, shifts, out, relu=True)
@@ -303,14 +283,14 @@ class NetEmitter:
         wm, shift = self.ws.cache[ck]
         return self.p.conv(cat, ck, wm, self._unit(wm.shape[0]), shift, 1, 1, 1, 0, wm.shape[0], ACT_RELU, out=out)
 
-    def hr_module(self, pfx, xs, lazy=False, defer=False, nblocks=4):
+    def hr_module(self, pfx, xs, lazy=False, nblocks=4):
         """One timm HighResolutionModule.  xs[j]: an Act, or (terms, shifts) = the previous module's fuse terms of branch j
         still un-summed.  With lazy=True the outputs are returned in that un-summed form too: a branch that runs as ONE
         chain launch (engine.hr_chain, bf16) sums + ReLUs them while staging its map into LDS, other consumers
-        materialise them (fuse_sum launch)."""
-        nb = len(xs)
-        if self.tp is not None and self.tp.bn_grouped and nb > 1:
+        materialise them (fuse_sum launch).  The training program emits the module depth-major (_hr_module_train)."""
+        if self.tp is not None:
             return self._hr_module_train(pfx, xs, nblocks)
+        nb = len(xs)
         xs = list(xs)
         p = self.p
         # lane j: branch j's four BasicBlocks; then lane i runs the fuse-layer conv chains INTO branch i (it waits for the
@@ -321,14 +301,12 @@ class NetEmitter:
         p.par_begin(nb)
         for j in range(nb):
             p.set_lane(j)
-            if not isinstance(xs[j], Act):       # deferred tails of the previous module's stride-2 fuse chains INTO branch j: on this lane,
-                xs[j] = ([self._resolve(t) for t in xs[j][0]], xs[j][1])     # in front of its chain (branches 0 / 1 have none and start at once)
             if isinstance(xs[j], Act):
                 C_, H, W = xs[j].C, xs[j].H, xs[j].W
             else:
                 t0, sh0 = xs[j][0][0], xs[j][1][0]
                 C_, H, W = t0.C, t0.H << sh0, t0.W << sh0
-            if self.tp is None and nblocks == 4 and p.can_chain(C_, H, W):      # (the chain launches are 4 BasicBlocks = 8 convs long)
+            if nblocks == 4 and p.can_chain(C_, H, W):      # (the chain launches are 4 BasicBlocks = 8 convs long)
                 srcs, shifts = ([xs[j]], [0]) if isinstance(xs[j], Act) else xs[j]
                 bp = "%s.branches.%d" % (pfx, j)
                 ws = [self.W("%s.%d.conv%d.weight" % (bp, k, c)) for k in range(4) for c in (1, 2)]
@@ -369,51 +347,42 @@ class NetEmitter:
                     lst.append((i, q + ".0", q + ".1", 1, False))
                 elif j < i:
                     lst.append((i, q + ".0.0", q + ".0.1", 3, i - j > 1))
-            if self.tp is None and nb > 1 and p.can_fuse_out(xs[j], [self.W(ck + ".weight").shape[0] for (_, ck, _, _, _) in lst]):
+            if nb > 1 and p.can_fuse_out(xs[j], [self.W(ck + ".weight").shape[0] for (_, ck, _, _, _) in lst]):
                 # the same lane goes on with ONE launch for all of them (its map staged in LDS once); the second region keeps only the
                 # 2nd / 3rd convs of the long stride-2 chains
                 outs = p.hr_fuse_out(xs[j], [(ck, self.W(ck + ".weight")) + tuple(self.ws.bn_fold(bk)) + (k, relu)
                                              for (_, ck, bk, k, relu) in lst])
                 for (i, _, _, _, _), o in zip(lst, outs):
                     first[(i, j)] = o
-        if self.tp is not None:              # training program: lane j also runs the fuse chains fed by branch j (program order)
-            sched = [(j, i, j) for j in range(nb) for i in range(nb) if i != j]
-        else:
-            # eval: the fuse-layer conv chains run in a second fork/join region, spread over the lanes by length (the three
-            # stride-2 chains fed by the 64x64 branch used to queue up behind it on ONE lane: the module's critical path).
-            # (Cross-lane event edges inside one region would express this without the join, but a capture in which two
-            # streams wait on each other's events crashes hipStreamEndCapture on ROCm 7.2.)
-            def cost_of(i, j):               # launches still to run for term (i, j)
-                if (i, j) in first:
-                    return max(i - j - 1, 0)
-                return (i - j) if j < i else 0.3
-            load = [0.0] * nb
-            sched = []
-            same_lane = FUSE_SAME_LANE and len(first) == nb * (nb - 1)      # every chain starts in a grouped launch:
-            for cost, i, j in sorted([(cost_of(i, j), i, j) for i in range(nb) for j in range(nb) if i != j], reverse=True):
-                if same_lane:                # its later convs follow on their SOURCE's lane -- one fork/join region per module
-                    ln = j
-                else:
-                    ln = min(range(nb), key=lambda k: load[k]) if cost > 0 else 0
-                load[ln] += cost
-                sched.append((ln, i, j))
-            second = any(c > 0 for c in load) and not same_lane
-            if second:
-                p.par_end()
-                p.par_begin(nb)
+        # the fuse-layer conv chains run in a second fork/join region, spread over the lanes by length (the three
+        # stride-2 chains fed by the 64x64 branch used to queue up behind it on ONE lane: the module's critical path).
+        # (Cross-lane event edges inside one region would express this without the join, but a capture in which two
+        # streams wait on each other's events crashes hipStreamEndCapture on ROCm 7.2.)
+        def cost_of(i, j):               # launches still to run for term (i, j)
+            if (i, j) in first:
+                return max(i - j - 1, 0)
+            return (i - j) if j < i else 0.3
+        load = [0.0] * nb
+        sched = []
+        same_lane = FUSE_SAME_LANE and len(first) == nb * (nb - 1)      # every chain starts in a grouped launch:
+        for cost, i, j in sorted([(cost_of(i, j), i, j) for i in range(nb) for j in range(nb) if i != j], reverse=True):
+            if same_lane:                # its later convs follow on their SOURCE's lane -- one fork/join region per module
+                ln = j
+            else:
+                ln = min(range(nb), key=lambda k: load[k]) if cost > 0 else 0
+            load[ln] += cost
+            sched.append((ln, i, j))
+        second = any(c > 0 for c in load) and not same_lane
+        if second:
+            p.par_end()
+            p.par_begin(nb)
         for i in range(nb):
             terms[i][i] = xs[i]
         for ln, i, j in sched:
             p.set_lane(ln)
             q = "%s.fuse_layers.%d.%d" % (pfx, i, j)
-            if (i, j) in first:
-                # the rest of a long stride-2 chain (same kernel, one conv per launch): now, on its source's lane -- or, when the
-                # consumer is the next module of the stage, deferred to that module's region and its TARGET's lane: the 64 x 64
-                # branch's lane is the module's critical path (chain + the grouped first-level launch), and its three small tail convs
-                # used to run behind it, in front of the join
-                t = _PendingTerm(first[(i, j)], [("%s.%d.0" % (q, k), "%s.%d.1" % (q, k), k != i - j - 1) for k in range(1, i - j)])
-                if not (self.tp is None and defer and lazy and same_lane and t.convs):
-                    t = self._resolve(t)
+            if (i, j) in first:          # the rest of a long stride-2 chain (same kernel, one conv per launch)
+                t = self._fuse_chain_rest(first[(i, j)], [("%s.%d.0" % (q, k), "%s.%d.1" % (q, k), k != i - j - 1) for k in range(1, i - j)])
             elif j > i:
                 t = self.conv_bn(xs[j], q + ".0", q + ".1", 1, 1, 0, relu=False)
             else:
@@ -422,7 +391,7 @@ class NetEmitter:
                     t = self.conv_bn(t, "%s.%d.0" % (q, k), "%s.%d.1" % (q, k), 3, 2, 1, relu=(k != i - j - 1))
             terms[i][j] = t
         p.par_end()
-        if lazy and self.tp is None:
+        if lazy:
             return [(terms[i], [max(j - i, 0) for j in range(nb)]) for i in range(nb)]
         outs = []
         p.par_begin(nb)                      # the nb fuse sums are independent of each other
@@ -431,22 +400,8 @@ class NetEmitter:
             out = p.act(xs[i].H, xs[i].W, xs[i].C)
             shifts = [max(j - i, 0) for j in range(nb)]
             outs.append(p.fuse_sum(terms[i], shifts, out, relu=True))
-            if self.tp is not None:
-                self.tp.kinks["%s.fuse%d" % (pfx, i)] = out
-                self._fuse_sum_tape(out, list(terms[i]), shifts)
         p.par_end()
         return outs
-
-    def _fuse_sum_tape(self, out, srcs, shifts):
-        tp = self.tp
-
-        def bwd():
-            if out.tbuf not in tp.grads:
-                return
-            go = tp.grad_of(out)
-            for s_, sh in zip(srcs, shifts):
-                tp.fuse_sum_bwd(go, out, tp.grad_of(s_), sh, True)
-        tp.tape.append(bwd)
 
     def hrnet(self, pfx, x, feat_outs=None, stem_done=False, name="hrnet_w18"):
         hcfg = HRNET_CFGS[name]
@@ -471,8 +426,7 @@ class NetEmitter:
                 xs = xs + [self.conv_bn(xs[-1], t + ".0", t + ".1", 3, 2, 1)]
             last_stage = si == len(stages) - 1
             for m in range(nmod):           # inside a stage the fuse sums stay un-summed for the next module's chain launches
-                xs = self.hr_module("%s%s.%d" % (pfx, stage, m), xs, lazy=(m + 1 < nmod) or (last_stage and self.tp is None),
-                                    defer=FUSE_DEFER and m + 1 < nmod, nblocks=nblk)
+                xs = self.hr_module("%s%s.%d" % (pfx, stage, m), xs, lazy=(m + 1 < nmod) or (last_stage and self.tp is None), nblocks=nblk)
         feats = []
         self.p.par_begin(len(xs))            # the four incre bottlenecks are independent
         for i, f in enumerate(xs):

@@ -124,10 +124,8 @@ class TrainProgram(Program):
         # ordered)
         self.wg_ws, self.wg_stream = _shared_wgrad_arena(device)
         self._wg_off, self._wg_items, self._wg_keys, self.wg_tabs = 0, [], set(), []
-        self.wg_defer = os.environ.get("CHECKERPOSE_AMD_WGRAD_DEFER", "1") != "0"        # A/B: one reduction launch per layer
         # grouped weight gradients: the partial-sum launches of up to wg_group_n layers wait for each other and go out as ONE launch
         # per kernel kind (cp_wgrad_group), every layer cut into its share of wg_group_blocks workgroups instead of a GPU's worth
-        self.wg_group = self.wg_defer and os.environ.get("CHECKERPOSE_AMD_WGRAD_GROUP", "1") != "0"
         self.wg_group_n = int(os.environ.get("CHECKERPOSE_AMD_WGRAD_GROUP_N", "64"))
         self.wg_group_flops = float(os.environ.get("CHECKERPOSE_AMD_WGRAD_GROUP_GFLOP", "40")) * 1e9     # bigger layers launch alone
         gb = [int(v) for v in os.environ.get("CHECKERPOSE_AMD_WGRAD_GROUP_BLOCKS", "512,1024,1024").split(",")]
@@ -135,11 +133,6 @@ class TrainProgram(Program):
                                 CP_WGRAD_ITEM_GENERIC_F32: gb[2], CP_WGRAD_ITEM_3X3_S2_SMALL: gb[1]}
         self.wg_reduce_n = int(os.environ.get("CHECKERPOSE_AMD_WGRAD_REDUCE_N", "96"))
         self._wgc_pending = []
-        # BatchNorm statistics + apply in ONE launch each way (grid barrier in between): measured SLOWER on MI355X -- 42.3 ms per step
-        # at best (256 blocks, slow polling) against 35.7 ms for the two-launch forms: the barrier costs >= 10 us per launch -> off
-        self.bn_fused = os.environ.get("CHECKERPOSE_AMD_BN_FUSED", "0") == "1"
-        # the BatchNorm passes of independent layers (HRNet branches at equal depth, a module's fuse convs) in one launch each
-        self.bn_grouped = os.environ.get("CHECKERPOSE_AMD_BN_GROUPED", "1") != "0"
         self.wgrad_flops = {}      # op index -> algorithmic FLOPs of that weight-gradient launch (bench_train roofline)
         self.n_fwd_ops = None
         self._touched, self.pslot_done, self.pslot_done_call = [], {}, {}
@@ -154,22 +147,14 @@ class TrainProgram(Program):
         self.half = 0
         for kind in ("views", "packs"):
             self._add(lib.cp_pack_batch, (lambda k: lambda P: self._batch_args(k, 0))(kind), "prep_%s_fwd" % kind, [], [])
-        self.prep_idx = set()      # op indices of weight-preparation launches
         self.arena = []            # gradient TBufs (not recycled: 288 GB of HBM; one zero fill instead of ~370)
         self.grad_arena = None
         self.kinks = {}            # activation key -> Act whose sign is the (Leaky)ReLU branch taken (tests: oracle FORCE_MASK)
         self.debug = {}            # name -> Acts of interest (tools/train_debug.py with CHECKERPOSE_AMD_NO_RECYCLE=1)
 
-    # ---- lanes: the FORWARD half keeps the eval program's fork/join structure (HRNet branches, decoder || refinement run as
-    # parallel hipGraph branches: the latency-bound small-map kernels overlap the 64x64 ones); the backward half is emitted
-    # after the last join and stays one ordered stream.  Scratch that is shared between launches is per lane (bn_ws).
-    # ---- weight preparation ops (packing, data-gradient / EdgeConv weight views, bias refreshes) read ONLY parameters and
-    # write buffers nobody but their one consumer touches: under graph capture they run on a second stream, chunks ahead of
-    # the compute stream (run_prep_range), instead of ~1100 serialized 4 us launches on the critical path.
-    def add_prep(self, fn, argb, name):
-        self.prep_idx.add(len(self.ops))
-        self._add(fn, argb, name, [], [])
-
+    # ---- lanes: the FORWARD half keeps the eval program's fork/join markers (the liveness planner keeps a region's tensors alive
+    # over the whole region); the backward half is emitted after the last join.  Both halves replay on one ordered stream.
+    # Scratch that is shared between launches is per lane (bn_ws).
     def add_item(self, kind, item):
         self.items[(kind, self.half)].append(item)
 
@@ -248,11 +233,8 @@ class TrainProgram(Program):
     # consumer kernel derives the coefficients itself) -- the accumulators of the whole step are zero-filled by ONE launch
     def _acc_slot(self, C_):
         off = self.acc_total
-        self.acc_total += int(self.lib.cp_bn_acc_doubles(C_)) + 2      # + the fused launches' barrier counter (zeroed with the sums)
+        self.acc_total += int(self.lib.cp_bn_acc_doubles(C_))
         return off
-
-    def _ctr_ptr(self, off, C_):
-        return self.acc_arena.data_ptr() + 8 * (off + int(self.lib.cp_bn_acc_doubles(C_)))
 
     def _acc_ptr(self, off):
         return self.acc_arena.data_ptr() + 8 * off
@@ -264,9 +246,6 @@ class TrainProgram(Program):
         xt = x.tbuf
         M = x.B * x.H * x.W
         off = bn["acc"]
-        if self.bn_fused:                 # statistics + apply in one launch: emitted by bn_apply (same tensor, directly behind)
-            bn["stats_of"] = x
-            return bn
         self._add(self.lib.cp_bn_stats_accumulate, lambda P: (self.dtype, P(xt), M, C_, x.cstride, x.coff, self._acc_ptr(off)),
                   "bn_stats", [xt], [])
         return bn
@@ -279,13 +258,6 @@ class TrainProgram(Program):
         off = bn["acc"]
         a1 = (bn["gamma"].data_ptr(), bn["beta"].data_ptr(), bn["rmean"].data_ptr(), bn["rvar"].data_ptr(), bn["momentum"], bn["eps"])
         mp, rp = bn["mean"].data_ptr(), bn["rstd"].data_ptr()
-        if bn.pop("stats_of", None) is x:
-            Cc = bn["C"]
-            self._add(self.lib.cp_bn_train_fused,
-                      lambda P: (self.dtype, P(xt), x.cstride, x.coff, self._acc_ptr(off), self._ctr_ptr(off, Cc)) + a1 +
-                                (P(rt) if rt is not None else None, rcs, rco, P(ot), out.cstride, out.coff, M, x.C, act, slope, mp, rp),
-                      "bn_fused", [xt, rt], [ot])
-            return out
         self._add(self.lib.cp_bn_apply,
                   lambda P: (self.dtype, P(xt), x.cstride, x.coff, self._acc_ptr(off)) + a1 +
                             (P(rt) if rt is not None else None, rcs, rco, P(ot), out.cstride, out.coff, M, x.C, act, slope, mp, rp),
@@ -318,14 +290,6 @@ class TrainProgram(Program):
         rcs, rco = (raw.cstride, raw.coff) if raw is not None else (0, 0)
         gcs, gco = (gres.cstride, gres.coff) if gres is not None else (0, 0)
         off = self._acc_slot(C_)
-        if self.bn_fused:
-            self._add(self.lib.cp_bn_bwd_fused,
-                      lambda P: (self.dtype, P(gt), gy.cstride, gy.coff, P(yt) if yt is not None else None, ycs, yco,
-                                 P(rt) if rt is not None else None, rcs, rco, mean_p, rstd_p, gam_p, self._acc_ptr(off), self._ctr_ptr(off, C_),
-                                 M, C_, act, slope, P(gt), gy.cstride, gy.coff, P(grt) if grt is not None else None, gcs, gco, 1,
-                                 dgamma_ptr, dbeta_ptr),
-                      "bn_bwd_fused", [gt, yt, rt, grt], [gt, grt])
-            return
         self._add(self.lib.cp_bn_bwd_accumulate,
                   lambda P: (self.dtype, P(gt), gy.cstride, gy.coff, P(yt) if yt is not None else None, ycs, yco,
                              P(rt) if rt is not None else None, rcs, rco, mean_p, rstd_p, M, C_, act, slope, self._acc_ptr(off)),
@@ -350,7 +314,7 @@ class TrainProgram(Program):
     def bn_train_group(self, members):
         """members: [(raw Act, C, gamma, beta, rmean, rvar, residual Act | None, out Act, act, slope)] of independent layers ->
         [bn dict]; statistics of all of them in one launch, apply (+residual, +activation) in a second one"""
-        if len(members) == 1 or self.bn_fused or not self.bn_grouped:
+        if len(members) == 1:
             out = []
             for raw, C_, g, b, rm, rv, res, y, act, slope in members:
                 bn = self.bn_stats(raw, C_, g, b, rm, rv)
@@ -394,7 +358,7 @@ class TrainProgram(Program):
 
     def bn_bwd_group(self, members):
         """members: [(gy, y, raw, bn, act, slope, gres, dgamma_ptr, dbeta_ptr)] as bn_bwd's arguments, independent layers"""
-        if len(members) == 1 or self.bn_fused or not self.bn_grouped:
+        if len(members) == 1:
             for m in members:
                 self.bn_bwd(*m)
             return
@@ -454,31 +418,27 @@ class TrainProgram(Program):
         dt, xt = dy.tbuf, x.tbuf
         name = "wgrad:%d->%d k%d s%d %dx%d" % (Cin, Cout, R, stride, x.H, x.W)
         flops = 2 * dy.B * d.Ho * d.Wo * R * S * Cin * Cout                # algorithmic, unpadded
-        if self.wg_group and flops < self.wg_group_flops:
+        if flops < self.wg_group_flops:
             self._wgc_pending.append(dict(d=d, dref=dref, dt=dt, xt=xt, dw=dw_ptr, flops=flops, k3s1=(R == 3 and stride == 1),
                                           pix=dy.B * d.Ho * d.Wo, cc=((Cout + 63) // 64) * ((Cin + 63) // 64), taps=R * S))
             if len(self._wgc_pending) >= self.wg_group_n:
                 self.flush_wgrad_compute()
             return
-        if not self.wg_defer:
-            wsp, wsn = self.wg_ws.data_ptr(), min(self.wg_ws.numel(), 160 << 20)
-            self._add(self.lib.cp_conv2d_wgrad_ws, lambda P: (dref, P(dt), P(xt), dw_ptr, wsp, wsn), name, [dt, xt], [])
-        else:
-            need = (int(self.lib.cp_conv2d_wgrad_scratch_bytes(dref)) + 255) // 256 * 256
-            if self._wg_off + need > self.wg_ws.numel():
-                self.flush_wgrad_compute()
-                self._flush_wgrad_reduce()
-            need = min(need, self.wg_ws.numel())
-            wsp = self.wg_ws.data_ptr() + self._wg_off
-            item, spare = CpWgradReduceItem(), CpWgradReduceItem()
-            base = self.wg_ws.data_ptr()      # any aligned non-null pointer: the plan only validates dy / x, it launches nothing
-            _abi.check(self.lib.cp_conv2d_wgrad_plan(dref, base, base, dw_ptr, wsp, need, C.byref(item)), "cp_conv2d_wgrad_plan")
-            self.keep.append(spare)
-            sref = C.byref(spare)
-            self._add(self.lib.cp_conv2d_wgrad_deferred, lambda P: (dref, P(dt), P(xt), dw_ptr, wsp, need, sref), name, [dt, xt], [])
-            if item.ws:                       # this layer owes a reduction (tiny layers add with atomics instead)
-                self._wg_items.append(item)
-                self._wg_off += need
+        need = (int(self.lib.cp_conv2d_wgrad_scratch_bytes(dref)) + 255) // 256 * 256
+        if self._wg_off + need > self.wg_ws.numel():
+            self.flush_wgrad_compute()
+            self._flush_wgrad_reduce()
+        need = min(need, self.wg_ws.numel())
+        wsp = self.wg_ws.data_ptr() + self._wg_off
+        item, spare = CpWgradReduceItem(), CpWgradReduceItem()
+        base = self.wg_ws.data_ptr()      # any aligned non-null pointer: the plan only validates dy / x, it launches nothing
+        _abi.check(self.lib.cp_conv2d_wgrad_plan(dref, base, base, dw_ptr, wsp, need, C.byref(item)), "cp_conv2d_wgrad_plan")
+        self.keep.append(spare)
+        sref = C.byref(spare)
+        self._add(self.lib.cp_conv2d_wgrad_deferred, lambda P: (dref, P(dt), P(xt), dw_ptr, wsp, need, sref), name, [dt, xt], [])
+        if item.ws:                       # this layer owes a reduction (tiny layers add with atomics instead)
+            self._wg_items.append(item)
+            self._wg_off += need
         self.wgrad_flops[len(self.ops) - 1] = flops
 
     def flush_wgrad_compute(self):
@@ -578,8 +538,8 @@ class TrainProgram(Program):
             self._dgrad(key, w, x, g, R, S, stride, pad)
 
     def conv_backward_group(self, members):
-        """conv_backward of INDEPENDENT layers [(key, w, x, g, R, S, stride, pad)]: the 3x3 / stride 1 data-gradient convs go out as
-        grouped launches (engine.conv3x3_group; members that accumulate into the same input gradient in separate rounds)"""
+        """conv_backward of INDEPENDENT layers [(key, w, x, g, R, S, stride, pad)]: every weight gradient first, the 3x3 / stride 1
+        data-gradient convs behind them"""
         dg = []
         for key, w, x, g, R, S, stride, pad in members:
             Cout, Cin = w.shape[0], w.shape[1]
@@ -589,16 +549,11 @@ class TrainProgram(Program):
             if stride == 1 and R == 3 and S == 3 and pad == 1:
                 gx = self.grad_of(x)
                 wt = self.weight_dgrad(w, Cout, Cin, 3, 3)
-                dg.append((g, key + "#dgrad", wt, self.const_vec(Cin, True), self.const_vec(Cin, False), ACT_NONE, 0.0, gx, gx))
+                dg.append((g, key + "#dgrad", wt, self.const_vec(Cin, True), self.const_vec(Cin, False), gx))
             else:
                 self._dgrad(key, w, x, g, R, S, stride, pad)
-        while dg:
-            seen, now, later = set(), [], []
-            for m in dg:
-                (later if id(m[8].tbuf) in seen else now).append(m)
-                seen.add(id(m[8].tbuf))
-            self.conv3x3_group(now)
-            dg = later
+        for g, key, wt, one, zero, gx in dg:
+            self.conv(g, key, wt, one, zero, 3, 3, 1, 1, wt.shape[0], residual=gx, out=gx)
 
     def _dgrad(self, key, w, x: Act, g: Act, R, S, stride, pad):
         Cout, Cin = w.shape[0], w.shape[1]
@@ -633,7 +588,7 @@ class TrainProgram(Program):
 
     def fuse_sum_bwd_group(self, members):
         """members: [(gout, out, gsrc, shift, relu)] writing DISTINCT gradient tensors (a module's whole fuse layer): one launch"""
-        if len(members) == 1 or not self.bn_grouped:
+        if len(members) == 1:
             for m in members:
                 self.fuse_sum_bwd(*m)
             return
@@ -735,16 +690,13 @@ class TrainProgram(Program):
         before.append(nmark)
         self.pslot_done_call = {k: before[i] for k, i in self.pslot_done.items()}
         self.n_fwd_ops = sum(1 for op in self.ops[:self.n_fwd_ops] if op[0] not in markers)
-        ci, prep_calls, flops = 0, set(), {}
+        ci, flops = 0, {}
         for i, op in enumerate(self.ops):
             if op[0] in markers:
                 continue
-            if i in self.prep_idx:
-                prep_calls.add(ci)
             if i in self.wgrad_flops:
                 flops[ci] = self.wgrad_flops[i]
             ci += 1
-        self.prep_calls = prep_calls
         self.wgrad_flops = flops           # re-keyed by launch (call) index, like everything bench_train reads
         return self
 
@@ -786,98 +738,6 @@ class TrainProgram(Program):
         raw = a.tbuf.fixed if a.tbuf.fixed is not None else self.workspace[a.tbuf.offset:a.tbuf.offset + a.tbuf.nbytes]
         flat = raw[:n * es].view(dt).view(a.B, a.H, a.W, a.cstride)
         return flat[..., a.coff:a.coff + a.C].float().cpu()
-
-    def run_lanes_range(self, streams, lo, hi):
-        """launches [lo, hi) with the fork/join structure of the schedule (streams[0] being captured into a hipGraph)"""
-        ptr = [st.cuda_stream for st in streams]
-        active, events = 1, []
-
-        def new_event():
-            events.append(torch.cuda.Event())
-            return events[-1]
-
-        ci = 0
-        for item in self.sched:
-            kind = item[0]
-            if kind == "op":
-                if lo <= ci < hi:
-                    fn, args, name = self.calls[item[1]]
-                    rc = fn(ptr[item[2] if item[2] < len(ptr) else 0], *args[1:])
-                    if rc != 0:
-                        _abi.check(rc, name)
-                ci += 1
-                continue
-            if not (lo <= ci < hi or (kind == "join" and ci == hi)):     # the join that closes the range's last region
-                continue
-            if kind == "fork":
-                active = min(item[1], len(streams))
-                ev = new_event()
-                ev.record(streams[0])
-                for k in range(1, active):
-                    streams[k].wait_event(ev)
-            elif kind == "sync":
-                if item[1] < len(streams) and item[2] < len(streams):
-                    ev = new_event()
-                    ev.record(streams[item[1]])
-                    streams[item[2]].wait_event(ev)
-            elif kind in ("mark", "wait"):
-                raise RuntimeError("mark/wait lane edges are not emitted in training programs")
-            else:
-                for k in range(1, active):
-                    ev = new_event()
-                    ev.record(streams[k])
-                    streams[0].wait_event(ev)
-                active = 1
-        return events
-
-    def run_prep_range(self, main, side, lo, hi, chunk=48):
-        """launches [lo, hi) with the weight-preparation ops on `side`, chunks ahead of the compute ops on `main` (both
-        torch.cuda.Stream; `main` is being captured).  Compute op j waits (one event per chunk) for every prep op < j."""
-        prep = [i for i in range(lo, hi) if i in self.prep_calls]
-        events = []
-        ev0 = torch.cuda.Event()
-        ev0.record(main)
-        side.wait_event(ev0)
-        events.append(ev0)
-        launched, waited = 0, 0               # prep ops launched on `side` / covered by a wait on `main`
-        chunk_ev = []                         # (number of prep ops covered, event)
-
-        def launch_chunk():
-            nonlocal launched
-            end = min(launched + chunk, len(prep))
-            for k in range(launched, end):
-                fn, args, name = self.calls[prep[k]]
-                rc = fn(side.cuda_stream, *args[1:])
-                if rc != 0:
-                    _abi.check(rc, name)
-            launched = end
-            ev = torch.cuda.Event()
-            ev.record(side)
-            chunk_ev.append((end, ev))
-            events.append(ev)
-
-        need = 0
-        for i in range(lo, hi):
-            if i in self.prep_calls:
-                need += 1
-                continue
-            while launched < min(len(prep), need + chunk):      # keep the side stream at least one chunk ahead
-                launch_chunk()
-            if waited < need:
-                for covered, ev in chunk_ev:
-                    if covered >= need:
-                        main.wait_event(ev)
-                        waited = covered
-                        break
-            fn, args, name = self.calls[i]
-            rc = fn(main.cuda_stream, *args[1:])
-            if rc != 0:
-                _abi.check(rc, name)
-        while launched < len(prep):
-            launch_chunk()
-        if chunk_ev:                          # join: the capture must end with every forked stream merged back
-            main.wait_event(chunk_ev[-1][1])
-        return events
 
     def run_range(self, stream_ptr, lo, hi):
         for fn, args, name in self.calls[lo:hi]:

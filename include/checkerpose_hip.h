@@ -149,12 +149,6 @@ int cp_pack_conv3x3_halo_weight(cp_stream_t stream, int dtype, const float* w, i
                                 void* packed);
 int cp_conv3x3_halo(cp_stream_t stream, const CpConvDesc* d, const void* in, const void* packed_w,
                     const float* scale, const float* shift, const void* residual, void* out);
-/* Grouped form for small layers: up to 16 INDEPENDENT 3x3 / stride 1 / pad 1 convs with <= 80 physical output channels on maps of at
- * least 8 x 16 pixels (the branches of an HRNet module at equal depth -- timm HighResolutionModule.forward runs them one after the
- * other; at the training batch each is a ~9 us launch) in ONE launch.  cp_conv3x3_halo_item: cp_conv3x3_halo's arguments, checked
- * and packed on the host (weights packed as for cp_conv3x3_halo); cp_conv3x3_halo_group: items in device memory, prefix = exclusive
- * prefix sum (n_items + 1) of item.blocks, lds_bytes = the largest item.lds_bytes.  Results are bit-identical to the single launches.
- * A residual may alias the output (in-place accumulation) but no two items may write the same tensor. */
 /* k = 2 / stride 1 / pad 1 conv with <= 80 output channels off the same LDS-staged halo tile (Index2Feat_module.patch_generator,
  * pipeline.py:144-145,156, where it runs over the whole map: N = 4096 keypoints, the low-resolution stages at N = 512): descriptor as
  * cp_conv2d_igemm with R = S = 2, stride 1, pad 1, Ho = H + 1, Wo = W + 1, o_sc = 1; weights by cp_pack_conv2x2_halo_weight from the
@@ -164,16 +158,6 @@ size_t cp_packed_conv2x2_halo_weight_bytes(int dtype, int Cout, int Cin_phys);
 int cp_pack_conv2x2_halo_weight(cp_stream_t stream, int dtype, const float* w, int Cout, int Cin, int cin_phys, void* packed);
 int cp_conv2x2_halo(cp_stream_t stream, const CpConvDesc* d, const void* in, const void* packed_w, const float* scale,
                     const float* shift, const void* residual, void* out);
-
-typedef struct CpConvGroupItem {
-  int32_t NT; uint32_t blocks, lds_bytes, pad;
-  unsigned long long params[25];       /* opaque: the kernel's parameter block */
-} CpConvGroupItem;
-int cp_conv3x3_halo_group_supported(int dtype, int H, int W, int Cout_phys);
-int cp_conv3x3_halo_item(const CpConvDesc* d, const void* in, const void* packed_w, const float* scale, const float* shift,
-                         const void* residual, void* out, CpConvGroupItem* item);
-int cp_conv3x3_halo_group(cp_stream_t stream, int dtype, const CpConvGroupItem* items_dev, const uint32_t* prefix_dev, int n_items,
-                          uint32_t total_blocks, uint32_t lds_bytes);
 
 /* conv3x3( UpsamplingBilinear2d(scale_factor=2)(in) ) without the upsampled tensor: the decoder's `up_net[1..2]` upsample + first
  * conv (pipeline.py:199-200, get_gdrn_upsample_module).  Descriptor as cp_conv3x3_halo, except that d->H, d->W (= Ho, Wo, both
@@ -737,17 +721,6 @@ int cp_bn_bwd_apply(cp_stream_t stream, int dtype, const void* dy, int dy_cstrid
                     int y_coff, const void* x, int x_cstride, int x_coff, const float* mean, const float* rstd,
                     const float* gamma, const double* acc, int M, int C, int act, float slope, void* dx, int dx_cstride,
                     int dx_coff, void* dres, int dres_cstride, int dres_coff, int dres_accumulate, float* dgamma, float* dbeta);
-/* The same two passes in ONE launch each (round 3): statistics over a block's rows -> grid barrier -> apply to the same rows.
- * `counter`: 4 zeroed bytes per call (zero them with the accumulators).  The grid (<= 512 blocks) is always co-resident on an
- * MI355X; the barrier's spin is bounded.  Arguments as cp_bn_stats_accumulate + cp_bn_apply / cp_bn_bwd_accumulate + cp_bn_bwd_apply. */
-int cp_bn_train_fused(cp_stream_t stream, int dtype, const void* x, int x_cstride, int x_coff, double* acc, uint32_t* counter,
-                      const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum, float eps,
-                      const void* res, int res_cstride, int res_coff, void* y, int y_cstride, int y_coff, int M, int C, int act,
-                      float slope, float* mean, float* rstd);
-int cp_bn_bwd_fused(cp_stream_t stream, int dtype, const void* dy, int dy_cstride, int dy_coff, const void* y, int y_cstride,
-                    int y_coff, const void* x, int x_cstride, int x_coff, const float* mean, const float* rstd, const float* gamma,
-                    double* acc, uint32_t* counter, int M, int C, int act, float slope, void* dx, int dx_cstride, int dx_coff,
-                    void* dres, int dres_cstride, int dres_coff, int dres_accumulate, float* dgamma, float* dbeta);
 
 /* Grouped BatchNorm passes: the same pass (statistics / apply / backward sums / backward apply) of up to CP_BN_GROUP_MAX
  * INDEPENDENT layers in ONE launch -- the branches of an HRNet module at equal depth (timm HighResolutionModule.forward runs
@@ -884,10 +857,6 @@ int cp_crop_resize_u8(cp_stream_t stream, const uint8_t* images, int n_img, int 
  * ------------------------------------------------------------------------------------------- */
 int cp_graph_begin_capture(cp_stream_t stream);
 int cp_graph_end_capture(cp_stream_t stream, void** graph_exec_out);
-/* Dataflow capture on ONE stream: name the graph nodes the next launch depends on (n = 0: none, a root of the graph), and
- * read back the node(s) the stream's next launch would wait for (after a launch: that launch's last kernel node). */
-int cp_graph_capture_set_deps(cp_stream_t stream, void* const* nodes, int n);
-int cp_graph_capture_tail(cp_stream_t stream, void** nodes_out, int cap, int* n_out);
 int cp_graph_launch(void* graph_exec, cp_stream_t stream);
 int cp_graph_destroy(void* graph_exec);
 
