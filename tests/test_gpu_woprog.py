@@ -12,6 +12,7 @@ from checkerpose_amd import _abi
 from checkerpose_amd._abi import CP_BF16, CP_F16
 from oracle import checkerpose_oracle as O
 from tests.common import det_image, det_tensor, golden, inject_feats
+from tests.free_running import assert_ids_match_own_logits
 from checkerpose_amd.synthetic import build_woprog
 from tests.test_woprog import code_band_ok, woprog_oracle
 
@@ -40,7 +41,9 @@ def _gemm_pack(lib, dtype, w, co, ci):
 
 def _cmp(out, ref, tol, band=2e-4, min_frac=0.99):
     """logits / seg within tol x the block's scale; ids equal wherever every bit of the code clears `band` on the reference side,
-    and that covers at least min_frac of the keypoints (no vacuous pass)"""
+    and that covers at least min_frac of the keypoints (no vacuous pass); at EVERY keypoint, band or not, the returned ids are the
+    oracle's code decode of the run's own logits"""
+    assert_ids_match_own_logits(out, init_bits=out[1].shape[1])
     for a, b, k in zip(out[:4], ref[:4], ("roi", "xb", "yb", "seg")):
         b = torch.as_tensor(np.asarray(b)) if not torch.is_tensor(b) else b
         a = a.float().cpu()
