@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("CHECKERPOSE_AMD_LIB") or os.path.join(_HERE, "libchec
 CP_F32, CP_BF16, CP_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 LOSS_BCE, LOSS_L1 = 0, 1
+POSE_ERR_ADD, POSE_ERR_ADI = 1, 2
 
 
 class CpConvDesc(C.Structure):
@@ -193,6 +194,8 @@ SIGNATURES = {
     "cp_correspondences_bbox": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I]),
     "cp_pnp_ransac_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_pnp_ransac": (_I, [_P, _P, _L, _P, _P, _I, _P, _L, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P]),
+    "cp_pose_errors_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_pose_errors": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
     "cp_edgeconv_bwd_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_edgeconv_gather_max_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F]),
     "cp_index2feat_gather_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),

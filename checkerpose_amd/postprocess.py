@@ -110,6 +110,19 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
     return R, t, inl, status, final
 
 
+def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add", "adi"), **estimate_kwargs):
+    """estimate_poses followed by metric.pose_errors against the given ground-truth poses: test.py's loop body from the detection
+    boxes to the ADD / ADD-S errors (:198-427) with only the errors leaving the GPU.
+      R_gt (B,3,3), t_gt (B,3,1) / (B,3): tensors or host arrays; vertices: a (V,3) array, a list with mesh_ids, or a metric.MeshSet
+      (units of p3d_xyz); estimate_kwargs go to estimate_poses.  Crops whose solver fell back to the identity pose (status 0) are
+      scored with it, as the reference scores them (from_id_to_pose returns R = I, t = 0 and test.py goes on).
+    -> (errors: dict kind -> (B,) f64 CUDA tensor, R, t, inliers, status, final boxes)"""
+    from . import metric
+    R, t, inl, status, final = estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, **estimate_kwargs)
+    errors = metric.pose_errors(R, t, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=kinds)
+    return errors, R, t, inl, status, final
+
+
 def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_y_id, check_seg=False, seg_mask=None,
                     use_progressivex=False, neighborhood_ball_radius=20, spatial_coherence_weight=0.1, prog_max_iters=400,
                     discard_bd_pixel=0, return_inliers=False, reprojErr_thresh=2, cv_max_iters=150, device="cuda:0", seed=0):

@@ -537,6 +537,27 @@ int cp_pnp_ransac(cp_stream_t stream, const float* p3d, long long p3d_bstride, c
                   int valid_stride, const float* cam_K, long long K_bstride, int B, int N, float reproj_threshold,
                   int iterations, uint32_t seed, double* pose, uint8_t* inliers, int32_t* status, void* scratch);
 
+/* Pose errors on the device (next-row N5; reference metric.py:8-18 -> bop_toolkit_lib/pose_error.py:147-184, called once per image
+ * by test.py:378-427 / test_lm.py:300-321): ADD = mean_i |P_est(p_i) - P_gt(p_i)| and ADD-S / ADI = mean_i min_j |P_gt(p_i) - P_est(p_j)|
+ * over an object's mesh vertices, for B poses at once.
+ *   pose_est, pose_gt fp64 (B,12) = [R row-major | t], the layout cp_pnp_ransac writes;
+ *   verts fp32 (sumV,3): the vertices of M meshes packed one after the other (16-byte aligned base), offsets int32 (M+1) with mesh m
+ *   at rows [offsets[m], offsets[m+1]); mesh_id int32 (B) names each pose's mesh (NULL = mesh 0 for all).  offsets NULL = ONE mesh
+ *   of Vmax vertices (M is ignored; mesh_id must be NULL too).  Vmax >= the largest mesh a pose refers to.
+ *   kinds: CP_POSE_ERR_ADD | CP_POSE_ERR_ADI, at least one; add / adi fp64 (B) are written for the kinds asked (the other may be NULL).
+ * Arithmetic: the relative pose Rr = I + R_est^T (R_gt - R_est) (= R_est^T R_gt for an orthonormal R_est, exactly I for equal poses),
+ * tr = R_est^T (t_gt - t_est) in fp64, then fp32 in the model frame: q_i = Rr p_i + tr, ADD = mean |q_i - p_i|, ADI = mean min_j
+ * |q_i - p_j| with direct-difference distances (no |q|^2 + |p|^2 - 2 q.p expansion), one square root per query, means summed in
+ * fp64 in a fixed order that depends on the mesh alone: results are bit-identical from call to call and do not depend on B.
+ * Error against the fp64 definition: a few fp32 roundings of (largest vertex norm + |tr| + error).  ADI costs V^2 distance
+ * evaluations per pose (all pairs, no spatial index).  A pose whose mesh id lies outside [0, M) or whose mesh is empty or larger
+ * than Vmax, or whose relative pose is not finite, gets NaN in both errors.  CP_ERR_RANGE: more than 2^24 - 1 workgroups (about
+ * B * ceil(Vmax / 1024) of them) -- split the batch.  scratch: cp_pose_errors_scratch_bytes(B, Vmax) bytes, 16-byte aligned (needed for ADI only). */
+enum { CP_POSE_ERR_ADD = 1, CP_POSE_ERR_ADI = 2 };
+size_t cp_pose_errors_scratch_bytes(int B, int Vmax);
+int cp_pose_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const float* verts, const int32_t* offsets,
+                   int M, const int32_t* mesh_id, int B, int Vmax, int kinds, double* add, double* adi, void* scratch);
+
 /* ---------------------------------------------------------------------------------------------
  * Training side: backward of the fused graph ops + the loss head of train.py:307-320.
  * Gradients are fp32; `pq` is the forward's saved GEMM output in `dtype`.
