@@ -558,6 +558,44 @@ size_t cp_pose_errors_scratch_bytes(int B, int Vmax);
 int cp_pose_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const float* verts, const int32_t* offsets,
                    int M, const int32_t* mesh_id, int B, int Vmax, int kinds, double* add, double* adi, void* scratch);
 
+/* Ground-truth side on the device (next-row N6; csrc/targets.hip).
+ *
+ * cp_encode_targets: the labels of the reference's data loader (bop_dataset_pytorch.py:293,356-380: project the N keypoints through
+ * K [R|t], discretise against the crop's FINAL box, MSB-first codes; lm_dataset_pytorch.py:393,438-462 with a per-sample object) for B
+ * crops in one launch.
+ *   p3d fp64, original units: (N,3) shared (p3d_bstride 0), (B,N,3) (p3d_bstride 3 N), or -- with obj_ids int32 (B), 1-based, device --
+ *   the object table (n_obj,N,3); cam_K fp64 3x3 row-major (K_bstride 0 shared | 9); R fp64 (B,9) row-major, t fp64 (B,3);
+ *   boxes int32 (B,4) x, y, w, h on the device = get_final_Bbox's result, S = crop_size_gt, a power of two in 8 .. 256 (bits = log2 S).
+ *   boxes_host: the same (B,4) values in HOST memory, no_detection_host: uint8 (B) in host memory or NULL -- read before the launch:
+ *   a flagged crop must carry the loader's dummy box (w = h = 0, :328-338) and gets all-zero labels; any other box needs w > 0 and
+ *   h > 0 (CP_ERR_INVALID otherwise, nothing is launched).
+ * Outputs (device): roi_mask_bit f32 (B,1,N); pixel_x_code, pixel_y_code f32 (B,bits,N) in {0,1}, MSB first; x_id, y_id int32 (B,N),
+ * the ids after the clip to [0, S-1]; optional (NULL to skip) proj_xy fp64 (B,N,2) and depth fp64 (B,N).
+ * Arithmetic: fp64 in the reference's order, compiled without floating-point contraction; u = x / z, id = trunc((u - bx) / (bw / S)),
+ * out of the RoI = u < bx or v < by or id >= S.  The conversion saturates at the int32 range (numpy's astype(int) is undefined there);
+ * a NaN quotient is out of the RoI with id 0. */
+int cp_encode_targets(cp_stream_t stream, const double* p3d, long long p3d_bstride, const int32_t* obj_ids, int n_obj,
+                      const double* cam_K, long long K_bstride, const double* R, const double* t, const int32_t* boxes,
+                      const int32_t* boxes_host, const uint8_t* no_detection_host, int B, int N, int S, float* roi_mask_bit,
+                      float* pixel_x_code, float* pixel_y_code, int32_t* x_id, int32_t* y_id, double* proj_xy, double* depth);
+
+/* cp_code_report: the code / mask figures test.py prints beside ADD (:432-457), one workgroup per crop.
+ *   pred_roi f32 (B,1,N), pred_x / pred_y f32 (B,nb,N) LOGITS (rows N apart, `*_bstride` elements between crops: slices of the
+ *   network's logit block work as they are), nb <= bits (a truncated `stage`); seg f32 (B,2,H,W) logits [visible | full];
+ *   gt_roi (B,1,N), gt_x / gt_y (B,bits,N): cp_encode_targets' labels, the first nb code rows are compared;
+ *   mask_visib / mask_full (B,S,S): uint8 (non-zero = set) or, with mask_f32 = 1, f32 (> 0.5 = set), read at the positions
+ *   F.interpolate(mode="nearest") takes for an (H,W) output (test.py:320-323).  Decisions are logit > 0.
+ * counts int32 (B, 10 + 2 nb): n_in_roi, roi-bit mismatches, sum |x id difference| and sum |y id difference| inside the RoI (ids of
+ *   the nb leading bits), visible mask: mismatching pixels, intersection, union, full mask: the same three, then the nb per-bit x
+ *   mismatches and the nb per-bit y mismatches inside the RoI.
+ * figures fp64 (B, 8 + 2 nb), formed from the counts as test.py does (npoint_in_roi clipped to >= 1; IoU = 1 for an empty union):
+ *   roi_bit_acc, reproj_x_acc, reproj_y_acc, visib_pixel_acc, visib_iou, full_pixel_acc, full_iou, bit_err_arr[0 .. 2 nb].
+ * Integer sums only (wave reductions + LDS, no atomics): bit-identical from call to call, independent of B. */
+int cp_code_report(cp_stream_t stream, const float* pred_roi, long long roi_bstride, const float* pred_x, long long x_bstride,
+                   const float* pred_y, long long y_bstride, int nb, const float* seg, int H, int W, const float* gt_roi,
+                   const float* gt_x, const float* gt_y, int bits, const void* mask_visib, const void* mask_full, int mask_f32, int S,
+                   int B, int N, int32_t* counts, double* figures);
+
 /* ---------------------------------------------------------------------------------------------
  * Training side: backward of the fused graph ops + the loss head of train.py:307-320.
  * Gradients are fp32; `pq` is the forward's saved GEMM output in `dtype`.
