@@ -54,22 +54,25 @@ def correspondences(outputs, roi_xy_ori=None, discard_bd_pixel=0, Bboxes=None):
 PNP_MAX_ITERS = 256        # csrc/pnp.hip: 4 rounds of 64 hypotheses
 
 
-def solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=0, reproj_threshold=2.0, iterations=150, seed=0):
+def solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=0, reproj_threshold=2.0, iterations=150, seed=0, return_hypotheses=False):
     """On-device twin of from_id_to_pose's cv2 branch (test_network_with_test_data.py:100-114; defaults reprojErr_thresh=2,
     cv_max_iters=150): EPnP + RANSAC over the correspondences of `correspondences()`.
       p3d_xyz (N,3) or (B,N,3) model keypoints in original units; p2d (B,N,2), valid (B,N,3) from correspondences();
       column 0 = all RoI keypoints | 1 = also inside the full mask | 2 = inside the visible mask (check_seg variants);
       cam_K (3,3) or (B,3,3).
-    Returns (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32: 0 = the reference's identity fallback)."""
-    if not (p2d.is_cuda and valid.is_cuda):
-        raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+    Returns (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32: 0 = the reference's identity fallback).
+    return_hypotheses=True adds a fifth value, the solver's hypothesis records as a (B, iterations, 14) f64 tensor
+    ([inlier count or -1, unused, R row-major, t]; include/checkerpose_hip.h), NaN where the solver wrote nothing: what
+    tests/pnp_stages.py replays.  It costs one fill of the scratch; the default path is unchanged."""
     if not 0 < int(iterations) <= PNP_MAX_ITERS:        # no silent clamp: cv2 would run them all
         raise ValueError("iterations (cv_max_iters) must be in 1..%d for cp_pnp_ransac, got %r" % (PNP_MAX_ITERS, iterations))
-    lib = _abi.load()
-    dev = p2d.device
     B, N, _ = p2d.shape
     if tuple(valid.shape) != (B, N, 3) or valid.dtype != torch.uint8 or not 0 <= column < 3:
         raise ValueError("valid must be the (B,N,3) uint8 tensor of correspondences(), column in 0..2")
+    if not (p2d.is_cuda and valid.is_cuda):
+        raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+    lib = _abi.load()
+    dev = p2d.device
     p3 = torch.as_tensor(p3d_xyz, dtype=torch.float32, device=dev).contiguous()
     K = torch.as_tensor(cam_K, dtype=torch.float32, device=dev).contiguous()
     if p3.shape[-2:] != (N, 3) or K.shape[-2:] != (3, 3):
@@ -79,12 +82,20 @@ def solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=0, reproj_threshold=2.0,
     pose = torch.empty(B, 12, dtype=torch.float64, device=dev)
     inl = torch.empty(B, N, dtype=torch.uint8, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
-    scratch = torch.empty(lib.cp_pnp_ransac_scratch_bytes(B, N), dtype=torch.uint8, device=dev)
+    nbytes = lib.cp_pnp_ransac_scratch_bytes(B, N)
+    if return_hypotheses:
+        hyp = torch.full((nbytes // 8,), float("nan"), dtype=torch.float64, device=dev)
+        scratch = hyp.view(torch.uint8)
+    else:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     st = torch.cuda.current_stream(dev).cuda_stream
     _abi.check(lib.cp_pnp_ransac(st, p3.data_ptr(), 3 * N if p3.dim() == 3 else 0, p2.data_ptr(), va.data_ptr() + column, 3, K.data_ptr(),
                                  9 if K.dim() == 3 else 0, B, N, float(reproj_threshold), int(iterations), int(seed) & 0xFFFFFFFF,
                                  pose.data_ptr(), inl.data_ptr(), status.data_ptr(), scratch.data_ptr()), "cp_pnp_ransac")
-    return pose[:, :9].view(B, 3, 3), pose[:, 9:].view(B, 3, 1), inl.bool(), status
+    out = (pose[:, :9].view(B, 3, 3), pose[:, 9:].view(B, 3, 1), inl.bool(), status)
+    if return_hypotheses:
+        out += (hyp[:B * int(iterations) * 14].view(B, int(iterations), 14),)
+    return out
 
 
 def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,

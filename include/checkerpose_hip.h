@@ -530,7 +530,14 @@ int cp_correspondences_bbox(cp_stream_t stream, const float* bits, const float* 
  *   inliers (>= the sample size; first on ties), final EPnP over its inliers.  Exactly 4 valid correspondences: no RANSAC, as in
  *   OpenCV (model_points == npoints) -- P3P on the first three, the fourth picks among the up-to-four poses, all four are inliers.
  * Outputs: pose fp64 (B,12) = [R row-major | t], inliers uint8 (B,N), status int32 (B): 1 = solved, 0 = identity fallback.
- * scratch: cp_pnp_ransac_scratch_bytes(B, N).  opencv-python is not part of the reference's tree: the algorithm is restated from
+ * scratch: cp_pnp_ransac_scratch_bytes(B, N) bytes, 8-byte aligned.  What the call leaves in it is part of the interface (the tests
+ *   replay the solver's decisions from it): one record of 14 doubles per hypothesis h of crop b at (b * iterations + h) * 14 --
+ *   [0] the inlier count of the hypothesis' pose among the valid correspondences, or -1 when its sample gave no pose (degenerate);
+ *   [1] unused, never written; [2..10] R row-major and [11..13] t, written only when [0] >= 0.  Hypotheses run in rounds of 64;
+ *   the records of a round that OpenCV's stopping rule (RANSACUpdateNumIters, confidence 0.99, on the best count of the earlier
+ *   rounds) cuts off are not written, nor is any record of a crop with fewer than 5 valid correspondences; bytes behind
+ *   B * iterations records are never touched.  A caller that wants to tell written records apart fills the scratch first.
+ * opencv-python is not part of the reference's tree: the algorithm is restated from
  * the publication / OpenCV's structure (oracle/pnp_oracle.py lists the deliberate differences); parity with cv2 is UNPINNED. */
 size_t cp_pnp_ransac_scratch_bytes(int B, int N);
 int cp_pnp_ransac(cp_stream_t stream, const float* p3d, long long p3d_bstride, const float* p2d, const uint8_t* valid,

@@ -59,8 +59,13 @@ def _solve_normal(A, b):
     return np.linalg.solve(A.T @ A, A.T @ b)
 
 
-def epnp(pw, uv, K):
-    """pw (n,3) model points, uv (n,2) pixels, K (3,3).  Returns (R (3,3), t (3,), mean reprojection error)."""
+def epnp(pw, uv, K, eig=None, axis_signs=(1.0, 1.0, 1.0)):
+    """pw (n,3) model points, uv (n,2) pixels, K (3,3).  Returns (R (3,3), t (3,), mean reprojection error).
+    eig: the symmetric eigen-solver applied to M^T M (-> ascending eigenvalues, eigenvectors in columns); None = LAPACK's
+    (np.linalg.eigh).  tests/pnp_stages.py passes a restatement of the device's cyclic Jacobi to measure what the choice moves.
+    axis_signs: the orientation of the three PCA axes the control points are put on.  An eigenvector's sign is the eigen-solver's
+    free choice, and under noise EPnP is NOT invariant to it (the unit-norm constraint on the 12-vector of control points is a
+    different one in each of the 8 frames): the result is unique only up to this choice."""
     pw, uv = np.asarray(pw, np.float64), np.asarray(uv, np.float64)
     n = pw.shape[0]
     fu, fv, uc, vc = K[0, 0], K[1, 1], K[0, 2], K[1, 2]
@@ -69,7 +74,7 @@ def epnp(pw, uv, K):
     P0 = pw - cw[0]
     ev, evec = np.linalg.eigh(P0.T @ P0)                       # ascending
     for i in range(3):
-        cw[i + 1] = cw[0] + np.sqrt(max(ev[2 - i], 0.0) / n) * evec[:, 2 - i]
+        cw[i + 1] = cw[0] + axis_signs[i] * np.sqrt(max(ev[2 - i], 0.0) / n) * evec[:, 2 - i]
     CC = (cw[1:] - cw[0]).T                                   # columns = control-point axes
     a123 = np.linalg.solve(CC, (pw - cw[0]).T).T              # (n,3)
     alphas = np.concatenate([1.0 - a123.sum(1, keepdims=True), a123], 1)      # (n,4)
@@ -79,7 +84,7 @@ def epnp(pw, uv, K):
         M[0::2, 3 * j + 2] = alphas[:, j] * (uc - uv[:, 0])
         M[1::2, 3 * j + 1] = alphas[:, j] * fv
         M[1::2, 3 * j + 2] = alphas[:, j] * (vc - uv[:, 1])
-    w, V = np.linalg.eigh(M.T @ M)                            # ascending: columns 0..3 = the null-space basis v1..v4
+    w, V = (eig or np.linalg.eigh)(M.T @ M)                            # ascending: columns 0..3 = the null-space basis v1..v4
     v = [V[:, i] for i in range(4)]
     L = np.zeros((6, 10))
     for r, (a, b) in enumerate(PAIRS):
@@ -248,9 +253,43 @@ def solve_four_points(pw4, uv4, K):
     return None if best is None else (best[1], best[2])
 
 
-def solve_pnp_ransac(p3d, p2d, valid, K, threshold=2.0, iterations=150, seed=0, crop=0):
+HYP_DOUBLES = 14            # one hypothesis record as cp_pnp_ransac leaves it in its scratch: [count, unused, R row-major (9), t (3)]
+
+
+def hypothesis_records(p3d, p2d, valid, K, threshold=2.0, iterations=150, seed=0, crop=0):
+    """The RANSAC loop of solve_pnp_ransac in the device's record layout: (iterations, 14) float64, NaN wherever the device writes
+    nothing -- the whole array below 5 valid points, the records of the rounds the stopping rule cuts off, the pose (and the unused
+    second word) of a hypothesis whose sample is degenerate (count -1)."""
+    p3d, p2d = np.asarray(p3d, np.float64), np.asarray(p2d, np.float64)
+    vid = np.nonzero(np.asarray(valid))[0]
+    nv, m = len(vid), 5
+    rec = np.full((iterations, HYP_DOUBLES), np.nan)
+    if nv < m:
+        return rec
+    best = -1
+    for h in range(iterations):
+        if h > 0 and h % 64 == 0 and h >= needed_iterations(best, nv, m, iterations):
+            break                                              # OpenCV's stopping rule, applied between rounds of 64 hypotheses
+        rec[h, 0] = -1
+        s = vid[sample_indices(seed, crop, h, nv, m)]
+        try:
+            R, t, err = epnp(p3d[s], p2d[s], K)
+        except np.linalg.LinAlgError:                          # coplanar / collinear sample: no barycentric frame
+            continue
+        if not np.isfinite(err):
+            continue
+        with np.errstate(all="ignore"):
+            d2 = ((project(p3d[vid], K, R, t) - p2d[vid]) ** 2).sum(1)
+        rec[h, 0] = int((d2 <= threshold * threshold).sum())
+        rec[h, 2:11], rec[h, 11:14] = R.reshape(9), t
+        best = max(best, int(rec[h, 0]))
+    return rec
+
+
+def solve_pnp_ransac(p3d, p2d, valid, K, threshold=2.0, iterations=150, seed=0, crop=0, records=None):
     """p3d (N,3), p2d (N,2), valid (N,) bool, K (3,3).  Returns (R, t, inlier mask (N,) bool, status): status 0 = the
-    reference's identity fallback (fewer than 4 valid points, or no hypothesis with a full sample of inliers)."""
+    reference's identity fallback (fewer than 4 valid points, or no hypothesis with a full sample of inliers).
+    records: hypothesis_records(...) of the same arguments, where the caller already holds them."""
     p3d, p2d = np.asarray(p3d, np.float64), np.asarray(p2d, np.float64)
     vid = np.nonzero(np.asarray(valid))[0]
     nv = len(vid)
@@ -264,28 +303,14 @@ def solve_pnp_ransac(p3d, p2d, valid, K, threshold=2.0, iterations=150, seed=0, 
         mask = np.zeros(len(p3d), bool)
         mask[vid] = True
         return rt[0], rt[1], mask, 1
-    m = 5
-    best_cnt, best_mask = m - 1, None
-    counts = []
-    for h in range(iterations):
-        if h > 0 and h % 64 == 0 and h >= needed_iterations(max(counts), nv, m, iterations):
-            break                                              # OpenCV's stopping rule, applied between rounds of 64 hypotheses
-        counts.append(-1)
-        s = vid[sample_indices(seed, crop, h, nv, m)]
-        try:
-            R, t, err = epnp(p3d[s], p2d[s], K)
-        except np.linalg.LinAlgError:                          # coplanar / collinear sample: no barycentric frame
-            continue
-        if not np.isfinite(err):
-            continue
-        d2 = ((project(p3d[vid], K, R, t) - p2d[vid]) ** 2).sum(1)
-        inl = d2 <= threshold * threshold
-        counts[-1] = int(inl.sum())
-        if inl.sum() > best_cnt:
-            best_cnt, best_mask = int(inl.sum()), inl
-    if best_mask is None:
+    rec = hypothesis_records(p3d, p2d, valid, K, threshold, iterations, seed, crop) if records is None else records
+    counts = np.where(np.isnan(rec[:, 0]), -1, rec[:, 0])
+    win = int(np.argmax(counts))                               # the most inliers, the first one on ties
+    if counts[win] < 5:                                        # ... and at least a full sample
         return ident
-    sel = vid[best_mask]
+    with np.errstate(all="ignore"):
+        d2 = ((project(p3d[vid], K, rec[win, 2:11].reshape(3, 3), rec[win, 11:14]) - p2d[vid]) ** 2).sum(1)
+    sel = vid[d2 <= threshold * threshold]
     R, t, _ = epnp(p3d[sel], p2d[sel], K)
     mask = np.zeros(len(p3d), bool)
     mask[sel] = True

@@ -52,6 +52,45 @@ def test_argument_validation_returns_before_launch(lib):
         _abi.check(-1, "x")
 
 
+def test_pnp_ransac_argument_checks_return_before_any_launch(lib):
+    """cp_pnp_ransac: every refusal below returns its code from the host-side checks (no device is needed to reach them, and
+    cp_kernel_log stays empty); the Python wrapper refuses what it can see itself with ValueError, before it asks for a device"""
+    one, N = C.c_void_p(64), 512
+
+    def call(**kw):
+        a = dict(p3d=one, p3d_bs=0, p2d=one, valid=one, vs=3, K=one, K_bs=0, B=2, N=N, thr=2.0, it=150, pose=one, inl=one, status=one,
+                 scratch=one)
+        a.update(kw)
+        lib.cp_kernel_log_begin()
+        rc = lib.cp_pnp_ransac(None, a["p3d"], a["p3d_bs"], a["p2d"], a["valid"], a["vs"], a["K"], a["K_bs"], a["B"], a["N"], a["thr"],
+                               a["it"], 1, a["pose"], a["inl"], a["status"], a["scratch"])
+        assert lib.cp_kernel_log() == b"", kw
+        return rc
+    assert call(N=4097) == -1 and call(N=0) == -1 and call(B=0) == -1 and call(vs=0) == -1
+    assert call(it=0) == -1 and call(it=257) == -1 and call(it=-5) == -1
+    assert call(thr=0.0) == -1 and call(thr=-2.0) == -1 and call(thr=float("nan")) == -1
+    for bs in (1, 3, N, 3 * N - 1, -3 * N):
+        assert call(p3d_bs=bs) == -1, bs
+    for bs in range(1, 9):
+        assert call(K_bs=bs) == -1, bs
+    assert call(K_bs=-9) == -1
+    for name in ("p3d", "p2d", "valid", "K", "pose", "inl", "status", "scratch"):
+        assert call(**{name: None}) == -1, name
+    assert call(pose=C.c_void_p(68)) == -3 and call(scratch=C.c_void_p(65)) == -3 and call(status=C.c_void_p(66)) == -3      # CP_ERR_ALIGN
+    assert lib.cp_pnp_ransac_scratch_bytes(3, 512) == 3 * 256 * 14 * 8
+
+    from checkerpose_amd.postprocess import solve_pnp_ransac
+    p3, p2, va, K = torch.zeros(8, 3), torch.zeros(2, 8, 2), torch.ones(2, 8, 3, dtype=torch.uint8), torch.eye(3)
+    for bad in (dict(iterations=0), dict(iterations=257), dict(iterations=-1), dict(column=3), dict(column=-1)):
+        with pytest.raises(ValueError):
+            solve_pnp_ransac(p3, p2, va, K, **bad)
+    for bad_valid in (va[:, :, :2], va[:, :7], va[:1], va.float(), va.bool()):
+        with pytest.raises(ValueError):
+            solve_pnp_ransac(p3, p2, bad_valid, K)
+    with pytest.raises(RuntimeError, match="no CPU fallback"):      # well-formed arguments on the host: still no fallback
+        solve_pnp_ransac(p3, p2, va, K)
+
+
 def test_modules_fail_loudly_without_gpu():
     from tests.common import build_net, det_image
     net = build_net(full=True)
