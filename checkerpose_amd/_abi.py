@@ -12,6 +12,7 @@ CP_F32, CP_BF16, CP_F16 = 0, 1, 2
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 LOSS_BCE, LOSS_L1 = 0, 1
 POSE_ERR_ADD, POSE_ERR_ADI = 1, 2
+BOP_ERR_MSSD, BOP_ERR_MSPD, BOP_ERR_PROJ, BOP_MAP_SMALL, BOP_MAP_LARGE = 1, 2, 4, 16, 32
 
 
 class CpConvDesc(C.Structure):
@@ -196,6 +197,9 @@ SIGNATURES = {
     "cp_pnp_ransac": (_I, [_P, _P, _L, _P, _P, _I, _P, _L, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P]),
     "cp_pose_errors_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_pose_errors": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _P]),
+    "cp_bop_errors_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "cp_bop_errors_map_scratch_bytes": (C.c_size_t, [_I, _I, _I, C.c_uint32]),
+    "cp_bop_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P, _P]),
     "cp_encode_targets": (_I, [_P, _P, _L, _P, _I, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_code_report": (_I, [_P, _P, _L, _P, _L, _P, _L, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cp_edgeconv_bwd_workspace_bytes": (C.c_size_t, [_I, _I, _I]),

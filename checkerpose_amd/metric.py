@@ -5,6 +5,7 @@ scripts (test.py:378-427, test_lm.py:300-321, compute_auc_posecnn test.py:37-57)
   Calculate_ADD_Error_BOP / _ADI_        the reference's names and numpy-in, float-out signatures (one pose; B = 1 of the above)
   MeshSet                                the packed vertex table of several objects, uploaded once, with their diameters
   compute_auc_posecnn, summarize         pass rates at 2 / 5 / 10 % of the diameter and the PoseCNN AUC (host: one float per image)
+  bop_errors, mssd / mspd / proj, SymmetrySet, bop_recall, summarize_bop      BOP's MSSD / MSPD / projection error (row N7): below
 
 ADI is an all-pairs search: V^2 distance evaluations per pose and no spatial index.  Measured on one MI355X (tools/pose_error_bench.py,
 profiles/pose_error_bench.json): one pose takes 0.16 / 0.36 / 1.44 ms at 4 096 / 20 480 / 61 440 vertices, 256 poses 0.60 / 11.6 / 101 ms
@@ -262,3 +263,286 @@ def summarize(errors, diameters, symmetric=None, mesh_ids=None):
     if ids is not None:
         res["per_mesh"] = {int(m): block(ids == m) for m in np.unique(ids)}
     return res
+
+
+# ---- BOP's MSSD / MSPD / projection error (cp_bop_errors) ---------------------------------------------------------
+# The twin of the three renderer-free functions of bop_toolkit_lib/pose_error.py (mssd :96-118, mspd :121-144, proj :217-232), of
+# misc.get_symmetry_transformations (:43-90) and of the recall eval_bop19_pose.py / eval_calc_scores.py compute from them.
+#   bop_errors(...)                        batched, on device tensors -- takes what solve_pnp_ransac returns
+#   mssd / mspd / proj                     bop_toolkit's names and numpy-in, float-out signatures (B = 1 of the above)
+#   SymmetrySet                            the packed symmetry transformations of several objects, uploaded once
+#   bop_recall, summarize_bop              recall per threshold and its mean (AR_MSSD / AR_MSPD); host: one float per pose
+BOP_KINDS = {"mssd": _abi.BOP_ERR_MSSD, "mspd": _abi.BOP_ERR_MSPD, "proj": _abi.BOP_ERR_PROJ}
+_BOP_MAPS = {None: 0, "small": _abi.BOP_MAP_SMALL, "large": _abi.BOP_MAP_LARGE}
+
+
+def _rotation_about(angle, axis):
+    """rotation by `angle` about `axis` through the origin (bop_toolkit_lib.transform.rotation_matrix restated, 3x3 part): the
+    axis is normalised first; R = cos I + (1 - cos) a a^T + sin [a]_x, summed in that order"""
+    import math
+    sina, cosa = math.sin(angle), math.cos(angle)
+    a = np.array(np.asarray(axis, dtype=np.float64).reshape(-1)[:3], dtype=np.float64, copy=True)
+    a /= math.sqrt(np.dot(a, a))
+    R = np.diag([cosa, cosa, cosa])
+    R += np.outer(a, a) * (1.0 - cosa)
+    a *= sina
+    R += np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
+    return R
+
+
+def symmetry_transformations(model_info, max_sym_disc_step=0.01):
+    """The symmetry set of one models_info.json entry as a list of {"R": (3,3), "t": (3,1)} (misc.get_symmetry_transformations
+    restated).  Discrete symmetries: the identity plus every 4x4 of "symmetries_discrete".  Each continuous symmetry is sampled at
+    count = ceil(pi / max_sym_disc_step) steps of 2 pi / count, i = 1 .. count - 1 -- so WITH a continuous symmetry the identity is
+    not in the set, which then has (count - 1) * (1 + number of discrete symmetries) members per continuous axis: every
+    discretised rotation composed with every discrete one."""
+    disc = [{"R": np.eye(3), "t": np.zeros((3, 1))}]
+    for sym in model_info.get("symmetries_discrete", ()):
+        m = np.reshape(np.asarray(sym, dtype=np.float64), (4, 4))
+        disc.append({"R": m[:3, :3], "t": m[:3, 3].reshape(3, 1)})
+    cont = []
+    for sym in model_info.get("symmetries_continuous", ()):
+        offset = np.asarray(sym["offset"], dtype=np.float64).reshape(3, 1)
+        count = int(np.ceil(np.pi / max_sym_disc_step))
+        step = 2.0 * np.pi / count
+        for i in range(1, count):
+            R = _rotation_about(i * step, sym["axis"])
+            cont.append({"R": R, "t": -R.dot(offset) + offset})
+    if not cont:
+        return disc
+    return [{"R": c["R"].dot(d["R"]), "t": c["R"].dot(d["t"]) + c["t"]} for d in disc for c in cont]
+
+
+class SymmetrySet:
+    """The symmetry transformations of M objects packed into one (sumS, 12) fp64 table [R row-major | t] + (M + 1) int32 offsets
+    (cp_bop_errors' layout), in MeshSet order.  Built on the host; the device copies are made once per device on first use."""
+
+    def __init__(self, table, offsets):
+        self.table = table                  # (sumS, 12) float64 CPU tensor
+        self.offsets = offsets              # (M + 1,) int32 CPU tensor
+        self.sizes = np.diff(offsets.numpy()).astype(np.int64)
+        self._dev = {}
+
+    @classmethod
+    def from_transforms(cls, sets):
+        """sets: one list of {"R": (3,3), "t": (3,) / (3,1)} per mesh (what bop_toolkit passes as `syms`)"""
+        rows, off = [], [0]
+        for syms in sets:
+            if len(syms) == 0:
+                raise ValueError("every mesh needs at least one symmetry transformation (the identity for an asymmetric object)")
+            for s in syms:
+                rows.append(np.concatenate([np.asarray(s["R"], dtype=np.float64).reshape(9), np.asarray(s["t"], dtype=np.float64).reshape(3)]))
+            off.append(len(rows))
+        if not rows:
+            raise ValueError("SymmetrySet needs at least one mesh")
+        return cls(torch.from_numpy(np.ascontiguousarray(np.stack(rows, 0))), torch.tensor(off, dtype=torch.int32))
+
+    @classmethod
+    def from_models_info(cls, infos, max_sym_disc_step=0.01):
+        """infos: one models_info.json entry (dict) per mesh, in MeshSet order -> misc.get_symmetry_transformations of each"""
+        if isinstance(infos, dict):
+            raise ValueError("pass a LIST of models_info entries, one per mesh in MeshSet order")
+        return cls.from_transforms([symmetry_transformations(i, max_sym_disc_step) for i in infos])
+
+    @classmethod
+    def identity(cls, M):
+        return cls.from_transforms([[{"R": np.eye(3), "t": np.zeros(3)}]] * int(M))
+
+    def transforms(self, m):
+        """mesh m's set back as bop_toolkit's list of {"R", "t"}"""
+        t = self.table.numpy()[int(self.offsets[m]):int(self.offsets[m + 1])]
+        return [{"R": r[:9].reshape(3, 3).copy(), "t": r[9:].reshape(3, 1).copy()} for r in t]
+
+    def __len__(self):
+        return int(self.offsets.numel()) - 1
+
+    def on(self, device):
+        """(table, offsets) on `device`, uploaded on the first call"""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._dev:
+            self._dev[key] = (self.table.to(device), self.offsets.to(device))
+        return self._dev[key]
+
+
+_IDENTITY_SETS = {}     # M -> SymmetrySet of M identities (symmetries=None)
+
+
+def bop_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, symmetries=None, mesh_ids=None, kinds=("mssd", "mspd", "proj"), _mapping=None):
+    """BOP's MSSD, MSPD and / or projection error of B poses against their ground truth, on the device (cp_bop_errors).
+      R_est, t_est: (B,3,3) / (B,3,1) CUDA tensors, e.g. straight from solve_pnp_ransac; R_gt, t_gt: the same shapes (tensors on the
+      same device, or host arrays, which are uploaded);  cam_K: (3,3) for every pose or (B,3,3), tensor or array;
+      vertices: one (V,3) array / tensor for every pose, a list of them, or a MeshSet; with several meshes `mesh_ids` (B,), on the
+      host or on the device, names each pose's mesh;  symmetries: a SymmetrySet in the same mesh order, a list of bop_toolkit `syms`
+      lists, or None = the identity alone for every mesh;  kinds: any of "mssd", "mspd", "proj".
+    MSSD comes in the vertices' units, MSPD and proj in pixels of cam_K.  A pose with a NaN / inf entry (either pose, or K), or a
+    device-side mesh id outside 0..M-1, scores NaN in every kind.  `_mapping` ("small" / "large") forces one of the kernel's two
+    mappings (measurement and tests: results are bit-identical).
+    -> dict kind -> (B,) float64 CUDA tensor."""
+    if not (torch.is_tensor(R_est) and torch.is_tensor(t_est) and R_est.is_cuda and t_est.is_cuda):
+        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    dev = R_est.device
+    mask = 0
+    for k in ([kinds] if isinstance(kinds, str) else kinds):
+        if k not in BOP_KINDS:
+            raise ValueError("kinds must be among %s, got %r" % (sorted(BOP_KINDS), k))
+        mask |= BOP_KINDS[k]
+    if not mask:
+        raise ValueError("kinds is empty: ask for \"mssd\", \"mspd\" and / or \"proj\"")
+    if _mapping not in _BOP_MAPS:
+        raise ValueError("_mapping must be None, \"small\" or \"large\"")
+    est = _as_poses(R_est, t_est)
+    B = est.shape[0]
+    if B == 0:
+        raise ValueError("no poses")
+    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
+    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
+    if tuple(K.shape) == (3, 3):
+        K, k_stride = K.reshape(9).contiguous(), 0
+    elif tuple(K.shape) == (B, 3, 3):
+        K, k_stride = K.reshape(B, 9).contiguous(), 9
+    else:
+        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
+    ms = vertices if isinstance(vertices, MeshSet) else _cached_meshset(vertices)
+    M = len(ms)
+    if symmetries is None:
+        if M not in _IDENTITY_SETS:
+            _IDENTITY_SETS[M] = SymmetrySet.identity(M)
+        ss = _IDENTITY_SETS[M]
+    else:
+        ss = symmetries if isinstance(symmetries, SymmetrySet) else SymmetrySet.from_transforms(symmetries)
+    if len(ss) != M:
+        raise ValueError("%d symmetry sets for %d meshes" % (len(ss), M))
+    verts, v_off = ms.on(dev)
+    table, s_off = ss.on(dev)
+    if mesh_ids is None:
+        if M != 1:
+            raise ValueError("several meshes need mesh_ids")
+        ids, vmax, smax = None, int(ms.sizes[0]), int(ss.sizes[0])
+    elif torch.is_tensor(mesh_ids) and mesh_ids.is_cuda:      # stays on the device: an id outside 0..M-1 scores NaN (cp_bop_errors)
+        if mesh_ids.numel() != B:
+            raise ValueError("mesh_ids must be (B,)")
+        ids = mesh_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+        vmax, smax = int(ms.sizes.max()), int(ss.sizes.max())
+    else:
+        ids_host = np.asarray(mesh_ids).reshape(-1).astype(np.int64)
+        if ids_host.shape[0] != B or ids_host.min() < 0 or ids_host.max() >= M:
+            raise ValueError("mesh_ids must be (B,) with values in 0..%d" % (M - 1))
+        used = np.unique(ids_host)
+        ids, vmax, smax = torch.from_numpy(ids_host.astype(np.int32)).to(dev), int(ms.sizes[used].max()), int(ss.sizes[used].max())
+    lib = _abi.load()
+    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k, bit in BOP_KINDS.items() if mask & bit}
+    scratch = torch.empty(lib.cp_bop_errors_map_scratch_bytes(B, smax, vmax, _BOP_MAPS[_mapping]), dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda k: out[k].data_ptr() if k in out else None   # noqa: E731
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_bop_errors(st, est.data_ptr(), gt.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(),
+                                     table.data_ptr(), s_off.data_ptr(), M, None if ids is None else ids.data_ptr(), B, vmax, smax,
+                                     mask | _BOP_MAPS[_mapping], ptr("mssd"), ptr("mspd"), ptr("proj"), scratch.data_ptr()),
+                   "cp_bop_errors")
+    return out
+
+
+def _one_bop(kind, R_est, t_est, R_gt, t_gt, K, pts, syms, device):
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
+    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
+    out = bop_errors(f(R_est, (1, 3, 3)), f(t_est, (1, 3, 1)), f(R_gt, (1, 3, 3)), f(t_gt, (1, 3, 1)),
+                     np.eye(3) if K is None else np.asarray(K, dtype=np.float64).reshape(3, 3), pts,
+                     symmetries=None if syms is None else [list(syms)], kinds=(kind,))
+    return float(out[kind][0])
+
+
+def mssd(R_est, t_est, R_gt, t_gt, pts, syms, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.mssd (numpy arrays of one pose -> float), scored on the device"""
+    return _one_bop("mssd", R_est, t_est, R_gt, t_gt, None, pts, syms, device)
+
+
+def mspd(R_est, t_est, R_gt, t_gt, K, pts, syms, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.mspd (numpy arrays of one pose -> float), scored on the device"""
+    return _one_bop("mspd", R_est, t_est, R_gt, t_gt, K, pts, syms, device)
+
+
+def proj(R_est, t_est, R_gt, t_gt, K, pts, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.proj (numpy arrays of one pose -> float), scored on the device"""
+    return _one_bop("proj", R_est, t_est, R_gt, t_gt, K, pts, None, device)
+
+
+def bop_thresholds(kind):
+    """eval_bop19_pose.py:46,51: the ten thresholds of correctness of MSSD (fractions of the diameter) and MSPD (pixels at width 640)"""
+    if kind == "mssd":
+        return np.arange(0.05, 0.51, 0.05)
+    if kind == "mspd":
+        return np.arange(5, 51, 5)
+    raise ValueError("%r has no default thresholds (BOP'19 scores \"mssd\" and \"mspd\"): pass `thresholds`" % (kind,))
+
+
+def bop_recall(errors, kind, diameters=None, im_width=None, thresholds=None, mesh_ids=None):
+    """Recall of one error kind over its thresholds, with ONE estimate per target as test.py produces (then BOP's greedy matching is
+    the comparison alone): eval_calc_scores.py:246-263 + pose_matching.py:68.
+      errors: (n,) tensor / array of `kind` ("mssd", "mspd" or "proj");  MSSD is divided by the diameter (`diameters`: a float, one
+      per pose, or -- with mesh_ids -- one per mesh), MSPD is multiplied by 640 / im_width, proj is taken as it is;  thresholds:
+      default bop_thresholds(kind).  A pose is correct when error < threshold, STRICT; NaN is a miss.
+    -> {"thresholds", "correct": (n, T) bool, "recall": (T,), "AR_<KIND>": their mean, "count"} and, with mesh_ids,
+       "per_mesh": {mesh id -> {"recall", "AR_<KIND>", "count"}}."""
+    if kind not in BOP_KINDS:
+        raise ValueError("kind must be among %s, got %r" % (sorted(BOP_KINDS), kind))
+    e = _to_numpy(errors).astype(np.float64).reshape(-1)
+    n = e.shape[0]
+    ids = None if mesh_ids is None else _to_numpy(mesh_ids).astype(np.int64).reshape(-1)
+    if kind == "mssd":
+        if diameters is None:
+            raise ValueError("MSSD is scored relative to the object diameter: pass `diameters`")
+        diam = np.asarray(diameters, dtype=np.float64).reshape(-1)
+        diam = diam[ids] if (ids is not None and diam.shape[0] != 1) else np.broadcast_to(diam, (n,))
+        e = e / diam
+    elif kind == "mspd":
+        if im_width is None:
+            raise ValueError("MSPD is scored at an image width of 640: pass `im_width`")
+        e = (640.0 / float(im_width)) * e
+    th = bop_thresholds(kind) if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    correct = e[:, None] < th[None, :]
+    name = "AR_" + kind.upper()
+
+    def block(sel):
+        c = correct[sel]
+        rec = c.mean(0) if c.shape[0] else np.full(th.shape[0], np.nan)
+        return {"recall": rec, name: float(rec.mean()), "count": int(c.shape[0])}
+
+    res = block(np.ones(n, bool))
+    res.update({"thresholds": th, "correct": correct})
+    if ids is not None:
+        res["per_mesh"] = {int(m): block(ids == m) for m in np.unique(ids)}
+    return res
+
+
+def summarize_bop(errors, diameters=None, im_width=None, mesh_ids=None, thresholds=None):
+    """bop_recall of every kind in `errors` (the dict bop_errors returns; other keys, e.g. "add", are ignored; "proj" only when
+    `thresholds` names it).  thresholds: optional dict kind -> thresholds.
+    -> {kind: bop_recall's dict} plus "AR_MSSD" / "AR_MSPD" at the top.  BOP's AR also averages VSD, which needs a renderer."""
+    thresholds = thresholds or {}
+    res = {}
+    for kind in BOP_KINDS:
+        if kind not in errors or (kind == "proj" and "proj" not in thresholds):
+            continue
+        res[kind] = bop_recall(errors[kind], kind, diameters=diameters, im_width=im_width, thresholds=thresholds.get(kind), mesh_ids=mesh_ids)
+        res["AR_" + kind.upper()] = res[kind]["AR_" + kind.upper()]
+    if not res:
+        raise ValueError("errors holds none of \"mssd\", \"mspd\" (or \"proj\" with thresholds)")
+    return res
+
+
+def score_poses(R_est, t_est, R_gt, t_gt, cam_K, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None):
+    """pose_errors and / or bop_errors by the kinds asked (postprocess.evaluate_poses, targets.evaluate_batch): kinds of "add" / "adi"
+    alone are exactly pose_errors -- nothing else is launched."""
+    names = [kinds] if isinstance(kinds, str) else list(kinds)
+    bop = [k for k in names if k in BOP_KINDS]
+    if not bop:
+        return pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=kinds)
+    rest = [k for k in names if k not in BOP_KINDS]
+    out = pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=rest) if rest else {}
+    out.update(bop_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, symmetries=symmetries, mesh_ids=mesh_ids, kinds=bop))
+    return out

@@ -121,16 +121,19 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
     return R, t, inl, status, final
 
 
-def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add", "adi"), **estimate_kwargs):
+def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None,
+                   **estimate_kwargs):
     """estimate_poses followed by metric.pose_errors against the given ground-truth poses: test.py's loop body from the detection
     boxes to the ADD / ADD-S errors (:198-427) with only the errors leaving the GPU.
       R_gt (B,3,3), t_gt (B,3,1) / (B,3): tensors or host arrays; vertices: a (V,3) array, a list with mesh_ids, or a metric.MeshSet
       (units of p3d_xyz); estimate_kwargs go to estimate_poses.  Crops whose solver fell back to the identity pose (status 0) are
       scored with it, as the reference scores them (from_id_to_pose returns R = I, t = 0 and test.py goes on).
+      kinds may also name "mssd", "mspd", "proj" (metric.bop_errors, with cam_K and `symmetries`: a metric.SymmetrySet, a list of
+      bop_toolkit `syms` lists, or None = the identity alone); without them nothing more is launched.
     -> (errors: dict kind -> (B,) f64 CUDA tensor, R, t, inliers, status, final boxes)"""
     from . import metric
     R, t, inl, status, final = estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, **estimate_kwargs)
-    errors = metric.pose_errors(R, t, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=kinds)
+    errors = metric.score_poses(R, t, R_gt, t_gt, cam_K, vertices, mesh_ids=mesh_ids, kinds=kinds, symmetries=symmetries)
     return errors, R, t, inl, status, final
 
 

@@ -565,6 +565,37 @@ size_t cp_pose_errors_scratch_bytes(int B, int Vmax);
 int cp_pose_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const float* verts, const int32_t* offsets,
                    int M, const int32_t* mesh_id, int B, int Vmax, int kinds, double* add, double* adi, void* scratch);
 
+/* BOP's MSSD, MSPD and projection error on the device (next-row N7; csrc/bop_error.hip; reference bop_toolkit_lib/pose_error.py:96-144
+ * mssd / mspd, :217-232 proj -- the errors eval_bop19_pose.py scores the LM-O / YCB-V tables by), for B poses at once.  With
+ * R_gs = R_gt R_s, t_gs = R_gt t_s + t_gt over the symmetry transformations s of the pose's mesh:
+ *   MSSD = min_s max_v |R_est p_v + t_est - (R_gs p_v + t_gs)|,   MSPD = min_s max_v |proj_est(p_v) - proj_gs(p_v)|  (pixels),
+ *   proj = mean_v |proj_est(p_v) - proj_gt(p_v)| (no symmetries),  proj_X(p) = first two rows of K [R | t] p_h over the third
+ *   (misc.project_pts: no guard on the depth; a vertex at depth exactly 0 is outside the contract).
+ *   pose_est, pose_gt fp64 (B,12) = [R row-major | t] as cp_pose_errors; cam_K fp64 row-major 3x3: (B,9) with k_stride = 9 or ONE
+ *   matrix with k_stride = 0;  verts fp32 (sumV,3) + v_offsets int32 (M+1): cp_pose_errors' vertex table (v_offsets NULL = one mesh
+ *   of Vmax vertices, M == 1);  syms fp64 (sumS,12) = [R_s row-major | t_s] + s_offsets int32 (M+1): mesh m owns the symmetry rows
+ *   [s_offsets[m], s_offsets[m+1]) (at least one: the identity is NOT implied);  mesh_ids int32 (B), or NULL when M == 1.
+ *   Vmax / Smax >= the largest mesh / symmetry set a pose refers to.
+ *   kinds: CP_BOP_ERR_MSSD | _MSPD | _PROJ, at least one; mssd / mspd / proj fp64 (B) are written for the kinds asked (the others
+ *   may be NULL).  Optionally CP_BOP_MAP_SMALL or CP_BOP_MAP_LARGE forces one of the two mappings of the main pass (measurement
+ *   and tests: the results are bit-identical either way; scratch then comes from cp_bop_errors_map_scratch_bytes with that bit).
+ * Arithmetic: everything per (pose, symmetry) -- R_gs, t_gs, D_s = R_est - R_gs, d_s = t_est - t_gs, K [R_est | t_est],
+ * K [R_gs | t_gs] -- is formed once in fp64 without contraction and rounded to fp32; the loop over the vertices is fp32:
+ * MSSD as |D_s p + d_s|^2 (linear in the difference: the translations never cancel in the loop), the estimate's projection once
+ * per vertex, maxima over SQUARED distances, one fp64 square root per (pose, symmetry), proj's distances summed in fp64 in a
+ * fixed order.  Every output is bit-identical from call to call, for a pose alone or in a batch, whichever kinds are asked and
+ * whichever mapping runs.  A pose with a non-finite entry in either pose or in its K, a mesh id outside [0, M), a mesh that is
+ * empty or larger than Vmax or a symmetry set that is empty or larger than Smax scores NaN in every kind asked.
+ * At most three launches (compose, main pass, final reduction), nothing allocates or synchronises.  CP_ERR_RANGE: a launch of
+ * 2^24 workgroups or more -- split the batch.  scratch: cp_bop_errors_scratch_bytes(B, Smax, Vmax) bytes, 16-byte aligned. */
+enum { CP_BOP_ERR_MSSD = 1, CP_BOP_ERR_MSPD = 2, CP_BOP_ERR_PROJ = 4, CP_BOP_MAP_SMALL = 16, CP_BOP_MAP_LARGE = 32 };
+size_t cp_bop_errors_scratch_bytes(int B, int Smax, int Vmax);
+size_t cp_bop_errors_map_scratch_bytes(int B, int Smax, int Vmax, unsigned map);   /* map: 0 (as the call chooses), CP_BOP_MAP_SMALL or _LARGE */
+int cp_bop_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const double* cam_K, int k_stride,
+                  const float* verts, const int32_t* v_offsets, const double* syms, const int32_t* s_offsets, int M,
+                  const int32_t* mesh_ids, int B, int Vmax, int Smax, unsigned kinds, double* mssd, double* mspd, double* proj,
+                  void* scratch);
+
 /* Ground-truth side on the device (next-row N6; csrc/targets.hip).
  *
  * cp_encode_targets: the labels of the reference's data loader (bop_dataset_pytorch.py:293,356-380: project the N keypoints through
