@@ -200,6 +200,10 @@ SIGNATURES = {
     "cp_bop_errors_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_bop_errors_map_scratch_bytes": (C.c_size_t, [_I, _I, _I, C.c_uint32]),
     "cp_bop_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, C.c_uint32, _P, _P, _P, _P]),
+    "cp_vsd_errors_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "cp_vsd_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "cp_vsd_from_depth": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "cp_render_depth": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "cp_encode_targets": (_I, [_P, _P, _L, _P, _I, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_code_report": (_I, [_P, _P, _L, _P, _L, _P, _L, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cp_edgeconv_bwd_workspace_bytes": (C.c_size_t, [_I, _I, _I]),

@@ -1,0 +1,512 @@
+// cp_vsd_errors: BOP's Visible Surface Discrepancy of a batch of poses on the device -- a depth rasteriser fused
+// with the pixel counting of bop_toolkit_lib/pose_error.py:17-93 (vsd), misc.py:110-163 (depth_im_to_dist_im_fast) and visibility.py
+// ('bop19' mode, 'step' cost).  The reference renders the mesh twice per pose through OpenGL (renderer_py.py:185-226, 422-555) and
+// then makes several full-frame numpy passes; here no depth image exists unless the caller asks for it.
+//
+// Render rule.  depth[y, x] = the smallest eye-space Z > 0 at which the ray through image point (x + 0.5, y + 0.5) meets a triangle
+// (no back-face culling, background 0), Z taken on the triangle's plane: 1 / Z is affine in the image.  Triangles of zero area
+// are skipped.  A pose with any vertex at Z <= 0 is not rendered: its errors are NaN.
+//
+// Launches (three, + one when meshes are involved):
+//   vsd_pose_kernel     per pose: P = K' [R | t] of the estimate and of the ground truth in double WITHOUT contraction, rounded to fp32
+//                       once (K' = fx, fy, cx, cy of K, skew 0, as render_object takes them); validity; the caller's
+//                       overlapping_sphere_projections shortcut (misc.py:309-331) in double; the pixel rectangles are initialised.
+//   vsd_vertex_kernel   per (pose, side, vertex): screen (u, v, Z, 1 / Z) in fp32 with explicit fma chains; the pose's pixel rectangle
+//                       and its "a vertex at Z <= 0" flag through INTEGER atomic min / max / or (order-independent).
+//   vsd_tile_kernel     a workgroup owns a 32 x 32 pixel tile of one pose, a lane 4 pixels of it (both depths in registers).  Per side
+//                       the mesh's triangles are set up 256 at a time: the ones whose bounding box meets the tile are compacted
+//                       into LDS as 16 floats (three edge functions and the 1 / Z plane as affine functions of the TILE-RELATIVE
+//                       sample index, so fp32 keeps sub-pixel resolution whatever the image size), then every wave walks the list
+//                       with broadcast reads and a wave-uniform reject against its 32 x 8 strip.  min() over triangles is exact in
+//                       any order, so the order in which the list is compacted does not reach the result.  Then the tile reads the
+//                       test depth, does the reference's distance / visibility arithmetic (fp64 square roots and quotients, the
+//                       fp32 difference against delta) and reduces INTEGER counts: wave shuffles, LDS, one row of scratch per tile.
+//                       Tiles outside the union of the two rectangles leave at once (or write zeros when depth images are asked).
+//   vsd_sum_kernel      per pose: the tile rows the rectangles reach, summed (integers), and the quotients.
+// Every output is a function of integer counts and per-pixel values: bit-identical from call to call, for a pose alone or in a
+// batch, with or without the depth output.  No floating-point atomics, no initialised scratch beyond what vsd_pose_kernel writes.
+#include "common.h"
+
+namespace {
+
+constexpr int VS_THREADS = 256;
+constexpr int VS_TILE = 32;                      // pixels per tile side
+constexpr int VS_PPL = 4;                        // pixels per lane: VS_TILE * VS_TILE / VS_THREADS
+constexpr int VS_STRIP = VS_TILE / (VS_THREADS / 64);   // rows per wave (8)
+constexpr int VS_CHUNK = 256;                    // triangles set up per round (16 KiB of LDS)
+constexpr int VS_TMAX = 16;                      // taus per call
+constexpr int VS_ROW = VS_TMAX + 2;              // ints per tile row: union, inter, cost[T]
+constexpr int VS_HDR = 40;                       // 4-byte words per pose: P_est[12] P_gt[12] rect_est[4] rect_gt[4] bad[2] ok skip
+enum { VS_MODE_VSD = 0, VS_MODE_RENDER = 1, VS_MODE_DEPTH = 2 };
+
+struct VsParams {
+  const double* est;          // (B, 12)
+  const double* gt;
+  const double* K;
+  const float* verts;
+  const int32_t* v_off;
+  const int32_t* faces;       // (sumF, 3), indices local to the mesh
+  const int32_t* f_off;
+  const int32_t* mesh_id;
+  const float* depth_test;    // (I, H, W)
+  const int32_t* image_id;    // nullptr: image 0
+  const double* diameters;    // per mesh (VSD) / per pose (DEPTH)
+  const float* in_est;        // DEPTH mode: (B, H, W)
+  const float* in_gt;
+  float* depth_out;           // (B, nsides, H, W) or nullptr
+  double* errors;             // (B, T)
+  int32_t* counts;            // (B, T + 2)
+  int32_t* hdr;               // (B, VS_HDR)
+  float4* sv;                 // (B, 2, Vmax)
+  int32_t* rows;              // (B, tiles, VS_ROW)
+  double taus[VS_TMAX];
+  float delta;
+  int k_stride, M, B, Vmax, H, W, I, T, normalise, sphere, mode, nsides, tx, ty, vchunks;
+};
+
+__device__ inline double vs_dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
+#pragma clang fp contract(off)
+  return (a0 * b0 + a1 * b1) + a2 * b2;
+}
+
+// P = [[fx 0 cx] [0 fy cy] [0 0 1]] [R | t] in double -> fp32 (3x4 row-major)
+__device__ inline void vs_krt(double fx, double fy, double cx, double cy, const double* q, float* __restrict__ P) {
+#pragma clang fp contract(off)
+  for (int c = 0; c < 4; ++c) {
+    const double r0 = c < 3 ? q[c] : q[9], r1 = c < 3 ? q[3 + c] : q[10], r2 = c < 3 ? q[6 + c] : q[11];
+    P[c] = (float)vs_dot3(fx, 0.0, cx, r0, r1, r2);
+    P[4 + c] = (float)vs_dot3(0.0, fy, cy, r0, r1, r2);
+    P[8 + c] = (float)r2;
+  }
+}
+
+__device__ inline bool vs_mesh(const VsParams& p, int b, int& vfirst, int& V, int& ffirst, int& F, int& m) {
+  vfirst = 0; V = 0; ffirst = 0; F = 0;
+  m = p.mesh_id ? p.mesh_id[b] : 0;
+  if (m < 0 || m >= p.M) return false;
+  vfirst = p.v_off[m];
+  V = p.v_off[m + 1] - vfirst;
+  ffirst = p.f_off[m];
+  F = p.f_off[m + 1] - ffirst;
+  if (vfirst < 0 || V <= 0 || V > p.Vmax || ffirst < 0 || F < 0) { V = 0; F = 0; return false; }
+  return true;
+}
+
+__global__ __launch_bounds__(VS_THREADS) void vsd_pose_kernel(VsParams p) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * VS_THREADS + threadIdx.x;
+  if (b >= p.B) return;
+  int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
+  const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
+  bool ok = true;
+  for (int k = 0; k < 9; ++k) ok = ok && isfinite(K[k]);
+  if (p.mode != VS_MODE_RENDER) {
+    const int img = p.image_id ? p.image_id[b] : 0;
+    ok = ok && img >= 0 && img < p.I;
+  }
+  int skip = 0;
+  if (p.mode == VS_MODE_DEPTH) {
+    for (int s = 0; s < 2; ++s) { h[24 + 4 * s] = 0; h[25 + 4 * s] = 0; h[26 + 4 * s] = p.W - 1; h[27 + 4 * s] = p.H - 1; }
+    h[32] = 0; h[33] = 0;
+  } else {
+    int vfirst, V, ffirst, F, m;
+    ok = vs_mesh(p, b, vfirst, V, ffirst, F, m) && ok;
+    const double* __restrict__ e = p.est + 12 * (size_t)b;
+    const double* __restrict__ g = p.gt + 12 * (size_t)b;
+    for (int k = 0; k < 12; ++k) ok = ok && isfinite(e[k]) && isfinite(g[k]);
+    float* __restrict__ P = (float*)h;
+    vs_krt(K[0], K[4], K[2], K[5], e, P);
+    vs_krt(K[0], K[4], K[2], K[5], g, P + 12);
+    for (int s = 0; s < 2; ++s) { h[24 + 4 * s] = INT_MAX; h[25 + 4 * s] = INT_MAX; h[26 + 4 * s] = INT_MIN; h[27 + 4 * s] = INT_MIN; }
+    h[32] = 0; h[33] = 0;
+    if (ok && p.sphere && p.mode == VS_MODE_VSD) {
+      // misc.overlapping_sphere_projections(diameter / 2, t_est, t_gt), as eval_calc_errors.py:299-318 calls it
+      const double radius = p.diameters[m] / 2.0;
+      bool overlap = false;
+      if (!(e[11] == 0.0 || g[11] == 0.0)) {
+        const double dx = e[9] / e[11] - g[9] / g[11], dy = e[10] / e[11] - g[10] / g[11];
+        overlap = sqrt(dx * dx + dy * dy) < radius * (1.0 / e[11] + 1.0 / g[11]);
+      }
+      skip = overlap ? 0 : 1;
+    }
+  }
+  h[34] = ok ? 1 : 0;
+  h[35] = skip;
+}
+
+// row . (x, y, z, 1): one fma chain
+__device__ __forceinline__ float vs_affine(const float* __restrict__ r, float x, float y, float z) {
+  return fmaf(r[2], z, fmaf(r[1], y, fmaf(r[0], x, r[3])));
+}
+
+__global__ __launch_bounds__(VS_THREADS) void vsd_vertex_kernel(VsParams p) {
+#pragma clang fp contract(off)
+  int blk = blockIdx.x;
+  const int vc = blk % p.vchunks;
+  blk /= p.vchunks;
+  const int s = blk % p.nsides, b = blk / p.nsides;
+  int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
+  if (!h[34] || h[35]) return;                                       // (uniform; no barrier in this kernel)
+  int vfirst, V, ffirst, F, m;
+  vs_mesh(p, b, vfirst, V, ffirst, F, m);
+  const int i = vc * VS_THREADS + threadIdx.x;
+  int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN, bad = 0;
+  if (i < V) {
+    const float* __restrict__ vt = p.verts + 3 * ((size_t)vfirst + i);
+    const float* __restrict__ P = (const float*)h + 12 * s;
+    const float x = vt[0], y = vt[1], z = vt[2];
+    const float pu = vs_affine(P, x, y, z), pv = vs_affine(P + 4, x, y, z), pw = vs_affine(P + 8, x, y, z);
+    const float iz = 1.0f / pw;
+    const float u = pu / pw, v = pv / pw;
+    p.sv[((size_t)b * 2 + s) * p.Vmax + i] = make_float4(u, v, pw, iz);
+    if (!(pw > 0.f) || !isfinite(u) || !isfinite(v)) {
+      bad = 1;
+    } else {
+      // pixel x is sampled at x + 0.5: the pixels whose sample can lie inside [u_min, u_max]; clamped in float first
+      const float cu = fminf(fmaxf(u - 0.5f, -2.f), (float)p.W + 1.f), cv = fminf(fmaxf(v - 0.5f, -2.f), (float)p.H + 1.f);
+      x0 = (int)floorf(cu); x1 = (int)ceilf(cu);
+      y0 = (int)floorf(cv); y1 = (int)ceilf(cv);
+    }
+  }
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    x0 = min(x0, __shfl_xor(x0, w, 64)); y0 = min(y0, __shfl_xor(y0, w, 64));
+    x1 = max(x1, __shfl_xor(x1, w, 64)); y1 = max(y1, __shfl_xor(y1, w, 64));
+    bad |= __shfl_xor(bad, w, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (x0 != INT_MAX) {
+      atomicMin(h + 24 + 4 * s, x0); atomicMin(h + 25 + 4 * s, y0);
+      atomicMax(h + 26 + 4 * s, x1); atomicMax(h + 27 + 4 * s, y1);
+    }
+    if (bad) atomicOr(h + 32 + s, 1);
+  }
+}
+
+// the reference's depth_im_to_dist_im_fast at pixel (x, y): integer x, y (NOT the sample point), float64 throughout
+__device__ __forceinline__ double vs_dist(double px, double py, float d) {
+#pragma clang fp contract(off)
+  const double dd = (double)d;
+  const double a = px * dd, c = py * dd;
+  return sqrt((a * a + c * c) + dd * dd);
+}
+
+// _estimate_visib_mask, 'bop19': (f32(dist_model) - f32(dist_test) <= delta or dist_test == 0) and dist_model > 0
+__device__ __forceinline__ bool vs_visible(double dist_test, double dist_model, float delta) {
+#pragma clang fp contract(off)
+  const float diff = (float)dist_model - (float)dist_test;
+  return (diff <= delta || dist_test == 0.0) && dist_model > 0.0;
+}
+
+__global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
+  __shared__ float4 s_tri[VS_CHUNK][4];          // e0 (a b c .) e1 (a b c .) e2 (a b c .) plane (A B C .): .w = ymin ymax - -
+  __shared__ int s_n;
+  __shared__ int s_cnt[VS_THREADS / 64][VS_ROW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tiles = p.tx * p.ty;
+  const int b = blockIdx.x / tiles, t = blockIdx.x % tiles;
+  const int ox = (t % p.tx) * VS_TILE, oy = (t / p.tx) * VS_TILE;
+  const int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
+  const bool live = h[34] && !h[35] && !h[32] && !h[33];
+  // the pose's rectangles against this tile
+  bool hit[2];
+  for (int s = 0; s < 2; ++s)
+    hit[s] = live && s < p.nsides && h[24 + 4 * s] <= ox + VS_TILE - 1 && h[26 + 4 * s] >= ox && h[25 + 4 * s] <= oy + VS_TILE - 1 &&
+             h[27 + 4 * s] >= oy;
+  if (!hit[0] && !hit[1] && !p.depth_out) return;                   // (uniform)
+  const int lx = lane & 31, ly0 = wave * VS_STRIP + (lane >> 5);    // the lane's pixels: (lx, ly0 + 2 k), k = 0..3
+  float dep[2][VS_PPL];
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int k = 0; k < VS_PPL; ++k) dep[s][k] = 0.f;
+
+  if (p.mode == VS_MODE_DEPTH) {
+#pragma unroll
+    for (int k = 0; k < VS_PPL; ++k) {
+      const int x = ox + lx, y = oy + ly0 + 2 * k;
+      if (hit[0] && x < p.W && y < p.H) {
+        const size_t at = ((size_t)b * p.H + y) * p.W + x;
+        dep[0][k] = p.in_est[at];
+        dep[1][k] = p.in_gt[at];
+      }
+    }
+  } else {
+    int vfirst, V, ffirst, F, m;
+    vs_mesh(p, b, vfirst, V, ffirst, F, m);
+    const float fx0 = (float)ox + 0.5f, fy0 = (float)oy + 0.5f;     // the tile's first sample point (exact in fp32)
+    const float wy0 = (float)(wave * VS_STRIP), wy1 = wy0 + (float)(VS_STRIP - 1);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (!hit[s]) continue;                                         // (uniform)
+      float best[VS_PPL];
+#pragma unroll
+      for (int k = 0; k < VS_PPL; ++k) best[k] = 0.f;                   // the largest 1 / Z so far: max is exact in any order
+      const float4* __restrict__ sv = p.sv + ((size_t)b * 2 + s) * p.Vmax;
+      for (int f0 = 0; f0 < F; f0 += VS_CHUNK) {
+        __syncthreads();
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+        const int f = f0 + tid;
+        if (f < F) {
+#pragma clang fp contract(off)
+          const int32_t* __restrict__ fi = p.faces + 3 * ((size_t)ffirst + f);
+          const int i0 = fi[0], i1 = fi[1], i2 = fi[2];
+          if (i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V) {
+            const float4 a = sv[i0], c = sv[i1], d = sv[i2];
+            const float ax = a.x - fx0, ay = a.y - fy0, cx = c.x - fx0, cy = c.y - fy0, dx = d.x - fx0, dy = d.y - fy0;
+            const float xmin = fminf(ax, fminf(cx, dx)), xmax = fmaxf(ax, fmaxf(cx, dx));
+            const float ymin = fminf(ay, fminf(cy, dy)), ymax = fmaxf(ay, fmaxf(cy, dy));
+            // twice the signed area; its sign turns every edge function non-negative inside
+            const float area = (cx - ax) * (dy - ay) - (dx - ax) * (cy - ay);
+            if (area != 0.f && xmax >= 0.f && xmin <= (float)(VS_TILE - 1) && ymax >= 0.f && ymin <= (float)(VS_TILE - 1)) {
+              const float sg = area > 0.f ? 1.f : -1.f, ia = 1.0f / area;
+              // edge i is opposite vertex i: E(q) = (x_b - x_a)(q_y - y_a) - (y_b - y_a)(q_x - x_a)
+              const float e0a = -(dy - cy), e0b = dx - cx, e0c = (dy - cy) * cx - (dx - cx) * cy;     // c -> d
+              const float e1a = -(ay - dy), e1b = ax - dx, e1c = (ay - dy) * dx - (ax - dx) * dy;     // d -> a
+              const float e2a = -(cy - ay), e2b = cx - ax, e2c = (cy - ay) * ax - (cx - ax) * ay;     // a -> c
+              // 1 / Z = iz_a + (E1 (iz_c - iz_a) + E2 (iz_d - iz_a)) / area
+              const float g1 = (c.w - a.w) * ia, g2 = (d.w - a.w) * ia;
+              const float pa = e1a * g1 + e2a * g2, pb = e1b * g1 + e2b * g2, pc = a.w + (e1c * g1 + e2c * g2);
+              const int at = atomicAdd(&s_n, 1);
+              s_tri[at][0] = make_float4(sg * e0a, sg * e0b, sg * e0c, ymin);
+              s_tri[at][1] = make_float4(sg * e1a, sg * e1b, sg * e1c, ymax);
+              s_tri[at][2] = make_float4(sg * e2a, sg * e2b, sg * e2c, 0.f);
+              s_tri[at][3] = make_float4(pa, pb, pc, 0.f);
+            }
+          }
+        }
+        __syncthreads();
+        const int n = s_n;
+        for (int j = 0; j < n; ++j) {
+          const float4 q0 = s_tri[j][0], q1 = s_tri[j][1];           // every lane reads the same address: a broadcast
+          const float tymin = __builtin_amdgcn_readfirstlane(q0.w), tymax = __builtin_amdgcn_readfirstlane(q1.w);
+          if (tymax < wy0 || tymin > wy1) continue;                  // wave-uniform: the triangle misses this wave's strip
+          const float4 q2 = s_tri[j][2], q3 = s_tri[j][3];
+          const float qx = (float)lx;
+#pragma unroll
+          for (int k = 0; k < VS_PPL; ++k) {
+            const float qy = (float)(ly0 + 2 * k);
+            const float w0 = fmaf(q0.x, qx, fmaf(q0.y, qy, q0.z));
+            const float w1 = fmaf(q1.x, qx, fmaf(q1.y, qy, q1.z));
+            const float w2 = fmaf(q2.x, qx, fmaf(q2.y, qy, q2.z));
+            const float iz = fmaf(q3.x, qx, fmaf(q3.y, qy, q3.z));
+            if (w0 >= 0.f && w1 >= 0.f && w2 >= 0.f && iz > best[k]) best[k] = iz;
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < VS_PPL; ++k) dep[s][k] = best[k] > 0.f ? 1.0f / best[k] : 0.f;      // one correctly rounded division per pixel
+    }
+  }
+
+  if (p.depth_out) {
+#pragma unroll
+    for (int k = 0; k < VS_PPL; ++k) {
+      const int x = ox + lx, y = oy + ly0 + 2 * k;
+      if (x < p.W && y < p.H)
+        for (int s = 0; s < p.nsides; ++s)
+          p.depth_out[(((size_t)b * p.nsides + s) * p.H + y) * p.W + x] = s == 0 ? dep[0][k] : dep[1][k];
+    }
+  }
+  if (p.mode == VS_MODE_RENDER || (!hit[0] && !hit[1])) return;     // (uniform)
+
+  // ---- the reference's counting on this tile
+  int cnt[VS_ROW];
+#pragma unroll
+  for (int k = 0; k < VS_ROW; ++k) cnt[k] = 0;
+  {
+#pragma clang fp contract(off)
+    const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    const int img = p.image_id ? p.image_id[b] : 0;
+    const float* __restrict__ test = p.depth_test + (size_t)img * p.H * p.W;
+    const double diam = p.diameters[p.mode == VS_MODE_DEPTH ? b : (p.mesh_id ? p.mesh_id[b] : 0)];
+#pragma unroll
+    for (int k = 0; k < VS_PPL; ++k) {
+      const int x = ox + lx, y = oy + ly0 + 2 * k;
+      const float de = dep[0][k], dg = dep[1][k];
+      if (x >= p.W || y >= p.H || (!(de > 0.f) && !(dg > 0.f))) continue;     // dist_model > 0 fails on both sides: no count moves
+      const float dt = test[(size_t)y * p.W + x];
+      const double px = ((double)x - cx) / fx, py = ((double)y - cy) / fy;
+      const double t_test = vs_dist(px, py, dt), t_est = vs_dist(px, py, de), t_gt = vs_dist(px, py, dg);
+      const bool vg = vs_visible(t_test, t_gt, p.delta);
+      const bool ve = vs_visible(t_test, t_est, p.delta) || (vg && t_est > 0.0);
+      cnt[0] += (vg || ve) ? 1 : 0;
+      if (vg && ve) {
+        cnt[1] += 1;
+        double dd = fabs(t_gt - t_est);
+        if (p.normalise) dd = dd / diam;
+#pragma unroll
+        for (int q = 0; q < VS_TMAX; ++q)
+          if (q < p.T) cnt[2 + q] += dd >= p.taus[q] ? 1 : 0;
+      }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VS_ROW; ++k) {
+    int v = cnt[k];
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) v += __shfl_xor(v, w, 64);
+    if (lane == 0) s_cnt[wave][k] = v;
+  }
+  __syncthreads();
+  if (tid < VS_ROW) {
+    int v = 0;
+    for (int w = 0; w < VS_THREADS / 64; ++w) v += s_cnt[w][tid];
+    p.rows[((size_t)b * tiles + t) * VS_ROW + tid] = v;
+  }
+}
+
+__global__ __launch_bounds__(64) void vsd_sum_kernel(VsParams p) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
+  const bool ok = h[34] != 0, skip = h[35] != 0, bad = h[32] || h[33];
+  int cnt[VS_ROW];
+#pragma unroll
+  for (int k = 0; k < VS_ROW; ++k) cnt[k] = 0;
+  if (ok && !skip && !bad) {
+    // the tiles vsd_tile_kernel counted on: the ones either rectangle reaches (the others were never written)
+    const int tiles = p.tx * p.ty;
+    for (int t = lane; t < tiles; t += 64) {
+      const int ox = (t % p.tx) * VS_TILE, oy = (t / p.tx) * VS_TILE;
+      bool hit = false;
+      for (int s = 0; s < 2; ++s)
+        hit = hit || (h[24 + 4 * s] <= ox + VS_TILE - 1 && h[26 + 4 * s] >= ox && h[25 + 4 * s] <= oy + VS_TILE - 1 && h[27 + 4 * s] >= oy);
+      if (!hit) continue;
+      const int32_t* __restrict__ r = p.rows + ((size_t)b * tiles + t) * VS_ROW;
+#pragma unroll
+      for (int k = 0; k < VS_ROW; ++k) cnt[k] += r[k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < VS_ROW; ++k)
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) cnt[k] += __shfl_xor(cnt[k], w, 64);
+  if (lane == 0) {
+#pragma clang fp contract(off)
+    const int uni = cnt[0], comp = cnt[0] - cnt[1];
+    p.counts[(size_t)b * (p.T + 2)] = cnt[0];
+    p.counts[(size_t)b * (p.T + 2) + 1] = cnt[1];
+#pragma unroll
+    for (int q = 0; q < VS_TMAX; ++q) {
+      if (q >= p.T) continue;
+      p.counts[(size_t)b * (p.T + 2) + 2 + q] = cnt[2 + q];
+      double e = 1.0;                                                // union == 0, or the sphere shortcut
+      if (!ok || (bad && !skip)) e = __builtin_nan("");
+      else if (!skip && uni > 0) e = (double)(cnt[2 + q] + comp) / (double)uni;
+      p.errors[(size_t)b * p.T + q] = e;
+    }
+  }
+}
+
+struct VsPlan { int tx, ty; long long tiles; };
+VsPlan vs_plan(int H, int W) {
+  VsPlan pl;
+  pl.tx = (W + VS_TILE - 1) / VS_TILE;
+  pl.ty = (H + VS_TILE - 1) / VS_TILE;
+  pl.tiles = (long long)pl.tx * pl.ty;
+  return pl;
+}
+
+size_t vs_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+void vs_carve(VsParams& p, void* scratch) {
+  char* at = (char*)scratch;
+  p.hdr = (int32_t*)at;
+  at += vs_align16((size_t)p.B * VS_HDR * sizeof(int32_t));
+  p.sv = (float4*)at;
+  at += (size_t)p.B * 2 * p.Vmax * sizeof(float4);
+  p.rows = (int32_t*)at;
+}
+
+int vs_launch(VsParams& p, hipStream_t st) {
+  const VsPlan pl = vs_plan(p.H, p.W);
+  p.tx = pl.tx; p.ty = pl.ty;
+  p.vchunks = (p.Vmax + VS_THREADS - 1) / VS_THREADS;
+  const long long tile_blocks = (long long)p.B * pl.tiles, vert_blocks = (long long)p.B * p.nsides * p.vchunks;
+  if (tile_blocks >= (1LL << 24) || vert_blocks >= (1LL << 24) || (long long)p.H * p.W >= (1LL << 31)) return CP_ERR_RANGE;
+  CP_LAUNCH(vsd_pose_kernel, dim3((unsigned)((p.B + VS_THREADS - 1) / VS_THREADS)), dim3(VS_THREADS), 0, st, p);
+  if (p.mode != VS_MODE_DEPTH) CP_LAUNCH(vsd_vertex_kernel, dim3((unsigned)vert_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(vsd_tile_kernel, dim3((unsigned)tile_blocks), dim3(VS_THREADS), 0, st, p);
+  if (p.mode != VS_MODE_RENDER) CP_LAUNCH(vsd_sum_kernel, dim3((unsigned)p.B), dim3(64), 0, st, p);
+  return cp_check_launch();
+}
+
+bool vs_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
+
+}  // namespace
+
+extern "C" size_t cp_vsd_errors_scratch_bytes(int B, int Vmax, int H, int W) {
+  if (B <= 0 || Vmax < 0 || H <= 0 || W <= 0) return 0;
+  const VsPlan pl = vs_plan(H, W);
+  return vs_align16((size_t)B * VS_HDR * sizeof(int32_t)) + (size_t)B * 2 * Vmax * sizeof(float4) +
+         vs_align16((size_t)B * pl.tiles * VS_ROW * sizeof(int32_t));
+}
+
+extern "C" int cp_vsd_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const double* cam_K, int k_stride,
+                             const float* verts, const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M,
+                             const int32_t* mesh_ids, const float* depth_test, const int32_t* image_ids, int I, int H, int W,
+                             double delta, const double* diameters, const double* taus, int T, int normalized_by_diameter,
+                             int sphere_check, int B, int Vmax, double* errors, int32_t* counts, float* depth_out, void* scratch) {
+  if (!pose_est || !pose_gt || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !depth_test || !diameters || !taus || !errors ||
+      !counts || !scratch)
+    return CP_ERR_INVALID;
+  if (B <= 0 || M <= 0 || Vmax <= 0 || I <= 0 || H <= 0 || W <= 0 || T < 1 || T > VS_TMAX || (k_stride != 0 && k_stride != 9) ||
+      !(delta == delta))
+    return CP_ERR_INVALID;
+  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
+  if (!image_ids && I != 1) return CP_ERR_INVALID;
+  if (vs_misaligned(scratch, 15) || vs_misaligned(pose_est, 7) || vs_misaligned(pose_gt, 7) || vs_misaligned(cam_K, 7) ||
+      vs_misaligned(diameters, 7) || vs_misaligned(errors, 7) || vs_misaligned(verts, 3) || vs_misaligned(v_offsets, 3) ||
+      vs_misaligned(faces, 3) || vs_misaligned(f_offsets, 3) || vs_misaligned(mesh_ids, 3) || vs_misaligned(depth_test, 3) ||
+      vs_misaligned(image_ids, 3) || vs_misaligned(counts, 3) || vs_misaligned(depth_out, 3))
+    return CP_ERR_ALIGN;
+  VsParams p = {};
+  p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
+  p.f_off = f_offsets; p.M = M; p.mesh_id = mesh_ids; p.depth_test = depth_test; p.image_id = image_ids; p.I = I; p.H = H; p.W = W;
+  p.delta = (float)delta; p.diameters = diameters; p.T = T; p.normalise = normalized_by_diameter ? 1 : 0; p.sphere = sphere_check ? 1 : 0;
+  p.B = B; p.Vmax = Vmax; p.errors = errors; p.counts = counts; p.depth_out = depth_out; p.mode = VS_MODE_VSD; p.nsides = 2;
+  for (int k = 0; k < T; ++k) p.taus[k] = taus[k];
+  vs_carve(p, scratch);
+  return vs_launch(p, (hipStream_t)stream);
+}
+
+extern "C" int cp_vsd_from_depth(cp_stream_t stream, const float* depth_est, const float* depth_gt, const double* cam_K, int k_stride,
+                                 const float* depth_test, const int32_t* image_ids, int I, int H, int W, double delta,
+                                 const double* diameters, const double* taus, int T, int normalized_by_diameter, int B, double* errors,
+                                 int32_t* counts, void* scratch) {
+  if (!depth_est || !depth_gt || !cam_K || !depth_test || !diameters || !taus || !errors || !counts || !scratch) return CP_ERR_INVALID;
+  if (B <= 0 || I <= 0 || H <= 0 || W <= 0 || T < 1 || T > VS_TMAX || (k_stride != 0 && k_stride != 9) || !(delta == delta))
+    return CP_ERR_INVALID;
+  if (!image_ids && I != 1) return CP_ERR_INVALID;
+  if (vs_misaligned(scratch, 15) || vs_misaligned(cam_K, 7) || vs_misaligned(diameters, 7) || vs_misaligned(errors, 7) ||
+      vs_misaligned(depth_est, 3) || vs_misaligned(depth_gt, 3) || vs_misaligned(depth_test, 3) || vs_misaligned(image_ids, 3) ||
+      vs_misaligned(counts, 3))
+    return CP_ERR_ALIGN;
+  VsParams p = {};
+  p.in_est = depth_est; p.in_gt = depth_gt; p.K = cam_K; p.k_stride = k_stride; p.depth_test = depth_test; p.image_id = image_ids;
+  p.I = I; p.H = H; p.W = W; p.delta = (float)delta; p.diameters = diameters; p.T = T; p.normalise = normalized_by_diameter ? 1 : 0;
+  p.B = B; p.Vmax = 0; p.errors = errors; p.counts = counts; p.mode = VS_MODE_DEPTH; p.nsides = 2;
+  for (int k = 0; k < T; ++k) p.taus[k] = taus[k];
+  vs_carve(p, scratch);
+  return vs_launch(p, (hipStream_t)stream);
+}
+
+extern "C" int cp_render_depth(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                               const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                               int H, int W, int B, int Vmax, float* depth_out, void* scratch) {
+  if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !depth_out || !scratch) return CP_ERR_INVALID;
+  if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
+  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
+  if (vs_misaligned(scratch, 15) || vs_misaligned(poses, 7) || vs_misaligned(cam_K, 7) || vs_misaligned(verts, 3) ||
+      vs_misaligned(v_offsets, 3) || vs_misaligned(faces, 3) || vs_misaligned(f_offsets, 3) || vs_misaligned(mesh_ids, 3) ||
+      vs_misaligned(depth_out, 3))
+    return CP_ERR_ALIGN;
+  VsParams p = {};
+  p.est = poses; p.gt = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
+  p.f_off = f_offsets; p.M = M; p.mesh_id = mesh_ids; p.H = H; p.W = W; p.B = B; p.Vmax = Vmax; p.depth_out = depth_out;
+  p.mode = VS_MODE_RENDER; p.nsides = 1; p.T = 1;
+  vs_carve(p, scratch);
+  return vs_launch(p, (hipStream_t)stream);
+}

@@ -6,6 +6,7 @@ scripts (test.py:378-427, test_lm.py:300-321, compute_auc_posecnn test.py:37-57)
   MeshSet                                the packed vertex table of several objects, uploaded once, with their diameters
   compute_auc_posecnn, summarize         pass rates at 2 / 5 / 10 % of the diameter and the PoseCNN AUC (host: one float per image)
   bop_errors, mssd / mspd / proj, SymmetrySet, bop_recall, summarize_bop      BOP's MSSD / MSPD / projection error (row N7): below
+  vsd_errors, vsd, render_depth, vsd_from_depth                               BOP's VSD with its depth rasteriser (row N8): below
 
 ADI is an all-pairs search: V^2 distance evaluations per pose and no spatial index.  Measured on one MI355X (tools/pose_error_bench.py,
 profiles/pose_error_bench.json): one pose takes 0.16 / 0.36 / 1.44 ms at 4 096 / 20 480 / 61 440 vertices, 256 poses 0.60 / 11.6 / 101 ms
@@ -48,19 +49,25 @@ class MeshSet:
     """The vertices of M objects packed into one (sumV, 3) fp32 table + (M + 1) int32 offsets (cp_pose_errors' layout), and their
     diameters.  Built on the host; the device copies are made once per device on first use."""
 
-    def __init__(self, verts, offsets, diameters):
+    def __init__(self, verts, offsets, diameters, faces=None, face_offsets=None):
         self.verts = verts                  # (sumV, 3) float32 CPU tensor
         self.offsets = offsets              # (M + 1,) int32 CPU tensor
         self.diameters = diameters          # (M,) float64 numpy
         self.sizes = np.diff(offsets.numpy()).astype(np.int64)
+        self.faces = faces                  # (sumF, 3) int32 CPU tensor, vertex indices local to each mesh, or None (VSD needs them)
+        self.face_offsets = face_offsets    # (M + 1,) int32 CPU tensor, or None
         self._dev = {}
+        self._dev_faces = {}
 
     @classmethod
-    def from_arrays(cls, arrays, diameters=None):
+    def from_arrays(cls, arrays, diameters=None, faces=None):
         """arrays: a list of (V_m, 3) arrays / tensors (or ONE such array); diameters: one per mesh, or None = computed as the
-        reference does (largest pairwise distance of the vertices)"""
+        reference does (largest pairwise distance of the vertices); faces: None, or one (F_m, 3) integer array of vertex indices
+        per mesh (or ONE such array with one mesh) -- the triangles vsd_errors / render_depth rasterise"""
         if torch.is_tensor(arrays) or isinstance(arrays, np.ndarray):
             arrays = [arrays]
+            if faces is not None and (torch.is_tensor(faces) or isinstance(faces, np.ndarray)):
+                faces = [faces]
         host = []
         for a in arrays:
             a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
@@ -78,20 +85,52 @@ class MeshSet:
         diameters = np.asarray(diameters, dtype=np.float64).reshape(-1)
         if diameters.shape[0] != len(host):
             raise ValueError("need one diameter per mesh")
-        return cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters)
+        ftab = foff = None
+        if faces is not None:
+            faces = list(faces)
+            if len(faces) != len(host):
+                raise ValueError("need one face array per mesh")
+            fhost = []
+            for f, a in zip(faces, host):
+                f = f.detach().cpu().numpy() if torch.is_tensor(f) else np.asarray(f)
+                if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
+                    raise ValueError("faces must be (F, 3) integer arrays, got %r %s" % (f.shape, f.dtype))
+                if f.shape[0] and (f.min() < 0 or f.max() >= a.shape[0]):
+                    raise ValueError("a face names a vertex outside 0..%d" % (a.shape[0] - 1))
+                fhost.append(np.ascontiguousarray(f, dtype=np.int32))
+            fo = np.zeros(len(fhost) + 1, dtype=np.int64)
+            fo[1:] = np.cumsum([f.shape[0] for f in fhost])
+            if fo[-1] >= 2 ** 31 // 3:
+                raise ValueError("face table too large for int32 offsets")
+            ftab = torch.from_numpy(np.concatenate(fhost, 0).reshape(-1, 3)) if fo[-1] else torch.zeros((1, 3), dtype=torch.int32)
+            foff = torch.from_numpy(fo.astype(np.int32))
+        return cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters, ftab, foff)
 
     def __len__(self):
         return int(self.offsets.numel()) - 1
 
-    def on(self, device):
-        """(verts, offsets) on `device`, uploaded on the first call"""
+    def _key(self, device):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+        return (device.type, device.index if device.index is not None else torch.cuda.current_device())
+
+    def on(self, device):
+        """(verts, offsets) on `device`, uploaded on the first call"""
+        key = self._key(device)
         if key not in self._dev:
             self._dev[key] = (self.verts.to(device), self.offsets.to(device))
         return self._dev[key]
+
+    def faces_on(self, device):
+        """(faces, face offsets, diameters) on `device`, uploaded on the first call; ValueError without a face table"""
+        if self.faces is None:
+            raise ValueError("this MeshSet has no faces: build it with MeshSet.from_arrays(..., faces=...) to render it")
+        key = self._key(device)
+        if key not in self._dev_faces:
+            self._dev_faces[key] = (self.faces.to(device), self.face_offsets.to(device),
+                                    torch.from_numpy(np.ascontiguousarray(self.diameters, dtype=np.float64)).to(device))
+        return self._dev_faces[key]
 
 
 def _as_poses(R, t, B=None):
@@ -477,6 +516,8 @@ def bop_thresholds(kind):
         return np.arange(0.05, 0.51, 0.05)
     if kind == "mspd":
         return np.arange(5, 51, 5)
+    if kind == "vsd":                                      # eval_bop19_pose.py:31,34: vsd_taus and its correct_th are the same ten values
+        return np.arange(0.05, 0.51, 0.05)
     raise ValueError("%r has no default thresholds (BOP'19 scores \"mssd\" and \"mspd\"): pass `thresholds`" % (kind,))
 
 
@@ -488,8 +529,10 @@ def bop_recall(errors, kind, diameters=None, im_width=None, thresholds=None, mes
       default bop_thresholds(kind).  A pose is correct when error < threshold, STRICT; NaN is a miss.
     -> {"thresholds", "correct": (n, T) bool, "recall": (T,), "AR_<KIND>": their mean, "count"} and, with mesh_ids,
        "per_mesh": {mesh id -> {"recall", "AR_<KIND>", "count"}}."""
+    if kind == "vsd":
+        return _vsd_recall(errors, thresholds, mesh_ids)
     if kind not in BOP_KINDS:
-        raise ValueError("kind must be among %s, got %r" % (sorted(BOP_KINDS), kind))
+        raise ValueError("kind must be among %s, got %r" % (sorted(BOP_KINDS) + ["vsd"], kind))
     e = _to_numpy(errors).astype(np.float64).reshape(-1)
     n = e.shape[0]
     ids = None if mesh_ids is None else _to_numpy(mesh_ids).astype(np.int64).reshape(-1)
@@ -519,10 +562,34 @@ def bop_recall(errors, kind, diameters=None, im_width=None, thresholds=None, mes
     return res
 
 
+def _vsd_recall(errors, thresholds, mesh_ids):
+    """bop_recall(.., "vsd"): errors (n, T), one column per tau (vsd_errors' "vsd"); a pose is correct for the pair (tau, threshold)
+    when its error at that tau < threshold, STRICT; NaN is a miss (eval_calc_scores.py:246-263 run once per tau).
+    -> {"thresholds", "correct": (n, T, Th) bool, "recall": (T, Th), "AR_VSD": their mean over all pairs, "count"} (+ "per_mesh")"""
+    e = _to_numpy(errors).astype(np.float64)
+    if e.ndim != 2:
+        raise ValueError("VSD errors must be (n, T), one column per tau; got %r" % (e.shape,))
+    th = bop_thresholds("vsd") if thresholds is None else np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    correct = e[:, :, None] < th[None, None, :]
+    ids = None if mesh_ids is None else _to_numpy(mesh_ids).astype(np.int64).reshape(-1)
+
+    def block(sel):
+        c = correct[sel]
+        rec = c.mean(0) if c.shape[0] else np.full(correct.shape[1:], np.nan)
+        return {"recall": rec, "AR_VSD": float(rec.mean()), "count": int(c.shape[0])}
+
+    res = block(np.ones(e.shape[0], bool))
+    res.update({"thresholds": th, "correct": correct})
+    if ids is not None:
+        res["per_mesh"] = {int(m): block(ids == m) for m in np.unique(ids)}
+    return res
+
+
 def summarize_bop(errors, diameters=None, im_width=None, mesh_ids=None, thresholds=None):
     """bop_recall of every kind in `errors` (the dict bop_errors returns; other keys, e.g. "add", are ignored; "proj" only when
     `thresholds` names it).  thresholds: optional dict kind -> thresholds.
-    -> {kind: bop_recall's dict} plus "AR_MSSD" / "AR_MSPD" at the top.  BOP's AR also averages VSD, which needs a renderer."""
+    -> {kind: bop_recall's dict} plus "AR_MSSD" / "AR_MSPD" at the top.  With "vsd" in `errors` (vsd_errors' (n, T) array) also
+    "vsd" / "AR_VSD", and -- when all three are there -- "AR" = mean(AR_VSD, AR_MSSD, AR_MSPD) (eval_bop19_pose.py:243)."""
     thresholds = thresholds or {}
     res = {}
     for kind in BOP_KINDS:
@@ -530,19 +597,242 @@ def summarize_bop(errors, diameters=None, im_width=None, mesh_ids=None, threshol
             continue
         res[kind] = bop_recall(errors[kind], kind, diameters=diameters, im_width=im_width, thresholds=thresholds.get(kind), mesh_ids=mesh_ids)
         res["AR_" + kind.upper()] = res[kind]["AR_" + kind.upper()]
+    if "vsd" in errors:
+        res["vsd"] = bop_recall(errors["vsd"], "vsd", thresholds=thresholds.get("vsd"), mesh_ids=mesh_ids)
+        res["AR_VSD"] = res["vsd"]["AR_VSD"]
+        if "AR_MSSD" in res and "AR_MSPD" in res:
+            res["AR"] = float(np.mean([res["AR_VSD"], res["AR_MSSD"], res["AR_MSPD"]]))
     if not res:
-        raise ValueError("errors holds none of \"mssd\", \"mspd\" (or \"proj\" with thresholds)")
+        raise ValueError("errors holds none of \"mssd\", \"mspd\", \"vsd\" (or \"proj\" with thresholds)")
     return res
 
 
-def score_poses(R_est, t_est, R_gt, t_gt, cam_K, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None):
-    """pose_errors and / or bop_errors by the kinds asked (postprocess.evaluate_poses, targets.evaluate_batch): kinds of "add" / "adi"
-    alone are exactly pose_errors -- nothing else is launched."""
+def score_poses(R_est, t_est, R_gt, t_gt, cam_K, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None, depth_test=None,
+                image_ids=None, **vsd_kwargs):
+    """pose_errors, bop_errors and / or vsd_errors by the kinds asked (postprocess.evaluate_poses, targets.evaluate_batch): kinds of
+    "add" / "adi" alone are exactly pose_errors -- nothing else is launched.  "vsd" needs `depth_test` (and a MeshSet with faces);
+    vsd_kwargs (delta, taus, normalized_by_diameter, sphere_check) go to vsd_errors; its (B, T) errors come back under "vsd"."""
     names = [kinds] if isinstance(kinds, str) else list(kinds)
+    want_vsd = "vsd" in names
+    names = [k for k in names if k != "vsd"]
+    if want_vsd and depth_test is None:
+        raise ValueError("kind \"vsd\" needs depth_test")
     bop = [k for k in names if k in BOP_KINDS]
-    if not bop:
+    if not bop and not want_vsd:
         return pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=kinds)
     rest = [k for k in names if k not in BOP_KINDS]
     out = pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=rest) if rest else {}
-    out.update(bop_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, symmetries=symmetries, mesh_ids=mesh_ids, kinds=bop))
+    if bop:
+        out.update(bop_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, symmetries=symmetries, mesh_ids=mesh_ids, kinds=bop))
+    if want_vsd:
+        out["vsd"] = vsd_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, depth_test, image_ids=image_ids, mesh_ids=mesh_ids,
+                                **vsd_kwargs)["vsd"]
     return out
+
+
+# ---- BOP's VSD (SURVEY.md 8f, row N8; cp_vsd_errors) ------------------------------------------------------------------------------------
+# The twin of bop_toolkit_lib/pose_error.py:17-93 (vsd) with the renderer it asks for: a depth rasteriser in HIP fused with the
+# reference's pixel counting.  The reference's own renderers (vispy / OpenGL / the C++ bop_renderer) do not run here.
+#   vsd_errors(...)                        batched, on device tensors -- takes what solve_pnp_ransac returns, and depth images
+#   vsd                                    bop_toolkit's name and signature (one pose; `renderer` is a MeshSet with faces)
+#   render_depth                           the rasteriser alone
+#   bop_recall(.., "vsd"), summarize_bop   recall per (tau, threshold) pair, AR_VSD and BOP'19's AR
+def _vsd_common(R, t, cam_K, meshes, mesh_ids):
+    if not (torch.is_tensor(R) and torch.is_tensor(t) and R.is_cuda and t.is_cuda):
+        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    if not isinstance(meshes, MeshSet):
+        raise ValueError("VSD renders triangles: pass a MeshSet built with faces")
+    if meshes.faces is None:
+        raise ValueError("this MeshSet has no faces: build it with MeshSet.from_arrays(..., faces=...) to render it")
+    dev = R.device
+    poses = _as_poses(R, t)
+    B = poses.shape[0]
+    if B == 0:
+        raise ValueError("no poses")
+    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
+    if tuple(K.shape) == (3, 3):
+        K, k_stride = K.reshape(9).contiguous(), 0
+    elif tuple(K.shape) == (B, 3, 3):
+        K, k_stride = K.reshape(B, 9).contiguous(), 9
+    else:
+        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
+    M = len(meshes)
+    if mesh_ids is None:
+        if M != 1:
+            raise ValueError("several meshes need mesh_ids")
+        ids, vmax = None, int(meshes.sizes[0])
+    elif torch.is_tensor(mesh_ids) and mesh_ids.is_cuda:
+        if mesh_ids.numel() != B:
+            raise ValueError("mesh_ids must be (B,)")
+        ids, vmax = mesh_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous(), int(meshes.sizes.max())
+    else:
+        ids_host = np.asarray(mesh_ids).reshape(-1).astype(np.int64)
+        if ids_host.shape[0] != B or ids_host.min() < 0 or ids_host.max() >= M:
+            raise ValueError("mesh_ids must be (B,) with values in 0..%d" % (M - 1))
+        ids, vmax = torch.from_numpy(ids_host.astype(np.int32)).to(dev), int(meshes.sizes[np.unique(ids_host)].max())
+    return dev, poses, B, K, k_stride, M, ids, vmax
+
+
+def _vsd_images(depth_test, image_ids, B, dev):
+    d = torch.as_tensor(depth_test)
+    if d.dim() == 2:
+        d = d[None]
+    if d.dim() != 3:
+        raise ValueError("depth_test must be (H,W) or (I,H,W), got %r" % (tuple(d.shape),))
+    d = d.to(device=dev, dtype=torch.float32).contiguous()
+    n_img = int(d.shape[0])
+    if image_ids is None:
+        if n_img == 1:
+            img = None
+        elif n_img == B:
+            img = torch.arange(B, dtype=torch.int32, device=dev)
+        else:
+            raise ValueError("%d depth images for %d poses need image_ids" % (n_img, B))
+    elif torch.is_tensor(image_ids) and image_ids.is_cuda:        # stays on the device: an id outside 0..I-1 scores NaN
+        if image_ids.numel() != B:
+            raise ValueError("image_ids must be (B,)")
+        img = image_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
+    else:
+        host = np.asarray(image_ids).reshape(-1).astype(np.int64)
+        if host.shape[0] != B or host.min() < 0 or host.max() >= n_img:
+            raise ValueError("image_ids must be (B,) with values in 0..%d" % (n_img - 1))
+        img = torch.from_numpy(host.astype(np.int32)).to(dev)
+    return d, img, n_img
+
+
+def _vsd_taus(taus):
+    import ctypes as C
+    tv = bop_thresholds("vsd") if taus is None else np.asarray(taus, dtype=np.float64).reshape(-1)
+    if not 1 <= tv.shape[0] <= 16 or not np.isfinite(tv).all():
+        raise ValueError("taus: 1 to 16 finite values")
+    return tv, (C.c_double * tv.shape[0])(*tv.tolist())
+
+
+def vsd_errors(R_est, t_est, R_gt, t_gt, cam_K, meshes, depth_test, image_ids=None, delta=15.0, taus=None, normalized_by_diameter=True,
+               mesh_ids=None, sphere_check=True, return_counts=False, return_depth=False):
+    """BOP's VSD of B poses against their ground truth, rendered and counted on the device (cp_vsd_errors).
+      R_est, t_est: (B,3,3) / (B,3,1) CUDA tensors; R_gt, t_gt: the same shapes (tensors or host arrays); cam_K: (3,3) or (B,3,3);
+      meshes: a MeshSet built with faces (with several meshes, mesh_ids (B,) names each pose's);  depth_test: (H,W) or (I,H,W) depth
+      images in the vertices' units (mm; 0 = no measurement), image_ids (B,) names each pose's image (default: the one image, or
+      image b for pose b when I == B);  delta: the visibility tolerance (15 mm for lm / lmo / ycbv);  taus: default
+      bop_thresholds("vsd");  sphere_check: the shortcut of bop_toolkit's caller (eval_calc_errors.py:299-318) -- a pose whose
+      sphere projection does not overlap the ground truth's is not rendered and scores 1.0 at every tau.
+    A pose with a NaN / inf entry, a device-side mesh / image id out of range, or any vertex at Z <= 0 scores NaN (a miss).
+    -> {"vsd": (B,T) float64 CUDA tensor} (+ "counts": (B,T+2) int32 = union, inter, cost count per tau; + "depth": (B,2,H,W)
+    float32 = the estimate's and the ground truth's render).  The counts are the same bits with or without the depth output."""
+    dev, est, B, K, k_stride, M, ids, vmax = _vsd_common(R_est, t_est, cam_K, meshes, mesh_ids)
+    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
+    d, img, n_img = _vsd_images(depth_test, image_ids, B, dev)
+    H, W = int(d.shape[1]), int(d.shape[2])
+    tv, ctaus = _vsd_taus(taus)
+    T = tv.shape[0]
+    verts, v_off = meshes.on(dev)
+    faces, f_off, diam = meshes.faces_on(dev)
+    lib = _abi.load()
+    err = torch.empty((B, T), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, T + 2), dtype=torch.int32, device=dev)
+    depth = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_depth else None
+    scratch = torch.empty(lib.cp_vsd_errors_scratch_bytes(B, vmax, H, W), dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_vsd_errors(st, est.data_ptr(), gt.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(),
+                                     faces.data_ptr(), f_off.data_ptr(), M, None if ids is None else ids.data_ptr(), d.data_ptr(),
+                                     None if img is None else img.data_ptr(), n_img, H, W, float(delta), diam.data_ptr(), ctaus, T,
+                                     1 if normalized_by_diameter else 0, 1 if sphere_check else 0, B, vmax, err.data_ptr(),
+                                     counts.data_ptr(), None if depth is None else depth.data_ptr(), scratch.data_ptr()),
+                   "cp_vsd_errors")
+    out = {"vsd": err}
+    if return_counts:
+        out["counts"] = counts
+    if return_depth:
+        out["depth"] = depth
+    return out
+
+
+def vsd_from_depth(depth_est, depth_gt, depth_test, cam_K, diameters, image_ids=None, delta=15.0, taus=None, normalized_by_diameter=True):
+    """vsd_errors' counting on caller-supplied renders (cp_vsd_from_depth): depth_est, depth_gt (B,H,W) float32 CUDA tensors;
+    diameters: a float or one per pose.  -> {"vsd": (B,T) f64, "counts": (B,T+2) int32}"""
+    if not (torch.is_tensor(depth_est) and torch.is_tensor(depth_gt) and depth_est.is_cuda and depth_gt.is_cuda):
+        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    if depth_est.dim() != 3 or depth_est.shape != depth_gt.shape:
+        raise ValueError("depth_est and depth_gt must both be (B,H,W)")
+    dev = depth_est.device
+    de = depth_est.to(torch.float32).contiguous()
+    dg = depth_gt.to(device=dev, dtype=torch.float32).contiguous()
+    B, H, W = (int(v) for v in de.shape)
+    if B == 0:
+        raise ValueError("no poses")
+    d, img, n_img = _vsd_images(depth_test, image_ids, B, dev)
+    if tuple(d.shape[1:]) != (H, W):
+        raise ValueError("depth_test is %r, the renders are %r" % (tuple(d.shape[1:]), (H, W)))
+    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
+    if tuple(K.shape) == (3, 3):
+        K, k_stride = K.reshape(9).contiguous(), 0
+    elif tuple(K.shape) == (B, 3, 3):
+        K, k_stride = K.reshape(B, 9).contiguous(), 9
+    else:
+        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
+    diam = np.asarray(diameters, dtype=np.float64).reshape(-1)
+    if diam.shape[0] not in (1, B):
+        raise ValueError("diameters: a float or one per pose")
+    diam = torch.from_numpy(np.array(np.broadcast_to(diam, (B,)), dtype=np.float64)).to(dev)
+    tv, ctaus = _vsd_taus(taus)
+    T = tv.shape[0]
+    lib = _abi.load()
+    err = torch.empty((B, T), dtype=torch.float64, device=dev)
+    counts = torch.empty((B, T + 2), dtype=torch.int32, device=dev)
+    scratch = torch.empty(lib.cp_vsd_errors_scratch_bytes(B, 0, H, W), dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_vsd_from_depth(st, de.data_ptr(), dg.data_ptr(), K.data_ptr(), k_stride, d.data_ptr(),
+                                         None if img is None else img.data_ptr(), n_img, H, W, float(delta), diam.data_ptr(), ctaus, T,
+                                         1 if normalized_by_diameter else 0, B, err.data_ptr(), counts.data_ptr(), scratch.data_ptr()),
+                   "cp_vsd_from_depth")
+    return {"vsd": err, "counts": counts}
+
+
+def render_depth(R, t, cam_K, meshes, size, mesh_ids=None):
+    """Depth images of B poses of `meshes` (a MeshSet with faces), rendered on the device (cp_render_depth): depth[b, y, x] is the
+    eye-space Z of the front-most surface on the ray through image point (x + 0.5, y + 0.5), 0 where there is none -- what
+    bop_toolkit's renderer.render_object(...)['depth'] holds.  size: (width, height), as bop_toolkit's renderers take it.
+    A pose with a non-finite entry or any vertex at Z <= 0 renders nothing (zeros).  -> (B,H,W) float32 CUDA tensor"""
+    dev, poses, B, K, k_stride, M, ids, vmax = _vsd_common(R, t, cam_K, meshes, mesh_ids)
+    W, H = int(size[0]), int(size[1])
+    if W <= 0 or H <= 0:
+        raise ValueError("size must be (width, height), both positive")
+    verts, v_off = meshes.on(dev)
+    faces, f_off, _ = meshes.faces_on(dev)
+    lib = _abi.load()
+    depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    scratch = torch.empty(lib.cp_vsd_errors_scratch_bytes(B, vmax, H, W), dtype=torch.uint8, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_render_depth(st, poses.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(), faces.data_ptr(),
+                                       f_off.data_ptr(), M, None if ids is None else ids.data_ptr(), H, W, B, vmax, depth.data_ptr(),
+                                       scratch.data_ptr()), "cp_render_depth")
+    return depth
+
+
+def vsd(R_est, t_est, R_gt, t_gt, depth_test, K, delta, taus, normalized_by_diameter, diameter, renderer, obj_id, cost_type="step",
+        device="cuda:0"):
+    """bop_toolkit_lib.pose_error.vsd (numpy arrays of one pose -> list of floats, one per tau), rendered and scored on the device.
+    `renderer` is a MeshSet with faces and `obj_id` the index of the object's mesh in it; `diameter` is the one the distances are
+    normalised by (it replaces the MeshSet's for this call).  Only the 'step' cost exists.  No sphere shortcut: that is the caller's."""
+    if cost_type != "step":
+        raise ValueError("only the 'step' pixel-wise matching cost is implemented")
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
+    if not isinstance(renderer, MeshSet) or renderer.faces is None:
+        raise ValueError("renderer must be a MeshSet built with faces")
+    m = int(obj_id)
+    if not 0 <= m < len(renderer):
+        raise ValueError("obj_id must be a mesh index in 0..%d" % (len(renderer) - 1))
+    v0, v1 = int(renderer.offsets[m]), int(renderer.offsets[m + 1])
+    f0, f1 = int(renderer.face_offsets[m]), int(renderer.face_offsets[m + 1])
+    one = MeshSet.from_arrays([renderer.verts[v0:v1]], diameters=[float(diameter)], faces=[renderer.faces[f0:f1]])
+    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
+    out = vsd_errors(f(R_est, (1, 3, 3)), f(t_est, (1, 3, 1)), f(R_gt, (1, 3, 3)), f(t_gt, (1, 3, 1)),
+                     np.asarray(K, dtype=np.float64).reshape(3, 3), one, np.asarray(depth_test, dtype=np.float32), delta=delta, taus=taus,
+                     normalized_by_diameter=normalized_by_diameter, sphere_check=False)
+    return [float(v) for v in out["vsd"][0].cpu()]

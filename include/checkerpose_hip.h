@@ -596,6 +596,46 @@ int cp_bop_errors(cp_stream_t stream, const double* pose_est, const double* pose
                   const int32_t* mesh_ids, int B, int Vmax, int Smax, unsigned kinds, double* mssd, double* mspd, double* proj,
                   void* scratch);
 
+/* BOP's Visible Surface Discrepancy on the device (next-row N8; csrc/vsd_error.hip; reference bop_toolkit_lib/pose_error.py:17-93 vsd,
+ * misc.py:110-163 depth_im_to_dist_im_fast, visibility.py in 'bop19' mode, the 'step' cost): a depth rasteriser fused with the
+ * reference's pixel counting, for B poses at once.
+ * Render rule (renderer_py.py:185-226, 422-555): depth[y, x] is the smallest eye-space Z > 0 at which the ray through image point
+ * (x + 0.5, y + 0.5) meets a triangle of the mesh under K' [R | t], K' = (fx, fy, cx, cy) of cam_K with skew 0; Z is the triangle
+ * plane's (perspective-correct); no back-face culling; background 0; triangles of zero area are skipped.
+ *   pose_est, pose_gt, cam_K, k_stride, verts, v_offsets, mesh_ids: as cp_bop_errors (v_offsets is required);
+ *   faces int32 (sumF,3) + f_offsets int32 (M+1): mesh m owns the rows [f_offsets[m], f_offsets[m+1]), vertex indices LOCAL to the
+ *   mesh (a triangle with an index outside [0, V_m) is skipped);
+ *   depth_test fp32 (I,H,W) in the vertices' units (mm), image_ids int32 (B) names each pose's image (NULL when I == 1);
+ *   delta: the visibility tolerance (compared in fp32, as the reference's fp32 difference is); diameters fp64 (M), device;
+ *   taus: T <= 16 doubles ON THE HOST (copied into the launch); normalized_by_diameter: |dist_gt - dist_est| / diameter first;
+ *   sphere_check != 0: the caller's shortcut of eval_calc_errors.py:299-318 -- when misc.overlapping_sphere_projections(diameter / 2,
+ *   t_est, t_gt) is false the pose is not rendered and every error is 1.0 (counts 0).
+ * Writes errors fp64 (B,T) = (count(dists >= tau) + union - inter) / union (1.0 when union == 0) and counts int32 (B,T+2) =
+ * union, inter, count per tau.  depth_out fp32 (B,2,H,W) (estimate, ground truth), or NULL: the counts do not depend on it.
+ * A pose with a non-finite entry (either pose or K), a mesh id outside [0, M), an image id outside [0, I), a mesh that is empty or
+ * larger than Vmax, or ANY vertex at Z <= 0 in either pose scores NaN in every tau (counts 0).
+ * The distance arithmetic is the reference's in fp64 (integer pixel x, y -- not the sample point); every output is a function of
+ * integer pixel counts: bit-identical from call to call, for a pose alone or in a batch, with or without depth_out.  Four launches
+ * (pose, vertex, tile, sum), nothing allocates or synchronises.  CP_ERR_RANGE: 2^24 workgroups or more (B * ceil(W/32) * ceil(H/32)
+ * tiles) -- split the batch.  scratch: cp_vsd_errors_scratch_bytes(B, Vmax, H, W) bytes, 16-byte aligned.
+ * cp_vsd_from_depth: the same counting on caller-supplied depth images depth_est, depth_gt fp32 (B,H,W); diameters fp64 (B), one
+ * per pose; scratch: cp_vsd_errors_scratch_bytes(B, 0, H, W).  Three launches (pose, tile, sum).
+ * cp_render_depth: poses + meshes -> depth_out fp32 (B,H,W) alone (a pose that is not rendered gives zeros); three launches;
+ * scratch as cp_vsd_errors. */
+size_t cp_vsd_errors_scratch_bytes(int B, int Vmax, int H, int W);
+int cp_vsd_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const double* cam_K, int k_stride,
+                  const float* verts, const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M,
+                  const int32_t* mesh_ids, const float* depth_test, const int32_t* image_ids, int I, int H, int W,
+                  double delta, const double* diameters, const double* taus, int T, int normalized_by_diameter,
+                  int sphere_check, int B, int Vmax, double* errors, int32_t* counts, float* depth_out, void* scratch);
+int cp_vsd_from_depth(cp_stream_t stream, const float* depth_est, const float* depth_gt, const double* cam_K, int k_stride,
+                      const float* depth_test, const int32_t* image_ids, int I, int H, int W, double delta,
+                      const double* diameters, const double* taus, int T, int normalized_by_diameter, int B, double* errors,
+                      int32_t* counts, void* scratch);
+int cp_render_depth(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                    const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                    int H, int W, int B, int Vmax, float* depth_out, void* scratch);
+
 /* Ground-truth side on the device (next-row N6; csrc/targets.hip).
  *
  * cp_encode_targets: the labels of the reference's data loader (bop_dataset_pytorch.py:293,356-380: project the N keypoints through
