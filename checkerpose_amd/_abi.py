@@ -206,6 +206,10 @@ SIGNATURES = {
     "cp_render_depth": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
     "cp_encode_targets": (_I, [_P, _P, _L, _P, _I, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_code_report": (_I, [_P, _P, _L, _P, _L, _P, _L, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
+    "cp_fps_scratch_bytes": (C.c_size_t, [_I, _L, _I, _I]),
+    "cp_fps": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "cp_pts_diameter_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_pts_diameter": (_I, [_P, _P, _P, _P, _I, _P, _P]),
     "cp_edgeconv_bwd_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_edgeconv_gather_max_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F]),
     "cp_index2feat_gather_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),

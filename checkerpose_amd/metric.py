@@ -60,9 +60,10 @@ class MeshSet:
         self._dev_faces = {}
 
     @classmethod
-    def from_arrays(cls, arrays, diameters=None, faces=None):
+    def from_arrays(cls, arrays, diameters=None, faces=None, device=None):
         """arrays: a list of (V_m, 3) arrays / tensors (or ONE such array); diameters: one per mesh, or None = computed as the
-        reference does (largest pairwise distance of the vertices); faces: None, or one (F_m, 3) integer array of vertex indices
+        reference does (largest pairwise distance of the vertices) -- on the host, or with `device` on that device
+        (prepare.pts_diameters: the same bits); faces: None, or one (F_m, 3) integer array of vertex indices
         per mesh (or ONE such array with one mesh) -- the triangles vsd_errors / render_depth rasterise"""
         if torch.is_tensor(arrays) or isinstance(arrays, np.ndarray):
             arrays = [arrays]
@@ -80,7 +81,10 @@ class MeshSet:
         off[1:] = np.cumsum([a.shape[0] for a in host])
         if off[-1] >= 2 ** 31:
             raise ValueError("vertex table too large for int32 offsets")
-        if diameters is None:
+        if diameters is None and device is not None:
+            from .prepare import pts_diameters
+            diameters = pts_diameters(host, device).cpu().numpy()
+        elif diameters is None:
             diameters = [calc_pts_diameter(a) for a in host]
         diameters = np.asarray(diameters, dtype=np.float64).reshape(-1)
         if diameters.shape[0] != len(host):

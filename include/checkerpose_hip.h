@@ -674,6 +674,32 @@ int cp_code_report(cp_stream_t stream, const float* pred_roi, long long roi_bstr
                    const float* gt_x, const float* gt_y, int bits, const void* mask_visib, const void* mask_full, int mask_f32, int S,
                    int B, int N, int32_t* counts, double* figures);
 
+/* Object preparation on the device (next-row N9; csrc/prepare.hip): the keypoints and the diameter every other row starts from.
+ * Both entry points take M point clouds as one fp64 table pts (sumV,3) (8-byte aligned) + offsets int32 (M+1) on the device, cloud m
+ * at rows [offsets[m], offsets[m+1]) -- MeshSet's layout in fp64 -- and offsets_host, the same M+1 values in HOST memory, read before
+ * anything is launched: offsets_host[0] == 0 and every cloud holds at least one point (CP_ERR_INVALID otherwise).  M <= 65535.
+ * All arithmetic is fp64 without contraction, square roots correctly rounded: results are numpy's bit for bit, identical from call
+ * to call and for a cloud alone or in a batch.  Coordinates must be finite (the caller checks).  Nothing allocates or synchronises.
+ *
+ * cp_fps: farthest-point sampling by the reference's rule (preprocess_data/get_fps_points.py:65-90).  Start = (max + min) / 2 of the
+ *   bounding box (not a vertex); every dist starts at (1.0 * sqrt((dx*dx + dy*dy) + dz*dz)) * 10 of the box extents; per sample
+ *   d = sqrt((ex*ex + ey*ey) + ez*ez), e = p - farthest; if d < dist: dist = d; the next sample is the FIRST index of the largest dist
+ *   (roots are compared, not squares).  npoint >= 1; npoint > V is legal (index 0 repeats once every dist is 0).
+ *   ids int32 (M,npoint): indices local to each cloud; xyz fp64 (M,npoint,3): those points.
+ *   slices: 0 = chosen from (M, largest cloud), or 1 .. 256 = the number of slices each cloud's dist is cut into (one workgroup
+ *   each; tests and measurement: the output does not depend on it).  Launches: fps_bbox_kernel, then npoint + 1 of fps_step_kernel
+ *   (cp_kernel_log lists the chain as ONE entry "fps_step_kernel x<npoint + 1>").
+ *   scratch: cp_fps_scratch_bytes(M, sumV, Vmax, slices) bytes, 8-byte aligned (Vmax = the largest cloud; 0 = bad arguments).
+ * cp_pts_diameter: diameters fp64 (M) = sqrt(max over all pairs of ((dx*dx + dy*dy) + dz*dz)) == bop_toolkit_lib.misc.calc_pts_diameter.
+ *   V^2 / 2 pair evaluations per cloud in tiles of 1024 x 1024 (pts_diameter_kernel, then pts_diameter_finish_kernel).
+ *   CP_ERR_RANGE: a cloud of more than 5792 * 1024 points.  scratch: cp_pts_diameter_scratch_bytes(M, Vmax) bytes, 8-byte aligned. */
+size_t cp_fps_scratch_bytes(int M, long long sumV, int Vmax, int slices);
+int cp_fps(cp_stream_t stream, const double* pts, const int32_t* offsets, const int32_t* offsets_host, int M, int npoint, int slices,
+           int32_t* ids, double* xyz, void* scratch);
+size_t cp_pts_diameter_scratch_bytes(int M, int Vmax);
+int cp_pts_diameter(cp_stream_t stream, const double* pts, const int32_t* offsets, const int32_t* offsets_host, int M,
+                    double* diameters, void* scratch);
+
 /* ---------------------------------------------------------------------------------------------
  * Training side: backward of the fused graph ops + the loss head of train.py:307-320.
  * Gradients are fp32; `pq` is the forward's saved GEMM output in `dtype`.
