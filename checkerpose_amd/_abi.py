@@ -204,6 +204,9 @@ SIGNATURES = {
     "cp_vsd_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P]),
     "cp_vsd_from_depth": (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cp_render_depth": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "cp_gt_info_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_gt_info": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_gt_info_from_depth": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_encode_targets": (_I, [_P, _P, _L, _P, _I, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_code_report": (_I, [_P, _P, _L, _P, _L, _P, _L, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cp_fps_scratch_bytes": (C.c_size_t, [_I, _L, _I, _I]),

@@ -7,6 +7,9 @@
 // (no back-face culling, background 0), Z taken on the triangle's plane: 1 / Z is affine in the image.  Triangles of zero area
 // are skipped.  A pose with any vertex at Z <= 0 is not rendered: its errors are NaN.
 //
+// The rasteriser's device functions (vs_krt, vs_project, vs_raster_tile) and the per-pixel distance / visibility arithmetic (vs_dist,
+// vs_visible) live in vsd_raster.h, which gt_info.hip (row N10) includes too.
+//
 // Launches (three, + one when meshes are involved):
 //   vsd_pose_kernel     per pose: P = K' [R | t] of the estimate and of the ground truth in double WITHOUT contraction, rounded to fp32
 //                       once (K' = fx, fy, cx, cy of K, skew 0, as render_object takes them); validity; the caller's
@@ -25,15 +28,10 @@
 //   vsd_sum_kernel      per pose: the tile rows the rectangles reach, summed (integers), and the quotients.
 // Every output is a function of integer counts and per-pixel values: bit-identical from call to call, for a pose alone or in a
 // batch, with or without the depth output.  No floating-point atomics, no initialised scratch beyond what vsd_pose_kernel writes.
-#include "common.h"
+#include "vsd_raster.h"
 
 namespace {
 
-constexpr int VS_THREADS = 256;
-constexpr int VS_TILE = 32;                      // pixels per tile side
-constexpr int VS_PPL = 4;                        // pixels per lane: VS_TILE * VS_TILE / VS_THREADS
-constexpr int VS_STRIP = VS_TILE / (VS_THREADS / 64);   // rows per wave (8)
-constexpr int VS_CHUNK = 256;                    // triangles set up per round (16 KiB of LDS)
 constexpr int VS_TMAX = 16;                      // taus per call
 constexpr int VS_ROW = VS_TMAX + 2;              // ints per tile row: union, inter, cost[T]
 constexpr int VS_HDR = 40;                       // 4-byte words per pose: P_est[12] P_gt[12] rect_est[4] rect_gt[4] bad[2] ok skip
@@ -64,32 +62,8 @@ struct VsParams {
   int k_stride, M, B, Vmax, H, W, I, T, normalise, sphere, mode, nsides, tx, ty, vchunks;
 };
 
-__device__ inline double vs_dot3(double a0, double a1, double a2, double b0, double b1, double b2) {
-#pragma clang fp contract(off)
-  return (a0 * b0 + a1 * b1) + a2 * b2;
-}
-
-// P = [[fx 0 cx] [0 fy cy] [0 0 1]] [R | t] in double -> fp32 (3x4 row-major)
-__device__ inline void vs_krt(double fx, double fy, double cx, double cy, const double* q, float* __restrict__ P) {
-#pragma clang fp contract(off)
-  for (int c = 0; c < 4; ++c) {
-    const double r0 = c < 3 ? q[c] : q[9], r1 = c < 3 ? q[3 + c] : q[10], r2 = c < 3 ? q[6 + c] : q[11];
-    P[c] = (float)vs_dot3(fx, 0.0, cx, r0, r1, r2);
-    P[4 + c] = (float)vs_dot3(0.0, fy, cy, r0, r1, r2);
-    P[8 + c] = (float)r2;
-  }
-}
-
 __device__ inline bool vs_mesh(const VsParams& p, int b, int& vfirst, int& V, int& ffirst, int& F, int& m) {
-  vfirst = 0; V = 0; ffirst = 0; F = 0;
-  m = p.mesh_id ? p.mesh_id[b] : 0;
-  if (m < 0 || m >= p.M) return false;
-  vfirst = p.v_off[m];
-  V = p.v_off[m + 1] - vfirst;
-  ffirst = p.f_off[m];
-  F = p.f_off[m + 1] - ffirst;
-  if (vfirst < 0 || V <= 0 || V > p.Vmax || ffirst < 0 || F < 0) { V = 0; F = 0; return false; }
-  return true;
+  return vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void vsd_pose_kernel(VsParams p) {
@@ -134,11 +108,6 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_pose_kernel(VsParams p) {
   h[35] = skip;
 }
 
-// row . (x, y, z, 1): one fma chain
-__device__ __forceinline__ float vs_affine(const float* __restrict__ r, float x, float y, float z) {
-  return fmaf(r[2], z, fmaf(r[1], y, fmaf(r[0], x, r[3])));
-}
-
 __global__ __launch_bounds__(VS_THREADS) void vsd_vertex_kernel(VsParams p) {
 #pragma clang fp contract(off)
   int blk = blockIdx.x;
@@ -151,51 +120,10 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_vertex_kernel(VsParams p) {
   vs_mesh(p, b, vfirst, V, ffirst, F, m);
   const int i = vc * VS_THREADS + threadIdx.x;
   int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN, bad = 0;
-  if (i < V) {
-    const float* __restrict__ vt = p.verts + 3 * ((size_t)vfirst + i);
-    const float* __restrict__ P = (const float*)h + 12 * s;
-    const float x = vt[0], y = vt[1], z = vt[2];
-    const float pu = vs_affine(P, x, y, z), pv = vs_affine(P + 4, x, y, z), pw = vs_affine(P + 8, x, y, z);
-    const float iz = 1.0f / pw;
-    const float u = pu / pw, v = pv / pw;
-    p.sv[((size_t)b * 2 + s) * p.Vmax + i] = make_float4(u, v, pw, iz);
-    if (!(pw > 0.f) || !isfinite(u) || !isfinite(v)) {
-      bad = 1;
-    } else {
-      // pixel x is sampled at x + 0.5: the pixels whose sample can lie inside [u_min, u_max]; clamped in float first
-      const float cu = fminf(fmaxf(u - 0.5f, -2.f), (float)p.W + 1.f), cv = fminf(fmaxf(v - 0.5f, -2.f), (float)p.H + 1.f);
-      x0 = (int)floorf(cu); x1 = (int)ceilf(cu);
-      y0 = (int)floorf(cv); y1 = (int)ceilf(cv);
-    }
-  }
-#pragma unroll
-  for (int w = 32; w > 0; w >>= 1) {
-    x0 = min(x0, __shfl_xor(x0, w, 64)); y0 = min(y0, __shfl_xor(y0, w, 64));
-    x1 = max(x1, __shfl_xor(x1, w, 64)); y1 = max(y1, __shfl_xor(y1, w, 64));
-    bad |= __shfl_xor(bad, w, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    if (x0 != INT_MAX) {
-      atomicMin(h + 24 + 4 * s, x0); atomicMin(h + 25 + 4 * s, y0);
-      atomicMax(h + 26 + 4 * s, x1); atomicMax(h + 27 + 4 * s, y1);
-    }
-    if (bad) atomicOr(h + 32 + s, 1);
-  }
-}
-
-// the reference's depth_im_to_dist_im_fast at pixel (x, y): integer x, y (NOT the sample point), float64 throughout
-__device__ __forceinline__ double vs_dist(double px, double py, float d) {
-#pragma clang fp contract(off)
-  const double dd = (double)d;
-  const double a = px * dd, c = py * dd;
-  return sqrt((a * a + c * c) + dd * dd);
-}
-
-// _estimate_visib_mask, 'bop19': (f32(dist_model) - f32(dist_test) <= delta or dist_test == 0) and dist_model > 0
-__device__ __forceinline__ bool vs_visible(double dist_test, double dist_model, float delta) {
-#pragma clang fp contract(off)
-  const float diff = (float)dist_model - (float)dist_test;
-  return (diff <= delta || dist_test == 0.0) && dist_model > 0.0;
+  if (i < V)
+    p.sv[((size_t)b * 2 + s) * p.Vmax + i] = vs_project((const float*)h + 12 * s, p.verts + 3 * ((size_t)vfirst + i), -2.f, (float)p.W + 1.f,
+                                                        -2.f, (float)p.H + 1.f, x0, y0, x1, y1, bad);
+  vs_rect_merge(x0, y0, x1, y1, bad, h + 24 + 4 * s, h + 32 + s);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
@@ -234,70 +162,10 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
   } else {
     int vfirst, V, ffirst, F, m;
     vs_mesh(p, b, vfirst, V, ffirst, F, m);
-    const float fx0 = (float)ox + 0.5f, fy0 = (float)oy + 0.5f;     // the tile's first sample point (exact in fp32)
-    const float wy0 = (float)(wave * VS_STRIP), wy1 = wy0 + (float)(VS_STRIP - 1);
 #pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      if (!hit[s]) continue;                                         // (uniform)
-      float best[VS_PPL];
-#pragma unroll
-      for (int k = 0; k < VS_PPL; ++k) best[k] = 0.f;                   // the largest 1 / Z so far: max is exact in any order
-      const float4* __restrict__ sv = p.sv + ((size_t)b * 2 + s) * p.Vmax;
-      for (int f0 = 0; f0 < F; f0 += VS_CHUNK) {
-        __syncthreads();
-        if (tid == 0) s_n = 0;
-        __syncthreads();
-        const int f = f0 + tid;
-        if (f < F) {
-#pragma clang fp contract(off)
-          const int32_t* __restrict__ fi = p.faces + 3 * ((size_t)ffirst + f);
-          const int i0 = fi[0], i1 = fi[1], i2 = fi[2];
-          if (i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V) {
-            const float4 a = sv[i0], c = sv[i1], d = sv[i2];
-            const float ax = a.x - fx0, ay = a.y - fy0, cx = c.x - fx0, cy = c.y - fy0, dx = d.x - fx0, dy = d.y - fy0;
-            const float xmin = fminf(ax, fminf(cx, dx)), xmax = fmaxf(ax, fmaxf(cx, dx));
-            const float ymin = fminf(ay, fminf(cy, dy)), ymax = fmaxf(ay, fmaxf(cy, dy));
-            // twice the signed area; its sign turns every edge function non-negative inside
-            const float area = (cx - ax) * (dy - ay) - (dx - ax) * (cy - ay);
-            if (area != 0.f && xmax >= 0.f && xmin <= (float)(VS_TILE - 1) && ymax >= 0.f && ymin <= (float)(VS_TILE - 1)) {
-              const float sg = area > 0.f ? 1.f : -1.f, ia = 1.0f / area;
-              // edge i is opposite vertex i: E(q) = (x_b - x_a)(q_y - y_a) - (y_b - y_a)(q_x - x_a)
-              const float e0a = -(dy - cy), e0b = dx - cx, e0c = (dy - cy) * cx - (dx - cx) * cy;     // c -> d
-              const float e1a = -(ay - dy), e1b = ax - dx, e1c = (ay - dy) * dx - (ax - dx) * dy;     // d -> a
-              const float e2a = -(cy - ay), e2b = cx - ax, e2c = (cy - ay) * ax - (cx - ax) * ay;     // a -> c
-              // 1 / Z = iz_a + (E1 (iz_c - iz_a) + E2 (iz_d - iz_a)) / area
-              const float g1 = (c.w - a.w) * ia, g2 = (d.w - a.w) * ia;
-              const float pa = e1a * g1 + e2a * g2, pb = e1b * g1 + e2b * g2, pc = a.w + (e1c * g1 + e2c * g2);
-              const int at = atomicAdd(&s_n, 1);
-              s_tri[at][0] = make_float4(sg * e0a, sg * e0b, sg * e0c, ymin);
-              s_tri[at][1] = make_float4(sg * e1a, sg * e1b, sg * e1c, ymax);
-              s_tri[at][2] = make_float4(sg * e2a, sg * e2b, sg * e2c, 0.f);
-              s_tri[at][3] = make_float4(pa, pb, pc, 0.f);
-            }
-          }
-        }
-        __syncthreads();
-        const int n = s_n;
-        for (int j = 0; j < n; ++j) {
-          const float4 q0 = s_tri[j][0], q1 = s_tri[j][1];           // every lane reads the same address: a broadcast
-          const float tymin = __builtin_amdgcn_readfirstlane(q0.w), tymax = __builtin_amdgcn_readfirstlane(q1.w);
-          if (tymax < wy0 || tymin > wy1) continue;                  // wave-uniform: the triangle misses this wave's strip
-          const float4 q2 = s_tri[j][2], q3 = s_tri[j][3];
-          const float qx = (float)lx;
-#pragma unroll
-          for (int k = 0; k < VS_PPL; ++k) {
-            const float qy = (float)(ly0 + 2 * k);
-            const float w0 = fmaf(q0.x, qx, fmaf(q0.y, qy, q0.z));
-            const float w1 = fmaf(q1.x, qx, fmaf(q1.y, qy, q1.z));
-            const float w2 = fmaf(q2.x, qx, fmaf(q2.y, qy, q2.z));
-            const float iz = fmaf(q3.x, qx, fmaf(q3.y, qy, q3.z));
-            if (w0 >= 0.f && w1 >= 0.f && w2 >= 0.f && iz > best[k]) best[k] = iz;
-          }
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < VS_PPL; ++k) dep[s][k] = best[k] > 0.f ? 1.0f / best[k] : 0.f;      // one correctly rounded division per pixel
-    }
+    for (int s = 0; s < 2; ++s)
+      if (hit[s])                                                    // (uniform)
+        vs_raster_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, ox, oy, tid, lx, ly0, wave, dep[s]);
   }
 
   if (p.depth_out) {

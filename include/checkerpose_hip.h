@@ -636,6 +636,40 @@ int cp_render_depth(cp_stream_t stream, const double* poses, const double* cam_K
                     const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
                     int H, int W, int B, int Vmax, float* depth_out, void* scratch);
 
+/* BOP ground-truth info and masks on the device (next-row N10; csrc/gt_info.hip; reference bop_toolkit scripts/calc_gt_info.py:72-175
+ * and scripts/calc_gt_masks.py:94-127): what scene_gt_info.json, mask/ and mask_visib/ hold, for B ground-truth poses at once.
+ * The object is rendered (cp_vsd_errors' render rule and rasteriser, csrc/vsd_raster.h) on the frame's pixel grid EXTENDED to
+ * x in [-W, 2W), y in [-H, 2H) -- the reference's 3W x 3H canvas with the principal point moved by (W, H), in frame coordinates.
+ * The canvas's 32 x 32 tile grid starts at (-32 ceil(W/32), -32 ceil(H/32)): frame pixel (0, 0) is a tile corner, and the in-frame
+ * depth is bit-identical to cp_render_depth's at (H, W).
+ *   poses fp64 (B,12) [R row-major | t]; cam_K, k_stride, verts, v_offsets, faces, f_offsets, M, mesh_ids, Vmax: as cp_render_depth;
+ *   depth fp32 (I,H,W), the sensor's depth in the vertices' units (mm; 0 = no measurement), image_ids int32 (B) (NULL when I == 1);
+ *   delta: the visibility tolerance, compared in fp32 as in cp_vsd_errors.
+ * With dist_gt / dist_im = depth_im_to_dist_im_fast of the in-frame render / of depth (fp64, integer pixel x, y):
+ *   mask = dist_gt > 0;  mask_visib = (f32(dist_gt) - f32(dist_im) <= delta or dist_im == 0) and dist_gt > 0   ('bop19')
+ *   counts int32 (B,3) = px_count_all (canvas pixels with depth > 0), px_count_valid (mask pixels with dist_im > 0), px_count_visib;
+ *   visib_fract fp64 (B) = visib / (double)all, 0.0 when all == 0;
+ *   boxes int32 (B,2,4) = bbox_obj (the canvas silhouette, frame coordinates, not clipped), bbox_visib (of mask_visib): each
+ *   [xmin, ymin, xmax - xmin, ymax - ymin]; BOTH are -1 -1 -1 -1 unless px_count_visib > 0;
+ *   ok uint8 (B): 0 for a pose that is not rendered -- a non-finite entry (pose or K), a mesh id outside [0, M), an image id outside
+ *   [0, I), a mesh that is empty or larger than Vmax, or ANY vertex at Z <= 0: counts 0, visib_fract 0, boxes -1, images 0;
+ *   mask, mask_visib uint8 (B,H,W) holding 0 / 255 (both or neither; NULL to skip), depth_gt fp32 (B,H,W) the in-frame render (or NULL).
+ * Tiles outside the pose's vertex rectangle leave at once, the canvas margin does no distance arithmetic, no image is stored unless
+ * asked.  Integer reductions only (wave shuffles, LDS, order-independent integer atomics): every output is bit-identical from call
+ * to call, for a pose alone or in a batch, with or without the optional images.  Four launches (pose, vertex, tile, finish), nothing
+ * allocates or synchronises.  CP_ERR_RANGE: 2^24 workgroups or more (B * 9 ceil(W/32) ceil(H/32) tiles at most) -- split the batch.
+ * scratch: cp_gt_info_scratch_bytes(B, Vmax) bytes, 16-byte aligned.
+ * cp_gt_info_from_depth: the same counting on a caller-supplied canvas depth_gt_large fp32 (B,3H,3W) (frame pixel (x, y) is
+ * [y + H][x + W]); three launches (pose, tile, finish); scratch: cp_gt_info_scratch_bytes(B, 0). */
+size_t cp_gt_info_scratch_bytes(int B, int Vmax);
+int cp_gt_info(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+               const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+               const float* depth, const int32_t* image_ids, int I, int H, int W, double delta, int B, int Vmax, int32_t* counts,
+               double* visib_fract, int32_t* boxes, uint8_t* ok, uint8_t* mask, uint8_t* mask_visib, float* depth_gt, void* scratch);
+int cp_gt_info_from_depth(cp_stream_t stream, const float* depth_gt_large, const double* cam_K, int k_stride, const float* depth,
+                          const int32_t* image_ids, int I, int H, int W, double delta, int B, int32_t* counts, double* visib_fract,
+                          int32_t* boxes, uint8_t* ok, uint8_t* mask, uint8_t* mask_visib, void* scratch);
+
 /* Ground-truth side on the device (next-row N6; csrc/targets.hip).
  *
  * cp_encode_targets: the labels of the reference's data loader (bop_dataset_pytorch.py:293,356-380: project the N keypoints through
