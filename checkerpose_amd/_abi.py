@@ -13,6 +13,7 @@ ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 LOSS_BCE, LOSS_L1 = 0, 1
 POSE_ERR_ADD, POSE_ERR_ADI = 1, 2
 BOP_ERR_MSSD, BOP_ERR_MSPD, BOP_ERR_PROJ, BOP_MAP_SMALL, BOP_MAP_LARGE = 1, 2, 4, 16, 32
+BOP_MATCH_NO_LDS, BOP_MATCH_SCRATCH_MASK, BOP_SCORES_NO_LDS = 1, 2, 1
 
 
 class CpConvDesc(C.Structure):
@@ -207,6 +208,9 @@ SIGNATURES = {
     "cp_gt_info_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_gt_info": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cp_gt_info_from_depth": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_bop_match_scratch_bytes": (C.c_size_t, [_I, _L, _I]),
+    "cp_bop_match": (_I, [_P, _P, _L, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _L, C.c_uint32, _P, _P, _P, _P, _P]),
+    "cp_bop_scores": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, C.c_uint32, _P]),
     "cp_encode_targets": (_I, [_P, _P, _L, _P, _I, _P, _L, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_code_report": (_I, [_P, _P, _L, _P, _L, _P, _L, _I, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P, _P]),
     "cp_fps_scratch_bytes": (C.c_size_t, [_I, _L, _I, _I]),

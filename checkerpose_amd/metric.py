@@ -532,7 +532,8 @@ def bop_recall(errors, kind, diameters=None, im_width=None, thresholds=None, mes
       per pose, or -- with mesh_ids -- one per mesh), MSPD is multiplied by 640 / im_width, proj is taken as it is;  thresholds:
       default bop_thresholds(kind).  A pose is correct when error < threshold, STRICT; NaN is a miss.
     -> {"thresholds", "correct": (n, T) bool, "recall": (T,), "AR_<KIND>": their mean, "count"} and, with mesh_ids,
-       "per_mesh": {mesh id -> {"recall", "AR_<KIND>", "count"}}."""
+       "per_mesh": {mesh id -> {"recall", "AR_<KIND>", "count"}}.
+    Several estimates or instances per target, or a targets file: checkerpose_amd.bop_eval does the matching (row N11)."""
     if kind == "vsd":
         return _vsd_recall(errors, thresholds, mesh_ids)
     if kind not in BOP_KINDS:
@@ -593,7 +594,8 @@ def summarize_bop(errors, diameters=None, im_width=None, mesh_ids=None, threshol
     """bop_recall of every kind in `errors` (the dict bop_errors returns; other keys, e.g. "add", are ignored; "proj" only when
     `thresholds` names it).  thresholds: optional dict kind -> thresholds.
     -> {kind: bop_recall's dict} plus "AR_MSSD" / "AR_MSPD" at the top.  With "vsd" in `errors` (vsd_errors' (n, T) array) also
-    "vsd" / "AR_VSD", and -- when all three are there -- "AR" = mean(AR_VSD, AR_MSSD, AR_MSPD) (eval_bop19_pose.py:243)."""
+    "vsd" / "AR_VSD", and -- when all three are there -- "AR" = mean(AR_VSD, AR_MSSD, AR_MSPD) (eval_bop19_pose.py:243).
+    One estimate per target is assumed; checkerpose_amd.bop_eval.evaluate_results matches several to several (row N11)."""
     thresholds = thresholds or {}
     res = {}
     for kind in BOP_KINDS:

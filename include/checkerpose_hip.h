@@ -670,6 +670,45 @@ int cp_gt_info_from_depth(cp_stream_t stream, const float* depth_gt_large, const
                           const int32_t* image_ids, int I, int H, int W, double delta, int B, int32_t* counts, double* visib_fract,
                           int32_t* boxes, uint8_t* ok, uint8_t* mask, uint8_t* mask_visib, void* scratch);
 
+/* BOP's matching of estimates to ground truths and its recall scores on the device (next-row N11; csrc/bop_match.hip; reference
+ * bop_toolkit_lib/pose_matching.py:9-90 match_poses and score.py:62-137 calc_localization_scores), for every (scene, image, object)
+ * group and every threshold column at once.
+ * cp_bop_match.  Group g owns the estimates [est_off[g], est_off[g+1]) of est_score fp64 (NE) / est_ids int32 (NE) -- in the order of
+ * the reference's `errs` list -- and the ground-truth slots [gt_off[g], gt_off[g+1]) in increasing gt_id; slot s writes output row
+ * gt_rows[s] (int32 (NG), a permutation; NULL = the slot itself).  Its errors are the n_e x n_g rows of errs fp64 (P, C_err) starting
+ * at row pair_off[g] (int64 (G+1)), estimate-major.  gt_valid uint8 (NG), by OUTPUT ROW (NULL = all valid).  Column c compares the
+ * error columns col_err int32 (C, E) against the thresholds col_th fp64 (C, E), E = 1 or 2.  max_ests > 0: only the first max_ests
+ * estimates in score order are matched (match_poses' max_ests_count).
+ * Semantics, exactly match_poses': estimates by decreasing score, ties in list order (a NaN score sorts last); for each, the valid
+ * and still unmatched ground truths are scanned in slot order and a candidate replaces the best so far only if EVERY element is
+ * STRICTLY below it, the best so far starting at the thresholds; NaN and inf never match.
+ * Outputs per (row, column): out_est int32 (NG, C) the matched estimate's est_ids entry or -1; out_score fp64 (NG, C); out_err and
+ * out_norm = error / threshold (fp64 division) fp64 (NG, C, E); an unmatched entry holds -1.0 (the reference's defaults).
+ * A group whose ground truths number more than 64 (or every group, with CP_BOP_MATCH_SCRATCH_MASK) keeps its matched set in
+ * ceil(n_g / 64) words of scratch starting at word mask_off[g] (int32 (G); mask_words = their total; a group whose words are missing
+ * or out of range stays unmatched, as does one whose table entries point outside NE / P).  CP_BOP_MATCH_NO_LDS reads the errors
+ * where they lie instead of staging a group's block (<= 4096 doubles) through LDS.  The flags change no output bit.
+ * One launch, a workgroup per group, a lane per column; nothing allocates or synchronises; bit-identical from call to call, for a
+ * group alone or in a batch, a column alone or among others.  scratch: cp_bop_match_scratch_bytes(NE, mask_words, C), 16-byte aligned.
+ * cp_bop_scores.  est_ids = cp_bop_match's out_est (NG, C); gt_obj / gt_scene int32 (NG): each row's index into the caller's object /
+ * scene list (a row with an index outside [0, n_obj) / [0, n_scene) counts nowhere); groups as above.  counts int32 (NB, 1 + C) laid
+ * out as [NB target counts | NB x C true positives], NB = 1 + n_obj + n_scene, bin 0 = total, 1 + o = object o, 1 + n_obj + s =
+ * scene s: targets of a group = min(n_top, its valid ground truths), or their number when n_top <= 0; true positives = valid rows
+ * with est_id != -1.  Integer reductions only (LDS bins when NB <= 128 and CP_BOP_SCORES_NO_LDS is not set, integer atomics).
+ * Three launches (zero, targets, tp).  The quotients tp / (double)targets and their means are the caller's. */
+#define CP_BOP_MATCH_NO_LDS 1u
+#define CP_BOP_MATCH_SCRATCH_MASK 2u
+#define CP_BOP_SCORES_NO_LDS 1u
+size_t cp_bop_match_scratch_bytes(int NE, long long mask_words, int C);
+int cp_bop_match(cp_stream_t stream, const double* errs, long long P, int C_err, const double* est_score, const int32_t* est_ids,
+                 int NE, const int32_t* est_off, const int32_t* gt_off, const long long* pair_off, int G, const int32_t* gt_rows,
+                 const uint8_t* gt_valid, int NG, const int32_t* col_err, const double* col_th, int C, int E, int max_ests,
+                 const int32_t* mask_off, long long mask_words, unsigned flags, int32_t* out_est, double* out_score,
+                 double* out_err, double* out_norm, void* scratch);
+int cp_bop_scores(cp_stream_t stream, const int32_t* est_ids, const uint8_t* gt_valid, const int32_t* gt_obj,
+                  const int32_t* gt_scene, int NG, const int32_t* gt_off, const int32_t* gt_rows, int G, int C, int n_obj,
+                  int n_scene, int n_top, unsigned flags, int32_t* counts);
+
 /* Ground-truth side on the device (next-row N6; csrc/targets.hip).
  *
  * cp_encode_targets: the labels of the reference's data loader (bop_dataset_pytorch.py:293,356-380: project the N keypoints through
