@@ -208,6 +208,10 @@ SIGNATURES = {
     "cp_gt_info_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_gt_info": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cp_gt_info_from_depth": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_mask_errors_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_mask_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_mask_overlap": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "cp_box_overlap": (_I, [_P, _P, _P, _I, _P]),
     "cp_bop_match_scratch_bytes": (C.c_size_t, [_I, _L, _I]),
     "cp_bop_match": (_I, [_P, _P, _L, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _I, _I, _I, _P, _L, C.c_uint32, _P, _P, _P, _P, _P]),
     "cp_bop_scores": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, C.c_uint32, _P]),

@@ -15,15 +15,18 @@ A group is one (scene, image, object) with the object's ground truths in the ima
 (tau, threshold) pair: 100 columns).  The reference runs its Python loops once per column.  The tables are organised on the host
 (dict work on a few thousand rows); errors, matching and counting run on the device.  There is no CPU fallback.
 
-Out of scope: the 'cus' / 'cou_*' errors, the COCO detection scores of eval_bop22_coco.py, score.calc_ap, VSD's 'bop18' visibility
-mode, and writing matches_*.json."""
+'cus' (row N12) is computed and scored at its own threshold 0.5 (eval_calc_scores.py:43); it is not part of AR.  The 'cou_*' errors
+have no place in the reference's scripts: metric.mask_errors / mask_overlap / box_overlap compute them.
+
+Out of scope: the COCO detection scores of eval_bop22_coco.py and calc_gt_coco.py, score.calc_ap, VSD's 'bop18' visibility mode, RGB
+rendering, and writing matches_*.json."""
 import numpy as np
 import torch
 
 from . import _abi
 from . import metric
 
-ERROR_KINDS = ("add", "adi", "ad", "mssd", "mspd", "proj", "vsd")
+ERROR_KINDS = ("add", "adi", "ad", "mssd", "mspd", "proj", "vsd", "cus")
 
 
 def _dev(device):
@@ -230,14 +233,15 @@ def _poses_of(ests, idx, dev):
 
 
 def calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=None, symmetries=None, symmetric_obj_ids=(), depths=None,
-                delta=15.0, taus=None, sphere_check=True):
+                delta=15.0, taus=None, sphere_check=True, size=None):
     """The errors of expand_pairs' pairs, on the device, by the rows that already compute them (metric.pose_errors / bop_errors /
-    vsd_errors), with eval_calc_errors.py's shortcuts: inf for "ad" / "add" / "adi" / "mssd" when |t_e - t_g| >= diameter
-    (:306-309), VSD's sphere check.
-      kind: "add", "adi", "ad" (ADI for symmetric_obj_ids, else ADD), "mssd", "mspd", "proj", "vsd";  meshes: a MeshSet (its
-      diameters are the models_info diameters; with faces for "vsd");  obj_index: {obj_id: index of its mesh};  scene_camera:
-      {scene_id: inout.load_scene_camera's dict} or one (3,3) K ("mspd", "proj", "vsd");  symmetries: as metric.bop_errors';
-      depths: {scene_id: {im_id: (H,W) depth in mm}} ("vsd");  delta, taus, sphere_check: metric.vsd_errors'.
+    vsd_errors / mask_errors), with eval_calc_errors.py's shortcuts: inf for "ad" / "add" / "adi" / "mssd" when |t_e - t_g| >=
+    diameter (:306-309), the sphere check of VSD and cus (a pair that fails it scores 1.0, :310-318, :357-362).
+      kind: "add", "adi", "ad" (ADI for symmetric_obj_ids, else ADD), "mssd", "mspd", "proj", "vsd", "cus";  meshes: a MeshSet (its
+      diameters are the models_info diameters; with faces for "vsd" / "cus");  obj_index: {obj_id: index of its mesh};  scene_camera:
+      {scene_id: inout.load_scene_camera's dict} or one (3,3) K ("mspd", "proj", "vsd", "cus");  symmetries: as metric.bop_errors';
+      depths: {scene_id: {im_id: (H,W) depth in mm}} ("vsd");  delta, taus, sphere_check: metric.vsd_errors';  size: (W, H) of the
+      frames ("cus").
     re / te / rete tables are the caller's (no kernel computes them): pass them to match() as they are.
     -> float64 CUDA tensor (P, 1), or (P, T) for "vsd", in the pairs' order."""
     if kind not in ERROR_KINDS:
@@ -258,7 +262,7 @@ def calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=None, symmetr
             raise ValueError("obj_id %r is not in obj_index" % (int(o),))
     mesh_ids = np.array([obj_index[int(o)] for o in objs], dtype=np.int64)
     K = None
-    if kind in ("mspd", "proj", "vsd"):
+    if kind in ("mspd", "proj", "vsd", "cus"):
         if scene_camera is None:
             raise ValueError("%r needs scene_camera (or one 3x3 K)" % (kind,))
         if isinstance(scene_camera, dict):
@@ -266,6 +270,10 @@ def calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=None, symmetr
                           for s, i in zip(es.gt_scene[pairs.pair_gt], es.gt_im[pairs.pair_gt])])
         else:
             K = np.asarray(scene_camera, dtype=np.float64).reshape(3, 3)
+    if kind == "cus":
+        if size is None:
+            raise ValueError("\"cus\" needs size=(W, H)")
+        return metric.mask_errors(Re, te, Rg, tg, K, meshes, size, mesh_ids=mesh_ids, kinds=("cus",), sphere_check=sphere_check)["cus"][:, None]
     if kind == "vsd":
         if depths is None:
             raise ValueError("\"vsd\" needs depths")
@@ -559,10 +567,11 @@ def calc_localization_scores(scene_ids, obj_ids, matches, n_top, do_print=False,
 
 
 def evaluate_results(evalset, ests, meshes, obj_index, scene_camera, im_width, symmetries=None, depths=None, delta=15.0,
-                     visib_gt_min=-1, kinds=("vsd", "mssd", "mspd")):
+                     visib_gt_min=-1, kinds=("vsd", "mssd", "mspd"), size=None):
     """scripts/eval_bop19_pose.py from the results table to the final scores: n_top = -1, metric.bop_thresholds' thresholds, MSSD
     divided by the diameter and MSPD multiplied by 640 / im_width before thresholding (eval_calc_scores.py:246-258), VSD over its ten
-    taus x ten thresholds.  Arguments: calc_errors'; "vsd" is scored when `depths` is given.
+    taus x ten thresholds.  Arguments: calc_errors'; "vsd" is scored when `depths` is given.  "cus" among the kinds (needs `size`)
+    is scored at its threshold 0.5 (eval_calc_scores.py:43) and reported as "AR_CUS"; it is not part of "AR".
     -> {"AR_VSD", "AR_MSSD", "AR_MSPD": the mean of the overall recall over the kind's columns, "AR": their mean (when all three are
     there), "recall": {kind: (C,) recalls, VSD tau-major}, "scores": {kind: localization_scores' dict}, "valid"}."""
     es = evalset
@@ -572,7 +581,8 @@ def evaluate_results(evalset, ests, meshes, obj_index, scene_camera, im_width, s
     for kind in kinds:
         if kind == "vsd" and depths is None:
             continue
-        errs = calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=scene_camera, symmetries=symmetries, depths=depths, delta=delta)
+        errs = calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=scene_camera, symmetries=symmetries, depths=depths, delta=delta,
+                           size=size)
         th = metric.bop_thresholds(kind)
         cols = None
         if kind == "mssd" and errs.shape[0]:

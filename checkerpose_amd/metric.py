@@ -7,6 +7,7 @@ scripts (test.py:378-427, test_lm.py:300-321, compute_auc_posecnn test.py:37-57)
   compute_auc_posecnn, summarize         pass rates at 2 / 5 / 10 % of the diameter and the PoseCNN AUC (host: one float per image)
   bop_errors, mssd / mspd / proj, SymmetrySet, bop_recall, summarize_bop      BOP's MSSD / MSPD / projection error (row N7): below
   vsd_errors, vsd, render_depth, vsd_from_depth                               BOP's VSD with its depth rasteriser (row N8): below
+  mask_errors, mask_overlap, box_overlap, cus / cou_bb_proj / cou_mask / cou_bb   BOP's overlap errors (row N12): at the end
 
 ADI is an all-pairs search: V^2 distance evaluations per pose and no spatial index.  Measured on one MI355X (tools/pose_error_bench.py,
 profiles/pose_error_bench.json): one pose takes 0.16 / 0.36 / 1.44 ms at 4 096 / 20 480 / 61 440 vertices, 256 poses 0.60 / 11.6 / 101 ms
@@ -522,22 +523,24 @@ def bop_thresholds(kind):
         return np.arange(5, 51, 5)
     if kind == "vsd":                                      # eval_bop19_pose.py:31,34: vsd_taus and its correct_th are the same ten values
         return np.arange(0.05, 0.51, 0.05)
+    if kind == "cus":                                      # eval_calc_scores.py:43
+        return np.array([0.5])
     raise ValueError("%r has no default thresholds (BOP'19 scores \"mssd\" and \"mspd\"): pass `thresholds`" % (kind,))
 
 
 def bop_recall(errors, kind, diameters=None, im_width=None, thresholds=None, mesh_ids=None):
     """Recall of one error kind over its thresholds, with ONE estimate per target as test.py produces (then BOP's greedy matching is
     the comparison alone): eval_calc_scores.py:246-263 + pose_matching.py:68.
-      errors: (n,) tensor / array of `kind` ("mssd", "mspd" or "proj");  MSSD is divided by the diameter (`diameters`: a float, one
-      per pose, or -- with mesh_ids -- one per mesh), MSPD is multiplied by 640 / im_width, proj is taken as it is;  thresholds:
+      errors: (n,) tensor / array of `kind` ("mssd", "mspd", "proj" or "cus");  MSSD is divided by the diameter (`diameters`: a float,
+      one per pose, or -- with mesh_ids -- one per mesh), MSPD is multiplied by 640 / im_width, proj and cus are taken as they are;  thresholds:
       default bop_thresholds(kind).  A pose is correct when error < threshold, STRICT; NaN is a miss.
     -> {"thresholds", "correct": (n, T) bool, "recall": (T,), "AR_<KIND>": their mean, "count"} and, with mesh_ids,
        "per_mesh": {mesh id -> {"recall", "AR_<KIND>", "count"}}.
     Several estimates or instances per target, or a targets file: checkerpose_amd.bop_eval does the matching (row N11)."""
     if kind == "vsd":
         return _vsd_recall(errors, thresholds, mesh_ids)
-    if kind not in BOP_KINDS:
-        raise ValueError("kind must be among %s, got %r" % (sorted(BOP_KINDS) + ["vsd"], kind))
+    if kind not in BOP_KINDS and kind != "cus":
+        raise ValueError("kind must be among %s, got %r" % (sorted(BOP_KINDS) + ["cus", "vsd"], kind))
     e = _to_numpy(errors).astype(np.float64).reshape(-1)
     n = e.shape[0]
     ids = None if mesh_ids is None else _to_numpy(mesh_ids).astype(np.int64).reshape(-1)
@@ -614,17 +617,21 @@ def summarize_bop(errors, diameters=None, im_width=None, mesh_ids=None, threshol
 
 
 def score_poses(R_est, t_est, R_gt, t_gt, cam_K, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None, depth_test=None,
-                image_ids=None, **vsd_kwargs):
-    """pose_errors, bop_errors and / or vsd_errors by the kinds asked (postprocess.evaluate_poses, targets.evaluate_batch): kinds of
-    "add" / "adi" alone are exactly pose_errors -- nothing else is launched.  "vsd" needs `depth_test` (and a MeshSet with faces);
-    vsd_kwargs (delta, taus, normalized_by_diameter, sphere_check) go to vsd_errors; its (B, T) errors come back under "vsd"."""
+                image_ids=None, size=None, **vsd_kwargs):
+    """pose_errors, bop_errors, vsd_errors and / or mask_errors by the kinds asked (postprocess.evaluate_poses, targets.evaluate_batch):
+    kinds of "add" / "adi" alone are exactly pose_errors -- nothing else is launched.  "vsd" needs `depth_test` (and a MeshSet with
+    faces); vsd_kwargs (delta, taus, normalized_by_diameter, sphere_check) go to vsd_errors; its (B, T) errors come back under "vsd".
+    "cus" / "cou_bb_proj" need `size` = (W, H) (and a MeshSet with faces): mask_errors, without the sphere shortcut."""
     names = [kinds] if isinstance(kinds, str) else list(kinds)
     want_vsd = "vsd" in names
-    names = [k for k in names if k != "vsd"]
+    masks = [k for k in names if k in MASK_KINDS]
+    names = [k for k in names if k != "vsd" and k not in MASK_KINDS]
     if want_vsd and depth_test is None:
         raise ValueError("kind \"vsd\" needs depth_test")
+    if masks and size is None:
+        raise ValueError("kinds \"cus\" / \"cou_bb_proj\" need size=(W, H)")
     bop = [k for k in names if k in BOP_KINDS]
-    if not bop and not want_vsd:
+    if not bop and not want_vsd and not masks:
         return pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=kinds)
     rest = [k for k in names if k not in BOP_KINDS]
     out = pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=mesh_ids, kinds=rest) if rest else {}
@@ -633,6 +640,8 @@ def score_poses(R_est, t_est, R_gt, t_gt, cam_K, vertices, mesh_ids=None, kinds=
     if want_vsd:
         out["vsd"] = vsd_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, depth_test, image_ids=image_ids, mesh_ids=mesh_ids,
                                 **vsd_kwargs)["vsd"]
+    if masks:
+        out.update(mask_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, size, mesh_ids=mesh_ids, kinds=masks))
     return out
 
 
@@ -842,3 +851,192 @@ def vsd(R_est, t_est, R_gt, t_gt, depth_test, K, delta, taus, normalized_by_diam
                      np.asarray(K, dtype=np.float64).reshape(3, 3), one, np.asarray(depth_test, dtype=np.float32), delta=delta, taus=taus,
                      normalized_by_diameter=normalized_by_diameter, sphere_check=False)
     return [float(v) for v in out["vsd"][0].cpu()]
+
+
+# ---- BOP's overlap errors (cp_mask_errors / cp_mask_overlap / cp_box_overlap) ------------------------------------
+# The twin of the last four functions of bop_toolkit_lib/pose_error.py: cou_mask :235-253, cus :256-286, cou_bb :289-297, cou_bb_proj
+# :300-330 (with misc.calc_2d_bbox / misc.iou).  With them every error of that file runs on the device.
+#   mask_errors(...)                       batched cus / cou_bb_proj: both silhouettes rasterised per tile, nothing stored unless asked
+#   mask_overlap(...)                      the counting half on caller-supplied masks: cou_mask, and cou_bb of the masks' boxes
+#   box_overlap(...)                       1 - iou of box pairs
+#   cou_mask, cou_bb, cus, cou_bb_proj     bop_toolkit's names and argument order (one pair)
+MASK_KINDS = ("cus", "cou_bb_proj")
+OVERLAP_KINDS = ("cou_mask", "cou_bb")
+
+
+def mask_errors(R_est, t_est, R_gt, t_gt, cam_K, meshes, size, mesh_ids=None, kinds=("cus", "cou_bb_proj"), sphere_check=False,
+                return_counts=False, return_boxes=False, return_masks=False):
+    """BOP's 'cus' (complement over union of the projected silhouettes) and / or 'cou_bb_proj' (of their bounding boxes) of B poses
+    against their ground truth, rendered and counted on the device (cp_mask_errors).
+      R_est, t_est: (B,3,3) / (B,3,1) CUDA tensors, e.g. straight from solve_pnp_ransac; R_gt, t_gt: the same shapes (tensors or host
+      arrays); cam_K: (3,3) or (B,3,3); meshes: a MeshSet built with faces (with several meshes, mesh_ids (B,) names each pair's);
+      size: (width, height) of the frame, as bop_toolkit's renderers take it;  kinds: any of "cus", "cou_bb_proj";
+      sphere_check: the shortcut of bop_toolkit's caller (eval_calc_errors.py:299-302,357-362), which belongs to 'cus' ALONE -- a pair
+      whose sphere projections do not overlap scores cus = 1.0 unrendered; cou_bb_proj is computed whatever the check says.
+    A silhouette pixel is set exactly where render_depth(..., size) > 0.  cus = 1 - inter / union, 1.0 when the union is empty.
+    cou_bb_proj = 1 - iou of the boxes (xmin, ymin, xmax - xmin, ymax - ymin): no + 1, not clipped; where a side's silhouette is
+    EMPTY (e.g. wholly outside the frame) the reference raises (xs.min() of nothing) -- here cou_bb_proj is NaN, a miss under the
+    strict `<` of the matching.  A pair with a NaN / inf entry, a device-side mesh id out of range, or any vertex at Z <= 0 on
+    either side scores NaN in both kinds.
+    -> dict kind -> (B,) float64 CUDA tensor; + "counts": (B,4) int32 = inter, union, n_est, n_gt and "ok": (B,) bool
+    (return_counts); + "boxes": (B,2,4) int32 = the estimate's and the ground truth's x, y, w, h, -1 where empty (return_boxes);
+    + "masks": (B,2,H,W) bool (return_masks).  A sphere-skipped pair that is not rendered (no "cou_bb_proj" among the kinds) has
+    counts 0, boxes -1 and empty masks.  The errors are the same bits with or without the optional outputs.
+    return_masks forfeits the early leave: every tile of every pair then walks its pixels to store them (zeros where nothing is
+    rendered), which is the stored-image cost the fused call otherwise avoids -- ask for masks only when they are wanted."""
+    names = [kinds] if isinstance(kinds, str) else list(kinds)
+    for k in names:
+        if k not in MASK_KINDS:
+            raise ValueError("kinds must be among %s, got %r" % (list(MASK_KINDS), k))
+    if not names:
+        raise ValueError("kinds is empty: ask for \"cus\", \"cou_bb_proj\" or both")
+    dev, est, B, K, k_stride, M, ids, vmax = _vsd_common(R_est, t_est, cam_K, meshes, mesh_ids)
+    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
+    if size is None:
+        raise ValueError("size=(width, height) is required: a MeshSet has no frame")
+    W, H = int(size[0]), int(size[1])
+    if W <= 0 or H <= 0:
+        raise ValueError("size must be (width, height), both positive")
+    verts, v_off = meshes.on(dev)
+    faces, f_off, diam = meshes.faces_on(dev)
+    lib = _abi.load()
+    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in MASK_KINDS if k in names}
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if return_counts else None
+    ok = torch.empty(B, dtype=torch.uint8, device=dev) if return_counts else None
+    boxes = torch.empty((B, 2, 4), dtype=torch.int32, device=dev) if return_boxes else None
+    masks = torch.empty((B, 2, H, W), dtype=torch.uint8, device=dev) if return_masks else None
+    scratch = torch.empty(lib.cp_mask_errors_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
+    ptr = lambda x: None if x is None else x.data_ptr()     # noqa: E731
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_mask_errors(st, est.data_ptr(), gt.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(),
+                                      faces.data_ptr(), f_off.data_ptr(), M, ptr(ids), diam.data_ptr(), H, W, 1 if sphere_check else 0,
+                                      B, vmax, ptr(out.get("cus")), ptr(out.get("cou_bb_proj")), ptr(counts), ptr(boxes), ptr(ok),
+                                      ptr(masks), scratch.data_ptr()), "cp_mask_errors")
+    if return_counts:
+        out["counts"], out["ok"] = counts, ok.view(torch.bool)
+    if return_boxes:
+        out["boxes"] = boxes
+    if return_masks:
+        out["masks"] = masks.view(torch.bool)
+    return out
+
+
+def _as_masks(m, dev=None):
+    m = torch.as_tensor(m)
+    if dev is not None:
+        m = m.to(dev)
+    if m.dim() == 2:
+        m = m[None]
+    if m.dim() != 3:
+        raise ValueError("masks must be (H,W) or (B,H,W), got %r" % (tuple(m.shape),))
+    if m.dtype == torch.bool:
+        return m.contiguous().view(torch.uint8)
+    if m.dtype == torch.uint8:
+        return m.contiguous()
+    return (m != 0).view(torch.uint8)                         # astype(bool) of any other type
+
+
+def mask_overlap(mask_est, mask_gt, kinds=("cou_mask", "cou_bb"), return_counts=False, return_boxes=False):
+    """pose_error.cou_mask of B mask pairs and / or cou_bb of the masks' bounding boxes, on the device in ONE launch (cp_mask_overlap).
+      mask_est, mask_gt: (B,H,W) (or (H,W)) CUDA tensors, bool or uint8 (any other dtype is compared with 0 first): nonzero = set,
+      as the reference's astype(bool) -- e.g. the network's predicted segmentation against mask_visib.
+    cou_mask = 1 - inter / union, 1.0 when the union is empty;  cou_bb = 1 - iou of the boxes (xmin, ymin, xmax - xmin, ymax - ymin)
+    of the two masks, NaN where a mask is empty (misc.calc_2d_bbox raises there).
+    -> dict kind -> (B,) float64 CUDA tensor (+ "counts": (B,4) int32 = inter, union, n_est, n_gt; + "boxes": (B,2,4) int32, -1 where empty)"""
+    names = [kinds] if isinstance(kinds, str) else list(kinds)
+    for k in names:
+        if k not in OVERLAP_KINDS:
+            raise ValueError("kinds must be among %s, got %r" % (list(OVERLAP_KINDS), k))
+    if not names and not return_counts and not return_boxes:
+        raise ValueError("kinds is empty: ask for \"cou_mask\", \"cou_bb\" or both")
+    if not (torch.is_tensor(mask_est) and mask_est.is_cuda):
+        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    dev = mask_est.device
+    me, mg = _as_masks(mask_est), _as_masks(mask_gt, dev)
+    if me.shape != mg.shape:
+        raise ValueError("mask_est is %r, mask_gt %r" % (tuple(me.shape), tuple(mg.shape)))
+    B, H, W = (int(v) for v in me.shape)
+    if B == 0 or H == 0 or W == 0:
+        raise ValueError("no masks")
+    lib = _abi.load()
+    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in OVERLAP_KINDS if k in names}
+    counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if return_counts else None
+    boxes = torch.empty((B, 2, 4), dtype=torch.int32, device=dev) if return_boxes else None
+    ptr = lambda x: None if x is None else x.data_ptr()     # noqa: E731
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_mask_overlap(st, me.data_ptr(), mg.data_ptr(), H, W, B, ptr(out.get("cou_mask")), ptr(out.get("cou_bb")),
+                                       ptr(counts), ptr(boxes)), "cp_mask_overlap")
+    if return_counts:
+        out["counts"] = counts
+    if return_boxes:
+        out["boxes"] = boxes
+    return out
+
+
+def box_overlap(bb_est, bb_gt):
+    """pose_error.cou_bb = 1 - misc.iou of B box pairs (x, y, w, h), on the device (cp_box_overlap): bb_est (B,4) CUDA tensor (any
+    real dtype; computed in float64), bb_gt the same shape (tensor or host array).  -> (B,) float64 CUDA tensor"""
+    if not (torch.is_tensor(bb_est) and bb_est.is_cuda):
+        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    dev = bb_est.device
+    a = bb_est.reshape(-1, 4).to(torch.float64).contiguous()
+    c = torch.as_tensor(bb_gt).to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous()
+    if a.shape != c.shape or a.shape[0] == 0:
+        raise ValueError("bb_est and bb_gt must both be (B,4), B > 0")
+    B = int(a.shape[0])
+    out = torch.empty(B, dtype=torch.float64, device=dev)
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(_abi.load().cp_box_overlap(st, a.data_ptr(), c.data_ptr(), B, out.data_ptr()), "cp_box_overlap")
+    return out
+
+
+def _one_device(device):
+    dev = torch.device(device)
+    if dev.type != "cuda" or not torch.cuda.is_available():
+        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
+    return dev
+
+
+def cou_mask(mask_est, mask_gt, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.cou_mask (two hxw arrays -> float), counted on the device"""
+    dev = _one_device(device)
+    f = lambda m: torch.from_numpy(np.ascontiguousarray(np.asarray(m).astype(bool))).to(dev)   # noqa: E731
+    return float(mask_overlap(f(mask_est), f(mask_gt), kinds=("cou_mask",))["cou_mask"][0])
+
+
+def cou_bb(bb_est, bb_gt, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.cou_bb (two boxes x, y, w, h -> float), on the device"""
+    dev = _one_device(device)
+    f = lambda b: torch.from_numpy(np.asarray(b, dtype=np.float64).reshape(1, 4)).to(dev)   # noqa: E731
+    return float(box_overlap(f(bb_est), f(bb_gt))[0])
+
+
+def _one_mask_error(kind, R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size, device):
+    dev = _one_device(device)
+    if not isinstance(renderer, MeshSet) or renderer.faces is None:
+        raise ValueError("renderer must be a MeshSet built with faces")
+    if size is None:
+        raise ValueError("size=(width, height) is required: a MeshSet has no frame")
+    m = int(obj_id)
+    if not 0 <= m < len(renderer):
+        raise ValueError("obj_id must be a mesh index in 0..%d" % (len(renderer) - 1))
+    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
+    out = mask_errors(f(R_est, (1, 3, 3)), f(t_est, (1, 3, 1)), f(R_gt, (1, 3, 3)), f(t_gt, (1, 3, 1)),
+                      np.asarray(K, dtype=np.float64).reshape(3, 3), renderer, size, mesh_ids=None if len(renderer) == 1 else [m],
+                      kinds=(kind,))
+    return float(out[kind][0])
+
+
+def cus(R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size=None, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.cus (numpy arrays of one pose -> float), rendered and counted on the device.  `renderer` is a
+    MeshSet with faces and `obj_id` the index of the object's mesh in it; size=(W, H) is required, because a MeshSet has no frame.
+    No sphere shortcut: that is the caller's."""
+    return _one_mask_error("cus", R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size, device)
+
+
+def cou_bb_proj(R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size=None, device="cuda:0"):
+    """bop_toolkit_lib.pose_error.cou_bb_proj, with cus' arguments.  NaN where the reference raises (a silhouette with no pixel)."""
+    return _one_mask_error("cou_bb_proj", R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size, device)

@@ -122,7 +122,7 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
 
 
 def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None,
-                   depth_test=None, image_ids=None, **estimate_kwargs):
+                   depth_test=None, image_ids=None, size=None, **estimate_kwargs):
     """estimate_poses followed by metric.pose_errors against the given ground-truth poses: test.py's loop body from the detection
     boxes to the ADD / ADD-S errors (:198-427) with only the errors leaving the GPU.
       R_gt (B,3,3), t_gt (B,3,1) / (B,3): tensors or host arrays; vertices: a (V,3) array, a list with mesh_ids, or a metric.MeshSet
@@ -132,11 +132,12 @@ def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, me
       bop_toolkit `syms` lists, or None = the identity alone); without them nothing more is launched.
       kind "vsd" (metric.vsd_errors at its defaults) needs `depth_test` (H,W) / (I,H,W) in the units of `vertices`, a MeshSet with
       faces, and `image_ids` (B,) when poses share images; its errors are (B, T), one column per tau.
+      kinds "cus" / "cou_bb_proj" (metric.mask_errors, no sphere shortcut) need `size` = (W, H) of the frame and a MeshSet with faces.
     -> (errors: dict kind -> (B,) f64 CUDA tensor, R, t, inliers, status, final boxes)"""
     from . import metric
     R, t, inl, status, final = estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, **estimate_kwargs)
     errors = metric.score_poses(R, t, R_gt, t_gt, cam_K, vertices, mesh_ids=mesh_ids, kinds=kinds, symmetries=symmetries,
-                                depth_test=depth_test, image_ids=image_ids)
+                                depth_test=depth_test, image_ids=image_ids, size=size)
     return errors, R, t, inl, status, final
 
 

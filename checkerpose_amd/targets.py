@@ -307,14 +307,14 @@ COLUMNS = ("all", "full", "visib")          # correspondences()' validity column
 def evaluate_batch(net, frames, masks_visib, masks_full, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None,
                    kinds=("add", "adi"), img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256, crop_size_gt=64,
                    resize_method="crop_square_resize", discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0,
-                   symmetries=None, depth_test=None, image_ids=None):
+                   symmetries=None, depth_test=None, image_ids=None, size=None):
     """test.py's loop body for a batch (:279-457), everything it scores per crop, without leaving the device: what
     `postprocess.evaluate_poses` does -- crops, ONE forward, correspondences, EPnP + RANSAC, ADD / ADD-S -- for the three correspondence
     sets the reference scores (all RoI keypoints | inside the predicted full mask | inside the visible mask, :335-368), plus `re` / `te`
     of each pose (called as test.py calls them, ground truth first: for rotation matrices the same angle up to rounding) and the code / mask report against labels made from the GT pose on the crops' final boxes.
       frames / masks_visib / masks_full / Bboxes (detections; None = no detection) / p3d_xyz / obj_ids / cam_K as in
       make_training_batch(is_train=False); R_gt, t_gt, vertices, mesh_ids, kinds, symmetries, depth_test, image_ids as in
-      postprocess.evaluate_poses (kind "vsd" needs depth_test).
+      postprocess.evaluate_poses (kind "vsd" needs depth_test; "cus" / "cou_bb_proj" need size = (W, H)).
     -> dict: "all" / "full" / "visib" -> {"errors": {kind: (B,) f64}, "R", "t", "status", "re", "te"}; "report": code_report's dict;
        "labels": encode_targets' dict; "final_Bboxes": (B,4) int array; "outputs": the network's tuple; "mask_crops": the GT
        (visible, full) uint8 crops (B,S,S)."""
@@ -343,7 +343,7 @@ def evaluate_batch(net, frames, masks_visib, masks_full, Bboxes, p3d_xyz, cam_K,
                                                 iterations=iterations, seed=seed)
         re, te = pose_re_te(R_gt, t_gt, R, t)      # test.py:388-389 passes the ground truth first: trace(R_gt . inv(R_pred))
         res[name] = {"errors": metric.score_poses(R, t, R_gt, t_gt, cam_K, vertices, mesh_ids=mesh_ids, kinds=kinds, symmetries=symmetries,
-                                                depth_test=depth_test, image_ids=image_ids),
+                                                depth_test=depth_test, image_ids=image_ids, size=size),
                      "R": R, "t": t,
                      "status": status, "re": re, "te": te}
     Rg = R_gt if torch.is_tensor(R_gt) else torch.from_numpy(np.ascontiguousarray(np.asarray(R_gt, dtype=np.float64))).to(frames.device)

@@ -670,6 +670,44 @@ int cp_gt_info_from_depth(cp_stream_t stream, const float* depth_gt_large, const
                           const int32_t* image_ids, int I, int H, int W, double delta, int B, int32_t* counts, double* visib_fract,
                           int32_t* boxes, uint8_t* ok, uint8_t* mask, uint8_t* mask_visib, void* scratch);
 
+/* BOP's overlap errors on the device (next-row N12; csrc/mask_error.hip; reference bop_toolkit_lib/pose_error.py:235-330 cou_mask, cus,
+ * cou_bb, cou_bb_proj with misc.calc_2d_bbox / misc.iou, misc.py:202-263): the four functions that close pose_error.py.
+ * cp_mask_errors: for B pairs (estimate, ground truth) of one mesh each under one K, on a W x H frame,
+ *   cus fp64 (B) = 1 - inter / (double)union of the two silhouettes, 1.0 when union == 0;
+ *   cou_bb_proj fp64 (B) = 1 - misc.iou of the silhouettes' boxes (xmin, ymin, xmax - xmin, ymax - ymin): no + 1, not clipped, the
+ *   intersection counted only when its width AND height are > 0.  Where a side's silhouette is EMPTY the reference raises (xs.min() of
+ *   nothing): NaN here.  (Either output may be NULL, not both.)
+ * A pixel of a side is set exactly where cp_render_depth's depth at (H, W) is > 0 (the render rule and rasteriser of cp_vsd_errors,
+ * csrc/vsd_raster.h).  pose_est, pose_gt, cam_K, k_stride, verts, v_offsets, faces, f_offsets, M, mesh_ids, Vmax: as cp_vsd_errors.
+ * A pair with a non-finite entry (either pose, K), a mesh id outside [0, M), a mesh that is empty or larger than Vmax, or ANY vertex
+ * at Z <= 0 on either side is not scored: ok = 0, both errors NaN, counts 0, boxes -1, masks 0.
+ * sphere_check != 0 (needs diameters fp64 (M)): misc.overlapping_sphere_projections(diameter / 2, t_est, t_gt) decided on the device,
+ * as eval_calc_errors.py:299-302,357-362 applies it to 'cus' ALONE: where it fails cus = 1.0 and -- unless cou_bb_proj is asked, which
+ * the shortcut never touches -- the pair is not rendered (counts 0, boxes -1, masks 0).  The launch list does not depend on it.
+ * Optional outputs (NULL to skip): counts int32 (B,4) = inter, union, n_est, n_gt; boxes int32 (B,2,4) = the estimate's and the
+ * ground truth's x, y, w, h (-1 -1 -1 -1 for an empty silhouette); ok uint8 (B); masks uint8 (B,2,H,W) holding 0 / 1.
+ * With masks asked no tile leaves early: every tile of every pair stores its pixels (zeros where nothing is rendered).
+ * Scratch layout: B headers of 52 4-byte words [P_est 12 | P_gt 12 | rect_est 4 | rect_gt 4 | bad 2 | ok | skip | render | inter
+ * union n_est n_gt | est xmin ymin xmax ymax | gt xmin ymin xmax ymax | 3 spare], rounded up to 16 bytes, then the screen records
+ * float4 (B, 2, Vmax).  cp_mask_errors_scratch_bytes(B, Vmax) bytes, 16-byte aligned.
+ * Four launches (pose, vertex, tile, finish); a workgroup per (pair, 32 x 32 tile) rasterises BOTH sides, so intersection and union
+ * are decided in registers; tiles outside both vertex rectangles leave at once.  Integer reductions only (wave shuffles, LDS, one
+ * order-independent integer atomic per value and tile): every output is bit-identical from call to call, for a pair alone or in a
+ * batch, with or without the optional outputs.  Nothing allocates or synchronises.  CP_ERR_RANGE: 2^24 workgroups or more.
+ * cp_mask_overlap: the counting half on caller-supplied masks uint8 (B,H,W), nonzero = set (any alignment): the same counts and boxes,
+ * cou_mask fp64 (B) (pose_error.cou_mask) and cou_bb fp64 (B) of the masks' boxes (NaN where a mask is empty); each output may be
+ * NULL, not all.  ONE launch, a workgroup per pair, no scratch.
+ * cp_box_overlap: out fp64 (B) = 1 - misc.iou(bb_est, bb_gt) (pose_error.cou_bb) of B box pairs x, y, w, h given as fp64 (B,4), in fp64
+ * without contraction in the reference's order of operations.  One launch. */
+size_t cp_mask_errors_scratch_bytes(int B, int Vmax);
+int cp_mask_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const double* cam_K, int k_stride,
+                   const float* verts, const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M,
+                   const int32_t* mesh_ids, const double* diameters, int H, int W, int sphere_check, int B, int Vmax, double* cus,
+                   double* cou_bb_proj, int32_t* counts, int32_t* boxes, uint8_t* ok, uint8_t* masks, void* scratch);
+int cp_mask_overlap(cp_stream_t stream, const uint8_t* mask_est, const uint8_t* mask_gt, int H, int W, int B, double* cou_mask,
+                    double* cou_bb, int32_t* counts, int32_t* boxes);
+int cp_box_overlap(cp_stream_t stream, const double* bb_est, const double* bb_gt, int B, double* out);
+
 /* BOP's matching of estimates to ground truths and its recall scores on the device (next-row N11; csrc/bop_match.hip; reference
  * bop_toolkit_lib/pose_matching.py:9-90 match_poses and score.py:62-137 calc_localization_scores), for every (scene, image, object)
  * group and every threshold column at once.
