@@ -158,7 +158,8 @@ def _mask_images(m):
 
 
 def make_training_batch(frames, masks_visib, masks_full, R, t, cam_K, Bboxes, p3d_xyz, is_train=True, padding_ratio=1.5,
-                        crop_size_img=256, crop_size_gt=64, resize_method="crop_square_resize", img_index=None, obj_ids=None):
+                        crop_size_img=256, crop_size_gt=64, resize_method="crop_square_resize", img_index=None, obj_ids=None,
+                        augment=None, backgrounds=None):
     """What the reference's loader returns for the samples of a batch (`__getitem__`, bop_dataset_pytorch.py:274-383), made on the
     device from full frames: `aug_Bbox` (is_train; it draws from np.random) or `padding_Bbox` per box on the host -> three
     `preprocess.get_roi_batch` launches (image INTER_LINEAR at crop_size_img, the two masks INTER_NEAREST at crop_size_gt, then / 255
@@ -170,8 +171,13 @@ def make_training_batch(frames, masks_visib, masks_full, R, t, cam_K, Bboxes, p3
         cam_K (R, t, cam_K as float64 device tensors in the shapes given; host arrays are uploaded), roi_mask_bits (B,1,N), pixel_x_codes (B,bits,N), pixel_y_codes (B,bits,N), roi_xy_oris (B,2,S,S) f32) -- the loader's 11
     entries in its order, every one a tensor on the frames' device; with obj_ids, `obj_ids` (int64 (B,)) follows cam_K as in the LM
     loader (12 entries).
-    The image stays uint8: the models normalise on the device (ToTensor + Normalize, cp_u8hwc_to_nhwc_norm).  Colour augmentation
-    (`apply_augmentation`, imgaug) and the LM loader's background replacement are NOT done here: augment the frames before the call."""
+    The image stays uint8: the models normalise on the device (ToTensor + Normalize, cp_u8hwc_to_nhwc_norm).
+    augment: an `augment.AugmentPlan` of B samples (`augment.sample_plan`), or None.  With a plan the frames go through
+    `augment.augment_frames` first -- the LM loader's background replacement (`replace_bg`, against masks_visib, from the pool
+    `backgrounds` uint8 (n_bg,H,W,3)) and the colour chain (`apply_augmentation`) -- computed only on the tiles that meet each
+    sample's crop window, and roi_x is cut from the augmented frames; the mask crops and every other entry are unaffected.  With None
+    (the default) nothing is augmented and the launches are the ones listed above.  Parity of the chain with imgaug is UNPINNED
+    (augment.py)."""
     if not (torch.is_tensor(frames) and frames.is_cuda):
         raise RuntimeError(_NO_CPU)
     if frames.dim() == 3:
@@ -186,7 +192,16 @@ def make_training_batch(frames, masks_visib, masks_full, R, t, cam_K, Bboxes, p3
         grown = [aug_Bbox(np.asarray(b), padding_ratio) for b in Bboxes]
     else:
         grown = [None if b is None else PP.padding_Bbox(b, padding_ratio) for b in Bboxes]
-    roi_x = PP.get_roi_batch(frames, grown, crop_size_img, PP.INTER_LINEAR, resize_method, img_index=img_index)
+    if augment is None:
+        roi_x = PP.get_roi_batch(frames, grown, crop_size_img, PP.INTER_LINEAR, resize_method, img_index=img_index)
+    else:
+        from . import augment as AUG
+        wins = np.zeros((len(grown), 4), dtype=np.int64)
+        for b, box in enumerate(grown):
+            if box is not None:                  # the window the crop reads (cp_crop_resize_u8): [x1, x2) x [y1, y2) inside the frame
+                wins[b] = PP.roi_window([int(v) for v in box], resize_method, W, H)[:4]
+        aug = AUG.augment_frames(frames, augment, masks=mv[..., 0], backgrounds=backgrounds, img_index=img_index, rects=wins)
+        roi_x = PP.get_roi_batch(aug, grown, crop_size_img, PP.INTER_LINEAR, resize_method, img_index=np.arange(len(grown)))
     roi_mask = PP.get_roi_batch(mv, grown, crop_size_gt, PP.INTER_NEAREST, resize_method, img_index=img_index)
     roi_entire = PP.get_roi_batch(mf, grown, crop_size_gt, PP.INTER_NEAREST, resize_method, img_index=img_index)
     final = [None if b is None else PP.get_final_Bbox(b, resize_method, W, H) for b in grown]

@@ -1125,6 +1125,23 @@ int cp_u8hwc_to_nhwc_norm(cp_stream_t stream, int dtype, const uint8_t* in, void
 int cp_crop_resize_u8(cp_stream_t stream, const uint8_t* images, int n_img, int H, int W, int C, const int32_t* windows,
                       const int32_t* img_idx, uint8_t* out, int B, int crop, int interpolation);
 
+/* Training-frame augmentation on the device (next-row N13; csrc/augment.hip; reference lm_dataset_pytorch.py:523-541 replace_bg and
+ * GDR_Net_Augmentation.py:161-178 build_augmentations): background swap, salt-and-pepper, 5 x 5 motion blur, coarse dropout, 5-tap
+ * separable Gaussian and one 256-entry table per channel (Add, Invert, Multiply, Multiply, Contrast composed) for B samples in ONE
+ * launch, integer arithmetic only.  frames uint8 (n_img,H,W,3); masks uint8 (n_img,H,W) (non-zero = keep the frame's pixel) and
+ * backgrounds uint8 (n_bg,H,W,3), both needed only by samples whose plan asks for the swap (NULL / n_bg = 0 otherwise); out uint8
+ * (B,H,W,3).  plan: device blob of cp_augment_plan_bytes(B) bytes, 16-byte aligned, made by checkerpose_amd/augment.py -- 256
+ * salt-and-pepper values, then per sample 44 int32 words [key, flags, bg_index, img_index, sp_thresh, drop_thresh, gh, gw, rect x1 y1
+ * x2 y2, gauss_w 5 (sum 4096), motion_w 25 (sum 65536), 2 spare] + the table uint8 (3,256); flags: 1 salt-and-pepper, 2 motion,
+ * 4 dropout, 8 Gaussian, 16 table, 32 rect (64 x 32 tiles that miss [x1,x2) x [y1,y2) are not computed: out is left as it was there).
+ * The steps, their rounding, the border rule (REFLECT_101) and the hash are stated in the kernel's header; the numpy restatement is
+ * tests/augment_stages.py.  A sample whose img_index is outside [0, n_img) is not written; a bg_index outside [0, n_bg) means no swap
+ * (the Python wrapper refuses both).  H, W >= 5 (four mirrored halo pixels), H, W < 2^15.  Nothing allocates or synchronises;
+ * bit-identical for a sample alone or in a batch, at any batch position, with or without a rect. */
+size_t cp_augment_plan_bytes(int B);
+int cp_augment_frames(cp_stream_t stream, const uint8_t* frames, int n_img, int H, int W, const uint8_t* masks,
+                      const uint8_t* backgrounds, int n_bg, const void* plan, int B, uint8_t* out);
+
 /* ---------------------------------------------------------------------------------------------
  * hipGraph helpers: capture the launch sequence of one forward (everything above is capture-safe:
  * no allocation, no synchronisation) and replay it with one call.
