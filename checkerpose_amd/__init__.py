@@ -22,3 +22,15 @@ def set_deterministic(on=True):
 def is_deterministic():
     from . import _abi
     return bool(_abi.load().cp_get_deterministic())
+
+
+_RENDER_NAMES = ("render_rgb", "sample_views", "render_views", "synthetic_batch")
+
+
+def __getattr__(name):
+    """row N14's entry points, imported on first use (render.py pulls in torch): checkerpose_amd.render_rgb, .sample_views,
+    .render_views, .synthetic_batch"""
+    if name in _RENDER_NAMES:
+        from . import render
+        return getattr(render, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -208,6 +208,8 @@ SIGNATURES = {
     "cp_gt_info_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_gt_info": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, C.c_double, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cp_gt_info_from_depth": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_render_rgb_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_render_rgb": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_double, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "cp_mask_errors_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_mask_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_mask_overlap": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

@@ -5,6 +5,7 @@
 
 #include "common.h"
 
+// 0.2.15: cp_render_rgb, cp_render_rgb_scratch_bytes;
 // 0.2.12: cp_bop_match, cp_bop_match_scratch_bytes, cp_bop_scores;
 // 0.2.11: cp_gt_info, cp_gt_info_from_depth, cp_gt_info_scratch_bytes;
 // 0.2.10: cp_fps, cp_fps_scratch_bytes, cp_pts_diameter, cp_pts_diameter_scratch_bytes;
@@ -15,7 +16,7 @@
 //        cp_graph_capture_set_deps and cp_graph_capture_tail removed (opt-in launch paths that lost their A/B measurements);
 // 0.2.4: cp_set_deterministic, cp_status_*; 0.2.3: cp_kernel_log (0.2.2: cp_graph_capture_set_deps / _tail; 0.2.1:
 // cp_pack_hr_chain_weight takes the folded-BN scale)
-extern "C" int cp_version(void) { return 214; }
+extern "C" int cp_version(void) { return 215; }
 
 // process-wide mode switch of the TRAINING entry points (include/checkerpose_hip.h): every accumulation in a fixed order
 std::atomic<int> g_cp_deterministic{0};

@@ -50,26 +50,37 @@ class MeshSet:
     """The vertices of M objects packed into one (sumV, 3) fp32 table + (M + 1) int32 offsets (cp_pose_errors' layout), and their
     diameters.  Built on the host; the device copies are made once per device on first use."""
 
-    def __init__(self, verts, offsets, diameters, faces=None, face_offsets=None):
+    def __init__(self, verts, offsets, diameters, faces=None, face_offsets=None, colors=None, normals=None):
         self.verts = verts                  # (sumV, 3) float32 CPU tensor
         self.offsets = offsets              # (M + 1,) int32 CPU tensor
         self.diameters = diameters          # (M,) float64 numpy
         self.sizes = np.diff(offsets.numpy()).astype(np.int64)
         self.faces = faces                  # (sumF, 3) int32 CPU tensor, vertex indices local to each mesh, or None (VSD needs them)
         self.face_offsets = face_offsets    # (M + 1,) int32 CPU tensor, or None
+        self.colors = colors                # (sumV, 3) float32 CPU tensor in [0, 1], rows as verts, or None (render.render_rgb)
+        self.normals = normals              # (sumV, 3) float32 CPU tensor, or None (phong shading needs them)
         self._dev = {}
         self._dev_faces = {}
+        self._dev_shading = {}
 
     @classmethod
-    def from_arrays(cls, arrays, diameters=None, faces=None, device=None):
+    def from_arrays(cls, arrays, diameters=None, faces=None, device=None, colors=None, normals=None):
         """arrays: a list of (V_m, 3) arrays / tensors (or ONE such array); diameters: one per mesh, or None = computed as the
         reference does (largest pairwise distance of the vertices) -- on the host, or with `device` on that device
         (prepare.pts_diameters: the same bits); faces: None, or one (F_m, 3) integer array of vertex indices
-        per mesh (or ONE such array with one mesh) -- the triangles vsd_errors / render_depth rasterise"""
+        per mesh (or ONE such array with one mesh) -- the triangles vsd_errors / render_depth rasterise;
+        colors: None, or per mesh a (V_m, 3) uint8 / float array of vertex colours or None (that mesh is 0.5 grey) -- as
+        renderer_py's add_object takes them: a mesh whose largest value is > 1 is divided by 255 (in float32);
+        normals: None, or one (V_m, 3) float array per mesh (every mesh): render.render_rgb's phong shading.
+        With both None the object is what it was before these arguments existed."""
         if torch.is_tensor(arrays) or isinstance(arrays, np.ndarray):
             arrays = [arrays]
             if faces is not None and (torch.is_tensor(faces) or isinstance(faces, np.ndarray)):
                 faces = [faces]
+            if colors is not None and (torch.is_tensor(colors) or isinstance(colors, np.ndarray)):
+                colors = [colors]
+            if normals is not None and (torch.is_tensor(normals) or isinstance(normals, np.ndarray)):
+                normals = [normals]
         host = []
         for a in arrays:
             a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
@@ -109,7 +120,38 @@ class MeshSet:
                 raise ValueError("face table too large for int32 offsets")
             ftab = torch.from_numpy(np.concatenate(fhost, 0).reshape(-1, 3)) if fo[-1] else torch.zeros((1, 3), dtype=torch.int32)
             foff = torch.from_numpy(fo.astype(np.int32))
-        return cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters, ftab, foff)
+        ctab = ntab = None
+        if colors is not None:
+            colors = list(colors)
+            if len(colors) != len(host):
+                raise ValueError("need one colour array (or None) per mesh")
+            chost = []
+            for c, a in zip(colors, host):
+                if c is None:
+                    chost.append(np.full(a.shape, 0.5, dtype=np.float32))
+                    continue
+                c = c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c)
+                if c.shape != a.shape:
+                    raise ValueError("colors must be (V, 3) like the vertices, got %r" % (c.shape,))
+                c = np.array(c, dtype=np.float32)
+                if not np.isfinite(c).all():
+                    raise ValueError("colors must be finite")
+                if c.max() > 1.0:
+                    c /= np.float32(255.0)
+                chost.append(c)
+            ctab = torch.from_numpy(np.ascontiguousarray(np.concatenate(chost, 0)))
+        if normals is not None:
+            normals = list(normals)
+            if len(normals) != len(host) or any(n is None for n in normals):
+                raise ValueError("need one normal array per mesh")
+            nhost = []
+            for n, a in zip(normals, host):
+                n = n.detach().cpu().numpy() if torch.is_tensor(n) else np.asarray(n)
+                if n.shape != a.shape:
+                    raise ValueError("normals must be (V, 3) like the vertices, got %r" % (n.shape,))
+                nhost.append(np.ascontiguousarray(n, dtype=np.float32))
+            ntab = torch.from_numpy(np.ascontiguousarray(np.concatenate(nhost, 0)))
+        return cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters, ftab, foff, ctab, ntab)
 
     def __len__(self):
         return int(self.offsets.numel()) - 1
@@ -136,6 +178,15 @@ class MeshSet:
             self._dev_faces[key] = (self.faces.to(device), self.face_offsets.to(device),
                                     torch.from_numpy(np.ascontiguousarray(self.diameters, dtype=np.float64)).to(device))
         return self._dev_faces[key]
+
+
+    def shading_on(self, device):
+        """(colors or None, normals or None) on `device`, uploaded on the first call"""
+        key = self._key(device)
+        if key not in self._dev_shading:
+            self._dev_shading[key] = (None if self.colors is None else self.colors.to(device),
+                                      None if self.normals is None else self.normals.to(device))
+        return self._dev_shading[key]
 
 
 def _as_poses(R, t, B=None):

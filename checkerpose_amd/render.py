@@ -1,0 +1,302 @@
+"""Shaded RGB training frames of coloured meshes, rendered on the device (csrc/render_rgb.hip).
+
+  render_rgb        B poses of a MeshSet -> uint8 (B,H,W,3) frames (+ depth, mask, boxes, ok), cp_render_rgb
+  sample_views      the host twin of bop_toolkit_lib.view_sampler.sample_views (float64 numpy; both modes)
+  render_views      the loop of bop_toolkit's scripts/render_train_imgs.py:128-214 without the files
+  synthetic_batch   render_rgb -> targets.make_training_batch: a training batch of an object nobody photographed
+
+Render rule (renderer_py.py:24-105, 422-518 and renderer.py:23-29 read as a rule; stated per sample in csrc/render_rgb.hip):
+coverage and the front-most surface are metric.render_depth's; over the winning triangle (the smallest face index among equal
+1 / Z) v_color, v_L = normalize(light - eye_pos) per VERTEX and v_normal are interpolated perspective-correctly;
+light_w = min(1, ambient_weight + max(dot(normalize(v_L), normalize(n)), 0)); the pixel is np.round(255 * light_w * v_color).
+  shading "flat":  n = normalize(cross(dFdx(eye_pos), dFdy(eye_pos))), the face normal turned towards the viewer whatever the winding;
+  shading "phong": n = the interpolated v_normal, taken as the shader writes it -- normalize(u_nm * vec4(a_normal, 1.0)).xyz, a
+                   FOUR-vector normalisation before .xyz: the per-vertex lengths differ (the fourth component is 1 - t . (R n), far
+                   from 0 at working distances) and weight the interpolation.  The quirk is kept, not corrected.
+Vertex colours are divided by 255 when the mesh's largest value is > 1, a mesh without colours is 0.5 grey, `surf_color` replaces
+both (renderer_py.add_object:313-352).
+
+ssaa f in {1, 2, 4}: samples on the f-times finer grid under K * f (render_train_imgs.py:98-103), each sample quantised to uint8,
+then f x f samples averaged per pixel as integers -- (s + 2) >> 2 for f = 2, round-half-even of s / 16 for f = 4.  This is the
+project's statement of cv2.resize(INTER_AREA)'s integer-factor path on 8-bit images.
+
+UNPINNED: (1) OpenGL's own output -- the shaders are GLSL and run nowhere this project runs, so the shading is pinned to the rule
+read from them (tests/render_rgb_stages.py, float64), as the depth render of row N8 is; (2) cv2's INTER_AREA -- cv2 is not
+available to the tests, as for the resize of row N3; (3) textured models (`texture_file` / `texture_uv`) are out of scope: GL's
+sampler rule cannot be read from the shader.  Specular terms, the C++ and vispy renderers, PLY reading and PNG writing are not here.
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _abi, metric
+
+SHADINGS = {"flat": 0, "phong": 1}
+
+
+def _pose_tensors(R, t):
+    """solve_pnp_ransac's device tensors as they are; host arrays / CPU tensors go to the current device (96 bytes per pose)"""
+    if torch.is_tensor(R) and R.is_cuda:
+        dev = R.device
+    elif torch.is_tensor(t) and t.is_cuda:
+        dev = t.device
+    else:
+        if not torch.cuda.is_available():
+            raise RuntimeError("checkerpose_amd.render: a CUDA/HIP device is required (no CPU fallback)")
+        dev = torch.device("cuda", torch.cuda.current_device())
+    R = torch.as_tensor(R).to(device=dev, dtype=torch.float64)
+    t = torch.as_tensor(t).to(device=dev, dtype=torch.float64)
+    return R, t
+
+
+def _vec3(x, name):
+    v = np.asarray(x, dtype=np.float64).reshape(-1)
+    if v.shape[0] != 3 or not np.isfinite(v).all():
+        raise ValueError("%s must be 3 finite values, got %r" % (name, x))
+    return (C.c_double * 3)(*v.tolist())
+
+
+def render_rgb(R, t, cam_K, meshes, size, mesh_ids=None, shading="phong", ambient_weight=0.5, light_cam_pos=(0, 0, 0),
+               bg_color=(0, 0, 0), surf_color=None, ssaa=1, bgr=False, return_depth=False, return_mask=False, return_boxes=False,
+               out=None):
+    """uint8 frames of B poses of `meshes` (a MeshSet built with faces, and colors / normals as the shading needs them), shaded as
+    bop_toolkit's RendererPython(mode='rgb') shades (module docstring), on the device (cp_render_rgb).
+      R, t: (B,3,3) / (B,3,1) or (B,3) -- solve_pnp_ransac's tensors, or host arrays; cam_K: (3,3) or (B,3,3);
+      size: (width, height); mesh_ids (B,) with several meshes;  shading "phong" (needs the MeshSet's normals) or "flat";
+      ambient_weight, light_cam_pos: renderer.py:23-29 -- the light in the reference's camera frame (x right, y UP, z towards the
+      viewer: OpenGL's), default at the camera;  bg_color, surf_color: RGB in [0, 1] (surf_color None: the mesh's colours, or grey);
+      ssaa 1, 2 or 4;  bgr: store the channels reversed (what cv2.imread gives the loaders);
+      out: a uint8 (B,H,W,3) contiguous tensor on the poses' device to write into.
+    return_depth / return_mask / return_boxes (ssaa == 1 only: they belong to the sample grid, and a caller who wants depth beside an
+    anti-aliased frame renders it with metric.render_depth, as render_train_imgs.py does): depth float32 (B,H,W), the same bits
+    as metric.render_depth; mask uint8 (B,H,W) = 255 where depth > 0; boxes int32 (B,4) = misc.calc_2d_bbox of the mask (x, y, w, h),
+    -1 where the mask is empty.
+    A pose with a non-finite entry, a singular R or any vertex at Z <= 0 is not rendered: ok = 0, background only.
+    -> {"rgb": uint8 (B,H,W,3), "ok": uint8 (B,)} (+ "depth", "mask", "boxes"), all on the device.  Four launches whatever the data."""
+    if shading not in SHADINGS:
+        raise ValueError("shading must be \"flat\" or \"phong\", got %r" % (shading,))
+    ssaa = int(ssaa)
+    if ssaa not in (1, 2, 4):
+        raise ValueError("ssaa must be 1, 2 or 4, got %r" % (ssaa,))
+    if ssaa != 1 and (return_depth or return_mask or return_boxes):
+        raise ValueError("depth, mask and boxes are made at ssaa=1 only: render them in a call of their own")
+    amb = float(ambient_weight)
+    if not math.isfinite(amb):
+        raise ValueError("ambient_weight must be finite")
+    light = np.asarray(light_cam_pos, dtype=np.float64).reshape(-1)
+    if light.shape[0] != 3:
+        raise ValueError("light_cam_pos must be 3 values")
+    light_c = _vec3(light * np.array([1.0, -1.0, -1.0]), "light_cam_pos")       # OpenGL's camera frame -> the poses'
+    bg_c = _vec3(bg_color, "bg_color")
+    if not isinstance(meshes, metric.MeshSet):
+        raise ValueError("render_rgb renders triangles: pass a MeshSet built with faces")
+    if shading == "phong" and meshes.normals is None:
+        raise ValueError("phong shading needs vertex normals: MeshSet.from_arrays(..., normals=...)")
+    W, H = int(size[0]), int(size[1])
+    if W <= 0 or H <= 0:
+        raise ValueError("size must be (width, height), both positive")
+    R, t = _pose_tensors(R, t)
+    dev, poses, B, K, k_stride, M, ids, vmax = metric._vsd_common(R, t, cam_K, meshes, mesh_ids)
+    verts, v_off = meshes.on(dev)
+    faces, f_off, _ = meshes.faces_on(dev)
+    colors, normals = meshes.shading_on(dev)
+    if surf_color is not None:
+        surf_c, colors = _vec3(surf_color, "surf_color"), None
+    else:
+        surf_c = _vec3((0.5, 0.5, 0.5), "surf_color")
+    if out is None:
+        out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
+    elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (B, H, W, 3)
+              and out.is_contiguous()):
+        raise ValueError("out must be a contiguous uint8 (%d,%d,%d,3) tensor on %s" % (B, H, W, dev))
+    lib = _abi.load()
+    res = {"rgb": out, "ok": torch.empty(B, dtype=torch.uint8, device=dev)}
+    if return_depth:
+        res["depth"] = torch.empty((B, H, W), dtype=torch.float32, device=dev)
+    if return_mask:
+        res["mask"] = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
+    if return_boxes:
+        res["boxes"] = torch.empty((B, 4), dtype=torch.int32, device=dev)
+    scratch = torch.empty(lib.cp_render_rgb_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
+    ptr = lambda k: res[k].data_ptr() if k in res else None      # noqa: E731
+    st = torch.cuda.current_stream(dev).cuda_stream
+    with torch.cuda.device(dev):
+        _abi.check(lib.cp_render_rgb(st, poses.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(), faces.data_ptr(),
+                                     f_off.data_ptr(), M, None if ids is None else ids.data_ptr(),
+                                     None if colors is None else colors.data_ptr(), None if normals is None else normals.data_ptr(),
+                                     surf_c, light_c, amb, bg_c, SHADINGS[shading], ssaa, 1 if bgr else 0, H, W, B, vmax,
+                                     out.data_ptr(), ptr("depth"), ptr("mask"), ptr("boxes"), res["ok"].data_ptr(), scratch.data_ptr()),
+                   "cp_render_rgb")
+    return res
+
+
+# ---- view sampling (host, float64) -------------------------------------------------------------------------------------------------
+def fibonacci_sampling(n_pts, radius=1.0):
+    """view_sampler.fibonacci_sampling: an odd number of points of the Fibonacci lattice on the sphere -> list of [x, y, z]"""
+    if n_pts % 2 != 1:
+        raise ValueError("fibonacci_sampling needs an odd number of points")
+    half = int(n_pts / 2)
+    golden = (math.sqrt(5.0) + 1.0) / 2.0
+    step = 2.0 * math.pi * (golden - 1.0)
+    pts = []
+    for i in range(-half, half + 1):
+        lat = math.asin((2 * i) / float(2 * half + 1))
+        lon = (step * i) % (2 * math.pi)
+        s = math.cos(lat) * radius
+        pts.append([math.cos(lon) * s, math.sin(lon) * s, math.tan(lat) * s])
+    return pts
+
+
+_ICO_FACES = ((0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+              (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1))
+
+
+def hinter_sampling(min_n_pts, radius=1.0):
+    """view_sampler.hinter_sampling: the icosahedron subdivided (edge midpoints, four faces per face) until it has at least
+    `min_n_pts` vertices, projected onto the sphere, ordered from the top vertex outwards ring by ring, each ring by azimuth
+    -> (points (n,3) float64, the subdivision level that created each point).  The ring order of points with EQUAL azimuth follows
+    the iteration order of Python sets of small integers, as the reference's does."""
+    g = (1.0 + math.sqrt(5.0)) / 2.0
+    pts = [(-1.0, g, 0.0), (1.0, g, 0.0), (-1.0, -g, 0.0), (1.0, -g, 0.0), (0.0, -1.0, g), (0.0, 1.0, g), (0.0, -1.0, -g), (0.0, 1.0, -g),
+           (g, 0.0, -1.0), (g, 0.0, 1.0), (-g, 0.0, -1.0), (-g, 0.0, 1.0)]
+    faces = list(_ICO_FACES)
+    level_of = [0] * len(pts)
+    level = 0
+    while len(pts) < min_n_pts:
+        level += 1
+        mid, split = {}, []
+        for face in faces:
+            corner = list(face)
+            for i in range(3):
+                a, b = face[i], face[(i + 1) % 3]
+                key = (a, b) if a < b else (b, a)
+                if key not in mid:
+                    mid[key] = len(pts)
+                    pts.append((0.5 * (np.array(pts[key[0]]) + np.array(pts[key[1]]))).tolist())
+                    level_of.append(level)
+                corner.append(mid[key])
+            split += [(corner[0], corner[3], corner[5]), (corner[3], corner[1], corner[4]), (corner[3], corner[4], corner[5]),
+                      (corner[5], corner[4], corner[2])]
+        faces = split
+    pts = np.array(pts)
+    pts *= np.reshape(radius / np.linalg.norm(pts, axis=1), (pts.shape[0], 1))
+    linked = {}
+    for face in faces:
+        for i in range(3):
+            linked.setdefault(face[i], set()).add(face[(i + 1) % 3])
+            linked[face[i]].add(face[(i + 2) % 3])
+
+    def azimuth(i):
+        return (math.atan2(pts[i][1], pts[i][0]) + 2.0 * math.pi) % (2.0 * math.pi)
+
+    order, ring, done = [], [int(np.argmax(pts[:, 2]))], [False] * pts.shape[0]
+    while len(order) != pts.shape[0]:
+        ring = sorted(ring, key=azimuth)
+        reached = []
+        for i in ring:
+            order.append(i)
+            done[i] = True
+            reached += [j for j in linked[i]]
+        ring = [j for j in set(reached) if not done[j]]
+    return pts[np.array(order), :], [level_of[i] for i in order]
+
+
+def sample_views(min_n_views, radius=1.0, azimuth_range=(0, 2 * math.pi), elev_range=(-0.5 * math.pi, 0.5 * math.pi),
+                 mode="hinterstoisser"):
+    """bop_toolkit_lib.view_sampler.sample_views on the host: viewpoints on a sphere of `radius` looking at its centre, those outside
+    the azimuth / elevation ranges dropped -> (list of {'R': (3,3), 't': (3,1)} float64, views_level).  As in the reference,
+    views_level has one entry per SAMPLED point (before the ranges cut any), and "fibonacci" rounds an even count up to odd."""
+    if mode == "hinterstoisser":
+        pts, levels = hinter_sampling(min_n_views, radius=radius)
+    elif mode == "fibonacci":
+        n = min_n_views if min_n_views % 2 == 1 else min_n_views + 1
+        pts = fibonacci_sampling(n, radius=radius)
+        levels = [0] * len(pts)
+    else:
+        raise ValueError("Unknown view sampling mode.")
+    c, s = math.cos(math.pi), math.sin(math.pi)             # the half turn about x, as a rotation matrix of angle pi is formed
+    flip = np.array([[1.0, 0.0, 0.0], [0.0, c, -s], [0.0, s, c]])
+    views = []
+    for pt in pts:
+        az = math.atan2(pt[1], pt[0])
+        if az < 0:
+            az += 2.0 * math.pi
+        elev = math.acos(np.linalg.norm([pt[0], pt[1], 0]) / np.linalg.norm(pt))
+        if pt[2] < 0:
+            elev = -elev
+        if not (azimuth_range[0] <= az <= azimuth_range[1] and elev_range[0] <= elev <= elev_range[1]):
+            continue
+        fwd = -np.array(pt)                                  # gluLookAt: forward, side, up
+        fwd /= np.linalg.norm(fwd)
+        side = np.cross(fwd, np.array([0.0, 0.0, 1.0]))
+        if np.count_nonzero(side) == 0:                      # looking along the z axis
+            side = np.array([1.0, 0.0, 0.0])
+        side /= np.linalg.norm(side)
+        up = np.cross(side, fwd)
+        R = flip.dot(np.array([[side[0], side[1], side[2]], [up[0], up[1], up[2]], [-fwd[0], -fwd[1], -fwd[2]]]))
+        views.append({"R": R, "t": -R.dot(np.array(pt).reshape((3, 1)))})
+    return views, levels
+
+
+def render_views(meshes, obj_ids, cam_K, size, radii, min_n_views, azimuth_range=(0, 2 * math.pi),
+                 elev_range=(-0.5 * math.pi, 0.5 * math.pi), depth_scale=1.0, ssaa=4, shading="phong", ambient_weight=0.5, batch=256,
+                 mode="hinterstoisser", device=None):
+    """The loop of scripts/render_train_imgs.py:128-214 without the files.  meshes: a MeshSet (faces, colours, normals) whose mesh m
+    is object obj_ids[m]; per object and radius the views of sample_views are rendered in batches of `batch` poses: the frame with
+    render_rgb (ssaa, shading, ambient_weight) and the depth with metric.render_depth at the frame's own K, divided by depth_scale.
+    mode: sample_views' (the script fixes "hinterstoisser"); device: where to render (default: the current CUDA/HIP device).
+    -> {obj_id: {"rgb": uint8 (n,H,W,3), "depth": float32 (n,H,W) (device tensors), "scene_gt": {im_id: [{'cam_R_m2c', 'cam_t_m2c',
+    'obj_id'}]}, "scene_camera": {im_id: {'cam_K', 'depth_scale', 'view_level'}}}} in bop_toolkit's structure."""
+    obj_ids = [int(o) for o in obj_ids]
+    if len(obj_ids) != len(meshes):
+        raise ValueError("need one object id per mesh")
+    if int(batch) <= 0:
+        raise ValueError("batch must be positive")
+    K = np.asarray(cam_K, dtype=np.float64).reshape(3, 3)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    result = {}
+    for m, obj_id in enumerate(obj_ids):
+        scene_camera, scene_gt, Rs, ts = {}, {}, [], []
+        for radius in radii:
+            views, levels = sample_views(min_n_views, radius, azimuth_range, elev_range, mode)
+            for view_id, view in enumerate(views):
+                im_id = len(Rs)
+                scene_camera[im_id] = {"cam_K": K, "depth_scale": depth_scale, "view_level": int(levels[view_id])}
+                scene_gt[im_id] = [{"cam_R_m2c": view["R"], "cam_t_m2c": view["t"], "obj_id": obj_id}]
+                Rs.append(view["R"])
+                ts.append(view["t"])
+        rgb, depth = [], []
+        for i0 in range(0, len(Rs), int(batch)):
+            Rb = torch.from_numpy(np.stack(Rs[i0:i0 + int(batch)])).to(device)
+            tb = torch.from_numpy(np.stack(ts[i0:i0 + int(batch)])).to(device)
+            ids = None if len(meshes) == 1 else torch.full((Rb.shape[0],), m, dtype=torch.int32, device=device)
+            rgb.append(render_rgb(Rb, tb, K, meshes, size, mesh_ids=ids, shading=shading, ambient_weight=ambient_weight, ssaa=ssaa)["rgb"])
+            depth.append(metric.render_depth(Rb, tb, K, meshes, size, mesh_ids=ids) / float(depth_scale))
+        H, W = int(size[1]), int(size[0])
+        result[obj_id] = {"rgb": torch.cat(rgb) if rgb else torch.empty((0, H, W, 3), dtype=torch.uint8, device=device),
+                          "depth": torch.cat(depth) if depth else torch.empty((0, H, W), dtype=torch.float32, device=device),
+                          "scene_gt": scene_gt, "scene_camera": scene_camera}
+    return result
+
+
+def synthetic_batch(meshes, mesh_ids, R, t, cam_K, size, p3d_xyz, augment=None, backgrounds=None, **render_kw):
+    """A training batch of rendered frames: render_rgb(..., return_mask=True, return_boxes=True), then targets.make_training_batch
+    with frame b for sample b, the mask as both masks_visib and masks_full (one object, nothing occludes it) and the boxes as the
+    ground-truth boxes -- exactly that composition, bit for bit.  render_kw goes to render_rgb (ssaa must stay 1: the mask belongs to
+    the sample grid); every sample must be rendered with a non-empty mask (ValueError otherwise: a sample needs its box).
+    The boxes (16 bytes per sample) pass through the host, where make_training_batch grows them; no frame does."""
+    from . import targets
+    for k in ("return_depth", "return_mask", "return_boxes", "out"):
+        if k in render_kw:
+            raise ValueError("synthetic_batch sets %s itself" % k)
+    Rt, tt = _pose_tensors(R, t)
+    r = render_rgb(Rt, tt, cam_K, meshes, size, mesh_ids=mesh_ids, return_mask=True, return_boxes=True, **render_kw)
+    boxes = r["boxes"].cpu().numpy()
+    if (boxes[:, 0] < 0).any():
+        raise ValueError("samples %r render nothing inside the frame: no box to crop" % (np.nonzero(boxes[:, 0] < 0)[0].tolist(),))
+    B = boxes.shape[0]
+    return targets.make_training_batch(r["rgb"], r["mask"], r["mask"], Rt, tt, cam_K, boxes, p3d_xyz, img_index=np.arange(B),
+                                       augment=augment, backgrounds=backgrounds)

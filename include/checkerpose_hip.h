@@ -670,6 +670,43 @@ int cp_gt_info_from_depth(cp_stream_t stream, const float* depth_gt_large, const
                           const int32_t* image_ids, int I, int H, int W, double delta, int B, int32_t* counts, double* visib_fract,
                           int32_t* boxes, uint8_t* ok, uint8_t* mask, uint8_t* mask_visib, void* scratch);
 
+/* Shaded RGB training frames of coloured meshes on the device (next-row N14; csrc/render_rgb.hip; reference bop_toolkit
+ * scripts/render_train_imgs.py:128-214 with renderer_py.py:24-105, 422-518 in mode 'rgb'): uint8 frames of B poses at once.
+ * Coverage and the front-most surface are cp_render_depth's rule and arithmetic (csrc/vsd_raster.h); among triangles of equal 1 / Z
+ * the smallest face index wins.  Over the winning triangle v_color, v_L = normalize(light - eye_pos) per VERTEX and v_normal are
+ * interpolated perspective-correctly;  light_w = min(1, ambient_weight + max(dot(normalize(v_L), normalize(n)), 0));
+ * rgb = round-half-even(255 * light_w * v_color) on the fp32 value, clamped to 0..255; elsewhere the quantised bg_color.
+ *   shading 0 (flat): n = the unit face normal turned towards the viewer whatever the winding (the shader's cross(dFdx, dFdy));
+ *   shading 1 (phong): n = the interpolated v_normal = normalize(u_nm * vec4(a_normal, 1)).xyz, u_nm = inverse([R t; 0 1])^T -- the
+ *   shader's FOUR-vector normalisation, kept: the per-vertex lengths differ and weight the interpolation.  Needs normals.
+ *   poses, cam_K, k_stride, verts, v_offsets, faces, f_offsets, M, mesh_ids, Vmax: as cp_render_depth;
+ *   colors fp32 (sumV,3) in [0, 1], rows as verts, or NULL: every vertex has surf_color; normals fp32 (sumV,3) or NULL (flat);
+ *   surf_color, light_pos, bg_color: 3 doubles each ON THE HOST; light_pos in the camera frame of the poses (x right, y down,
+ *   z forward: the reference's light_cam_pos with y and z negated);
+ *   ssaa 1, 2 or 4: samples on the ssaa-times finer grid under K * ssaa, each quantised to uint8, then ssaa x ssaa samples averaged
+ *   as integers: (s + 2) >> 2, or round-half-even of s / 16 -- equal bit for bit to a plain render at (ssaa W, ssaa H) under
+ *   K * ssaa averaged so (the project's statement of cv2.INTER_AREA on 8-bit images, not pinned against cv2);
+ *   bgr != 0: the channels are stored in reverse order.
+ * Writes rgb uint8 (B,H,W,3) and ok uint8 (B): 0 for a pose that is not rendered (a non-finite entry of the pose or K, a singular R,
+ * a mesh id outside [0, M), a mesh that is empty or larger than Vmax, ANY vertex at Z <= 0): background only, depth and mask 0,
+ * box -1.  Optional, ssaa == 1 only (NULL to skip; CP_ERR_INVALID with ssaa > 1): depth fp32 (B,H,W), bit-identical to
+ * cp_render_depth's; mask uint8 (B,H,W) = 255 where depth > 0; boxes int32 (B,4) = xmin, ymin, xmax - xmin, ymax - ymin of the
+ * mask (misc.calc_2d_bbox), -1 -1 -1 -1 when it is empty.
+ * Four launches (pose, vertex, tile, finish) whatever the data and the options; a workgroup per (pose, 32 x 32 tile of the sample
+ * grid); tiles outside the pose's vertex rectangle store the background and leave.  Integer reductions only (LDS integer sums of
+ * the samples, wave shuffles and one order-independent integer atomic per box limit and tile): every output is bit-identical from
+ * call to call, for a pose alone or in a batch, with or without the optional outputs.  Nothing allocates or synchronises.
+ * CP_ERR_RANGE: 2^24 workgroups or more (B * ceil(ssaa W / 32) * ceil(ssaa H / 32) tiles) -- split the batch.
+ * Scratch layout: B headers of 48 4-byte words [P 12 | rect 4 | bad | ok | R t 12 | normal matrix 12 | box 4 | sign | spare],
+ * rounded up to 16 bytes, then four float4 (B, Vmax) tables (screen record, eye position, v_L, v_normal), each rounded up to 16
+ * bytes.  cp_render_rgb_scratch_bytes(B, Vmax) bytes, 16-byte aligned. */
+size_t cp_render_rgb_scratch_bytes(int B, int Vmax);
+int cp_render_rgb(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                  const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                  const float* colors, const float* normals, const double* surf_color, const double* light_pos,
+                  double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B, int Vmax,
+                  uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch);
+
 /* BOP's overlap errors on the device (next-row N12; csrc/mask_error.hip; reference bop_toolkit_lib/pose_error.py:235-330 cou_mask, cus,
  * cou_bb, cou_bb_proj with misc.calc_2d_bbox / misc.iou, misc.py:202-263): the four functions that close pose_error.py.
  * cp_mask_errors: for B pairs (estimate, ground truth) of one mesh each under one K, on a W x H frame,
