@@ -25,12 +25,18 @@ def is_deterministic():
 
 
 _RENDER_NAMES = ("render_rgb", "sample_views", "render_views", "synthetic_batch")
+_COCO_NAMES = ("annotate_masks", "calc_gt_coco", "mask_ious", "box_ious", "CocoSet", "eval_bop22_coco", "check_coco_results",
+               "save_coco_results")
 
 
 def __getattr__(name):
     """row N14's entry points, imported on first use (render.py pulls in torch): checkerpose_amd.render_rgb, .sample_views,
-    .render_views, .synthetic_batch"""
+    .render_views, .synthetic_batch; row N15's likewise (coco_eval.py): .annotate_masks, .calc_gt_coco, .mask_ious, .box_ious, .CocoSet,
+    .eval_bop22_coco, .check_coco_results, .save_coco_results (coco_eval.evaluate is reached through the module)"""
     if name in _RENDER_NAMES:
         from . import render
         return getattr(render, name)
+    if name in _COCO_NAMES:
+        from . import coco_eval
+        return getattr(coco_eval, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

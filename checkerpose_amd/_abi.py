@@ -210,6 +210,14 @@ SIGNATURES = {
     "cp_gt_info_from_depth": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_render_rgb_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_render_rgb": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_double, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "cp_coco_pack": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "cp_coco_rle_count": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cp_coco_rle_write": (_I, [_P, _P, _I, _I, _I, _P, _P, _L]),
+    "cp_coco_mask_iou": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P]),
+    "cp_coco_box_iou": (_I, [_P, _P, _I, _P, _I, _P, _I, _P]),
+    "cp_coco_match_scratch_bytes": (C.c_size_t, [_I]),
+    "cp_coco_match": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_coco_accumulate": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
     "cp_mask_errors_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_mask_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_mask_overlap": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

@@ -1180,6 +1180,50 @@ int cp_augment_frames(cp_stream_t stream, const uint8_t* frames, int n_img, int 
                       const uint8_t* backgrounds, int n_bg, const void* plan, int B, uint8_t* out);
 
 /* ---------------------------------------------------------------------------------------------
+ * BOP'22 COCO detection / segmentation scores on the device (next-row N15; csrc/coco_eval.hip; reference bop_toolkit
+ * scripts/calc_gt_coco.py, scripts/eval_bop22_coco.py, bop_toolkit_lib/pycoco_utils.py and pycocotools' COCOeval as the script drives
+ * it).  The rule of every stage is stated in the kernel file's header; the numpy restatement is tests/coco_stages.py.  Nothing
+ * allocates or synchronises; every output is bit-identical from call to call and for an item alone or in a batch.
+ *
+ * cp_coco_pack: masks uint8 (N,H,W), nonzero = set -> bits (N,H,WW) with WW = ceil(W / 32) 32-bit words per row (bit x & 31 of word
+ *   x >> 5, zero past W), area (N) and box (N,4) = xmin ymin xmax ymax, -1s for an empty mask.
+ * cp_coco_rle_count / cp_coco_rle_write: pycoco_utils.binary_mask_to_rle of the packed masks -- n_runs (N) per mask, then, with
+ *   offsets (N + 1 int64, device; the exclusive cumulative sum of n_runs) the concatenated int32 run lengths counts (total).  A mask
+ *   whose stretch [offsets[n], offsets[n + 1]) does not lie in [0, total) is not written.
+ * cp_coco_mask_iou / cp_coco_box_iou: out[p] (float64) for the listed pairs (P,2) = (detection, ground truth) indices; masks as
+ *   cp_coco_pack left them, boxes float64 x y w h (maskApi bbIou).  A pair with an index out of range scores NaN.
+ * cp_coco_match: COCOeval.evaluateImg for n_groups (image, category) groups.  offsets: det_off, gt_off, iou_off, n_groups + 1 int32
+ *   each, one after the other -- a HOST copy (checked: each starts at 0, ascends and ends at ND / NGT / P, no group keeps more than
+ *   CP_COCO_KEEP detections, iou stretch = D x G) and a DEVICE copy (read by the kernel, which checks it again).  A group's detections
+ *   are in descending score order, its ground truth in input order; iou holds each group's (D,G) matrix row-major.  det_area (ND),
+ *   gt_area (NGT) float64, gt_ignore (NGT) uint8, iou_thrs (CP_COCO_THRS) and area_rng (CP_COCO_AREAS x 2: lo hi) float64 on the
+ *   device.  -> dt_match int32 (ND, AREAS, THRS): index of the matched ground truth within its group + 1, 0 = none; dt_ignore uint8 of
+ *   that shape; gt_ignore_out uint8 (NGT, AREAS).  scratch: cp_coco_match_scratch_bytes(NGT) bytes, uninitialised.
+ * cp_coco_accumulate: COCOeval.accumulate for K categories whose groups are contiguous.  offsets: cat_det_off, cat_gt_off, K + 1 each,
+ *   host and device copies as above; det_rank (ND): the detection's position in its group; order (ND): detection indices, each
+ *   category's stretch in stable descending score order; max_dets: HOST, CP_COCO_MAXDETS values in [1, CP_COCO_KEEP]; rec_thrs
+ *   (CP_COCO_RECS) float64 device.  -> precision float64 (THRS, RECS, K, AREAS, MAXDETS), recall (THRS, K, AREAS, MAXDETS), -1 where a
+ *   category has no unignored ground truth.
+ * ------------------------------------------------------------------------------------------- */
+enum { CP_COCO_THRS = 10, CP_COCO_RECS = 101, CP_COCO_AREAS = 4, CP_COCO_MAXDETS = 3, CP_COCO_KEEP = 100 };
+int cp_coco_pack(cp_stream_t stream, const uint8_t* masks, int N, int H, int W, uint32_t* bits, int32_t* area, int32_t* box);
+int cp_coco_rle_count(cp_stream_t stream, const uint32_t* bits, int N, int H, int W, int32_t* n_runs);
+int cp_coco_rle_write(cp_stream_t stream, const uint32_t* bits, int N, int H, int W, const int64_t* offsets, int32_t* counts,
+                      long long total);
+int cp_coco_mask_iou(cp_stream_t stream, const uint32_t* det_bits, const int32_t* det_area, const int32_t* det_box, int ND,
+                     const uint32_t* gt_bits, const int32_t* gt_area, const int32_t* gt_box, int NG, int H, int W,
+                     const int32_t* pairs, int P, double* out);
+int cp_coco_box_iou(cp_stream_t stream, const double* det_box, int ND, const double* gt_box, int NG, const int32_t* pairs, int P,
+                    double* out);
+size_t cp_coco_match_scratch_bytes(int NGT);
+int cp_coco_match(cp_stream_t stream, const double* iou, const int32_t* offsets_host, const int32_t* offsets_dev, int n_groups, int ND,
+                  int NGT, int P, const double* det_area, const double* gt_area, const uint8_t* gt_ignore, const double* iou_thrs,
+                  const double* area_rng, int32_t* dt_match, uint8_t* dt_ignore, uint8_t* gt_ignore_out, void* scratch);
+int cp_coco_accumulate(cp_stream_t stream, const int32_t* dt_match, const uint8_t* dt_ignore, const uint8_t* gt_ignore,
+                       const int32_t* det_rank, const int32_t* order, const int32_t* offsets_host, const int32_t* offsets_dev, int K,
+                       int ND, int NGT, const int32_t* max_dets, const double* rec_thrs, double* precision, double* recall);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph helpers: capture the launch sequence of one forward (everything above is capture-safe:
  * no allocation, no synchronisation) and replay it with one call.
  * ------------------------------------------------------------------------------------------- */
