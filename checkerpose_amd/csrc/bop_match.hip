@@ -252,14 +252,11 @@ __global__ __launch_bounds__(BS_THREADS) void bop_scores_tp_kernel(BsParams p) {
   }
 }
 
-size_t bm_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-bool bm_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
-
 }  // namespace
 
 extern "C" size_t cp_bop_match_scratch_bytes(int NE, long long mask_words, int C) {
   if (NE < 0 || mask_words < 0 || C <= 0) return 0;
-  return bm_align16((size_t)NE * sizeof(int32_t)) + bm_align16((size_t)mask_words * C * sizeof(unsigned long long)) + 16;
+  return cp_align16_up((size_t)NE * sizeof(int32_t)) + cp_align16_up((size_t)mask_words * C * sizeof(unsigned long long)) + 16;
 }
 
 extern "C" int cp_bop_match(cp_stream_t stream, const double* errs, long long P, int C_err, const double* est_score,
@@ -272,10 +269,10 @@ extern "C" int cp_bop_match(cp_stream_t stream, const double* errs, long long P,
   if (G <= 0 || NG <= 0 || C <= 0 || C_err <= 0 || NE < 0 || P < 0 || mask_words < 0 || (E != 1 && E != 2)) return CP_ERR_INVALID;
   if ((P > 0 && !errs) || (NE > 0 && (!est_score || !est_ids)) || (mask_words > 0 && !mask_off)) return CP_ERR_INVALID;
   if (flags & ~(unsigned)(CP_BOP_MATCH_NO_LDS | CP_BOP_MATCH_SCRATCH_MASK)) return CP_ERR_INVALID;
-  if (bm_misaligned(scratch, 15) || bm_misaligned(errs, 7) || bm_misaligned(est_score, 7) || bm_misaligned(pair_off, 7) ||
-      bm_misaligned(col_th, 7) || bm_misaligned(out_score, 7) || bm_misaligned(out_err, 7) || bm_misaligned(out_norm, 7) ||
-      bm_misaligned(est_ids, 3) || bm_misaligned(est_off, 3) || bm_misaligned(gt_off, 3) || bm_misaligned(gt_rows, 3) ||
-      bm_misaligned(col_err, 3) || bm_misaligned(mask_off, 3) || bm_misaligned(out_est, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(errs, 7) || cp_misaligned(est_score, 7) || cp_misaligned(pair_off, 7) ||
+      cp_misaligned(col_th, 7) || cp_misaligned(out_score, 7) || cp_misaligned(out_err, 7) || cp_misaligned(out_norm, 7) ||
+      cp_misaligned(est_ids, 3) || cp_misaligned(est_off, 3) || cp_misaligned(gt_off, 3) || cp_misaligned(gt_rows, 3) ||
+      cp_misaligned(col_err, 3) || cp_misaligned(mask_off, 3) || cp_misaligned(out_est, 3))
     return CP_ERR_ALIGN;
   if (G >= (1 << 30) || (long long)NG * C * E >= (1LL << 40) || P >= (1LL << 40) / C_err) return CP_ERR_RANGE;
   BmParams p = {};
@@ -284,7 +281,7 @@ extern "C" int cp_bop_match(cp_stream_t stream, const double* errs, long long P,
   p.col_th = col_th; p.C = C; p.E = E; p.max_ests = max_ests; p.mask_off = mask_off; p.mask_words = mask_words; p.flags = flags;
   p.out_est = out_est; p.out_score = out_score; p.out_err = out_err; p.out_norm = out_norm;
   p.order = (int32_t*)scratch;
-  p.masks = mask_words > 0 ? (unsigned long long*)((char*)scratch + bm_align16((size_t)NE * sizeof(int32_t))) : nullptr;
+  p.masks = mask_words > 0 ? (unsigned long long*)((char*)scratch + cp_align16_up((size_t)NE * sizeof(int32_t))) : nullptr;
   const unsigned threads = C <= 64 ? 64u : (C <= 128 ? 128u : (unsigned)BM_THREADS);
   CP_LAUNCH(bop_match_kernel, dim3((unsigned)G), dim3(threads), 0, (hipStream_t)stream, p);
   return cp_check_launch();
@@ -296,8 +293,8 @@ extern "C" int cp_bop_scores(cp_stream_t stream, const int32_t* est_ids, const u
   if (!est_ids || !gt_obj || !gt_scene || !gt_off || !counts) return CP_ERR_INVALID;
   if (NG <= 0 || G <= 0 || C <= 0 || n_obj <= 0 || n_scene <= 0) return CP_ERR_INVALID;
   if (flags & ~(unsigned)CP_BOP_SCORES_NO_LDS) return CP_ERR_INVALID;
-  if (bm_misaligned(est_ids, 3) || bm_misaligned(gt_obj, 3) || bm_misaligned(gt_scene, 3) || bm_misaligned(gt_off, 3) ||
-      bm_misaligned(gt_rows, 3) || bm_misaligned(counts, 3))
+  if (cp_misaligned(est_ids, 3) || cp_misaligned(gt_obj, 3) || cp_misaligned(gt_scene, 3) || cp_misaligned(gt_off, 3) ||
+      cp_misaligned(gt_rows, 3) || cp_misaligned(counts, 3))
     return CP_ERR_ALIGN;
   const long long NB = 1LL + n_obj + n_scene;
   if (NB * (1LL + C) >= (1LL << 31) || (long long)NG * C >= (1LL << 40)) return CP_ERR_RANGE;

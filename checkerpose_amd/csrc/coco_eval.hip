@@ -372,8 +372,6 @@ __global__ __launch_bounds__(CE_ACC_THREADS) void coco_accumulate_kernel(AccPara
   }
 }
 
-bool ce_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
-
 // offsets (n + 1 values) start at 0, ascend and end at `end`
 bool ce_ascending(const int32_t* off, int n, long long end) {
   if (off[0] != 0 || off[n] != end) return false;
@@ -387,7 +385,7 @@ bool ce_ascending(const int32_t* off, int n, long long end) {
 extern "C" int cp_coco_pack(cp_stream_t stream, const uint8_t* masks, int N, int H, int W, uint32_t* bits, int32_t* area, int32_t* box) {
   if (!masks || !bits || !area || !box) return CP_ERR_INVALID;
   if (N < 1 || H < 1 || W < 1) return CP_ERR_INVALID;
-  if (ce_misaligned(bits, 3) || ce_misaligned(area, 3) || ce_misaligned(box, 3)) return CP_ERR_ALIGN;
+  if (cp_misaligned(bits, 3) || cp_misaligned(area, 3) || cp_misaligned(box, 3)) return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) - 4096 || N >= (1 << 24)) return CP_ERR_RANGE;
   CP_LAUNCH(coco_pack_kernel, dim3((unsigned)N), dim3(CE_PACK_THREADS), 0, (hipStream_t)stream, masks, bits, area, box, H, W, (W + 31) / 32);
   return cp_check_launch();
@@ -396,7 +394,7 @@ extern "C" int cp_coco_pack(cp_stream_t stream, const uint8_t* masks, int N, int
 extern "C" int cp_coco_rle_count(cp_stream_t stream, const uint32_t* bits, int N, int H, int W, int32_t* n_runs) {
   if (!bits || !n_runs) return CP_ERR_INVALID;
   if (N < 1 || H < 1 || W < 1) return CP_ERR_INVALID;
-  if (ce_misaligned(bits, 3) || ce_misaligned(n_runs, 3)) return CP_ERR_ALIGN;
+  if (cp_misaligned(bits, 3) || cp_misaligned(n_runs, 3)) return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) - 4096 || N >= (1 << 24)) return CP_ERR_RANGE;
   CP_LAUNCH(coco_rle_kernel<false>, dim3((unsigned)N), dim3(CE_RLE_THREADS), 0, (hipStream_t)stream, bits, H, W, (W + 31) / 32,
             (const int64_t*)nullptr, n_runs, (int32_t*)nullptr, 0LL);
@@ -407,7 +405,7 @@ extern "C" int cp_coco_rle_write(cp_stream_t stream, const uint32_t* bits, int N
                                  long long total) {
   if (!bits || !offsets || !counts) return CP_ERR_INVALID;
   if (N < 1 || H < 1 || W < 1 || total < 1) return CP_ERR_INVALID;
-  if (ce_misaligned(bits, 3) || ce_misaligned(offsets, 7) || ce_misaligned(counts, 3)) return CP_ERR_ALIGN;
+  if (cp_misaligned(bits, 3) || cp_misaligned(offsets, 7) || cp_misaligned(counts, 3)) return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) - 4096 || N >= (1 << 24)) return CP_ERR_RANGE;
   CP_LAUNCH(coco_rle_kernel<true>, dim3((unsigned)N), dim3(CE_RLE_THREADS), 0, (hipStream_t)stream, bits, H, W, (W + 31) / 32, offsets,
             (int32_t*)nullptr, counts, total);
@@ -419,8 +417,8 @@ extern "C" int cp_coco_mask_iou(cp_stream_t stream, const uint32_t* det_bits, co
                                 const int32_t* pairs, int P, double* out) {
   if (!det_bits || !det_area || !det_box || !gt_bits || !gt_area || !gt_box || !pairs || !out) return CP_ERR_INVALID;
   if (ND < 1 || NG < 1 || H < 1 || W < 1 || P < 1) return CP_ERR_INVALID;
-  if (ce_misaligned(det_bits, 3) || ce_misaligned(det_area, 3) || ce_misaligned(det_box, 3) || ce_misaligned(gt_bits, 3) ||
-      ce_misaligned(gt_area, 3) || ce_misaligned(gt_box, 3) || ce_misaligned(pairs, 3) || ce_misaligned(out, 7))
+  if (cp_misaligned(det_bits, 3) || cp_misaligned(det_area, 3) || cp_misaligned(det_box, 3) || cp_misaligned(gt_bits, 3) ||
+      cp_misaligned(gt_area, 3) || cp_misaligned(gt_box, 3) || cp_misaligned(pairs, 3) || cp_misaligned(out, 7))
     return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) - 4096) return CP_ERR_RANGE;
   IouParams p = {};
@@ -434,7 +432,7 @@ extern "C" int cp_coco_box_iou(cp_stream_t stream, const double* det_box, int ND
                                int P, double* out) {
   if (!det_box || !gt_box || !pairs || !out) return CP_ERR_INVALID;
   if (ND < 1 || NG < 1 || P < 1) return CP_ERR_INVALID;
-  if (ce_misaligned(det_box, 7) || ce_misaligned(gt_box, 7) || ce_misaligned(pairs, 3) || ce_misaligned(out, 7)) return CP_ERR_ALIGN;
+  if (cp_misaligned(det_box, 7) || cp_misaligned(gt_box, 7) || cp_misaligned(pairs, 3) || cp_misaligned(out, 7)) return CP_ERR_ALIGN;
   CP_LAUNCH(coco_box_iou_kernel, dim3((unsigned)((P + CE_THREADS - 1) / CE_THREADS)), dim3(CE_THREADS), 0, (hipStream_t)stream, det_box, ND,
             gt_box, NG, pairs, P, out);
   return cp_check_launch();
@@ -459,8 +457,8 @@ extern "C" int cp_coco_match(cp_stream_t stream, const double* iou, const int32_
     const long long D = (long long)doff[g + 1] - doff[g], G = (long long)goff[g + 1] - goff[g];
     if (D > CP_COCO_KEEP || (long long)ioff[g + 1] - ioff[g] != D * G) return CP_ERR_INVALID;
   }
-  if (ce_misaligned(iou, 7) || ce_misaligned(offsets_dev, 3) || ce_misaligned(det_area, 7) || ce_misaligned(gt_area, 7) ||
-      ce_misaligned(iou_thrs, 7) || ce_misaligned(area_rng, 7) || ce_misaligned(dt_match, 3))
+  if (cp_misaligned(iou, 7) || cp_misaligned(offsets_dev, 3) || cp_misaligned(det_area, 7) || cp_misaligned(gt_area, 7) ||
+      cp_misaligned(iou_thrs, 7) || cp_misaligned(area_rng, 7) || cp_misaligned(dt_match, 3))
     return CP_ERR_ALIGN;
   MatchParams p = {};
   p.iou = iou; p.offs = offsets_dev; p.n_groups = n_groups; p.ND = ND; p.NGT = NGT; p.P = P; p.det_area = det_area; p.gt_area = gt_area;
@@ -480,8 +478,8 @@ extern "C" int cp_coco_accumulate(cp_stream_t stream, const int32_t* dt_match, c
   if (!ce_ascending(offsets_host, K, ND) || !ce_ascending(offsets_host + (K + 1), K, NGT)) return CP_ERR_INVALID;
   for (int m = 0; m < CE_M; ++m)
     if (max_dets[m] < 1 || max_dets[m] > CP_COCO_KEEP) return CP_ERR_INVALID;
-  if (ce_misaligned(dt_match, 3) || ce_misaligned(det_rank, 3) || ce_misaligned(order, 3) || ce_misaligned(offsets_dev, 3) ||
-      ce_misaligned(rec_thrs, 7) || ce_misaligned(precision, 7) || ce_misaligned(recall, 7))
+  if (cp_misaligned(dt_match, 3) || cp_misaligned(det_rank, 3) || cp_misaligned(order, 3) || cp_misaligned(offsets_dev, 3) ||
+      cp_misaligned(rec_thrs, 7) || cp_misaligned(precision, 7) || cp_misaligned(recall, 7))
     return CP_ERR_ALIGN;
   AccParams p = {};
   p.dt_match = dt_match; p.dt_ignore = dt_ignore; p.gt_ignore = gt_ignore; p.det_rank = det_rank; p.order = order; p.offs = offsets_dev;

@@ -258,6 +258,9 @@ static inline int cp_num_cus() {
   return n;
 }
 static inline bool cp_aligned16(const void* p) { return (((uintptr_t)p) & 15u) == 0; }
+static inline size_t cp_align16_up(size_t n) { return (n + 15) & ~(size_t)15; }      // scratch carving
+// an entry point's pointer check: q is not on a (mask + 1)-byte boundary (nullptr, an absent optional argument, never is)
+static inline bool cp_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
 // the branch-free epilogue activation (cp_act_apply: max(v, v * s + 0)) is LeakyReLU only for slopes in [0, 1]: anything else
 // (a slope > 1, a negative one, NaN) is refused at the entry point instead of computed wrongly
 static inline bool cp_act_ok(int act, float slope) { return act != 2 /* CP_ACT_LEAKY */ || (slope >= 0.f && slope <= 1.f); }

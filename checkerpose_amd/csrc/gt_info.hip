@@ -5,19 +5,18 @@
 // rendered tile by tile with vsd_raster.h's rasteriser (the render rule is stated there), and nothing is stored unless asked.
 //
 // Tile grid.  32 x 32 tiles starting at (-32 ceil(W/32), -32 ceil(H/32)): frame pixel (0, 0) is a tile corner, so an in-frame tile
-// runs vs_raster_tile with the arguments cp_render_depth's tile of the (W, H) frame does -- the in-frame depth is the same bits.
+// runs vs_depth_tile with the arguments cp_render_depth's tile of the (W, H) frame does -- the in-frame depth is the same bits.
 // Tile pixels outside the canvas (the grid overshoots it on every side) count nowhere.
 //
 // Launches (four; three from a caller's canvas):
-//   gt_info_pose_kernel    per pose: P = K' [R | t] (vs_krt), validity, the rectangle and the integer accumulators initialised.
-//   gt_info_vertex_kernel  per (pose, 256 vertices): screen records (vs_project, clamped to the canvas) and the pose's pixel rectangle.
+//   gt_info_pose_kernel    per pose: P = K' [R | t] (vs_side_init), validity, the rectangle and the integer accumulators initialised.
+//   gt_info_vertex_kernel  per (pose, 256 vertices): screen records (vs_vertex_chunk, clamped to the canvas) and the pose's pixel rectangle.
 //   gt_info_tile_kernel    a workgroup per (pose, canvas tile).  A tile the rectangle misses leaves at once (or writes zeros into the
 //                          images asked for, when it lies in the frame).  Otherwise: the depth of its 1024 pixels; in the canvas,
 //                          depth > 0 counts into px_count_all and the silhouette's box; IN THE FRAME ONLY the reference's distance
 //                          arithmetic (fp64 square roots and quotients without contraction, the fp32 difference against delta)
 //                          gives mask, mask_visib, px_count_valid, px_count_visib and the visible box.  Three sums, four minima and
-//                          four maxima are reduced as INTEGERS: wave shuffles, LDS, then one atomicAdd / Min / Max per value and
-//                          tile into the pose's accumulators (order-independent).
+//                          four maxima are reduced as INTEGERS into the pose's accumulators (vs_acc_reduce: order-independent).
 //   gt_info_finish_kernel  per pose: the quotient, the two boxes as x, y, w, h (both gated on px_count_visib > 0), ok.
 // Every output is a function of integer counts and per-pixel values: bit-identical from call to call, for a pose alone or in a
 // batch, with or without the images.  No floating-point atomics, no initialised scratch beyond what gt_info_pose_kernel writes.
@@ -25,9 +24,10 @@
 
 namespace {
 
-// 4-byte words per pose: P[12] rect[4] bad ok | all valid visib | obj xmin ymin xmax ymax | visib xmin ymin xmax ymax
+// 4-byte words per pose: VsHdr<1> (P rect bad ok) | all valid visib | obj xmin ymin xmax ymax | visib xmin ymin xmax ymax
+using GiH = VsHdr<1>;
 constexpr int GI_HDR = 32;
-constexpr int GI_RECT = 12, GI_BAD = 16, GI_OK = 17, GI_ACC = 18, GI_NACC = 11;
+constexpr int GI_ACC = GiH::USER, GI_NSUM = 3, GI_NACC = 11;
 enum { GI_MODE_RENDER = 0, GI_MODE_DEPTH = 1 };
 
 struct GiParams {
@@ -54,66 +54,56 @@ struct GiParams {
   int k_stride, M, B, Vmax, H, W, I, mode, tx, ty, x0, y0, vchunks;
 };
 
-// identity of accumulator k: sums 0, minima INT_MAX, maxima INT_MIN
-__device__ __forceinline__ int gi_identity(int k) { return k < 3 ? 0 : (((k - 3) & 3) < 2 ? INT_MAX : INT_MIN); }
-
 __global__ __launch_bounds__(VS_THREADS) void gt_info_pose_kernel(GiParams p) {
 #pragma clang fp contract(off)
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.B) return;
   int32_t* __restrict__ h = p.hdr + (size_t)b * GI_HDR;
   const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
-  bool ok = true;
-  for (int k = 0; k < 9; ++k) ok = ok && isfinite(K[k]);
+  bool ok = vs_finite(K, 9);
   const int img = p.image_id ? p.image_id[b] : 0;
   ok = ok && img >= 0 && img < p.I;
   if (p.mode == GI_MODE_DEPTH) {
     for (int k = 0; k < 12; ++k) h[k] = 0;
-    h[GI_RECT] = -p.W; h[GI_RECT + 1] = -p.H; h[GI_RECT + 2] = 2 * p.W - 1; h[GI_RECT + 3] = 2 * p.H - 1;
+    vs_rect_set(h + GiH::RECT(0), -p.W, -p.H, 2 * p.W - 1, 2 * p.H - 1);
   } else {
     int vfirst, V, ffirst, F, m;
     ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m) && ok;
     const double* __restrict__ q = p.poses + 12 * (size_t)b;
-    for (int k = 0; k < 12; ++k) ok = ok && isfinite(q[k]);
-    vs_krt(K[0], K[4], K[2], K[5], q, (float*)h);
-    h[GI_RECT] = INT_MAX; h[GI_RECT + 1] = INT_MAX; h[GI_RECT + 2] = INT_MIN; h[GI_RECT + 3] = INT_MIN;
+    ok = ok && vs_finite(q, 12);
+    vs_side_init(K, 1.0, q, (float*)h + GiH::P(0), h + GiH::RECT(0));
   }
-  h[GI_BAD] = 0;
-  h[GI_OK] = ok ? 1 : 0;
-  for (int k = 0; k < GI_NACC; ++k) h[GI_ACC + k] = gi_identity(k);
+  h[GiH::BAD(0)] = 0;
+  h[GiH::OK] = ok ? 1 : 0;
+  for (int k = 0; k < GI_NACC; ++k) h[GI_ACC + k] = vs_acc_identity<GI_NSUM>(k);
   for (int k = GI_ACC + GI_NACC; k < GI_HDR; ++k) h[k] = 0;
 }
 
 __global__ __launch_bounds__(VS_THREADS) void gt_info_vertex_kernel(GiParams p) {
-  const int vc = blockIdx.x % p.vchunks, b = blockIdx.x / p.vchunks;
+  int b, s, vc;
+  vs_vertex_block(p.vchunks, 1, b, s, vc);
   int32_t* __restrict__ h = p.hdr + (size_t)b * GI_HDR;
-  if (!h[GI_OK]) return;                                             // (uniform; no barrier in this kernel)
+  if (!h[GiH::OK]) return;                                           // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
   vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const int i = vc * VS_THREADS + threadIdx.x;
-  int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN, bad = 0;
-  if (i < V)
-    p.sv[(size_t)b * p.Vmax + i] = vs_project((const float*)h, p.verts + 3 * ((size_t)vfirst + i), -(float)p.W - 2.f, 2.f * (float)p.W + 1.f,
-                                              -(float)p.H - 2.f, 2.f * (float)p.H + 1.f, x0, y0, x1, y1, bad);
-  vs_rect_merge(x0, y0, x1, y1, bad, h + GI_RECT, h + GI_BAD);
+  const float4 canvas = make_float4(-(float)p.W - 2.f, 2.f * (float)p.W + 1.f, -(float)p.H - 2.f, 2.f * (float)p.H + 1.f);
+  vs_vertex_chunk((const float*)h + GiH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, canvas, p.sv + (size_t)b * p.Vmax, h + GiH::RECT(0),
+                  h + GiH::BAD(0));
 }
 
 __global__ __launch_bounds__(VS_THREADS) void gt_info_tile_kernel(GiParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];
   __shared__ int s_n;
   __shared__ int s_red[VS_THREADS / 64][GI_NACC];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles = p.tx * p.ty;
-  const int b = blockIdx.x / tiles, t = blockIdx.x % tiles;
-  const int ox = p.x0 + (t % p.tx) * VS_TILE, oy = p.y0 + (t / p.tx) * VS_TILE;      // first pixel, frame coordinates (any sign)
+  const VsTile c = vs_tile(p.tx, p.ty, p.x0, p.y0);
+  const int b = c.b, ox = c.ox, oy = c.oy;                           // first pixel, frame coordinates (any sign)
   int32_t* __restrict__ h = p.hdr + (size_t)b * GI_HDR;
-  const bool live = h[GI_OK] && !h[GI_BAD];
-  const bool hit = live && h[GI_RECT] <= ox + VS_TILE - 1 && h[GI_RECT + 2] >= ox && h[GI_RECT + 1] <= oy + VS_TILE - 1 && h[GI_RECT + 3] >= oy;
+  const bool live = h[GiH::OK] && !h[GiH::BAD(0)];
+  const bool hit = live && vs_tile_hit(h + GiH::RECT(0), ox, oy);
   const bool in_frame = ox >= 0 && ox < p.W && oy >= 0 && oy < p.H;                  // the grid is anchored at frame pixel (0, 0)
   const bool store = in_frame && (p.mask || p.depth_gt);
   if (!hit && !store) return;                                        // (uniform)
-  const int lx = lane & 31, ly0 = wave * VS_STRIP + (lane >> 5);    // the lane's pixels: (lx, ly0 + 2 k), k = 0..3
-  const int x = ox + lx;
+  const int x = ox + c.lx;
   float dep[VS_PPL];
 #pragma unroll
   for (int k = 0; k < VS_PPL; ++k) dep[k] = 0.f;
@@ -121,23 +111,23 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_tile_kernel(GiParams p) {
     if (p.mode == GI_MODE_DEPTH) {
 #pragma unroll
       for (int k = 0; k < VS_PPL; ++k) {
-        const int y = oy + ly0 + 2 * k;
+        const int y = oy + c.y(k);
         if (x >= -p.W && x < 2 * p.W && y >= -p.H && y < 2 * p.H) dep[k] = p.large[((size_t)b * 3 * p.H + (y + p.H)) * 3 * p.W + (x + p.W)];
       }
     } else {
       int vfirst, V, ffirst, F, m;
       vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-      vs_raster_tile(s_tri, &s_n, p.sv + (size_t)b * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, ox, oy, tid, lx, ly0, wave, dep);
+      vs_depth_tile(s_tri, &s_n, p.sv + (size_t)b * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep);
     }
   }
 
   int acc[GI_NACC];
 #pragma unroll
-  for (int k = 0; k < GI_NACC; ++k) acc[k] = gi_identity(k);
+  for (int k = 0; k < GI_NACC; ++k) acc[k] = vs_acc_identity<GI_NSUM>(k);
   // ---- the canvas: the truncated silhouette's count and box (no distance arithmetic)
 #pragma unroll
   for (int k = 0; k < VS_PPL; ++k) {
-    const int y = oy + ly0 + 2 * k;
+    const int y = oy + c.y(k);
     if (dep[k] > 0.f && x >= -p.W && x < 2 * p.W && y >= -p.H && y < 2 * p.H) {
       acc[0] += 1;
       acc[3] = min(acc[3], x); acc[4] = min(acc[4], y); acc[5] = max(acc[5], x); acc[6] = max(acc[6], y);
@@ -150,7 +140,7 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_tile_kernel(GiParams p) {
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k) {
-      const int y = oy + ly0 + 2 * k;
+      const int y = oy + c.y(k);
       if (x >= p.W || y >= p.H) continue;
       const float dg = dep[k];
       bool m = false, vis = false;
@@ -174,30 +164,7 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_tile_kernel(GiParams p) {
   }
   if (!hit) return;                                                  // (uniform) zeros were stored, nothing to count
 
-#pragma unroll
-  for (int k = 0; k < GI_NACC; ++k) {
-    int v = acc[k];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) {
-      const int o = __shfl_xor(v, w, 64);
-      v = k < 3 ? v + o : (((k - 3) & 3) < 2 ? min(v, o) : max(v, o));
-    }
-    if (lane == 0) s_red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < GI_NACC) {
-    const int k = tid;
-    int v = s_red[0][k];
-    for (int w = 1; w < VS_THREADS / 64; ++w) {
-      const int o = s_red[w][k];
-      v = k < 3 ? v + o : (((k - 3) & 3) < 2 ? min(v, o) : max(v, o));
-    }
-    if (v != gi_identity(k)) {
-      if (k < 3) atomicAdd(h + GI_ACC + k, v);
-      else if (((k - 3) & 3) < 2) atomicMin(h + GI_ACC + k, v);
-      else atomicMax(h + GI_ACC + k, v);
-    }
-  }
+  vs_acc_reduce<GI_NSUM, GI_NACC>(acc, s_red, h + GI_ACC);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void gt_info_finish_kernel(GiParams p) {
@@ -205,58 +172,41 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_finish_kernel(GiParams p) 
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.B) return;
   const int32_t* __restrict__ h = p.hdr + (size_t)b * GI_HDR;
-  const bool live = h[GI_OK] && !h[GI_BAD];
+  const bool live = h[GiH::OK] && !h[GiH::BAD(0)];
   const int32_t* __restrict__ a = h + GI_ACC;
   const int all = live ? a[0] : 0, valid = live ? a[1] : 0, visib = live ? a[2] : 0;
   p.counts[3 * (size_t)b] = all;
   p.counts[3 * (size_t)b + 1] = valid;
   p.counts[3 * (size_t)b + 2] = visib;
   p.fract[b] = all > 0 ? (double)visib / (double)all : 0.0;
-  int32_t* __restrict__ bx = p.boxes + 8 * (size_t)b;
-  for (int s = 0; s < 2; ++s) {
-    const int32_t* __restrict__ r = a + 3 + 4 * s;
-    const bool have = visib > 0;                                     // bbox_obj is gated on the VISIBLE count too
-    bx[4 * s] = have ? r[0] : -1;
-    bx[4 * s + 1] = have ? r[1] : -1;
-    bx[4 * s + 2] = have ? r[2] - r[0] : -1;
-    bx[4 * s + 3] = have ? r[3] - r[1] : -1;
-  }
+  for (int s = 0; s < 2; ++s)                                        // bbox_obj is gated on the VISIBLE count too
+    vs_box_xywh(a + GI_NSUM + 4 * s, visib > 0, p.boxes + 8 * (size_t)b + 4 * s);
   p.ok[b] = live ? 1 : 0;
 }
-
-size_t gi_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 void gi_carve(GiParams& p, void* scratch) {
   char* at = (char*)scratch;
   p.hdr = (int32_t*)at;
-  at += gi_align16((size_t)p.B * GI_HDR * sizeof(int32_t));
+  at += cp_align16_up((size_t)p.B * GI_HDR * sizeof(int32_t));
   p.sv = (float4*)at;
 }
 
 int gi_launch(GiParams& p, hipStream_t st) {
-  const int fx = (p.W + VS_TILE - 1) / VS_TILE, fy = (p.H + VS_TILE - 1) / VS_TILE;      // the frame's tiles
-  if ((long long)p.H * p.W >= (1LL << 31) / 9) return CP_ERR_RANGE;
-  p.x0 = -VS_TILE * fx; p.y0 = -VS_TILE * fy;
-  p.tx = fx + (2 * p.W + VS_TILE - 1) / VS_TILE;                                         // up to pixel 2W - 1
-  p.ty = fy + (2 * p.H + VS_TILE - 1) / VS_TILE;
-  p.vchunks = (p.Vmax + VS_THREADS - 1) / VS_THREADS;
-  const long long tile_blocks = (long long)p.B * p.tx * p.ty, vert_blocks = (long long)p.B * p.vchunks;
-  if (tile_blocks >= (1LL << 24) || vert_blocks >= (1LL << 24)) return CP_ERR_RANGE;
-  const unsigned pose_blocks = (unsigned)((p.B + VS_THREADS - 1) / VS_THREADS);
-  CP_LAUNCH(gt_info_pose_kernel, dim3(pose_blocks), dim3(VS_THREADS), 0, st, p);
-  if (p.mode == GI_MODE_RENDER) CP_LAUNCH(gt_info_vertex_kernel, dim3((unsigned)vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(gt_info_tile_kernel, dim3((unsigned)tile_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(gt_info_finish_kernel, dim3(pose_blocks), dim3(VS_THREADS), 0, st, p);
+  VsGrid g;
+  if ((long long)p.H * p.W >= (1LL << 31) / 9 || !vs_grid(p.W, p.H, 1, true, p.B, 1, p.Vmax, g)) return CP_ERR_RANGE;
+  p.tx = g.tx; p.ty = g.ty; p.x0 = g.x0; p.y0 = g.y0; p.vchunks = g.vchunks;
+  CP_LAUNCH(gt_info_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
+  if (p.mode == GI_MODE_RENDER) CP_LAUNCH(gt_info_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(gt_info_tile_kernel, dim3(g.tile_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(gt_info_finish_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   return cp_check_launch();
 }
-
-bool gi_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
 
 }  // namespace
 
 extern "C" size_t cp_gt_info_scratch_bytes(int B, int Vmax) {
   if (B <= 0 || Vmax < 0) return 0;
-  return gi_align16((size_t)B * GI_HDR * sizeof(int32_t)) + gi_align16((size_t)B * Vmax * sizeof(float4));
+  return cp_align16_up((size_t)B * GI_HDR * sizeof(int32_t)) + cp_align16_up((size_t)B * Vmax * sizeof(float4));
 }
 
 extern "C" int cp_gt_info(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
@@ -271,10 +221,10 @@ extern "C" int cp_gt_info(cp_stream_t stream, const double* poses, const double*
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (!image_ids && I != 1) return CP_ERR_INVALID;
   if ((mask == nullptr) != (mask_visib == nullptr)) return CP_ERR_INVALID;
-  if (gi_misaligned(scratch, 15) || gi_misaligned(poses, 7) || gi_misaligned(cam_K, 7) || gi_misaligned(visib_fract, 7) ||
-      gi_misaligned(verts, 3) || gi_misaligned(v_offsets, 3) || gi_misaligned(faces, 3) || gi_misaligned(f_offsets, 3) ||
-      gi_misaligned(mesh_ids, 3) || gi_misaligned(depth, 3) || gi_misaligned(image_ids, 3) || gi_misaligned(counts, 3) ||
-      gi_misaligned(boxes, 3) || gi_misaligned(depth_gt, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(visib_fract, 7) ||
+      cp_misaligned(verts, 3) || cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) ||
+      cp_misaligned(mesh_ids, 3) || cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) ||
+      cp_misaligned(boxes, 3) || cp_misaligned(depth_gt, 3))
     return CP_ERR_ALIGN;
   GiParams p = {};
   p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
@@ -293,8 +243,8 @@ extern "C" int cp_gt_info_from_depth(cp_stream_t stream, const float* depth_gt_l
   if (B <= 0 || I <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9) || !(delta == delta)) return CP_ERR_INVALID;
   if (!image_ids && I != 1) return CP_ERR_INVALID;
   if ((mask == nullptr) != (mask_visib == nullptr)) return CP_ERR_INVALID;
-  if (gi_misaligned(scratch, 15) || gi_misaligned(cam_K, 7) || gi_misaligned(visib_fract, 7) || gi_misaligned(depth_gt_large, 3) ||
-      gi_misaligned(depth, 3) || gi_misaligned(image_ids, 3) || gi_misaligned(counts, 3) || gi_misaligned(boxes, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(cam_K, 7) || cp_misaligned(visib_fract, 7) || cp_misaligned(depth_gt_large, 3) ||
+      cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
   GiParams p = {};
   p.large = depth_gt_large; p.K = cam_K; p.k_stride = k_stride; p.depth = depth; p.image_id = image_ids; p.I = I; p.H = H; p.W = W;

@@ -4,19 +4,19 @@
 // makes full-frame numpy passes; here both silhouettes of a 32 x 32 tile are rasterised by the same workgroup (vsd_raster.h's
 // rasteriser, the render rule is stated there), so intersection and union are decided in registers and no image exists unless asked.
 //
-// Mask rule.  A pixel of a side is set exactly where cp_render_depth's depth is > 0: vs_raster_tile is called as cp_render_depth
+// Mask rule.  A pixel of a side is set exactly where cp_render_depth's depth is > 0: vs_depth_tile is called as cp_render_depth
 // calls it (the frame's tile grid, the same arguments), the 1 / Z plane included -- a covered sample whose fp32 plane value is not
 // positive is background there, so it is here.
 //
 // Launches of cp_mask_errors (four):
-//   mask_error_pose_kernel    per pair: P = K' [R | t] of both sides (vs_krt), validity, the caller's overlapping_sphere_projections
-//                             shortcut (misc.py:309-331, as vsd_pose_kernel states it), the rectangles and accumulators initialised.
-//   mask_error_vertex_kernel  per (pair, side, 256 vertices): screen records (vs_project), the side's pixel rectangle and its "a vertex
-//                             at Z <= 0" flag through integer atomics (vs_rect_merge).
+//   mask_error_pose_kernel    per pair: P = K' [R | t] of both sides (vs_side_init), validity, the caller's
+//                             overlapping_sphere_projections shortcut (vs_sphere_skip), the rectangles and accumulators initialised.
+//   mask_error_vertex_kernel  per (pair, side, 256 vertices): screen records, the side's pixel rectangle and its "a vertex at Z <= 0"
+//                             flag through integer atomics (vs_vertex_chunk).
 //   mask_error_tile_kernel    a workgroup per (pair, frame tile).  A tile outside both rectangles leaves at once (or writes zeros when
 //                             the masks are asked).  Otherwise both sides' depths of its 1024 pixels, then four sums (inter, union,
-//                             n_est, n_gt), four minima and four maxima (both silhouettes' xmin ymin xmax ymax) reduced as INTEGERS:
-//                             wave shuffles, LDS, one atomicAdd / Min / Max per value and tile into the pair's accumulators.
+//                             n_est, n_gt), four minima and four maxima (both silhouettes' xmin ymin xmax ymax) reduced as INTEGERS
+//                             into the pair's accumulators (vs_acc_reduce).
 //   mask_error_finish_kernel  per pair: cus = 1 - inter / (double)union (1.0 when union == 0) and cou_bb_proj = 1 - iou of the two
 //                             boxes (x, y, xmax - xmin, ymax - ymin: no + 1, not clipped), integer arithmetic until the one quotient.
 // The sphere shortcut belongs to 'cus' alone (eval_calc_errors.py:357-362): a skipped pair scores cus = 1.0 and is rendered only when
@@ -27,9 +27,10 @@
 
 namespace {
 
-// 4-byte words per pair: P_est[12] P_gt[12] rect_est[4] rect_gt[4] bad[2] ok skip render | inter union n_est n_gt | est box | gt box
+// 4-byte words per pair: VsHdr<2> (P rect bad of both sides, ok) skip render | inter union n_est n_gt | est box | gt box
+using MeH = VsHdr<2>;
 constexpr int ME_HDR = 52;
-constexpr int ME_RECT = 24, ME_BAD = 32, ME_OK = 34, ME_SKIP = 35, ME_RENDER = 36, ME_ACC = 37, ME_NACC = 12;
+constexpr int ME_SKIP = MeH::USER, ME_RENDER = ME_SKIP + 1, ME_ACC = ME_SKIP + 2, ME_NSUM = 4, ME_NACC = 12;
 constexpr int MO_THREADS = 512;
 
 struct MeParams {
@@ -52,10 +53,6 @@ struct MeParams {
   float4* sv;                 // (B, 2, Vmax)
   int k_stride, M, B, Vmax, H, W, sphere, tx, ty, vchunks;
 };
-
-// identity of accumulator k: sums 0, minima INT_MAX, maxima INT_MIN
-__device__ __forceinline__ int me_identity(int k) { return k < 4 ? 0 : ((k & 3) < 2 ? INT_MAX : INT_MIN); }
-__device__ __forceinline__ int me_combine(int k, int a, int b) { return k < 4 ? a + b : ((k & 3) < 2 ? min(a, b) : max(a, b)); }
 
 // 1 - misc.iou of two boxes x, y, w, h; T = long long (exact) or double (the caller's values): one quotient at the end
 template <typename T>
@@ -88,14 +85,7 @@ __device__ __forceinline__ void me_results(const int32_t* __restrict__ a, double
   if (counts)
     for (int k = 0; k < 4; ++k) counts[k] = a[k];
   if (boxes)
-    for (int s = 0; s < 2; ++s) {
-      const int32_t* __restrict__ r = a + 4 + 4 * s;
-      const bool have = a[2 + s] > 0;
-      boxes[4 * s] = have ? r[0] : -1;
-      boxes[4 * s + 1] = have ? r[1] : -1;
-      boxes[4 * s + 2] = have ? r[2] - r[0] : -1;
-      boxes[4 * s + 3] = have ? r[3] - r[1] : -1;
-    }
+    for (int s = 0; s < 2; ++s) vs_box_xywh(a + 4 + 4 * s, a[2 + s] > 0, boxes + 4 * s);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void mask_error_pose_kernel(MeParams p) {
@@ -104,73 +94,46 @@ __global__ __launch_bounds__(VS_THREADS) void mask_error_pose_kernel(MeParams p)
   if (b >= p.B) return;
   int32_t* __restrict__ h = p.hdr + (size_t)b * ME_HDR;
   const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
-  bool ok = true;
-  for (int k = 0; k < 9; ++k) ok = ok && isfinite(K[k]);
   int vfirst, V, ffirst, F, m;
-  ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m) && ok;
+  bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
   const double* __restrict__ e = p.est + 12 * (size_t)b;
   const double* __restrict__ g = p.gt + 12 * (size_t)b;
-  for (int k = 0; k < 12; ++k) ok = ok && isfinite(e[k]) && isfinite(g[k]);
-  float* __restrict__ P = (float*)h;
-  vs_krt(K[0], K[4], K[2], K[5], e, P);
-  vs_krt(K[0], K[4], K[2], K[5], g, P + 12);
-  for (int s = 0; s < 2; ++s) {
-    h[ME_RECT + 4 * s] = INT_MAX; h[ME_RECT + 4 * s + 1] = INT_MAX; h[ME_RECT + 4 * s + 2] = INT_MIN; h[ME_RECT + 4 * s + 3] = INT_MIN;
-  }
-  h[ME_BAD] = 0; h[ME_BAD + 1] = 0;
-  int skip = 0;
-  if (ok && p.sphere) {
-    // misc.overlapping_sphere_projections(0.5 * diameter, t_est, t_gt), as eval_calc_errors.py:299-302 calls it
-    const double radius = p.diameters[m] / 2.0;
-    bool overlap = false;
-    if (!(e[11] == 0.0 || g[11] == 0.0)) {
-      const double dx = e[9] / e[11] - g[9] / g[11], dy = e[10] / e[11] - g[10] / g[11];
-      overlap = sqrt(dx * dx + dy * dy) < radius * (1.0 / e[11] + 1.0 / g[11]);
-    }
-    skip = overlap ? 0 : 1;
-  }
-  h[ME_OK] = ok ? 1 : 0;
+  ok = ok && vs_pose_finite(K, e) && vs_finite(g, 12);
+  vs_side_init(K, 1.0, e, (float*)h + MeH::P(0), h + MeH::RECT(0));
+  vs_side_init(K, 1.0, g, (float*)h + MeH::P(1), h + MeH::RECT(1));
+  h[MeH::BAD(0)] = 0; h[MeH::BAD(1)] = 0;
+  const int skip = (ok && p.sphere) ? vs_sphere_skip(e, g, p.diameters[m] / 2.0) : 0;
+  h[MeH::OK] = ok ? 1 : 0;
   h[ME_SKIP] = skip;
   h[ME_RENDER] = (ok && !(skip && !p.bbp)) ? 1 : 0;                   // the shortcut is cus' alone: cou_bb_proj still renders
-  for (int k = 0; k < ME_NACC; ++k) h[ME_ACC + k] = me_identity(k);
+  for (int k = 0; k < ME_NACC; ++k) h[ME_ACC + k] = vs_acc_identity<ME_NSUM>(k);
   for (int k = ME_ACC + ME_NACC; k < ME_HDR; ++k) h[k] = 0;
 }
 
 __global__ __launch_bounds__(VS_THREADS) void mask_error_vertex_kernel(MeParams p) {
-  int blk = blockIdx.x;
-  const int vc = blk % p.vchunks;
-  blk /= p.vchunks;
-  const int s = blk & 1, b = blk >> 1;
+  int b, s, vc;
+  vs_vertex_block(p.vchunks, 2, b, s, vc);
   int32_t* __restrict__ h = p.hdr + (size_t)b * ME_HDR;
   if (!h[ME_RENDER]) return;                                         // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
   vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const int i = vc * VS_THREADS + threadIdx.x;
-  int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN, bad = 0;
-  if (i < V)
-    p.sv[((size_t)b * 2 + s) * p.Vmax + i] = vs_project((const float*)h + 12 * s, p.verts + 3 * ((size_t)vfirst + i), -2.f, (float)p.W + 1.f,
-                                                        -2.f, (float)p.H + 1.f, x0, y0, x1, y1, bad);
-  vs_rect_merge(x0, y0, x1, y1, bad, h + ME_RECT + 4 * s, h + ME_BAD + s);
+  vs_vertex_chunk((const float*)h + MeH::P(s), p.verts + 3 * (size_t)vfirst, V, vc, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f),
+                  p.sv + ((size_t)b * 2 + s) * p.Vmax, h + MeH::RECT(s), h + MeH::BAD(s));
 }
 
 __global__ __launch_bounds__(VS_THREADS) void mask_error_tile_kernel(MeParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];
   __shared__ int s_n;
   __shared__ int s_red[VS_THREADS / 64][ME_NACC];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles = p.tx * p.ty;
-  const int b = blockIdx.x / tiles, t = blockIdx.x % tiles;
-  const int ox = (t % p.tx) * VS_TILE, oy = (t / p.tx) * VS_TILE;
+  const VsTile c = vs_tile(p.tx, p.ty, 0, 0);
+  const int b = c.b, ox = c.ox, oy = c.oy;
   int32_t* __restrict__ h = p.hdr + (size_t)b * ME_HDR;
-  const bool live = h[ME_RENDER] && !h[ME_BAD] && !h[ME_BAD + 1];
+  const bool live = h[ME_RENDER] && !h[MeH::BAD(0)] && !h[MeH::BAD(1)];
   bool hit[2];
-  for (int s = 0; s < 2; ++s)
-    hit[s] = live && h[ME_RECT + 4 * s] <= ox + VS_TILE - 1 && h[ME_RECT + 4 * s + 2] >= ox && h[ME_RECT + 4 * s + 1] <= oy + VS_TILE - 1 &&
-             h[ME_RECT + 4 * s + 3] >= oy;
+  for (int s = 0; s < 2; ++s) hit[s] = live && vs_tile_hit(h + MeH::RECT(s), ox, oy);
   // (uniform) with masks asked no tile leaves early: each one walks its pixels to store them, zeros where nothing is rendered
   if (!hit[0] && !hit[1] && !p.masks) return;
-  const int lx = lane & 31, ly0 = wave * VS_STRIP + (lane >> 5);    // the lane's pixels: (lx, ly0 + 2 k), k = 0..3
-  const int x = ox + lx;
+  const int x = ox + c.lx;
   float dep[2][VS_PPL];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
@@ -182,15 +145,15 @@ __global__ __launch_bounds__(VS_THREADS) void mask_error_tile_kernel(MeParams p)
 #pragma unroll
     for (int s = 0; s < 2; ++s)
       if (hit[s])                                                    // (uniform)
-        vs_raster_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, ox, oy, tid, lx, ly0, wave, dep[s]);
+        vs_depth_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep[s]);
   }
 
   int acc[ME_NACC];
 #pragma unroll
-  for (int k = 0; k < ME_NACC; ++k) acc[k] = me_identity(k);
+  for (int k = 0; k < ME_NACC; ++k) acc[k] = vs_acc_identity<ME_NSUM>(k);
 #pragma unroll
   for (int k = 0; k < VS_PPL; ++k) {
-    const int y = oy + ly0 + 2 * k;
+    const int y = oy + c.y(k);
     if (x >= p.W || y >= p.H) continue;
     const bool e = dep[0][k] > 0.f, g = dep[1][k] > 0.f;
     acc[0] += (e && g) ? 1 : 0;
@@ -205,33 +168,16 @@ __global__ __launch_bounds__(VS_THREADS) void mask_error_tile_kernel(MeParams p)
   }
   if (!hit[0] && !hit[1]) return;                                    // (uniform) zeros were stored, nothing to count
 
-#pragma unroll
-  for (int k = 0; k < ME_NACC; ++k) {
-    int v = acc[k];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) v = me_combine(k, v, __shfl_xor(v, w, 64));
-    if (lane == 0) s_red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < ME_NACC) {
-    const int k = tid;
-    int v = s_red[0][k];
-    for (int w = 1; w < VS_THREADS / 64; ++w) v = me_combine(k, v, s_red[w][k]);
-    if (v != me_identity(k)) {
-      if (k < 4) atomicAdd(h + ME_ACC + k, v);
-      else if ((k & 3) < 2) atomicMin(h + ME_ACC + k, v);
-      else atomicMax(h + ME_ACC + k, v);
-    }
-  }
+  vs_acc_reduce<ME_NSUM, ME_NACC>(acc, s_red, h + ME_ACC);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void mask_error_finish_kernel(MeParams p) {
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.B) return;
   const int32_t* __restrict__ h = p.hdr + (size_t)b * ME_HDR;
-  const bool ok = h[ME_OK] != 0, skip = h[ME_SKIP] != 0, rendered = h[ME_RENDER] != 0, bad = h[ME_BAD] || h[ME_BAD + 1];
+  const bool ok = h[MeH::OK] != 0, skip = h[ME_SKIP] != 0, rendered = h[ME_RENDER] != 0, bad = h[MeH::BAD(0)] || h[MeH::BAD(1)];
   int32_t a[ME_NACC];
-  for (int k = 0; k < ME_NACC; ++k) a[k] = (rendered && !bad) ? h[ME_ACC + k] : me_identity(k);
+  for (int k = 0; k < ME_NACC; ++k) a[k] = (rendered && !bad) ? h[ME_ACC + k] : vs_acc_identity<ME_NSUM>(k);
   double cou, cou_bb;
   me_results(a, cou, cou_bb, p.counts ? p.counts + 4 * (size_t)b : nullptr, p.boxes ? p.boxes + 8 * (size_t)b : nullptr);
   const double nan = __builtin_nan("");
@@ -253,7 +199,7 @@ struct MoParams {
 
 __global__ __launch_bounds__(MO_THREADS) void mask_overlap_kernel(MoParams p) {
   __shared__ int s_red[MO_THREADS / 64][ME_NACC];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int b = blockIdx.x;
   const int n = p.H * p.W;                                           // (< 2^31: checked by the caller)
   const uint8_t* __restrict__ me = p.est + (size_t)b * n;
@@ -261,7 +207,7 @@ __global__ __launch_bounds__(MO_THREADS) void mask_overlap_kernel(MoParams p) {
   const bool words = (((uintptr_t)me | (uintptr_t)mg) & 3) == 0;      // (uniform) both rows of this pair start on a 4-byte boundary
   int acc[ME_NACC];
 #pragma unroll
-  for (int k = 0; k < ME_NACC; ++k) acc[k] = me_identity(k);
+  for (int k = 0; k < ME_NACC; ++k) acc[k] = vs_acc_identity<ME_NSUM>(k);
   for (int i = 4 * tid; i < n; i += 4 * MO_THREADS) {
     const int cnt = min(4, n - i);
     uint32_t we = 0, wg = 0;
@@ -283,19 +229,12 @@ __global__ __launch_bounds__(MO_THREADS) void mask_overlap_kernel(MoParams p) {
       if (++x == p.W) { x = 0; ++y; }
     }
   }
-#pragma unroll
-  for (int k = 0; k < ME_NACC; ++k) {
-    int v = acc[k];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) v = me_combine(k, v, __shfl_xor(v, w, 64));
-    if (lane == 0) s_red[wave][k] = v;
-  }
-  __syncthreads();
+  vs_acc_waves<ME_NSUM, ME_NACC>(acc, s_red);
   if (tid == 0) {
     int32_t a[ME_NACC];
     for (int k = 0; k < ME_NACC; ++k) {
       int v = s_red[0][k];
-      for (int w = 1; w < MO_THREADS / 64; ++w) v = me_combine(k, v, s_red[w][k]);
+      for (int w = 1; w < MO_THREADS / 64; ++w) v = vs_acc_combine<ME_NSUM>(k, v, s_red[w][k]);
       a[k] = v;
     }
     double cou, cou_bb;
@@ -314,14 +253,11 @@ __global__ __launch_bounds__(VS_THREADS) void box_overlap_kernel(const double* _
   out[b] = me_cou_box<double>(p[0], p[1], p[2], p[3], q[0], q[1], q[2], q[3]);
 }
 
-size_t me_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-bool me_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
-
 }  // namespace
 
 extern "C" size_t cp_mask_errors_scratch_bytes(int B, int Vmax) {
   if (B <= 0 || Vmax < 0) return 0;
-  return me_align16((size_t)B * ME_HDR * sizeof(int32_t)) + me_align16((size_t)B * 2 * Vmax * sizeof(float4));
+  return cp_align16_up((size_t)B * ME_HDR * sizeof(int32_t)) + cp_align16_up((size_t)B * 2 * Vmax * sizeof(float4));
 }
 
 extern "C" int cp_mask_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const double* cam_K, int k_stride,
@@ -334,27 +270,25 @@ extern "C" int cp_mask_errors(cp_stream_t stream, const double* pose_est, const 
   if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (sphere_check && !diameters) return CP_ERR_INVALID;
-  if (me_misaligned(scratch, 15) || me_misaligned(pose_est, 7) || me_misaligned(pose_gt, 7) || me_misaligned(cam_K, 7) ||
-      me_misaligned(diameters, 7) || me_misaligned(cus, 7) || me_misaligned(cou_bb_proj, 7) || me_misaligned(verts, 3) ||
-      me_misaligned(v_offsets, 3) || me_misaligned(faces, 3) || me_misaligned(f_offsets, 3) || me_misaligned(mesh_ids, 3) ||
-      me_misaligned(counts, 3) || me_misaligned(boxes, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(pose_est, 7) || cp_misaligned(pose_gt, 7) || cp_misaligned(cam_K, 7) ||
+      cp_misaligned(diameters, 7) || cp_misaligned(cus, 7) || cp_misaligned(cou_bb_proj, 7) || cp_misaligned(verts, 3) ||
+      cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) ||
+      cp_misaligned(counts, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
   MeParams p = {};
   p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
   p.f_off = f_offsets; p.M = M; p.mesh_id = mesh_ids; p.diameters = diameters; p.H = H; p.W = W; p.sphere = sphere_check ? 1 : 0;
   p.B = B; p.Vmax = Vmax; p.cus = cus; p.bbp = cou_bb_proj; p.counts = counts; p.boxes = boxes; p.ok = ok; p.masks = masks;
   p.hdr = (int32_t*)scratch;
-  p.sv = (float4*)((char*)scratch + me_align16((size_t)B * ME_HDR * sizeof(int32_t)));
-  p.tx = (W + VS_TILE - 1) / VS_TILE; p.ty = (H + VS_TILE - 1) / VS_TILE;
-  p.vchunks = (Vmax + VS_THREADS - 1) / VS_THREADS;
-  const long long tile_blocks = (long long)B * p.tx * p.ty, vert_blocks = (long long)B * 2 * p.vchunks;
-  if (tile_blocks >= (1LL << 24) || vert_blocks >= (1LL << 24) || (long long)H * W >= (1LL << 31)) return CP_ERR_RANGE;
+  p.sv = (float4*)((char*)scratch + cp_align16_up((size_t)B * ME_HDR * sizeof(int32_t)));
+  VsGrid g;
+  if (!vs_grid(W, H, 1, false, B, 2, Vmax, g) || (long long)H * W >= (1LL << 31)) return CP_ERR_RANGE;
+  p.tx = g.tx; p.ty = g.ty; p.vchunks = g.vchunks;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned pair_blocks = (unsigned)((B + VS_THREADS - 1) / VS_THREADS);
-  CP_LAUNCH(mask_error_pose_kernel, dim3(pair_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(mask_error_vertex_kernel, dim3((unsigned)vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(mask_error_tile_kernel, dim3((unsigned)tile_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(mask_error_finish_kernel, dim3(pair_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(mask_error_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(mask_error_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(mask_error_tile_kernel, dim3(g.tile_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(mask_error_finish_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   return cp_check_launch();
 }
 
@@ -362,7 +296,7 @@ extern "C" int cp_mask_overlap(cp_stream_t stream, const uint8_t* mask_est, cons
                                double* cou_mask, double* cou_bb, int32_t* counts, int32_t* boxes) {
   if (!mask_est || !mask_gt || (!cou_mask && !cou_bb && !counts && !boxes)) return CP_ERR_INVALID;
   if (B <= 0 || H <= 0 || W <= 0) return CP_ERR_INVALID;
-  if (me_misaligned(cou_mask, 7) || me_misaligned(cou_bb, 7) || me_misaligned(counts, 3) || me_misaligned(boxes, 3)) return CP_ERR_ALIGN;
+  if (cp_misaligned(cou_mask, 7) || cp_misaligned(cou_bb, 7) || cp_misaligned(counts, 3) || cp_misaligned(boxes, 3)) return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) - 4 * MO_THREADS || B >= (1 << 24)) return CP_ERR_RANGE;
   MoParams p = {};
   p.est = mask_est; p.gt = mask_gt; p.cou_mask = cou_mask; p.cou_bb = cou_bb; p.counts = counts; p.boxes = boxes; p.H = H; p.W = W; p.B = B;
@@ -372,7 +306,7 @@ extern "C" int cp_mask_overlap(cp_stream_t stream, const uint8_t* mask_est, cons
 
 extern "C" int cp_box_overlap(cp_stream_t stream, const double* bb_est, const double* bb_gt, int B, double* out) {
   if (!bb_est || !bb_gt || !out || B <= 0) return CP_ERR_INVALID;
-  if (me_misaligned(bb_est, 7) || me_misaligned(bb_gt, 7) || me_misaligned(out, 7)) return CP_ERR_ALIGN;
+  if (cp_misaligned(bb_est, 7) || cp_misaligned(bb_gt, 7) || cp_misaligned(out, 7)) return CP_ERR_ALIGN;
   CP_LAUNCH(box_overlap_kernel, dim3((unsigned)((B + VS_THREADS - 1) / VS_THREADS)), dim3(VS_THREADS), 0, (hipStream_t)stream, bb_est,
             bb_gt, out, B);
   return cp_check_launch();

@@ -3,12 +3,10 @@
 // ssaa > 1, from its 4x supersampled render followed by cv2.resize(INTER_AREA).  The reference renders through OpenGL, which does not
 // run here: the shading is pinned to the RULE read from its GLSL, not to OpenGL's output.
 //
-// Render rule, per sample.  Coverage and the front-most surface are vsd_raster.h's rule (sample at the pixel centre, no culling,
-// zero-area triangles skipped, a pose with any vertex at Z <= 0 not rendered); the tile walk below is vs_raster_tile's arithmetic
-// (the same edge functions and 1 / Z plane: at ssaa = 1 the depth is cp_render_depth's, bit for bit) and additionally keeps the
-// winning face -- among triangles of equal 1 / Z the SMALLEST face index, so the order in which LDS is compacted cannot reach the
-// result.  The varyings v_color, v_L = normalize(light - eye_pos) PER VERTEX and v_normal are interpolated perspective-correctly over
-// the winner, with barycentrics recomputed from its vertices' screen records.
+// Shading rule, per sample.  Coverage and the front-most surface are vsd_raster.h's render rule and walk (vs_raster_tile<true>: at
+// ssaa = 1 the depth is cp_render_depth's, bit for bit), which also names the winning face.  The varyings v_color,
+// v_L = normalize(light - eye_pos) PER VERTEX and v_normal are interpolated perspective-correctly over the winner, with barycentrics
+// recomputed from its vertices' screen records.
 //   flat    f_normal = normalize(cross(dFdx(eye_pos), dFdy(eye_pos))): the unit face normal turned towards the viewer whatever the winding
 //   phong   v_normal = normalize(u_nm * vec4(a_normal, 1.0)).xyz as the shader writes it: a FOUR-vector normalisation before .xyz, so
 //           the per-vertex lengths differ and weight the interpolation (kept on purpose); u_nm = inverse(model-view)^T
@@ -25,11 +23,12 @@
 // no high-resolution image is ever stored.
 //
 // Launches (four, whatever the data and the options):
-//   rgb_pose_kernel     per pose: P = (K f)' [R | t] (vs_krt), [R | t] and the normal matrix in fp32, validity, accumulators.
-//   rgb_vertex_kernel   per (pose, 256 vertices): the screen record (vs_project), the eye position, v_L, for phong v_normal; the rectangle.
+//   rgb_pose_kernel     per pose: P = (K f)' [R | t] (vs_side_init), [R | t] and the normal matrix in fp32, validity, accumulators.
+//   rgb_vertex_kernel   per (pose, 256 vertices): the screen record and the rectangle (vs_vertex_chunk), the eye position, v_L, for
+//                       phong v_normal.
 //   rgb_tile_kernel     a workgroup per (pose, 32 x 32 sample tile), 4 samples per lane.  Tiles the rectangle misses store the
 //                       background and leave.  Otherwise: the walk, the shading of each covered sample, the stores; with f = 1 the
-//                       optional depth, mask (0 / 255) and the box limits (integers: wave shuffles, LDS, one atomic per value and tile).
+//                       optional depth, mask (0 / 255) and the box limits (integers: vs_acc_reduce).
 //   rgb_finish_kernel   per pose: ok, the box as x, y, w, h (-1 when nothing is covered).
 // No floating-point atomics; nothing allocates or synchronises; every output is bit-identical from call to call, for a pose alone or
 // in a batch, with or without the optional outputs.
@@ -37,9 +36,10 @@
 
 namespace {
 
-// 4-byte words per pose: P[12] rect[4] bad ok | RT[12] | NM[12] = N (3x3) c (3) | box xmin ymin xmax ymax | sign(fx fy) | spare
+// 4-byte words per pose: VsHdr<1> (P rect bad ok) | RT[12] | NM[12] = N (3x3) c (3) | box xmin ymin xmax ymax | sign(fx fy) | spare
+using RrH = VsHdr<1>;
 constexpr int RR_HDR = 48;
-constexpr int RR_RECT = 12, RR_BAD = 16, RR_OK = 17, RR_RT = 18, RR_NM = 30, RR_BOX = 42, RR_SK = 46;
+constexpr int RR_RT = RrH::USER, RR_NM = RR_RT + 12, RR_BOX = RR_NM + 12, RR_SK = RR_BOX + 4;
 enum { RR_FLAT = 0, RR_PHONG = 1 };
 
 struct RrParams {
@@ -80,15 +80,11 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_pose_kernel(RrParams p) {
   if (b >= p.B) return;
   int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
   const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
-  bool ok = true;
-  for (int k = 0; k < 9; ++k) ok = ok && isfinite(K[k]);
   int vfirst, V, ffirst, F, m;
-  ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m) && ok;
+  bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
   const double* __restrict__ q = p.poses + 12 * (size_t)b;
-  for (int k = 0; k < 12; ++k) ok = ok && isfinite(q[k]);
-  const double s = (double)p.f;                                       // 1, 2 or 4: the products are exact
-  vs_krt(K[0] * s, K[4] * s, K[2] * s, K[5] * s, q, (float*)h);
-  h[RR_RECT] = INT_MAX; h[RR_RECT + 1] = INT_MAX; h[RR_RECT + 2] = INT_MIN; h[RR_RECT + 3] = INT_MIN;
+  ok = ok && vs_pose_finite(K, q);
+  vs_side_init(K, (double)p.f, q, (float*)h + RrH::P(0), h + RrH::RECT(0));      // P = (K f)' [R | t]
   float* __restrict__ rt = (float*)(h + RR_RT);
   for (int r = 0; r < 3; ++r) {
     for (int c = 0; c < 3; ++c) rt[4 * r + c] = (float)q[3 * r + c];
@@ -104,26 +100,26 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_pose_kernel(RrParams p) {
   float* __restrict__ nm = (float*)(h + RR_NM);
   for (int k = 0; k < 9; ++k) nm[k] = (float)N[k];
   for (int c = 0; c < 3; ++c) nm[9 + c] = (float)((N[c] * q[9] + N[3 + c] * q[10]) + N[6 + c] * q[11]);
-  h[RR_BAD] = 0;
-  h[RR_OK] = ok ? 1 : 0;
-  h[RR_BOX] = INT_MAX; h[RR_BOX + 1] = INT_MAX; h[RR_BOX + 2] = INT_MIN; h[RR_BOX + 3] = INT_MIN;
+  h[RrH::BAD(0)] = 0;
+  h[RrH::OK] = ok ? 1 : 0;
+  vs_rect_set(h + RR_BOX, INT_MAX, INT_MAX, INT_MIN, INT_MIN);
   h[RR_SK] = (K[0] > 0.0) == (K[4] > 0.0) ? 1 : -1;
   h[RR_SK + 1] = 0;
 }
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_vertex_kernel(RrParams p) {
 #pragma clang fp contract(off)
-  const int vc = blockIdx.x % p.vchunks, b = blockIdx.x / p.vchunks;
+  int b, s, vc;
+  vs_vertex_block(p.vchunks, 1, b, s, vc);
   int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
-  if (!h[RR_OK]) return;                                             // (uniform; no barrier in this kernel)
+  if (!h[RrH::OK]) return;                                           // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
   vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const int i = vc * VS_THREADS + threadIdx.x;
-  int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN, bad = 0;
-  if (i < V) {
+  const float4 grid = make_float4(-2.f, (float)(p.f * p.W) + 1.f, -2.f, (float)(p.f * p.H) + 1.f);      // the sample grid
+  // besides the screen record: the eye position, v_L and, for phong, v_normal of the vertex
+  const auto shading_records = [&](int i, const float* __restrict__ vt) {
+#pragma clang fp contract(off)
     const size_t at = (size_t)b * p.Vmax + i;
-    const float* __restrict__ vt = p.verts + 3 * ((size_t)vfirst + i);
-    p.sv[at] = vs_project((const float*)h, vt, -2.f, (float)(p.f * p.W) + 1.f, -2.f, (float)(p.f * p.H) + 1.f, x0, y0, x1, y1, bad);
     const float* __restrict__ rt = (const float*)(h + RR_RT);
     const float ex = vs_affine(rt, vt[0], vt[1], vt[2]), ey = vs_affine(rt + 4, vt[0], vt[1], vt[2]), ez = vs_affine(rt + 8, vt[0], vt[1], vt[2]);
     p.eye[at] = make_float4(ex, ey, ez, 0.f);
@@ -140,73 +136,9 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_vertex_kernel(RrParams p) {
       const float nl = sqrtf(((nx * nx + ny * ny) + nz * nz) + nw * nw);    // the shader's 4-vector length
       p.vn[at] = make_float4(nx / nl, ny / nl, nz / nl, 0.f);
     }
-  }
-  vs_rect_merge(x0, y0, x1, y1, bad, h + RR_RECT, h + RR_BAD);
-}
-
-// vs_raster_tile's walk (the same setup, the same edge / 1 / Z arithmetic, the same record) that also keeps the winning face in
-// face[k]: the record's spare word carries the face index, and of two triangles with equal 1 / Z the smaller index wins.
-// iz[k] = the largest 1 / Z (0 = background).  Called by ALL threads of the workgroup.
-__device__ __forceinline__ void rr_raster_tile(float4 (*__restrict__ s_tri)[4], int* __restrict__ s_n, const float4* __restrict__ sv,
-                                               const int32_t* __restrict__ faces, int F, int V, int ox, int oy, int tid, int lx, int ly0,
-                                               int wave, float (&best)[VS_PPL], int (&face)[VS_PPL]) {
-  const float fx0 = (float)ox + 0.5f, fy0 = (float)oy + 0.5f;
-  const float wy0 = (float)(wave * VS_STRIP), wy1 = wy0 + (float)(VS_STRIP - 1);
-#pragma unroll
-  for (int k = 0; k < VS_PPL; ++k) { best[k] = 0.f; face[k] = INT_MAX; }
-  for (int f0 = 0; f0 < F; f0 += VS_CHUNK) {
-    __syncthreads();
-    if (tid == 0) *s_n = 0;
-    __syncthreads();
-    const int f = f0 + tid;
-    if (f < F) {
-#pragma clang fp contract(off)
-      const int32_t* __restrict__ fi = faces + 3 * (size_t)f;
-      const int i0 = fi[0], i1 = fi[1], i2 = fi[2];
-      if (i0 >= 0 && i0 < V && i1 >= 0 && i1 < V && i2 >= 0 && i2 < V) {
-        const float4 a = sv[i0], c = sv[i1], d = sv[i2];
-        const float ax = a.x - fx0, ay = a.y - fy0, cx = c.x - fx0, cy = c.y - fy0, dx = d.x - fx0, dy = d.y - fy0;
-        const float xmin = fminf(ax, fminf(cx, dx)), xmax = fmaxf(ax, fmaxf(cx, dx));
-        const float ymin = fminf(ay, fminf(cy, dy)), ymax = fmaxf(ay, fmaxf(cy, dy));
-        const float area = (cx - ax) * (dy - ay) - (dx - ax) * (cy - ay);
-        if (area != 0.f && xmax >= 0.f && xmin <= (float)(VS_TILE - 1) && ymax >= 0.f && ymin <= (float)(VS_TILE - 1)) {
-          const float sg = area > 0.f ? 1.f : -1.f, ia = 1.0f / area;
-          const float e0a = -(dy - cy), e0b = dx - cx, e0c = (dy - cy) * cx - (dx - cx) * cy;     // c -> d
-          const float e1a = -(ay - dy), e1b = ax - dx, e1c = (ay - dy) * dx - (ax - dx) * dy;     // d -> a
-          const float e2a = -(cy - ay), e2b = cx - ax, e2c = (cy - ay) * ax - (cx - ax) * ay;     // a -> c
-          const float g1 = (c.w - a.w) * ia, g2 = (d.w - a.w) * ia;
-          const float pa = e1a * g1 + e2a * g2, pb = e1b * g1 + e2b * g2, pc = a.w + (e1c * g1 + e2c * g2);
-          const int at = atomicAdd(s_n, 1);
-          s_tri[at][0] = make_float4(sg * e0a, sg * e0b, sg * e0c, ymin);
-          s_tri[at][1] = make_float4(sg * e1a, sg * e1b, sg * e1c, ymax);
-          s_tri[at][2] = make_float4(sg * e2a, sg * e2b, sg * e2c, __int_as_float(f));
-          s_tri[at][3] = make_float4(pa, pb, pc, 0.f);
-        }
-      }
-    }
-    __syncthreads();
-    const int n = *s_n;
-    for (int j = 0; j < n; ++j) {
-      const float4 q0 = s_tri[j][0], q1 = s_tri[j][1];           // every lane reads the same address: a broadcast
-      const float tymin = __builtin_amdgcn_readfirstlane(q0.w), tymax = __builtin_amdgcn_readfirstlane(q1.w);
-      if (tymax < wy0 || tymin > wy1) continue;                  // wave-uniform: the triangle misses this wave's strip
-      const float4 q2 = s_tri[j][2], q3 = s_tri[j][3];
-      const int fj = __builtin_amdgcn_readfirstlane(__float_as_int(q2.w));
-      const float qx = (float)lx;
-#pragma unroll
-      for (int k = 0; k < VS_PPL; ++k) {
-        const float qy = (float)(ly0 + 2 * k);
-        const float w0 = fmaf(q0.x, qx, fmaf(q0.y, qy, q0.z));
-        const float w1 = fmaf(q1.x, qx, fmaf(q1.y, qy, q1.z));
-        const float w2 = fmaf(q2.x, qx, fmaf(q2.y, qy, q2.z));
-        const float iz = fmaf(q3.x, qx, fmaf(q3.y, qy, q3.z));
-        if (w0 >= 0.f && w1 >= 0.f && w2 >= 0.f && iz > 0.f && (iz > best[k] || (iz == best[k] && fj < face[k]))) {
-          best[k] = iz;
-          face[k] = fj;
-        }
-      }
-    }
-  }
+  };
+  vs_vertex_chunk((const float*)h + RrH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, grid, p.sv + (size_t)b * p.Vmax, h + RrH::RECT(0),
+                  h + RrH::BAD(0), shading_records);
 }
 
 __device__ __forceinline__ float rr_mix(float w0, float w1, float w2, float a, float c, float d) {
@@ -268,15 +200,12 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];
   __shared__ int s_n;
   __shared__ int s_red[VS_THREADS / 64][4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles = p.tx * p.ty;
-  const int b = blockIdx.x / tiles, t = blockIdx.x % tiles;
-  const int ox = (t % p.tx) * VS_TILE, oy = (t / p.tx) * VS_TILE;    // first SAMPLE of the tile
+  const VsTile c = vs_tile(p.tx, p.ty, 0, 0);                         // (of the SAMPLE grid)
+  const int tid = c.tid, b = c.b, ox = c.ox, oy = c.oy, lx = c.lx;
   const int f = p.f, ot = VS_TILE / f;                                // output pixels per tile side
   int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
-  const bool live = h[RR_OK] && !h[RR_BAD];
-  const bool hit = live && h[RR_RECT] <= ox + VS_TILE - 1 && h[RR_RECT + 2] >= ox && h[RR_RECT + 1] <= oy + VS_TILE - 1 && h[RR_RECT + 3] >= oy;
-  const int lx = lane & 31, ly0 = wave * VS_STRIP + (lane >> 5);     // the lane's samples: (lx, ly0 + 2 k), k = 0..3
+  const bool live = h[RrH::OK] && !h[RrH::BAD(0)];
+  const bool hit = live && vs_tile_hit(h + RrH::RECT(0), ox, oy);
   const int c0 = p.bgr ? 2 : 0, c2 = p.bgr ? 0 : 2;
 
   if (!hit) {                                                         // (uniform) background only
@@ -297,7 +226,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
   const size_t vbase = (size_t)b * p.Vmax;
   float best[VS_PPL];
   int face[VS_PPL];
-  rr_raster_tile(s_tri, &s_n, p.sv + vbase, faces, F, V, ox, oy, tid, lx, ly0, wave, best, face);
+  vs_raster_tile<true>(s_tri, &s_n, p.sv + vbase, faces, F, V, c, best, face);
 
   // f >= 2: the samples' integer sums (at most 16 x 16 output pixels per tile) take over the triangle records' LDS after the walk
   int (*__restrict__ s_sum)[VS_TILE * VS_TILE / 4] = (int (*)[VS_TILE * VS_TILE / 4])s_tri;
@@ -310,7 +239,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
   int bx0 = INT_MAX, by0 = INT_MAX, bx1 = INT_MIN, by1 = INT_MIN;
 #pragma unroll
   for (int k = 0; k < VS_PPL; ++k) {
-    const int ly = ly0 + 2 * k;
+    const int ly = c.y(k);
     const int sx = ox + lx, sy = oy + ly;                             // the sample, on the f W x f H grid
     if (sx >= f * p.W || sy >= f * p.H) continue;
     int col[3] = {p.bg[0], p.bg[1], p.bg[2]};
@@ -319,7 +248,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
     if (f == 1) {
       const size_t at = ((size_t)b * p.H + sy) * p.W + sx;
       p.rgb[3 * at + c0] = (uint8_t)col[0]; p.rgb[3 * at + 1] = (uint8_t)col[1]; p.rgb[3 * at + c2] = (uint8_t)col[2];
-      if (p.depth) p.depth[at] = cov ? 1.0f / best[k] : 0.f;          // one correctly rounded division per pixel, as vs_raster_tile
+      if (p.depth) p.depth[at] = vs_depth_of(best[k]);
       if (p.mask) p.mask[at] = cov ? 255 : 0;
       if (cov) { bx0 = min(bx0, sx); by0 = min(by0, sy); bx1 = max(bx1, sx); by1 = max(by1, sy); }
     } else {
@@ -349,46 +278,19 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
     return;
   }
   if (!p.boxes) return;                                               // (uniform)
-  int acc[4] = {bx0, by0, bx1, by1};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    int v = acc[k];
-#pragma unroll
-    for (int w = 32; w > 0; w >>= 1) {
-      const int o = __shfl_xor(v, w, 64);
-      v = k < 2 ? min(v, o) : max(v, o);
-    }
-    if (lane == 0) s_red[wave][k] = v;
-  }
-  __syncthreads();
-  if (tid < 4) {
-    const int k = tid;
-    int v = s_red[0][k];
-    for (int w = 1; w < VS_THREADS / 64; ++w) v = k < 2 ? min(v, s_red[w][k]) : max(v, s_red[w][k]);
-    if (k < 2) { if (v != INT_MAX) atomicMin(h + RR_BOX + k, v); }
-    else if (v != INT_MIN) atomicMax(h + RR_BOX + k, v);
-  }
+  const int acc[4] = {bx0, by0, bx1, by1};
+  vs_acc_reduce<0, 4>(acc, s_red, h + RR_BOX);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_finish_kernel(RrParams p) {
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.B) return;
   const int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
-  const bool live = h[RR_OK] && !h[RR_BAD];
+  const bool live = h[RrH::OK] && !h[RrH::BAD(0)];
   p.ok[b] = live ? 1 : 0;
-  if (p.boxes) {
-    const int32_t* __restrict__ r = h + RR_BOX;
-    const bool have = live && r[0] != INT_MAX;
-    int32_t* __restrict__ bx = p.boxes + 4 * (size_t)b;
-    bx[0] = have ? r[0] : -1;
-    bx[1] = have ? r[1] : -1;
-    bx[2] = have ? r[2] - r[0] : -1;
-    bx[3] = have ? r[3] - r[1] : -1;
-  }
+  if (p.boxes) vs_box_xywh(h + RR_BOX, live && h[RR_BOX] != INT_MAX, p.boxes + 4 * (size_t)b);
 }
 
-size_t rr_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-bool rr_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
 int rr_quant_host(double v) {
   if (!(v > 0.0)) return 0;
   const float q = __builtin_rintf(255.0f * (float)v);
@@ -399,7 +301,7 @@ int rr_quant_host(double v) {
 
 extern "C" size_t cp_render_rgb_scratch_bytes(int B, int Vmax) {
   if (B <= 0 || Vmax < 0) return 0;
-  return rr_align16((size_t)B * RR_HDR * sizeof(int32_t)) + 4 * rr_align16((size_t)B * Vmax * sizeof(float4));
+  return cp_align16_up((size_t)B * RR_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)B * Vmax * sizeof(float4));
 }
 
 extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
@@ -418,9 +320,9 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   if (!(ambient_weight == ambient_weight) || __builtin_isinf(ambient_weight)) return CP_ERR_INVALID;
   for (int k = 0; k < 3; ++k)
     if (!__builtin_isfinite(surf_color[k]) || !__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(bg_color[k])) return CP_ERR_INVALID;
-  if (rr_misaligned(scratch, 15) || rr_misaligned(poses, 7) || rr_misaligned(cam_K, 7) || rr_misaligned(verts, 3) ||
-      rr_misaligned(v_offsets, 3) || rr_misaligned(faces, 3) || rr_misaligned(f_offsets, 3) || rr_misaligned(mesh_ids, 3) ||
-      rr_misaligned(colors, 3) || rr_misaligned(normals, 3) || rr_misaligned(depth, 3) || rr_misaligned(boxes, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(verts, 3) ||
+      cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) ||
+      cp_misaligned(colors, 3) || cp_misaligned(normals, 3) || cp_misaligned(depth, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
   RrParams p = {};
   p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
@@ -430,22 +332,20 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   for (int k = 0; k < 3; ++k) { p.surf[k] = (float)surf_color[k]; p.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
   const long long sw = (long long)ssaa * W, sh = (long long)ssaa * H;
   if (sw >= (1LL << 24) || sh >= (1LL << 24) || (long long)H * W >= (1LL << 31) / 3) return CP_ERR_RANGE;
-  p.tx = (int)((sw + VS_TILE - 1) / VS_TILE); p.ty = (int)((sh + VS_TILE - 1) / VS_TILE);
-  p.vchunks = (Vmax + VS_THREADS - 1) / VS_THREADS;
-  const long long tile_blocks = (long long)B * p.tx * p.ty, vert_blocks = (long long)B * p.vchunks;
-  if (tile_blocks >= (1LL << 24) || vert_blocks >= (1LL << 24)) return CP_ERR_RANGE;
+  VsGrid g;
+  if (!vs_grid(W, H, ssaa, false, B, 1, Vmax, g)) return CP_ERR_RANGE;
+  p.tx = g.tx; p.ty = g.ty; p.vchunks = g.vchunks;
   char* at = (char*)scratch;
-  const size_t rec = rr_align16((size_t)B * Vmax * sizeof(float4));
-  p.hdr = (int32_t*)at; at += rr_align16((size_t)B * RR_HDR * sizeof(int32_t));
+  const size_t rec = cp_align16_up((size_t)B * Vmax * sizeof(float4));
+  p.hdr = (int32_t*)at; at += cp_align16_up((size_t)B * RR_HDR * sizeof(int32_t));
   p.sv = (float4*)at; at += rec;
   p.eye = (float4*)at; at += rec;
   p.vl = (float4*)at; at += rec;
   p.vn = (float4*)at;
   hipStream_t st = (hipStream_t)stream;
-  const unsigned pose_blocks = (unsigned)((B + VS_THREADS - 1) / VS_THREADS);
-  CP_LAUNCH(rgb_pose_kernel, dim3(pose_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(rgb_vertex_kernel, dim3((unsigned)vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(rgb_tile_kernel, dim3((unsigned)tile_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(rgb_finish_kernel, dim3(pose_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(rgb_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(rgb_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(rgb_tile_kernel, dim3(g.tile_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(rgb_finish_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   return cp_check_launch();
 }

@@ -3,27 +3,19 @@
 // ('bop19' mode, 'step' cost).  The reference renders the mesh twice per pose through OpenGL (renderer_py.py:185-226, 422-555) and
 // then makes several full-frame numpy passes; here no depth image exists unless the caller asks for it.
 //
-// Render rule.  depth[y, x] = the smallest eye-space Z > 0 at which the ray through image point (x + 0.5, y + 0.5) meets a triangle
-// (no back-face culling, background 0), Z taken on the triangle's plane: 1 / Z is affine in the image.  Triangles of zero area
-// are skipped.  A pose with any vertex at Z <= 0 is not rendered: its errors are NaN.
-//
-// The rasteriser's device functions (vs_krt, vs_project, vs_raster_tile) and the per-pixel distance / visibility arithmetic (vs_dist,
-// vs_visible) live in vsd_raster.h, which gt_info.hip (row N10) includes too.
+// The render rule, the rasteriser and the scaffold of the four kernels are vsd_raster.h's, shared with rows N10, N12 and N14; a pose
+// that the rule does not render (a vertex at Z <= 0) has NaN errors.
 //
 // Launches (three, + one when meshes are involved):
-//   vsd_pose_kernel     per pose: P = K' [R | t] of the estimate and of the ground truth in double WITHOUT contraction, rounded to fp32
-//                       once (K' = fx, fy, cx, cy of K, skew 0, as render_object takes them); validity; the caller's
-//                       overlapping_sphere_projections shortcut (misc.py:309-331) in double; the pixel rectangles are initialised.
-//   vsd_vertex_kernel   per (pose, side, vertex): screen (u, v, Z, 1 / Z) in fp32 with explicit fma chains; the pose's pixel rectangle
-//                       and its "a vertex at Z <= 0" flag through INTEGER atomic min / max / or (order-independent).
-//   vsd_tile_kernel     a workgroup owns a 32 x 32 pixel tile of one pose, a lane 4 pixels of it (both depths in registers).  Per side
-//                       the mesh's triangles are set up 256 at a time: the ones whose bounding box meets the tile are compacted
-//                       into LDS as 16 floats (three edge functions and the 1 / Z plane as affine functions of the TILE-RELATIVE
-//                       sample index, so fp32 keeps sub-pixel resolution whatever the image size), then every wave walks the list
-//                       with broadcast reads and a wave-uniform reject against its 32 x 8 strip.  min() over triangles is exact in
-//                       any order, so the order in which the list is compacted does not reach the result.  Then the tile reads the
-//                       test depth, does the reference's distance / visibility arithmetic (fp64 square roots and quotients, the
-//                       fp32 difference against delta) and reduces INTEGER counts: wave shuffles, LDS, one row of scratch per tile.
+//   vsd_pose_kernel     per pose: P = K' [R | t] of the estimate and of the ground truth (vs_side_init; K' as render_object takes
+//                       it); validity; the caller's overlapping_sphere_projections shortcut (vs_sphere_skip) in double; the pixel
+//                       rectangles are initialised.
+//   vsd_vertex_kernel   per (pose, side, 256 vertices): screen records (vs_project); the side's pixel rectangle and its "a vertex at
+//                       Z <= 0" flag through INTEGER atomic min / max / or (vs_rect_merge: order-independent).
+//   vsd_tile_kernel     a workgroup owns a 32 x 32 pixel tile of one pose, a lane 4 pixels of it (both depths in registers): the
+//                       walk over the mesh's triangles (vs_depth_tile) once per side.  Then the tile reads the test depth, does
+//                       the reference's distance / visibility arithmetic (fp64 square roots and quotients, the fp32 difference
+//                       against delta) and reduces INTEGER counts: wave shuffles, LDS, one row of scratch per tile.
 //                       Tiles outside the union of the two rectangles leave at once (or write zeros when depth images are asked).
 //   vsd_sum_kernel      per pose: the tile rows the rectangles reach, summed (integers), and the quotients.
 // Every output is a function of integer counts and per-pixel values: bit-identical from call to call, for a pose alone or in a
@@ -34,7 +26,9 @@ namespace {
 
 constexpr int VS_TMAX = 16;                      // taus per call
 constexpr int VS_ROW = VS_TMAX + 2;              // ints per tile row: union, inter, cost[T]
-constexpr int VS_HDR = 40;                       // 4-byte words per pose: P_est[12] P_gt[12] rect_est[4] rect_gt[4] bad[2] ok skip
+using VsH = VsHdr<2>;                            // a pose's header: P, rect and bad of the estimate and the ground truth, ok, then
+constexpr int VS_SKIP = VsH::USER;               // the sphere shortcut's verdict;
+constexpr int VS_HDR = 40;                       // 4-byte words per pose (the rest is spare)
 enum { VS_MODE_VSD = 0, VS_MODE_RENDER = 1, VS_MODE_DEPTH = 2 };
 
 struct VsParams {
@@ -72,77 +66,53 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_pose_kernel(VsParams p) {
   if (b >= p.B) return;
   int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
   const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
-  bool ok = true;
-  for (int k = 0; k < 9; ++k) ok = ok && isfinite(K[k]);
+  bool ok = vs_finite(K, 9);
   if (p.mode != VS_MODE_RENDER) {
     const int img = p.image_id ? p.image_id[b] : 0;
     ok = ok && img >= 0 && img < p.I;
   }
   int skip = 0;
   if (p.mode == VS_MODE_DEPTH) {
-    for (int s = 0; s < 2; ++s) { h[24 + 4 * s] = 0; h[25 + 4 * s] = 0; h[26 + 4 * s] = p.W - 1; h[27 + 4 * s] = p.H - 1; }
-    h[32] = 0; h[33] = 0;
+    for (int s = 0; s < 2; ++s) vs_rect_set(h + VsH::RECT(s), 0, 0, p.W - 1, p.H - 1);
   } else {
     int vfirst, V, ffirst, F, m;
     ok = vs_mesh(p, b, vfirst, V, ffirst, F, m) && ok;
     const double* __restrict__ e = p.est + 12 * (size_t)b;
     const double* __restrict__ g = p.gt + 12 * (size_t)b;
-    for (int k = 0; k < 12; ++k) ok = ok && isfinite(e[k]) && isfinite(g[k]);
-    float* __restrict__ P = (float*)h;
-    vs_krt(K[0], K[4], K[2], K[5], e, P);
-    vs_krt(K[0], K[4], K[2], K[5], g, P + 12);
-    for (int s = 0; s < 2; ++s) { h[24 + 4 * s] = INT_MAX; h[25 + 4 * s] = INT_MAX; h[26 + 4 * s] = INT_MIN; h[27 + 4 * s] = INT_MIN; }
-    h[32] = 0; h[33] = 0;
-    if (ok && p.sphere && p.mode == VS_MODE_VSD) {
-      // misc.overlapping_sphere_projections(diameter / 2, t_est, t_gt), as eval_calc_errors.py:299-318 calls it
-      const double radius = p.diameters[m] / 2.0;
-      bool overlap = false;
-      if (!(e[11] == 0.0 || g[11] == 0.0)) {
-        const double dx = e[9] / e[11] - g[9] / g[11], dy = e[10] / e[11] - g[10] / g[11];
-        overlap = sqrt(dx * dx + dy * dy) < radius * (1.0 / e[11] + 1.0 / g[11]);
-      }
-      skip = overlap ? 0 : 1;
-    }
+    ok = ok && vs_finite(e, 12) && vs_finite(g, 12);
+    vs_side_init(K, 1.0, e, (float*)h + VsH::P(0), h + VsH::RECT(0));
+    vs_side_init(K, 1.0, g, (float*)h + VsH::P(1), h + VsH::RECT(1));
+    if (ok && p.sphere && p.mode == VS_MODE_VSD) skip = vs_sphere_skip(e, g, p.diameters[m] / 2.0);
   }
-  h[34] = ok ? 1 : 0;
-  h[35] = skip;
+  h[VsH::BAD(0)] = 0; h[VsH::BAD(1)] = 0;
+  h[VsH::OK] = ok ? 1 : 0;
+  h[VS_SKIP] = skip;
 }
 
 __global__ __launch_bounds__(VS_THREADS) void vsd_vertex_kernel(VsParams p) {
 #pragma clang fp contract(off)
-  int blk = blockIdx.x;
-  const int vc = blk % p.vchunks;
-  blk /= p.vchunks;
-  const int s = blk % p.nsides, b = blk / p.nsides;
+  int b, s, vc;
+  vs_vertex_block(p.vchunks, p.nsides, b, s, vc);
   int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
-  if (!h[34] || h[35]) return;                                       // (uniform; no barrier in this kernel)
+  if (!h[VsH::OK] || h[VS_SKIP]) return;                             // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
   vs_mesh(p, b, vfirst, V, ffirst, F, m);
-  const int i = vc * VS_THREADS + threadIdx.x;
-  int x0 = INT_MAX, y0 = INT_MAX, x1 = INT_MIN, y1 = INT_MIN, bad = 0;
-  if (i < V)
-    p.sv[((size_t)b * 2 + s) * p.Vmax + i] = vs_project((const float*)h + 12 * s, p.verts + 3 * ((size_t)vfirst + i), -2.f, (float)p.W + 1.f,
-                                                        -2.f, (float)p.H + 1.f, x0, y0, x1, y1, bad);
-  vs_rect_merge(x0, y0, x1, y1, bad, h + 24 + 4 * s, h + 32 + s);
+  vs_vertex_chunk((const float*)h + VsH::P(s), p.verts + 3 * (size_t)vfirst, V, vc, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f),
+                  p.sv + ((size_t)b * 2 + s) * p.Vmax, h + VsH::RECT(s), h + VsH::BAD(s));
 }
 
 __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];          // e0 (a b c .) e1 (a b c .) e2 (a b c .) plane (A B C .): .w = ymin ymax - -
   __shared__ int s_n;
   __shared__ int s_cnt[VS_THREADS / 64][VS_ROW];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int tiles = p.tx * p.ty;
-  const int b = blockIdx.x / tiles, t = blockIdx.x % tiles;
-  const int ox = (t % p.tx) * VS_TILE, oy = (t / p.tx) * VS_TILE;
+  const VsTile c = vs_tile(p.tx, p.ty, 0, 0);
+  const int tid = c.tid, lane = c.lane, wave = c.wave, b = c.b, ox = c.ox, oy = c.oy, lx = c.lx;
   const int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
-  const bool live = h[34] && !h[35] && !h[32] && !h[33];
+  const bool live = h[VsH::OK] && !h[VS_SKIP] && !h[VsH::BAD(0)] && !h[VsH::BAD(1)];
   // the pose's rectangles against this tile
   bool hit[2];
-  for (int s = 0; s < 2; ++s)
-    hit[s] = live && s < p.nsides && h[24 + 4 * s] <= ox + VS_TILE - 1 && h[26 + 4 * s] >= ox && h[25 + 4 * s] <= oy + VS_TILE - 1 &&
-             h[27 + 4 * s] >= oy;
+  for (int s = 0; s < 2; ++s) hit[s] = live && s < p.nsides && vs_tile_hit(h + VsH::RECT(s), ox, oy);
   if (!hit[0] && !hit[1] && !p.depth_out) return;                   // (uniform)
-  const int lx = lane & 31, ly0 = wave * VS_STRIP + (lane >> 5);    // the lane's pixels: (lx, ly0 + 2 k), k = 0..3
   float dep[2][VS_PPL];
 #pragma unroll
   for (int s = 0; s < 2; ++s)
@@ -152,7 +122,7 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
   if (p.mode == VS_MODE_DEPTH) {
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k) {
-      const int x = ox + lx, y = oy + ly0 + 2 * k;
+      const int x = ox + lx, y = oy + c.y(k);
       if (hit[0] && x < p.W && y < p.H) {
         const size_t at = ((size_t)b * p.H + y) * p.W + x;
         dep[0][k] = p.in_est[at];
@@ -165,13 +135,13 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
 #pragma unroll
     for (int s = 0; s < 2; ++s)
       if (hit[s])                                                    // (uniform)
-        vs_raster_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, ox, oy, tid, lx, ly0, wave, dep[s]);
+        vs_depth_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep[s]);
   }
 
   if (p.depth_out) {
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k) {
-      const int x = ox + lx, y = oy + ly0 + 2 * k;
+      const int x = ox + lx, y = oy + c.y(k);
       if (x < p.W && y < p.H)
         for (int s = 0; s < p.nsides; ++s)
           p.depth_out[(((size_t)b * p.nsides + s) * p.H + y) * p.W + x] = s == 0 ? dep[0][k] : dep[1][k];
@@ -192,7 +162,7 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
     const double diam = p.diameters[p.mode == VS_MODE_DEPTH ? b : (p.mesh_id ? p.mesh_id[b] : 0)];
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k) {
-      const int x = ox + lx, y = oy + ly0 + 2 * k;
+      const int x = ox + lx, y = oy + c.y(k);
       const float de = dep[0][k], dg = dep[1][k];
       if (x >= p.W || y >= p.H || (!(de > 0.f) && !(dg > 0.f))) continue;     // dist_model > 0 fails on both sides: no count moves
       const float dt = test[(size_t)y * p.W + x];
@@ -222,14 +192,14 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
   if (tid < VS_ROW) {
     int v = 0;
     for (int w = 0; w < VS_THREADS / 64; ++w) v += s_cnt[w][tid];
-    p.rows[((size_t)b * tiles + t) * VS_ROW + tid] = v;
+    p.rows[((size_t)b * p.tx * p.ty + c.t) * VS_ROW + tid] = v;
   }
 }
 
 __global__ __launch_bounds__(64) void vsd_sum_kernel(VsParams p) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
-  const bool ok = h[34] != 0, skip = h[35] != 0, bad = h[32] || h[33];
+  const bool ok = h[VsH::OK] != 0, skip = h[VS_SKIP] != 0, bad = h[VsH::BAD(0)] || h[VsH::BAD(1)];
   int cnt[VS_ROW];
 #pragma unroll
   for (int k = 0; k < VS_ROW; ++k) cnt[k] = 0;
@@ -238,10 +208,7 @@ __global__ __launch_bounds__(64) void vsd_sum_kernel(VsParams p) {
     const int tiles = p.tx * p.ty;
     for (int t = lane; t < tiles; t += 64) {
       const int ox = (t % p.tx) * VS_TILE, oy = (t / p.tx) * VS_TILE;
-      bool hit = false;
-      for (int s = 0; s < 2; ++s)
-        hit = hit || (h[24 + 4 * s] <= ox + VS_TILE - 1 && h[26 + 4 * s] >= ox && h[25 + 4 * s] <= oy + VS_TILE - 1 && h[27 + 4 * s] >= oy);
-      if (!hit) continue;
+      if (!vs_tile_hit(h + VsH::RECT(0), ox, oy) && !vs_tile_hit(h + VsH::RECT(1), ox, oy)) continue;
       const int32_t* __restrict__ r = p.rows + ((size_t)b * tiles + t) * VS_ROW;
 #pragma unroll
       for (int k = 0; k < VS_ROW; ++k) cnt[k] += r[k];
@@ -268,48 +235,33 @@ __global__ __launch_bounds__(64) void vsd_sum_kernel(VsParams p) {
   }
 }
 
-struct VsPlan { int tx, ty; long long tiles; };
-VsPlan vs_plan(int H, int W) {
-  VsPlan pl;
-  pl.tx = (W + VS_TILE - 1) / VS_TILE;
-  pl.ty = (H + VS_TILE - 1) / VS_TILE;
-  pl.tiles = (long long)pl.tx * pl.ty;
-  return pl;
-}
-
-size_t vs_align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
 void vs_carve(VsParams& p, void* scratch) {
   char* at = (char*)scratch;
   p.hdr = (int32_t*)at;
-  at += vs_align16((size_t)p.B * VS_HDR * sizeof(int32_t));
+  at += cp_align16_up((size_t)p.B * VS_HDR * sizeof(int32_t));
   p.sv = (float4*)at;
   at += (size_t)p.B * 2 * p.Vmax * sizeof(float4);
   p.rows = (int32_t*)at;
 }
 
 int vs_launch(VsParams& p, hipStream_t st) {
-  const VsPlan pl = vs_plan(p.H, p.W);
-  p.tx = pl.tx; p.ty = pl.ty;
-  p.vchunks = (p.Vmax + VS_THREADS - 1) / VS_THREADS;
-  const long long tile_blocks = (long long)p.B * pl.tiles, vert_blocks = (long long)p.B * p.nsides * p.vchunks;
-  if (tile_blocks >= (1LL << 24) || vert_blocks >= (1LL << 24) || (long long)p.H * p.W >= (1LL << 31)) return CP_ERR_RANGE;
-  CP_LAUNCH(vsd_pose_kernel, dim3((unsigned)((p.B + VS_THREADS - 1) / VS_THREADS)), dim3(VS_THREADS), 0, st, p);
-  if (p.mode != VS_MODE_DEPTH) CP_LAUNCH(vsd_vertex_kernel, dim3((unsigned)vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(vsd_tile_kernel, dim3((unsigned)tile_blocks), dim3(VS_THREADS), 0, st, p);
+  VsGrid g;
+  if (!vs_grid(p.W, p.H, 1, false, p.B, p.nsides, p.Vmax, g) || (long long)p.H * p.W >= (1LL << 31)) return CP_ERR_RANGE;
+  p.tx = g.tx; p.ty = g.ty; p.vchunks = g.vchunks;
+  CP_LAUNCH(vsd_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
+  if (p.mode != VS_MODE_DEPTH) CP_LAUNCH(vsd_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
+  CP_LAUNCH(vsd_tile_kernel, dim3(g.tile_blocks), dim3(VS_THREADS), 0, st, p);
   if (p.mode != VS_MODE_RENDER) CP_LAUNCH(vsd_sum_kernel, dim3((unsigned)p.B), dim3(64), 0, st, p);
   return cp_check_launch();
 }
-
-bool vs_misaligned(const void* q, uintptr_t mask) { return ((uintptr_t)q & mask) != 0; }
 
 }  // namespace
 
 extern "C" size_t cp_vsd_errors_scratch_bytes(int B, int Vmax, int H, int W) {
   if (B <= 0 || Vmax < 0 || H <= 0 || W <= 0) return 0;
-  const VsPlan pl = vs_plan(H, W);
-  return vs_align16((size_t)B * VS_HDR * sizeof(int32_t)) + (size_t)B * 2 * Vmax * sizeof(float4) +
-         vs_align16((size_t)B * pl.tiles * VS_ROW * sizeof(int32_t));
+  const size_t tiles = (size_t)((W + VS_TILE - 1) / VS_TILE) * (size_t)((H + VS_TILE - 1) / VS_TILE);
+  return cp_align16_up((size_t)B * VS_HDR * sizeof(int32_t)) + (size_t)B * 2 * Vmax * sizeof(float4) +
+         cp_align16_up((size_t)B * tiles * VS_ROW * sizeof(int32_t));
 }
 
 extern "C" int cp_vsd_errors(cp_stream_t stream, const double* pose_est, const double* pose_gt, const double* cam_K, int k_stride,
@@ -325,10 +277,10 @@ extern "C" int cp_vsd_errors(cp_stream_t stream, const double* pose_est, const d
     return CP_ERR_INVALID;
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (!image_ids && I != 1) return CP_ERR_INVALID;
-  if (vs_misaligned(scratch, 15) || vs_misaligned(pose_est, 7) || vs_misaligned(pose_gt, 7) || vs_misaligned(cam_K, 7) ||
-      vs_misaligned(diameters, 7) || vs_misaligned(errors, 7) || vs_misaligned(verts, 3) || vs_misaligned(v_offsets, 3) ||
-      vs_misaligned(faces, 3) || vs_misaligned(f_offsets, 3) || vs_misaligned(mesh_ids, 3) || vs_misaligned(depth_test, 3) ||
-      vs_misaligned(image_ids, 3) || vs_misaligned(counts, 3) || vs_misaligned(depth_out, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(pose_est, 7) || cp_misaligned(pose_gt, 7) || cp_misaligned(cam_K, 7) ||
+      cp_misaligned(diameters, 7) || cp_misaligned(errors, 7) || cp_misaligned(verts, 3) || cp_misaligned(v_offsets, 3) ||
+      cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) || cp_misaligned(depth_test, 3) ||
+      cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) || cp_misaligned(depth_out, 3))
     return CP_ERR_ALIGN;
   VsParams p = {};
   p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
@@ -348,9 +300,9 @@ extern "C" int cp_vsd_from_depth(cp_stream_t stream, const float* depth_est, con
   if (B <= 0 || I <= 0 || H <= 0 || W <= 0 || T < 1 || T > VS_TMAX || (k_stride != 0 && k_stride != 9) || !(delta == delta))
     return CP_ERR_INVALID;
   if (!image_ids && I != 1) return CP_ERR_INVALID;
-  if (vs_misaligned(scratch, 15) || vs_misaligned(cam_K, 7) || vs_misaligned(diameters, 7) || vs_misaligned(errors, 7) ||
-      vs_misaligned(depth_est, 3) || vs_misaligned(depth_gt, 3) || vs_misaligned(depth_test, 3) || vs_misaligned(image_ids, 3) ||
-      vs_misaligned(counts, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(cam_K, 7) || cp_misaligned(diameters, 7) || cp_misaligned(errors, 7) ||
+      cp_misaligned(depth_est, 3) || cp_misaligned(depth_gt, 3) || cp_misaligned(depth_test, 3) || cp_misaligned(image_ids, 3) ||
+      cp_misaligned(counts, 3))
     return CP_ERR_ALIGN;
   VsParams p = {};
   p.in_est = depth_est; p.in_gt = depth_gt; p.K = cam_K; p.k_stride = k_stride; p.depth_test = depth_test; p.image_id = image_ids;
@@ -367,9 +319,9 @@ extern "C" int cp_render_depth(cp_stream_t stream, const double* poses, const do
   if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !depth_out || !scratch) return CP_ERR_INVALID;
   if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (vs_misaligned(scratch, 15) || vs_misaligned(poses, 7) || vs_misaligned(cam_K, 7) || vs_misaligned(verts, 3) ||
-      vs_misaligned(v_offsets, 3) || vs_misaligned(faces, 3) || vs_misaligned(f_offsets, 3) || vs_misaligned(mesh_ids, 3) ||
-      vs_misaligned(depth_out, 3))
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(verts, 3) ||
+      cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) ||
+      cp_misaligned(depth_out, 3))
     return CP_ERR_ALIGN;
   VsParams p = {};
   p.est = poses; p.gt = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
