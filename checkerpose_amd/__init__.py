@@ -27,16 +27,21 @@ def is_deterministic():
 _RENDER_NAMES = ("render_rgb", "sample_views", "render_views", "synthetic_batch")
 _COCO_NAMES = ("annotate_masks", "calc_gt_coco", "mask_ious", "box_ious", "CocoSet", "eval_bop22_coco", "check_coco_results",
                "save_coco_results")
+_VISIBILITY_NAMES = ("compute_vis_hpr", "hpr_visibility", "overall_visibility")
 
 
 def __getattr__(name):
     """row N14's entry points, imported on first use (render.py pulls in torch): checkerpose_amd.render_rgb, .sample_views,
     .render_views, .synthetic_batch; row N15's likewise (coco_eval.py): .annotate_masks, .calc_gt_coco, .mask_ious, .box_ious, .CocoSet,
-    .eval_bop22_coco, .check_coco_results, .save_coco_results (coco_eval.evaluate is reached through the module)"""
+    .eval_bop22_coco, .check_coco_results, .save_coco_results (coco_eval.evaluate is reached through the module); row N16's likewise
+    (visibility.py): .compute_vis_hpr, .hpr_visibility, .overall_visibility"""
     if name in _RENDER_NAMES:
         from . import render
         return getattr(render, name)
     if name in _COCO_NAMES:
         from . import coco_eval
         return getattr(coco_eval, name)
+    if name in _VISIBILITY_NAMES:
+        from . import visibility
+        return getattr(visibility, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -231,6 +231,8 @@ SIGNATURES = {
     "cp_fps": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cp_pts_diameter_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_pts_diameter": (_I, [_P, _P, _P, _P, _I, _P, _P]),
+    "cp_hpr_visibility_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "cp_hpr_visibility": (_I, [_P, _P, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P]),
     "cp_edgeconv_bwd_workspace_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_edgeconv_gather_max_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F]),
     "cp_index2feat_gather_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I]),

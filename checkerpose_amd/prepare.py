@@ -8,8 +8,9 @@ and its diameter -- for an object that is not one of the reference's 44 pickles 
                                                       p3d_normed with its centroid / range, and a MeshSet
 Ids and diameters are the reference's bit for bit (tests/golden/prepare.npz): the kernels keep numpy's unfused fp64 expressions and
 compare roots, not squares.  Timing: tools/prepare_bench.py, profiles/prepare_bench.json.
-Not here: reading PLY files (pass the vertex array), the kNN graph (construction-time, on the CPU for its tie order:
-model/init.py) and the convex-hull visibility statistic of get_overall_visibility.py.  There is no CPU fallback."""
+Not here: reading PLY files (pass the vertex array) and the kNN graph (construction-time, on the CPU for its tie order:
+model/init.py).  The convex-hull visibility statistic of get_overall_visibility.py is row N16: checkerpose_amd/visibility.py.
+There is no CPU fallback."""
 import pickle
 
 import numpy as np

@@ -848,6 +848,27 @@ size_t cp_pts_diameter_scratch_bytes(int M, int Vmax);
 int cp_pts_diameter(cp_stream_t stream, const double* pts, const int32_t* offsets, const int32_t* offsets_host, int M,
                     double* diameters, void* scratch);
 
+/* Self-occlusion measure on the device (next-row N16; csrc/visibility.hip): the per-view rule of the reference's
+ * preprocess_data/get_overall_visibility.py:20-42 (compute_vis_hpr: hidden point removal) for n_views poses of ONE cloud in one launch.
+ * pts fp64 (V,3), R fp64 (n_views,3,3), t fp64 (3) with t_stride 0 or (n_views,3) with t_stride 3, all 8-byte aligned, on the device.
+ * Per view: pc = R p + t, flipped = pc + 2 (radius - |pc|) pc / |pc| with radius = max |pc| * 10^radius_param, the convex hull of
+ * the flipped points plus the viewpoint (0,0,0) by a bounded, deterministic insertion; a vertex is visible
+ * when it is a vertex of that hull.  fp64 without contraction, no floating-point atomics; the outputs do not depend on the call,
+ * on the batch a view is in, on the order of the views or on `workgroups`.
+ *   counts int32 (V): the number of views with status 0 in which each vertex is visible (zeroed by the call).
+ *   mask: null, or uint8 (n_views,V) of 0 / 1 (a view with nonzero status: zeros).
+ *   status int32 (n_views): 0 ok; 1 degenerate cloud (the initial tetrahedron has a zero extent: coincident, collinear or coplanar
+ *     flipped points); 2 a horizon that is not a simple cycle of at least 3 edges; 3 face table full; 4 more than V + 1 insertions;
+ *     5 a vertex at the viewpoint (norm 0) or a non-finite norm / radius.  The caller reads it; a failing view never spins.
+ *   workgroups: 0 = chosen from (n_views, V), or 1 .. 65535 = the number of workgroups that share the views (tests, measurement).
+ *   scratch: cp_hpr_visibility_scratch_bytes(n_views, V, workgroups) bytes, 8-byte aligned (0 = bad arguments): one slab per
+ *   WORKGROUP, not per view.  CP_ERR_INVALID: a null pointer (mask may be null), n_views < 1, V < 4, t_stride not 0 / 3,
+ *   radius_param not in [0, 8] (NaN included), workgroups < 0; CP_ERR_RANGE: V > 2^22, workgroups > 65535.  One hipMemsetAsync and one
+ *   launch (hpr_visibility_kernel); nothing allocates or synchronises. */
+size_t cp_hpr_visibility_scratch_bytes(int n_views, int V, int workgroups);
+int cp_hpr_visibility(cp_stream_t stream, const double* pts, const double* R, const double* t, int t_stride, int n_views, int V,
+                      double radius_param, int workgroups, int32_t* counts, uint8_t* mask, int32_t* status, void* scratch);
+
 /* ---------------------------------------------------------------------------------------------
  * Training side: backward of the fused graph ops + the loss head of train.py:307-320.
  * Gradients are fp32; `pq` is the forward's saved GEMM output in `dtype`.
