@@ -98,15 +98,198 @@ def solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=0, reproj_threshold=2.0,
     return out
 
 
+GC_MAX_ITERS, GC_NMAX, GC_MAX_EDGES, GC_LO_MAX, GC_Q = 512, 4096, 1 << 21, 8, 1 << 16        # csrc/pnp_gc.hip
+
+
+class RadiusGraph:
+    """The neighbourhood graphs of M objects (radius_graph): CSR on the device.  offsets (M,N+1) int32 = row starts of object m
+    relative to base[m]; indices int32 = neighbours, ascending per row; base (M,) int64; totals = directed edges per object (host)."""
+
+    def __init__(self, offsets, indices, base, totals, radius):
+        self.offsets, self.indices, self.base, self.totals, self.radius = offsets, indices, base, [int(x) for x in totals], float(radius)
+        self.M, self.N = int(offsets.shape[0]), int(offsets.shape[1]) - 1
+        self.max_edges, self.n_indices = max(self.totals), sum(self.totals)
+
+    def neighbours(self, m=0):
+        """object m's graph on the host: (offsets (N+1,), indices) numpy int32"""
+        b = sum(self.totals[:m])
+        return self.offsets[m].cpu().numpy(), self.indices[b:b + self.totals[m]].cpu().numpy()
+
+
+def radius_graph(p3d_xyz, radius=20.0, device="cuda:0"):
+    """Row N17, once per object: the graph over which solve_pnp_gc's Potts term acts (the reference's neighborhood_ball_radius = 20).
+    p3d_xyz (N,3) or (M,N,3) model keypoints (a tensor on a device stays there); pair {i,j}, i != j, is an edge when the squared
+    distance, in fp64 from the fp32 coordinates, is <= radius^2.  MODEL space: static per object and symmetric -- which space
+    pyprogressivex's FLANN radius graph lives in cannot be checked here (parity UNPINNED).  N <= 4096, at most 2^21 directed edges
+    per object (ValueError).  Two launches (count, fill) with one host read of the edge totals in between."""
+    if torch.is_tensor(p3d_xyz) and p3d_xyz.is_cuda:
+        device = p3d_xyz.device
+    pts = torch.as_tensor(p3d_xyz, dtype=torch.float32)
+    if pts.dim() == 2:
+        pts = pts[None]
+    if pts.dim() != 3 or pts.shape[2] != 3 or not 1 <= pts.shape[1] <= GC_NMAX or pts.shape[0] < 1:
+        raise ValueError("p3d_xyz must be (N,3) or (M,N,3) with 1 <= N <= %d, got %r" % (GC_NMAX, tuple(pts.shape)))
+    radius = float(radius)
+    if not 0.0 <= radius < 1e150:
+        raise ValueError("radius must be a finite number >= 0, got %r" % radius)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+    lib = _abi.load()
+    pts = pts.to(dev).contiguous()
+    M, N = int(pts.shape[0]), int(pts.shape[1])
+    offsets = torch.empty(M, N + 1, dtype=torch.int32, device=dev)
+    totals = torch.empty(M, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _abi.check(lib.cp_radius_graph_count(st, pts.data_ptr(), M, N, radius, offsets.data_ptr(), totals.data_ptr()), "cp_radius_graph_count")
+        tot = totals.cpu().tolist()
+        if max(tot) > GC_MAX_EDGES:
+            raise ValueError("radius_graph: object %d has %d directed edges at radius %g, more than %d" % (tot.index(max(tot)), max(tot), radius, GC_MAX_EDGES))
+        base = torch.tensor([sum(tot[:m]) for m in range(M)], dtype=torch.int64).to(dev)
+        indices = torch.empty(max(sum(tot), 1), dtype=torch.int32, device=dev)
+        _abi.check(lib.cp_radius_graph_fill(st, pts.data_ptr(), M, N, radius, offsets.data_ptr(), base.data_ptr(), indices.data_ptr(), sum(tot)),
+                   "cp_radius_graph_fill")
+    return RadiusGraph(offsets, indices, base, tot, radius)
+
+
+def graphcut_label(cin, offsets, indices, w):
+    """cp_graphcut_label: the labelling step of solve_pnp_gc alone.  cin (B,N) / (N,) int32 CUDA (-1 = not a node), one symmetric CSR
+    graph (offsets (N+1,), indices, columns ascending, int32 CUDA), w = capacity per direction of an edge (integer, Q = 65536 is the
+    source capacity).  -> (labels (B,N) bool = the minimal source side of a minimum cut, flow value (B,) int64, status (B,) int32,
+    sweeps (B,) int32); RuntimeError where the kernel's sweep bound did not suffice."""
+    if not (cin.is_cuda and offsets.is_cuda and indices.is_cuda):
+        raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+    if cin.dim() == 1:
+        cin = cin[None]
+    B, N = cin.shape
+    if cin.dtype != torch.int32 or offsets.dtype != torch.int32 or indices.dtype != torch.int32 or tuple(offsets.shape) != (N + 1,):
+        raise ValueError("cin (B,N), offsets (N+1,), indices: int32 tensors")
+    E = int(indices.numel())
+    if not 1 <= N <= GC_NMAX or E > GC_MAX_EDGES or not 0 <= int(w) <= 1 << 28:
+        raise ValueError("N in 1..%d, at most %d directed edges, w in 0..2^28" % (GC_NMAX, GC_MAX_EDGES))
+    lib = _abi.load()
+    dev = cin.device
+    cin, offsets = cin.contiguous(), offsets.contiguous()
+    indices = indices.contiguous() if E else torch.zeros(1, dtype=torch.int32, device=dev)
+    labels = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    flow = torch.empty(B, dtype=torch.int64, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    sweeps = torch.empty(B, dtype=torch.int32, device=dev)
+    scratch = torch.empty(B * max(E, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _abi.check(lib.cp_graphcut_label(st, cin.data_ptr(), offsets.data_ptr(), indices.data_ptr(), B, N, E, int(w), labels.data_ptr(),
+                                         flow.data_ptr(), status.data_ptr(), sweeps.data_ptr(), scratch.data_ptr(), scratch.numel() * 4),
+                   "cp_graphcut_label")
+    bad = torch.nonzero(status < 0).flatten().tolist()
+    if bad:
+        raise RuntimeError("cp_graphcut_label: problem %d hit the sweep bound (status %d)" % (bad[0], int(status[bad[0]])))
+    return labels.bool(), flow, status, sweeps
+
+
+def solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=None, column=0, reproj_threshold=2.0, spatial_coherence_weight=0.1,
+                 iterations=400, min_inliers=6, seed=0, return_stages=False):
+    """Graph-cut RANSAC on the device (row N17): what the reference's `--use_progressivex` branch (pyprogressivex.find6DPoses with
+    maximum_model_number = 1, test_network_with_test_data.py:68-99) comes down to.  The rule is this project's own -- parity with
+    pyprogressivex (its sampler, confidence default, unary kernel, inner RANSAC, neighbourhood space, PEARL's model validation) is
+    UNPINNED; tests/gc_stages.py restates it in numpy, include/checkerpose_hip.h states it in full:
+      hypotheses from 4 correspondences (P3P + the fourth point), MSAC score, OpenCV's stopping rule between rounds of 64;
+      the winner's inlier set = the minimal source side of the minimum cut of [unary: squared residual / threshold^2 against 1;
+      Potts: spatial_coherence_weight per edge of `graph` between two valid points], in integers (Q = 65536);
+      EPnP over that set, repeated (at most 8 times) while the MSAC score improves.
+    Inputs and outputs as solve_pnp_ransac; graph = radius_graph(...) of the model keypoints, graph_ids (B,) = the object of each crop
+    (required when the graph holds more than one); iterations in 1..512; fewer than min_inliers valid points or labelled inliers ->
+    the identity with status 0 (the reference's `num_valid >= 6` rule).
+    -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32[, stages]); stages (return_stages=True): dict with
+       hypotheses (B,iterations,14) f64 [count or -1, score, R, t], steps (B,9,30) f64 [k, P_k (12), score(P_k), |L_k|, refit ok,
+       Q_k (12), score(Q_k), sweeps], cin (B,9,N) int32 (-1 invalid; -2 where the step did not run), labels (B,9,N) uint8 (255 where
+       the step did not run); NaN where the solver wrote nothing.
+    RuntimeError naming the crop where the max-flow's sweep bound was hit (never an approximate labelling)."""
+    if not 0 < int(iterations) <= GC_MAX_ITERS:          # no silent clamp
+        raise ValueError("iterations (prog_max_iters) must be in 1..%d for cp_pnp_gc, got %r" % (GC_MAX_ITERS, iterations))
+    if not isinstance(graph, RadiusGraph):
+        raise ValueError("graph must be the RadiusGraph of the model keypoints (postprocess.radius_graph)")
+    B, N, _ = p2d.shape
+    if tuple(valid.shape) != (B, N, 3) or valid.dtype != torch.uint8 or not 0 <= column < 3:
+        raise ValueError("valid must be the (B,N,3) uint8 tensor of correspondences(), column in 0..2")
+    if graph.N != N:
+        raise ValueError("the graph is over %d keypoints, the crops have %d" % (graph.N, N))
+    if graph.M > 1 and graph_ids is None:
+        raise ValueError("graph_ids is required: the graph holds %d objects" % graph.M)
+    lam = float(spatial_coherence_weight)
+    if not 0.0 <= lam <= 4096.0:
+        raise ValueError("spatial_coherence_weight must be in 0..4096, got %r" % spatial_coherence_weight)
+    if not 4 <= int(min_inliers) or not float(reproj_threshold) > 0:
+        raise ValueError("min_inliers must be >= 4 and reproj_threshold > 0")
+    if not (p2d.is_cuda and valid.is_cuda):
+        raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+    lib = _abi.load()
+    dev = p2d.device
+    gid = None
+    if graph_ids is not None:
+        gid = torch.as_tensor(graph_ids).to(device=dev, dtype=torch.int32).contiguous()
+        if tuple(gid.shape) != (B,):
+            raise ValueError("graph_ids must be (B,)")
+    p3 = torch.as_tensor(p3d_xyz, dtype=torch.float32, device=dev).contiguous()
+    K = torch.as_tensor(cam_K, dtype=torch.float32, device=dev).contiguous()
+    if p3.shape[-2:] != (N, 3) or K.shape[-2:] != (3, 3):
+        raise ValueError("p3d_xyz must be (N,3) / (B,N,3) and cam_K (3,3) / (B,3,3)")
+    p2 = p2d.contiguous().float()
+    va = valid.contiguous()
+    pose = torch.empty(B, 12, dtype=torch.float64, device=dev)
+    inl = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    nbytes = lib.cp_pnp_gc_scratch_bytes(B, N, graph.max_edges)
+    if nbytes == 0:
+        raise ValueError("cp_pnp_gc: bad shape (B = %d, N = %d, max_edges = %d)" % (B, N, graph.max_edges))
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    S = GC_LO_MAX + 1
+    o_steps = B * GC_MAX_ITERS * 14
+    o_cin = (o_steps + B * S * 30) * 8
+    o_lab = o_cin + B * S * N * 4
+    raw = scratch.view(torch.uint8)
+    if return_stages:
+        scratch[:o_steps + B * S * 30] = float("nan")
+        raw[o_cin:o_lab].view(torch.int32).fill_(-2)
+        raw[o_lab:o_lab + B * S * N].fill_(255)
+    w = int(np.floor(lam * GC_Q + 0.5))
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _abi.check(lib.cp_pnp_gc(st, p3.data_ptr(), 3 * N if p3.dim() == 3 else 0, p2.data_ptr(), va.data_ptr() + column, 3, K.data_ptr(),
+                                 9 if K.dim() == 3 else 0, graph.offsets.data_ptr(), graph.indices.data_ptr(), graph.base.data_ptr(),
+                                 gid.data_ptr() if gid is not None else None, graph.M, graph.max_edges, graph.n_indices, B, N,
+                                 float(reproj_threshold), w, int(iterations), int(min_inliers), int(seed) & 0xFFFFFFFF,
+                                 pose.data_ptr(), inl.data_ptr(), status.data_ptr(), scratch.data_ptr()), "cp_pnp_gc")
+    bad = torch.nonzero(status < 0).flatten().tolist()
+    if bad:
+        code = int(status[bad[0]])
+        raise RuntimeError("cp_pnp_gc: crop %d %s (status %d); %d of %d crops failed"
+                           % (bad[0], "hit the max-flow's sweep bound" if code == -1 else "names a graph outside the RadiusGraph", code, len(bad), B))
+    out = (pose[:, :9].view(B, 3, 3), pose[:, 9:].view(B, 3, 1), inl.bool(), status)
+    if return_stages:
+        out += (dict(hypotheses=scratch[:B * int(iterations) * 14].view(B, int(iterations), 14),
+                     steps=scratch[o_steps:o_steps + B * S * 30].view(B, S, 30),
+                     cin=raw[o_cin:o_lab].view(torch.int32).view(B, S, N), labels=raw[o_lab:o_lab + B * S * N].view(B, S, N)),)
+    return out
+
+
 def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
-                   resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0):
+                   resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0, solver="epnp",
+                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400):
     """The inner loop of the reference's test.py (:198-330) for a whole batch without leaving the GPU: detection boxes on full uint8
     frames -> padded RoI crops (`padding_Bbox` + `get_roi`, bop_dataset_pytorch.py:344-354; preprocess.get_roi_batch) -> network forward
     (uint8 input, normalised on the device) -> correspondences from the crops' final boxes (`get_final_Bbox`; N2) -> EPnP + RANSAC (N4).
       frames: uint8 CUDA tensor (n_img, H, W, 3) or (H, W, 3); Bboxes: (B, 4) detection boxes (x, y, w, h), None = no detection;
       p3d_xyz (N,3) / (B,N,3) model keypoints in original units; cam_K (3,3) / (B,3,3); obj_ids for the LM shared estimator.
+      solver "epnp" (default): solve_pnp_ransac; "gc": solve_pnp_gc (row N17, the `--use_progressivex` path) over `graph` =
+      radius_graph(p3d_xyz) with spatial_coherence_weight and prog_max_iters iterations; obj_ids then also name each crop's graph.
     -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32 (0: identity fallback), final boxes (B,4) int array)"""
     from . import preprocess as PP
+    if solver not in ("epnp", "gc"):
+        raise ValueError("solver must be 'epnp' or 'gc', got %r" % (solver,))
+    if solver == "gc" and graph is None:
+        raise ValueError("solver='gc' needs graph=radius_graph(p3d_xyz)")
     if frames.dim() == 3:
         frames = frames.unsqueeze(0)
     H, W = int(frames.shape[1]), int(frames.shape[2])
@@ -116,6 +299,11 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
     with torch.no_grad():
         out = net(crops, None) if obj_ids is None else net(crops, None, obj_ids)
     p2d, valid, _ = correspondences(out, discard_bd_pixel=discard_bd_pixel, Bboxes=final)
+    if solver == "gc":
+        R, t, inl, status = solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=obj_ids if graph.M > 1 else None,
+                                         column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
+                                         spatial_coherence_weight=spatial_coherence_weight, iterations=prog_max_iters, seed=seed)
+        return R, t, inl, status, final
     R, t, inl, status = solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
                                          iterations=iterations, seed=seed)
     return R, t, inl, status, final
@@ -143,17 +331,24 @@ def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, me
 
 def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_y_id, check_seg=False, seg_mask=None,
                     use_progressivex=False, neighborhood_ball_radius=20, spatial_coherence_weight=0.1, prog_max_iters=400,
-                    discard_bd_pixel=0, return_inliers=False, reprojErr_thresh=2, cv_max_iters=150, device="cuda:0", seed=0):
+                    discard_bd_pixel=0, return_inliers=False, reprojErr_thresh=2, cv_max_iters=150, device="cuda:0", seed=0,
+                    progx_backend=None):
     """Same name, arguments (numpy arrays of ONE image) and returns as the reference's `from_id_to_pose`
     (test_network_with_test_data.py:32-115), with its cv2 branch running on the device (`cp_pnp_ransac`):
       the validity mask is built exactly as :50-66 (RoI bit > 0.5, optional seg mask at the predicted pixel, optional border
       discard), then EPnP + RANSAC (reprojErr_thresh, cv_max_iters) -> R (3,3), t (3,1) [, inlier indices into ALL keypoints];
       fewer than 4 valid correspondences -> R = I, t = 0, inliers None (:111-114).
-    `use_progressivex=True` is the third-party pyprogressivex solver of the reference and is not rebuilt: ValueError.
+    `use_progressivex=True` is the third-party pyprogressivex solver of the reference and is not rebuilt: ValueError, unless
+    progx_backend="device" asks for this project's graph-cut RANSAC (solve_pnp_gc, row N17; parity with pyprogressivex UNPINNED):
+    neighborhood_ball_radius -> radius_graph, spatial_coherence_weight, prog_max_iters, reprojErr_thresh -> the solver; fewer than 6
+    valid points -> the identity; inliers None, as in the reference (:99).
     For whole batches straight from the network's outputs use correspondences() + solve_pnp_ransac() instead."""
     import numpy as np
-    if use_progressivex:
-        raise ValueError("use_progressivex=True needs the third-party pyprogressivex solver; only the cv2 (EPnP + RANSAC) branch is built")
+    if progx_backend not in (None, "device"):
+        raise ValueError("progx_backend must be None or 'device', got %r" % (progx_backend,))
+    if use_progressivex and progx_backend is None:
+        raise ValueError("use_progressivex=True needs the third-party pyprogressivex solver, which is not built; "
+                         "progx_backend='device' runs this project's graph-cut RANSAC (solve_pnp_gc) in its place")
     num_all_pt = p3d_xyz.shape[0]
     roi_h, roi_w, _ = roi_xy_ori.shape
     disc_p2d = roi_xy_ori[pixel_y_id, pixel_x_id]
@@ -164,7 +359,21 @@ def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_
         bd_mask = np.zeros((roi_h, roi_w))
         bd_mask[discard_bd_pixel:(roi_h - discard_bd_pixel), discard_bd_pixel:(roi_w - discard_bd_pixel)] = 1.0
         valid_mask = np.logical_and(valid_mask, bd_mask[pixel_y_id, pixel_x_id] > 0.5)
-    if int(valid_mask.sum()) < 4:
+    if use_progressivex:
+        R_predict, t_predict, inliers = np.eye(3), np.zeros((3, 1)), None
+        if int(valid_mask.sum()) >= 6:                # :68
+            dev = torch.device(device)
+            valid = torch.zeros(1, num_all_pt, 3, dtype=torch.uint8, device=dev)
+            valid[0, :, 0] = torch.from_numpy(np.ascontiguousarray(valid_mask)).to(dev)
+            p2d = torch.from_numpy(np.ascontiguousarray(disc_p2d, dtype=np.float32)).to(dev)[None]
+            p3 = torch.from_numpy(np.ascontiguousarray(p3d_xyz, dtype=np.float32)).to(dev)
+            R, t, inl, status = solve_pnp_gc(p3, p2d, valid, torch.from_numpy(np.ascontiguousarray(cam_K, dtype=np.float32)).to(dev),
+                                             radius_graph(p3, float(neighborhood_ball_radius)), column=0,
+                                             reproj_threshold=float(reprojErr_thresh), spatial_coherence_weight=float(spatial_coherence_weight),
+                                             iterations=int(prog_max_iters), seed=seed)
+            if int(status[0]) == 1:
+                R_predict, t_predict = R[0].cpu().numpy(), t[0].cpu().numpy()
+    elif int(valid_mask.sum()) < 4:
         R_predict, t_predict, inliers = np.eye(3), np.zeros((3, 1)), None
     else:
         dev = torch.device(device)

@@ -544,6 +544,55 @@ int cp_pnp_ransac(cp_stream_t stream, const float* p3d, long long p3d_bstride, c
                   int valid_stride, const float* cam_K, long long K_bstride, int B, int N, float reproj_threshold,
                   int iterations, uint32_t seed, double* pose, uint8_t* inliers, int32_t* status, void* scratch);
 
+/* Graph-cut RANSAC pose solver (row N17): what the reference's `--use_progressivex` path (pyprogressivex.find6DPoses,
+ * test_network_with_test_data.py:68-99) comes down to with maximum_model_number = 1 -- RANSAC from a minimal solver, a locally
+ * optimised model whose inlier set is a two-label graph cut over a neighbourhood graph, a refit over that labelling repeated while
+ * it improves.  pyprogressivex is not part of the reference's tree: the rule is this project's own (tests/gc_stages.py restates
+ * it in numpy); parity with pyprogressivex -- its sampler, confidence default, unary kernel, inner RANSAC, neighbourhood space and
+ * PEARL's model validation -- is UNPINNED.
+ *
+ * cp_radius_graph_count / _fill: the neighbourhood graphs of M objects of N (<= 4096) fp32 keypoints each, pts (M,N,3): pair {i,j},
+ *   i != j, is an edge when dx*dx + dy*dy + dz*dz <= radius^2, evaluated in fp64 from the fp32 coordinates without contraction
+ *   (MODEL space: static per object and symmetric; which space pyprogressivex's FLANN graph lives in cannot be checked).
+ *   count writes offsets int32 (M,N+1) -- the CSR row starts of object m RELATIVE to that object's first edge -- and totals int32
+ *   (M) = directed edges per object.  The caller reads the totals, refuses more than 2^21 per object, forms base int64 (M) = the
+ *   exclusive prefix sums of the totals and calls fill, which writes indices int32 [n_indices] (n_indices = sum of the totals):
+ *   the neighbours of keypoint i of object m at base[m] + offsets[m][i] ..., ascending.
+ * cp_graphcut_label: the labelling alone, B problems over ONE graph (offsets (N+1), indices [n_edges], symmetric, columns ascending):
+ *   cin int32 (B,N), -1 = not a node.  Network: s->i = Q = 65536, i->t = cin_i, i<->j = w per direction on every edge between two
+ *   nodes.  labels uint8 (B,N) = the MINIMAL source side of a minimum cut (unique, whatever the maximum flow), flow_value int64 (B)
+ *   = the value of the maximum flow, status int32 (B): 0, or -1 when the bounded number of push-relabel sweeps did not suffice
+ *   (labels 0, flow_value -1: never an approximate labelling); sweeps int32 (B) or NULL: sweeps run (the one
+ *   output that depends on thread timing).  scratch: at least
+ *   B * max(n_edges, 1) * 4 bytes (`scratch_bytes` says how many there are).  0 <= w <= 2^28.
+ * cp_pnp_gc: inputs and outputs as cp_pnp_ransac; the graph of crop b is object graph_ids[b] (NULL: object 0; required when M > 1),
+ *   max_edges = the largest total of any object, w = floor(spatial_coherence_weight * 65536 + 0.5), iterations in 1..512,
+ *   min_inliers >= 4.  Per crop: hypotheses in rounds of 64 -- hypothesis h draws 4 distinct valid correspondences by the hash of
+ *   (seed, crop, h), P3P on three, the fourth picks the root; count = valid points with r^2 <= thr^2, score = sum of 1 - r^2/thr^2
+ *   over them (MSAC); OpenCV's stopping rule on the counts between rounds (sample size 4).  Winner P_0 = the first record with the
+ *   largest score among those with count >= 4.  Step k = 0..8: cin_i = floor(min(r_i^2/thr^2, 2^14) * 65536 + 0.5) under P_k,
+ *   L_k = the labelling above; stop if |L_k| < min_inliers; for k < 8: Q_k = EPnP over L_k (cp_pnp_ransac's refit), stop if it
+ *   fails or score(Q_k) <= score(P_k), else P_{k+1} = Q_k.  Returned: the last P_k and L_k with status 1 when |L_k| >= min_inliers,
+ *   else the identity with status 0 (also with fewer than min_inliers valid points or no record with count >= 4).  status -1: the
+ *   sweep bound was hit, -2: graph_ids[b] / base outside the graph (identity pose, no inliers either way).
+ *   scratch: cp_pnp_gc_scratch_bytes(B, N, max_edges) bytes (0 = bad arguments), 8-byte aligned; what the call leaves is part of the
+ *   interface, at byte offsets: 0: hypothesis records, 14 doubles at (b * iterations + h) * 14 = [count or -1, score, R, t] (score
+ *   and pose only when count >= 0; unwritten as in cp_pnp_ransac); B*512*14*8: step records, 30 doubles at (b * 9 + k) * 30 =
+ *   [k, P_k (12), score(P_k), |L_k|, refit 1 / 0, Q_k (12), score(Q_k), sweeps (timing-dependent)], a word written only when its stage ran; then
+ *   cin int32 (B,9,N), then labels uint8 (B,9,N), then (8-byte aligned) the flows. */
+int cp_radius_graph_count(cp_stream_t stream, const float* pts, int M, int N, double radius, int32_t* offsets, int32_t* totals);
+int cp_radius_graph_fill(cp_stream_t stream, const float* pts, int M, int N, double radius, const int32_t* offsets,
+                         const int64_t* base, int32_t* indices, long long n_indices);
+int cp_graphcut_label(cp_stream_t stream, const int32_t* cin, const int32_t* offsets, const int32_t* indices, int B, int N,
+                      long long n_edges, int32_t w, uint8_t* labels, int64_t* flow_value, int32_t* status, int32_t* sweeps,
+                      void* scratch, size_t scratch_bytes);
+size_t cp_pnp_gc_scratch_bytes(int B, int N, long long max_edges);
+int cp_pnp_gc(cp_stream_t stream, const float* p3d, long long p3d_bstride, const float* p2d, const uint8_t* valid,
+              int valid_stride, const float* cam_K, long long K_bstride, const int32_t* g_offsets, const int32_t* g_indices,
+              const int64_t* g_base, const int32_t* graph_ids, int M, long long max_edges, long long n_indices, int B, int N,
+              float reproj_threshold, int32_t w, int iterations, int min_inliers, uint32_t seed, double* pose,
+              uint8_t* inliers, int32_t* status, void* scratch);
+
 /* Pose errors on the device (next-row N5; reference metric.py:8-18 -> bop_toolkit_lib/pose_error.py:147-184, called once per image
  * by test.py:378-427 / test_lm.py:300-321): ADD = mean_i |P_est(p_i) - P_gt(p_i)| and ADD-S / ADI = mean_i min_j |P_gt(p_i) - P_est(p_j)|
  * over an object's mesh vertices, for B poses at once.
