@@ -28,13 +28,15 @@ _RENDER_NAMES = ("render_rgb", "sample_views", "render_views", "synthetic_batch"
 _COCO_NAMES = ("annotate_masks", "calc_gt_coco", "mask_ious", "box_ious", "CocoSet", "eval_bop22_coco", "check_coco_results",
                "save_coco_results")
 _VISIBILITY_NAMES = ("compute_vis_hpr", "hpr_visibility", "overall_visibility")
+_VIS_NAMES = ("vis_poses", "depth_diff_vis", "select_estimates", "vis_est_poses", "vis_gt_poses")
 
 
 def __getattr__(name):
     """row N14's entry points, imported on first use (render.py pulls in torch): checkerpose_amd.render_rgb, .sample_views,
     .render_views, .synthetic_batch; row N15's likewise (coco_eval.py): .annotate_masks, .calc_gt_coco, .mask_ious, .box_ious, .CocoSet,
     .eval_bop22_coco, .check_coco_results, .save_coco_results (coco_eval.evaluate is reached through the module); row N16's likewise
-    (visibility.py): .compute_vis_hpr, .hpr_visibility, .overall_visibility"""
+    (visibility.py): .compute_vis_hpr, .hpr_visibility, .overall_visibility; row N18's likewise (vis.py): .vis_poses, .depth_diff_vis,
+    .select_estimates, .vis_est_poses, .vis_gt_poses"""
     if name in _RENDER_NAMES:
         from . import render
         return getattr(render, name)
@@ -44,4 +46,7 @@ def __getattr__(name):
     if name in _VISIBILITY_NAMES:
         from . import visibility
         return getattr(visibility, name)
+    if name in _VIS_NAMES:
+        from . import vis
+        return getattr(vis, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

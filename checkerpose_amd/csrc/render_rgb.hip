@@ -32,15 +32,9 @@
 //   rgb_finish_kernel   per pose: ok, the box as x, y, w, h (-1 when nothing is covered).
 // No floating-point atomics; nothing allocates or synchronises; every output is bit-identical from call to call, for a pose alone or
 // in a batch, with or without the optional outputs.
-#include "vsd_raster.h"
+#include "render_shade.h"
 
 namespace {
-
-// 4-byte words per pose: VsHdr<1> (P rect bad ok) | RT[12] | NM[12] = N (3x3) c (3) | box xmin ymin xmax ymax | sign(fx fy) | spare
-using RrH = VsHdr<1>;
-constexpr int RR_HDR = 48;
-constexpr int RR_RT = RrH::USER, RR_NM = RR_RT + 12, RR_BOX = RR_NM + 12, RR_SK = RR_BOX + 4;
-enum { RR_FLAT = 0, RR_PHONG = 1 };
 
 struct RrParams {
   const double* poses;        // (B, 12)
@@ -58,57 +52,21 @@ struct RrParams {
   int32_t* boxes;             // (B, 4) or nullptr
   uint8_t* ok;                // (B)
   int32_t* hdr;               // (B, RR_HDR)
-  float4* sv;                 // (B, Vmax) screen records
-  float4* eye;                // (B, Vmax)
-  float4* vl;                 // (B, Vmax)
-  float4* vn;                 // (B, Vmax), phong
-  float surf[3], light[3], ambient;
+  RrTables T;                 // the (B, Vmax) tables, the light, the ambient weight, the shading (render_shade.h)
+  float surf[3];
   int bg[3];                  // the quantised background
-  int k_stride, M, B, Vmax, H, W, f, shading, bgr, tx, ty, vchunks;
+  int k_stride, M, B, Vmax, H, W, f, bgr, tx, ty, vchunks;
 };
 
-// round-half-even(255 v) of an fp32 colour value, clamped to 0..255 (NaN -> 0)
-__device__ __forceinline__ int rr_quant(float v) {
-#pragma clang fp contract(off)
-  const float q = rintf(255.0f * v);
-  return q >= 255.f ? 255 : (q > 0.f ? (int)q : 0);
-}
-
 __global__ __launch_bounds__(VS_THREADS) void rgb_pose_kernel(RrParams p) {
-#pragma clang fp contract(off)
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.B) return;
-  int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
-  const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
   int vfirst, V, ffirst, F, m;
-  bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const double* __restrict__ q = p.poses + 12 * (size_t)b;
-  ok = ok && vs_pose_finite(K, q);
-  vs_side_init(K, (double)p.f, q, (float*)h + RrH::P(0), h + RrH::RECT(0));      // P = (K f)' [R | t]
-  float* __restrict__ rt = (float*)(h + RR_RT);
-  for (int r = 0; r < 3; ++r) {
-    for (int c = 0; c < 3; ++c) rt[4 * r + c] = (float)q[3 * r + c];
-    rt[4 * r + 3] = (float)q[9 + r];
-  }
-  // u_nm = inverse([R t; 0 1])^T = [R^-T 0; -(R^-1 t)^T 1]: N = R^-T (cofactors / det), c = R^-1 t = N^T t
-  const double c00 = q[4] * q[8] - q[5] * q[7], c01 = q[5] * q[6] - q[3] * q[8], c02 = q[3] * q[7] - q[4] * q[6];
-  const double c10 = q[2] * q[7] - q[1] * q[8], c11 = q[0] * q[8] - q[2] * q[6], c12 = q[1] * q[6] - q[0] * q[7];
-  const double c20 = q[1] * q[5] - q[2] * q[4], c21 = q[2] * q[3] - q[0] * q[5], c22 = q[0] * q[4] - q[1] * q[3];
-  const double det = (q[0] * c00 + q[1] * c01) + q[2] * c02;
-  ok = ok && isfinite(det) && det != 0.0;
-  const double N[9] = {c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det};
-  float* __restrict__ nm = (float*)(h + RR_NM);
-  for (int k = 0; k < 9; ++k) nm[k] = (float)N[k];
-  for (int c = 0; c < 3; ++c) nm[9 + c] = (float)((N[c] * q[9] + N[3 + c] * q[10]) + N[6 + c] * q[11]);
-  h[RrH::BAD(0)] = 0;
-  h[RrH::OK] = ok ? 1 : 0;
-  vs_rect_set(h + RR_BOX, INT_MAX, INT_MAX, INT_MIN, INT_MIN);
-  h[RR_SK] = (K[0] > 0.0) == (K[4] > 0.0) ? 1 : -1;
-  h[RR_SK + 1] = 0;
+  const bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+  rr_pose_record(p.K + (size_t)p.k_stride * b, p.poses + 12 * (size_t)b, (double)p.f, ok, p.hdr + (size_t)b * RR_HDR);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_vertex_kernel(RrParams p) {
-#pragma clang fp contract(off)
   int b, s, vc;
   vs_vertex_block(p.vchunks, 1, b, s, vc);
   int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
@@ -116,84 +74,11 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_vertex_kernel(RrParams p) {
   int vfirst, V, ffirst, F, m;
   vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
   const float4 grid = make_float4(-2.f, (float)(p.f * p.W) + 1.f, -2.f, (float)(p.f * p.H) + 1.f);      // the sample grid
-  // besides the screen record: the eye position, v_L and, for phong, v_normal of the vertex
   const auto shading_records = [&](int i, const float* __restrict__ vt) {
-#pragma clang fp contract(off)
-    const size_t at = (size_t)b * p.Vmax + i;
-    const float* __restrict__ rt = (const float*)(h + RR_RT);
-    const float ex = vs_affine(rt, vt[0], vt[1], vt[2]), ey = vs_affine(rt + 4, vt[0], vt[1], vt[2]), ez = vs_affine(rt + 8, vt[0], vt[1], vt[2]);
-    p.eye[at] = make_float4(ex, ey, ez, 0.f);
-    const float lx = p.light[0] - ex, ly = p.light[1] - ey, lz = p.light[2] - ez;
-    const float ll = sqrtf((lx * lx + ly * ly) + lz * lz);
-    p.vl[at] = make_float4(lx / ll, ly / ll, lz / ll, 0.f);
-    if (p.shading == RR_PHONG) {
-      const float* __restrict__ nm = (const float*)(h + RR_NM);
-      const float* __restrict__ nr = p.normals + 3 * ((size_t)vfirst + i);
-      const float nx = fmaf(nm[2], nr[2], fmaf(nm[1], nr[1], nm[0] * nr[0]));
-      const float ny = fmaf(nm[5], nr[2], fmaf(nm[4], nr[1], nm[3] * nr[0]));
-      const float nz = fmaf(nm[8], nr[2], fmaf(nm[7], nr[1], nm[6] * nr[0]));
-      const float nw = 1.0f - fmaf(nm[11], nr[2], fmaf(nm[10], nr[1], nm[9] * nr[0]));
-      const float nl = sqrtf(((nx * nx + ny * ny) + nz * nz) + nw * nw);    // the shader's 4-vector length
-      p.vn[at] = make_float4(nx / nl, ny / nl, nz / nl, 0.f);
-    }
+    rr_vertex_record(p.T, h, (size_t)b * p.Vmax + i, vt, p.normals ? p.normals + 3 * ((size_t)vfirst + i) : nullptr);
   };
-  vs_vertex_chunk((const float*)h + RrH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, grid, p.sv + (size_t)b * p.Vmax, h + RrH::RECT(0),
+  vs_vertex_chunk((const float*)h + RrH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, grid, p.T.sv + (size_t)b * p.Vmax, h + RrH::RECT(0),
                   h + RrH::BAD(0), shading_records);
-}
-
-__device__ __forceinline__ float rr_mix(float w0, float w1, float w2, float a, float c, float d) {
-#pragma clang fp contract(off)
-  return (w0 * a + w1 * c) + w2 * d;
-}
-
-// the same interpolation with w0 = 1 - w1 - w2 implied: three equal values give that value EXACTLY (a mesh of one colour, the 0.5
-// grey a mesh without colours gets inside a coloured MeshSet), whatever the weights' rounded sum is
-__device__ __forceinline__ float rr_mix_col(float w1, float w2, float a, float c, float d) {
-#pragma clang fp contract(off)
-  return a + (w1 * (c - a) + w2 * (d - a));
-}
-
-// the shaded, quantised colour of the sample (qx, qy) (tile-relative indices) on face fidx
-__device__ __forceinline__ void rr_shade(const RrParams& p, const int32_t* __restrict__ h, const int32_t* __restrict__ faces, size_t vbase,
-                                         size_t cbase, int fidx, float fx0, float fy0, float qx, float qy, int (&out)[3]) {
-#pragma clang fp contract(off)
-  const int32_t* __restrict__ fi = faces + 3 * (size_t)fidx;
-  const int i0 = fi[0], i1 = fi[1], i2 = fi[2];
-  const float4 a = p.sv[vbase + i0], c = p.sv[vbase + i1], d = p.sv[vbase + i2];
-  const float ax = a.x - fx0, ay = a.y - fy0, cx = c.x - fx0, cy = c.y - fy0, dx = d.x - fx0, dy = d.y - fy0;
-  const float area = (cx - ax) * (dy - ay) - (dx - ax) * (cy - ay);   // (the walk's expression: the same bits, never 0 here)
-  // edge i is opposite vertex i, differences first; perspective-correct weights w_i = E_i / Z_i / sum_j E_j / Z_j
-  const float e0 = (dx - cx) * (qy - cy) - (dy - cy) * (qx - cx);
-  const float e1 = (ax - dx) * (qy - dy) - (ay - dy) * (qx - dx);
-  const float e2 = (cx - ax) * (qy - ay) - (cy - ay) * (qx - ax);
-  const float p0 = e0 * a.w, p1 = e1 * c.w, p2 = e2 * d.w;
-  const float ps = (p0 + p1) + p2;
-  const float w0 = p0 / ps, w1 = p1 / ps, w2 = p2 / ps;
-  const float4 la = p.vl[vbase + i0], lc = p.vl[vbase + i1], ld = p.vl[vbase + i2];
-  const float lx = rr_mix(w0, w1, w2, la.x, lc.x, ld.x), ly = rr_mix(w0, w1, w2, la.y, lc.y, ld.y), lz = rr_mix(w0, w1, w2, la.z, lc.z, ld.z);
-  float nx, ny, nz;
-  if (p.shading == RR_PHONG) {
-    const float4 na = p.vn[vbase + i0], nc = p.vn[vbase + i1], nd = p.vn[vbase + i2];
-    nx = rr_mix(w0, w1, w2, na.x, nc.x, nd.x); ny = rr_mix(w0, w1, w2, na.y, nc.y, nd.y); nz = rr_mix(w0, w1, w2, na.z, nc.z, nd.z);
-  } else {
-    const float4 ea = p.eye[vbase + i0], ec = p.eye[vbase + i1], ed = p.eye[vbase + i2];
-    const float ux = ec.x - ea.x, uy = ec.y - ea.y, uz = ec.z - ea.z, vx = ed.x - ea.x, vy = ed.y - ea.y, vz = ed.z - ea.z;
-    nx = uy * vz - uz * vy; ny = uz * vx - ux * vz; nz = ux * vy - uy * vx;
-    // n . eye_a = det[eye_a eye_c eye_d] has the sign of (screen area) * sign(fx fy): towards the viewer means n . eye < 0
-    if ((area > 0.f) == (h[RR_SK] > 0)) { nx = -nx; ny = -ny; nz = -nz; }
-  }
-  const float ll = sqrtf((lx * lx + ly * ly) + lz * lz), nl = sqrtf((nx * nx + ny * ny) + nz * nz);
-  const float dt = ((lx * nx + ly * ny) + lz * nz) / (ll * nl);
-  float lw = p.ambient + (dt > 0.f ? dt : 0.f);                        // (NaN from a zero-length vector: no diffuse term)
-  if (lw > 1.0f) lw = 1.0f;
-  float r = p.surf[0], g = p.surf[1], bl = p.surf[2];
-  if (p.colors) {
-    const float* __restrict__ ca = p.colors + 3 * (cbase + i0);
-    const float* __restrict__ cc = p.colors + 3 * (cbase + i1);
-    const float* __restrict__ cd = p.colors + 3 * (cbase + i2);
-    r = rr_mix_col(w1, w2, ca[0], cc[0], cd[0]); g = rr_mix_col(w1, w2, ca[1], cc[1], cd[1]); bl = rr_mix_col(w1, w2, ca[2], cc[2], cd[2]);
-  }
-  out[0] = rr_quant(lw * r); out[1] = rr_quant(lw * g); out[2] = rr_quant(lw * bl);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
@@ -226,7 +111,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
   const size_t vbase = (size_t)b * p.Vmax;
   float best[VS_PPL];
   int face[VS_PPL];
-  vs_raster_tile<true>(s_tri, &s_n, p.sv + vbase, faces, F, V, c, best, face);
+  vs_raster_tile<true>(s_tri, &s_n, p.T.sv + vbase, faces, F, V, c, best, face);
 
   // f >= 2: the samples' integer sums (at most 16 x 16 output pixels per tile) take over the triangle records' LDS after the walk
   int (*__restrict__ s_sum)[VS_TILE * VS_TILE / 4] = (int (*)[VS_TILE * VS_TILE / 4])s_tri;
@@ -244,7 +129,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
     if (sx >= f * p.W || sy >= f * p.H) continue;
     int col[3] = {p.bg[0], p.bg[1], p.bg[2]};
     const bool cov = best[k] > 0.f;
-    if (cov) rr_shade(p, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, col);
+    if (cov) rr_shade(p.T, p.colors, p.surf, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, col);
     if (f == 1) {
       const size_t at = ((size_t)b * p.H + sy) * p.W + sx;
       p.rgb[3 * at + c0] = (uint8_t)col[0]; p.rgb[3 * at + 1] = (uint8_t)col[1]; p.rgb[3 * at + c2] = (uint8_t)col[2];
@@ -291,12 +176,6 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_finish_kernel(RrParams p) {
   if (p.boxes) vs_box_xywh(h + RR_BOX, live && h[RR_BOX] != INT_MAX, p.boxes + 4 * (size_t)b);
 }
 
-int rr_quant_host(double v) {
-  if (!(v > 0.0)) return 0;
-  const float q = __builtin_rintf(255.0f * (float)v);
-  return q >= 255.f ? 255 : (int)q;
-}
-
 }  // namespace
 
 extern "C" size_t cp_render_rgb_scratch_bytes(int B, int Vmax) {
@@ -327,9 +206,9 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   RrParams p = {};
   p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
   p.M = M; p.mesh_id = mesh_ids; p.colors = colors; p.normals = normals; p.rgb = rgb; p.depth = depth; p.mask = mask; p.boxes = boxes;
-  p.ok = ok; p.B = B; p.Vmax = Vmax; p.H = H; p.W = W; p.f = ssaa; p.shading = shading; p.bgr = bgr ? 1 : 0;
-  p.ambient = (float)ambient_weight;
-  for (int k = 0; k < 3; ++k) { p.surf[k] = (float)surf_color[k]; p.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
+  p.ok = ok; p.B = B; p.Vmax = Vmax; p.H = H; p.W = W; p.f = ssaa; p.T.shading = shading; p.bgr = bgr ? 1 : 0;
+  p.T.ambient = (float)ambient_weight;
+  for (int k = 0; k < 3; ++k) { p.surf[k] = (float)surf_color[k]; p.T.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
   const long long sw = (long long)ssaa * W, sh = (long long)ssaa * H;
   if (sw >= (1LL << 24) || sh >= (1LL << 24) || (long long)H * W >= (1LL << 31) / 3) return CP_ERR_RANGE;
   VsGrid g;
@@ -338,10 +217,10 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   char* at = (char*)scratch;
   const size_t rec = cp_align16_up((size_t)B * Vmax * sizeof(float4));
   p.hdr = (int32_t*)at; at += cp_align16_up((size_t)B * RR_HDR * sizeof(int32_t));
-  p.sv = (float4*)at; at += rec;
-  p.eye = (float4*)at; at += rec;
-  p.vl = (float4*)at; at += rec;
-  p.vn = (float4*)at;
+  p.T.sv = (float4*)at; at += rec;
+  p.T.eye = (float4*)at; at += rec;
+  p.T.vl = (float4*)at; at += rec;
+  p.T.vn = (float4*)at;
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(rgb_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(rgb_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);

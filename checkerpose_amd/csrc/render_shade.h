@@ -1,0 +1,152 @@
+// The shading half that render_rgb.hip (row N14) and vis_poses.hip (row N18) share, on top of vsd_raster.h's scaffold: the pose and
+// vertex records of a shaded render, the shading of one covered sample, and the uint8 quantisation.  The shading rule itself is
+// stated at the top of render_rgb.hip.  The .hip files keep their kernels, params structs and entry points.
+//
+//   RrH, RR_HDR, RR_RT .. RR_SK     the header words of a shaded pose: VsHdr<1> | R t | normal matrix | box | sign(fx fy) | spare
+//   rr_quant, rr_quant_host         round-half-even(255 v) of an fp32 colour value, clamped to 0..255
+//   rr_pose_record                  a pose kernel's body: P = (K scale)' [R | t], [R | t] and the normal matrix in fp32, validity
+//   rr_vertex_record                per vertex, beside the screen record: the eye position, v_L and, for phong, v_normal
+//   RrTables, rr_shade              the shaded, quantised colour of one sample on one face.  The colour source is an argument: the
+//                                   mesh's vertex colours (interpolated), or one surface colour when `colors` is null
+#pragma once
+#include "vsd_raster.h"
+
+namespace {
+
+// 4-byte words per pose: VsHdr<1> (P rect bad ok) | RT[12] | NM[12] = N (3x3) c (3) | box xmin ymin xmax ymax | sign(fx fy) | spare
+using RrH = VsHdr<1>;
+constexpr int RR_HDR = 48;
+constexpr int RR_RT = RrH::USER, RR_NM = RR_RT + 12, RR_BOX = RR_NM + 12, RR_SK = RR_BOX + 4;
+enum { RR_FLAT = 0, RR_PHONG = 1 };
+
+// round-half-even(255 v) of an fp32 colour value, clamped to 0..255 (NaN -> 0)
+__device__ __forceinline__ int rr_quant(float v) {
+#pragma clang fp contract(off)
+  const float q = rintf(255.0f * v);
+  return q >= 255.f ? 255 : (q > 0.f ? (int)q : 0);
+}
+
+inline int rr_quant_host(double v) {
+  if (!(v > 0.0)) return 0;
+  const float q = __builtin_rintf(255.0f * (float)v);
+  return q >= 255.f ? 255 : (int)q;
+}
+
+// The header h of one pose q (12 doubles) under K (9 doubles) scaled by `scale`; mesh_ok: vs_mesh_rows' verdict (and whatever else
+// the caller checked).  Everything but the accumulators' meaning is here: the box starts empty.
+__device__ inline void rr_pose_record(const double* __restrict__ K, const double* __restrict__ q, double scale, bool mesh_ok,
+                                      int32_t* __restrict__ h) {
+#pragma clang fp contract(off)
+  bool ok = mesh_ok && vs_pose_finite(K, q);
+  vs_side_init(K, scale, q, (float*)h + RrH::P(0), h + RrH::RECT(0));      // P = (K f)' [R | t]
+  float* __restrict__ rt = (float*)(h + RR_RT);
+  for (int r = 0; r < 3; ++r) {
+    for (int c = 0; c < 3; ++c) rt[4 * r + c] = (float)q[3 * r + c];
+    rt[4 * r + 3] = (float)q[9 + r];
+  }
+  // u_nm = inverse([R t; 0 1])^T = [R^-T 0; -(R^-1 t)^T 1]: N = R^-T (cofactors / det), c = R^-1 t = N^T t
+  const double c00 = q[4] * q[8] - q[5] * q[7], c01 = q[5] * q[6] - q[3] * q[8], c02 = q[3] * q[7] - q[4] * q[6];
+  const double c10 = q[2] * q[7] - q[1] * q[8], c11 = q[0] * q[8] - q[2] * q[6], c12 = q[1] * q[6] - q[0] * q[7];
+  const double c20 = q[1] * q[5] - q[2] * q[4], c21 = q[2] * q[3] - q[0] * q[5], c22 = q[0] * q[4] - q[1] * q[3];
+  const double det = (q[0] * c00 + q[1] * c01) + q[2] * c02;
+  ok = ok && isfinite(det) && det != 0.0;
+  const double N[9] = {c00 / det, c01 / det, c02 / det, c10 / det, c11 / det, c12 / det, c20 / det, c21 / det, c22 / det};
+  float* __restrict__ nm = (float*)(h + RR_NM);
+  for (int k = 0; k < 9; ++k) nm[k] = (float)N[k];
+  for (int c = 0; c < 3; ++c) nm[9 + c] = (float)((N[c] * q[9] + N[3 + c] * q[10]) + N[6 + c] * q[11]);
+  h[RrH::BAD(0)] = 0;
+  h[RrH::OK] = ok ? 1 : 0;
+  vs_rect_set(h + RR_BOX, INT_MAX, INT_MAX, INT_MIN, INT_MIN);
+  h[RR_SK] = (K[0] > 0.0) == (K[4] > 0.0) ? 1 : -1;
+  h[RR_SK + 1] = 0;
+}
+
+// the per-vertex tables of a shaded render, (poses, Vmax) float4 each, and what the shading needs beside them
+struct RrTables {
+  float4* sv;                 // screen records
+  float4* eye;
+  float4* vl;
+  float4* vn;                 // phong
+  float light[3], ambient;
+  int shading;
+};
+
+// besides the screen record: the eye position, v_L and, for phong, v_normal of vertex vt (its normal: nr) -> row `at` of the tables
+__device__ __forceinline__ void rr_vertex_record(const RrTables& T, const int32_t* __restrict__ h, size_t at, const float* __restrict__ vt,
+                                                 const float* __restrict__ nr) {
+#pragma clang fp contract(off)
+  const float* __restrict__ rt = (const float*)(h + RR_RT);
+  const float ex = vs_affine(rt, vt[0], vt[1], vt[2]), ey = vs_affine(rt + 4, vt[0], vt[1], vt[2]), ez = vs_affine(rt + 8, vt[0], vt[1], vt[2]);
+  T.eye[at] = make_float4(ex, ey, ez, 0.f);
+  const float lx = T.light[0] - ex, ly = T.light[1] - ey, lz = T.light[2] - ez;
+  const float ll = sqrtf((lx * lx + ly * ly) + lz * lz);
+  T.vl[at] = make_float4(lx / ll, ly / ll, lz / ll, 0.f);
+  if (T.shading == RR_PHONG) {
+    const float* __restrict__ nm = (const float*)(h + RR_NM);
+    const float nx = fmaf(nm[2], nr[2], fmaf(nm[1], nr[1], nm[0] * nr[0]));
+    const float ny = fmaf(nm[5], nr[2], fmaf(nm[4], nr[1], nm[3] * nr[0]));
+    const float nz = fmaf(nm[8], nr[2], fmaf(nm[7], nr[1], nm[6] * nr[0]));
+    const float nw = 1.0f - fmaf(nm[11], nr[2], fmaf(nm[10], nr[1], nm[9] * nr[0]));
+    const float nl = sqrtf(((nx * nx + ny * ny) + nz * nz) + nw * nw);    // the shader's 4-vector length
+    T.vn[at] = make_float4(nx / nl, ny / nl, nz / nl, 0.f);
+  }
+}
+
+__device__ __forceinline__ float rr_mix(float w0, float w1, float w2, float a, float c, float d) {
+#pragma clang fp contract(off)
+  return (w0 * a + w1 * c) + w2 * d;
+}
+
+// the same interpolation with w0 = 1 - w1 - w2 implied: three equal values give that value EXACTLY (a mesh of one colour, the 0.5
+// grey a mesh without colours gets inside a coloured MeshSet), whatever the weights' rounded sum is
+__device__ __forceinline__ float rr_mix_col(float w1, float w2, float a, float c, float d) {
+#pragma clang fp contract(off)
+  return a + (w1 * (c - a) + w2 * (d - a));
+}
+
+// the shaded, quantised colour of the sample (qx, qy) (tile-relative indices) on face fidx; the colour is `colors` (rows from cbase,
+// interpolated) or, with colors == nullptr, the one colour `surf`
+__device__ __forceinline__ void rr_shade(const RrTables& T, const float* __restrict__ colors, const float (&surf)[3],
+                                         const int32_t* __restrict__ h, const int32_t* __restrict__ faces, size_t vbase, size_t cbase,
+                                         int fidx, float fx0, float fy0, float qx, float qy, int (&out)[3]) {
+#pragma clang fp contract(off)
+  const int32_t* __restrict__ fi = faces + 3 * (size_t)fidx;
+  const int i0 = fi[0], i1 = fi[1], i2 = fi[2];
+  const float4 a = T.sv[vbase + i0], c = T.sv[vbase + i1], d = T.sv[vbase + i2];
+  const float ax = a.x - fx0, ay = a.y - fy0, cx = c.x - fx0, cy = c.y - fy0, dx = d.x - fx0, dy = d.y - fy0;
+  const float area = (cx - ax) * (dy - ay) - (dx - ax) * (cy - ay);   // (the walk's expression: the same bits, never 0 here)
+  // edge i is opposite vertex i, differences first; perspective-correct weights w_i = E_i / Z_i / sum_j E_j / Z_j
+  const float e0 = (dx - cx) * (qy - cy) - (dy - cy) * (qx - cx);
+  const float e1 = (ax - dx) * (qy - dy) - (ay - dy) * (qx - dx);
+  const float e2 = (cx - ax) * (qy - ay) - (cy - ay) * (qx - ax);
+  const float p0 = e0 * a.w, p1 = e1 * c.w, p2 = e2 * d.w;
+  const float ps = (p0 + p1) + p2;
+  const float w0 = p0 / ps, w1 = p1 / ps, w2 = p2 / ps;
+  const float4 la = T.vl[vbase + i0], lc = T.vl[vbase + i1], ld = T.vl[vbase + i2];
+  const float lx = rr_mix(w0, w1, w2, la.x, lc.x, ld.x), ly = rr_mix(w0, w1, w2, la.y, lc.y, ld.y), lz = rr_mix(w0, w1, w2, la.z, lc.z, ld.z);
+  float nx, ny, nz;
+  if (T.shading == RR_PHONG) {
+    const float4 na = T.vn[vbase + i0], nc = T.vn[vbase + i1], nd = T.vn[vbase + i2];
+    nx = rr_mix(w0, w1, w2, na.x, nc.x, nd.x); ny = rr_mix(w0, w1, w2, na.y, nc.y, nd.y); nz = rr_mix(w0, w1, w2, na.z, nc.z, nd.z);
+  } else {
+    const float4 ea = T.eye[vbase + i0], ec = T.eye[vbase + i1], ed = T.eye[vbase + i2];
+    const float ux = ec.x - ea.x, uy = ec.y - ea.y, uz = ec.z - ea.z, vx = ed.x - ea.x, vy = ed.y - ea.y, vz = ed.z - ea.z;
+    nx = uy * vz - uz * vy; ny = uz * vx - ux * vz; nz = ux * vy - uy * vx;
+    // n . eye_a = det[eye_a eye_c eye_d] has the sign of (screen area) * sign(fx fy): towards the viewer means n . eye < 0
+    if ((area > 0.f) == (h[RR_SK] > 0)) { nx = -nx; ny = -ny; nz = -nz; }
+  }
+  const float ll = sqrtf((lx * lx + ly * ly) + lz * lz), nl = sqrtf((nx * nx + ny * ny) + nz * nz);
+  const float dt = ((lx * nx + ly * ny) + lz * nz) / (ll * nl);
+  float lw = T.ambient + (dt > 0.f ? dt : 0.f);                        // (NaN from a zero-length vector: no diffuse term)
+  if (lw > 1.0f) lw = 1.0f;
+  float r = surf[0], g = surf[1], bl = surf[2];
+  if (colors) {
+    const float* __restrict__ ca = colors + 3 * (cbase + i0);
+    const float* __restrict__ cc = colors + 3 * (cbase + i1);
+    const float* __restrict__ cd = colors + 3 * (cbase + i2);
+    r = rr_mix_col(w1, w2, ca[0], cc[0], cd[0]); g = rr_mix_col(w1, w2, ca[1], cc[1], cd[1]); bl = rr_mix_col(w1, w2, ca[2], cc[2], cd[2]);
+  }
+  out[0] = rr_quant(lw * r); out[1] = rr_quant(lw * g); out[2] = rr_quant(lw * bl);
+}
+
+}  // namespace

@@ -756,6 +756,48 @@ int cp_render_rgb(cp_stream_t stream, const double* poses, const double* cam_K, 
                   double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B, int Vmax,
                   uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch);
 
+/* Poses drawn over the photograph on the device (next-row N18; csrc/vis_poses.hip; reference bop_toolkit_lib/visualization.py:90-235
+ * vis_object_poses as scripts/vis_est_poses.py and vis_gt_poses.py drive it, text excluded): for I images and P poses at once,
+ * the composite of every image's poses, their 2-D boxes, and the half-and-half blend with the frame.
+ * Per image, poses in the order given: m_rgb / m_depth of a pose are cp_render_rgb's (ssaa 1, background 0 0 0) of that pose alone, bit
+ * for bit, with the pose's row of surf_colors fp64 (P,3) (NULL: the mesh's colours, 0.5 grey without any);  ren_rgb = 0, ren_depth = 0;
+ *   m = m_depth != 0 and (ren_depth == 0 or m_depth < ren_depth) on the fp32 depths (strict: the earlier of two equal depths stays);
+ *   ren_depth[m] = m_depth;  resolve 1: ren_rgb[m] = m_rgb;  resolve 0: ren_rgb = min(255, ren_rgb + m_rgb) as integers;
+ *   boxes int32 (P,4) = x, y, xmax - xmin, ymax - ymin over the pixels where ANY channel of m_rgb is > 0 (a black surface occludes
+ *   but has no box), -1 four times without any;  with draw_boxes 1 a pixel on the one-pixel outline through (x, y), (x + w, y + h) of
+ *   any box of its image adds int(c * 255) of box_color (3 doubles ON THE HOST, as light_pos: cp_render_rgb's);
+ *   vis uint8 (I,H,W,3) = min(255, (frames + ren_rgb) / 2 + outline) as integers;  ren_rgb uint8 (I,H,W,3), ren_depth fp32 (I,H,W).
+ *   ok uint8 (P): 0 for a pose that is not rendered (cp_render_rgb's rule, an image id outside [0, I), a non-finite surface colour):
+ *   it is skipped, its box is -1.
+ * cam_K fp64 (9) shared (k_stride 0) or (I,9) PER IMAGE (k_stride 9); image_of_pose int32 (P); the CSR img_off int32 (I+1) /
+ * pose_order int32 (P) -- the poses of image i in drawing order -- on the device AND, the same values, in host memory
+ * (img_off_host, pose_order_host: checked before anything is launched -- img_off[0] == 0, monotone, img_off[I] == P, every entry of
+ * pose_order in [0, P): CP_ERR_INVALID otherwise).  The other mesh arguments, shading, ambient_weight: as cp_render_rgb.
+ * Four launches whatever the data (pose, vertex, scene tile: a workgroup per (image, 32 x 32 tile) that keeps the per-pose frames in
+ * registers, finish: per pixel); integer reductions only; every output is bit-identical from call to call, for an image alone or in
+ * a batch.  Nothing allocates or synchronises.  CP_ERR_RANGE: 2^24 workgroups or more in a launch, or I * H * W * 3 >= 2^31.
+ * scratch: cp_vis_poses_scratch_bytes(P, Vmax, I) bytes (cp_render_rgb's layout for P poses), 16-byte aligned.
+ * cp_depth_diff_vis (visualization.py:206-235, depth_for_vis :76-88): for I renders ren_depth fp32 (I,H,W) against sensor depths depth
+ * fp32 (n_depth,H,W), image_ids int32 (I) naming each render's (NULL: image i when n_depth == I, image 0 when n_depth == 1):
+ *   valid = depth > 0 and ren_depth > 0;  dd = valid ? ren_depth - depth : 0 (fp32);  red = 255 where valid and dd < (float)delta;
+ *   m0 = min dd over ALL pixels;  x = dd - m0 (fp32);  over x > 0, in fp64: n = (x - mn) / (mx / s) + 0.2 with mn = min x,
+ *   mx = max (x - mn), s = the caller's 1.0 - 0.2;  green = blue = (uint8)(255 n);  everything 0 where not valid.
+ *   out uint8 (I,H,W,3);  stats fp64 (I,3) = min, max, mean of dd over the valid pixels (NaN without any; the mean is a fixed-order
+ *   fp64 sum);  diff_ok uint8 (I): 0 when dd holds fewer than three distinct values (the reference raises or divides 0 by 0): zeros.
+ * Five launches; minima and maxima through order-preserving integer keys and integer atomics, no floating-point atomics.
+ * scratch: cp_depth_diff_vis_scratch_bytes(I, H, W) bytes, 16-byte aligned. */
+size_t cp_vis_poses_scratch_bytes(int P, int Vmax, int I);
+int cp_vis_poses(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                 const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                 const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                 const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host, const int32_t* pose_order_host,
+                 const uint8_t* frames, int shading, double ambient_weight, const double* light_pos, const double* box_color,
+                 int resolve, int draw_boxes, int H, int W, int P, int I, int Vmax, uint8_t* vis, uint8_t* ren_rgb, float* ren_depth,
+                 int32_t* boxes, uint8_t* ok, void* scratch);
+size_t cp_depth_diff_vis_scratch_bytes(int I, int H, int W);
+int cp_depth_diff_vis(cp_stream_t stream, const float* ren_depth, const float* depth, const int32_t* image_ids, int n_depth,
+                      double delta, double s, int H, int W, int I, uint8_t* out, double* stats, uint8_t* diff_ok, void* scratch);
+
 /* BOP's overlap errors on the device (next-row N12; csrc/mask_error.hip; reference bop_toolkit_lib/pose_error.py:235-330 cou_mask, cus,
  * cou_bb, cou_bb_proj with misc.calc_2d_bbox / misc.iou, misc.py:202-263): the four functions that close pose_error.py.
  * cp_mask_errors: for B pairs (estimate, ground truth) of one mesh each under one K, on a W x H frame,
