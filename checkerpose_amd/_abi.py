@@ -365,6 +365,22 @@ def check(code, what=""):
         raise RuntimeError("checkerpose_hip %s failed: %s (code %d)" % (what, msg, code))
 
 
+def marshal(args):
+    """the arguments of a C entry point as ctypes takes them: None -> a null pointer, a tensor -> its data_ptr(), everything else
+    (ints, floats, ctypes arrays and pointers) as it is"""
+    return [a.data_ptr() if hasattr(a, "data_ptr") else a for a in args]
+
+
+def call(name, dev, *args):
+    """The launch epilogue: entry point `name` on the current stream of `dev` (prepended to the marshalled `args`), run with `dev`
+    as the current device; a non-zero return code raises (check).  torch is given the device's index, not the torch.device: it
+    resolves an index several times faster, and None (a bare "cuda") means the current device to both of its calls."""
+    import torch
+    fn, idx = getattr(load(), name), dev.index
+    with torch.cuda.device(idx):
+        check(fn(torch.cuda.current_stream(idx).cuda_stream, *marshal(args)), name)
+
+
 def device_table(items, blocks, device):
     """The device-side form of a grouped launch: `items` (ctypes structs of ONE type, the kernels' parameter blocks) as a byte tensor
     on `device` plus the exclusive prefix sum (len(items) + 1 uint32 entries) of `blocks` (workgroups per item) -- block b of the launch

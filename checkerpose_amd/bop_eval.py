@@ -23,17 +23,13 @@ rendering, and writing matches_*.json."""
 import numpy as np
 import torch
 
-from . import _abi
-from . import metric
+from . import _abi, metric, scene
 
 ERROR_KINDS = ("add", "adi", "ad", "mssd", "mspd", "proj", "vsd", "cus")
 
 
 def _dev(device):
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("checkerpose_amd.bop_eval: a CUDA/HIP device is required (no CPU fallback)")
-    return dev
+    return scene.cuda_device("bop_eval", device)
 
 
 def _i32(a, dev):
@@ -250,7 +246,7 @@ def calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=None, symmetr
     dev = _dev(es.device)
     P = int(pairs.pair_est.shape[0])
     if P == 0:
-        return torch.zeros((0, 1 if kind != "vsd" else len(metric._vsd_taus(taus)[0])), dtype=torch.float64, device=dev)
+        return torch.zeros((0, 1 if kind != "vsd" else len(metric.vsd_taus(taus)[0])), dtype=torch.float64, device=dev)
     src = pairs.est_src[pairs.pair_est]
     Re, te = _poses_of(ests, src, dev)
     tabs = es.on_device()
@@ -341,7 +337,6 @@ def _launch_match(dev, errs, est_score, est_ids, est_off, gt_off, pair_off, gt_r
     mask_off = np.where(on_scratch, np.cumsum(words) - words, -1)
     mask_words = int(words.sum())
     flags = (_abi.BOP_MATCH_NO_LDS if _stage == "global" else 0) | (_abi.BOP_MATCH_SCRATCH_MASK if _mask == "scratch" else 0)
-    lib = _abi.load()
     f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)     # noqa: E731
     t_score, t_ids, t_eoff, t_goff = f64(est_score), _i32(est_ids, dev), _i32(est_off, dev), _i32(gt_off, dev)
     t_poff = torch.from_numpy(np.ascontiguousarray(pair_off, dtype=np.int64)).to(dev)
@@ -352,15 +347,11 @@ def _launch_match(dev, errs, est_score, est_ids, est_off, gt_off, pair_off, gt_r
     out = {"est_id": torch.empty((NG, C), dtype=torch.int32, device=dev), "score": torch.empty((NG, C), dtype=torch.float64, device=dev),
            "error": torch.empty((NG, C, E), dtype=torch.float64, device=dev),
            "error_norm": torch.empty((NG, C, E), dtype=torch.float64, device=dev)}
-    scratch = torch.empty(lib.cp_bop_match_scratch_bytes(NE, mask_words, C), dtype=torch.uint8, device=dev)
-    ptr = lambda x: None if x is None or x.numel() == 0 else x.data_ptr()     # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_bop_match(st, ptr(errs), P, C_err, ptr(t_score), ptr(t_ids), NE, t_eoff.data_ptr(), t_goff.data_ptr(),
-                                    t_poff.data_ptr(), G, ptr(t_rows), ptr(t_valid), NG, t_cols.data_ptr(), t_th.data_ptr(), C, E,
-                                    int(max_ests), t_moff.data_ptr(), mask_words, flags, out["est_id"].data_ptr(),
-                                    out["score"].data_ptr(), out["error"].data_ptr(), out["error_norm"].data_ptr(), scratch.data_ptr()),
-                   "cp_bop_match")
+    scratch = torch.empty(_abi.load().cp_bop_match_scratch_bytes(NE, mask_words, C), dtype=torch.uint8, device=dev)
+    nz = lambda x: None if x is None or x.numel() == 0 else x     # noqa: E731  (an empty table goes in as a null pointer)
+    _abi.call("cp_bop_match", dev, nz(errs), P, C_err, nz(t_score), nz(t_ids), NE, t_eoff, t_goff, t_poff, G, nz(t_rows), nz(t_valid), NG,
+              t_cols, t_th, C, E, int(max_ests), t_moff, mask_words, flags, out["est_id"], out["score"], out["error"], out["error_norm"],
+              scratch)
     out["thresholds"] = th
     return out
 
@@ -397,7 +388,6 @@ def _launch_scores(dev, est_id, valid, gt_obj_index, gt_scene_index, gt_off, gt_
     NG, C = int(est_id.shape[0]), int(est_id.shape[1])
     G = int(gt_off.shape[0]) - 1
     NB = 1 + n_obj + n_scene
-    lib = _abi.load()
     counts = torch.empty((NB * (1 + C),), dtype=torch.int32, device=dev)
     t_valid = None if valid is None else (valid.to(device=dev, dtype=torch.uint8).contiguous() if torch.is_tensor(valid)
                                           else torch.from_numpy(np.ascontiguousarray(valid, dtype=np.uint8)).to(dev))
@@ -405,12 +395,8 @@ def _launch_scores(dev, est_id, valid, gt_obj_index, gt_scene_index, gt_off, gt_
     t_obj, t_scene, t_off = as32(gt_obj_index), as32(gt_scene_index), as32(gt_off)
     t_rows = None if gt_rows is None else as32(gt_rows)
     est_id = est_id.contiguous()
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_bop_scores(st, est_id.data_ptr(), None if t_valid is None else t_valid.data_ptr(), t_obj.data_ptr(),
-                                     t_scene.data_ptr(), NG, t_off.data_ptr(), None if t_rows is None else t_rows.data_ptr(), G, C,
-                                     n_obj, n_scene, int(n_top), _abi.BOP_SCORES_NO_LDS if _bins == "global" else 0,
-                                     counts.data_ptr()), "cp_bop_scores")
+    _abi.call("cp_bop_scores", dev, est_id, t_valid, t_obj, t_scene, NG, t_off, t_rows, G, C, n_obj, n_scene, int(n_top),
+              _abi.BOP_SCORES_NO_LDS if _bins == "global" else 0, counts)
     c = counts.cpu().numpy().astype(np.int64)
     return c[:NB], c[NB:].reshape(NB, C)
 

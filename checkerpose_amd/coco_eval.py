@@ -19,7 +19,7 @@ import json
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, scene
 
 T, R, A, M, KEEP = 10, 101, 4, 3, 100
 MAX_DETS = (1, 10, 100)
@@ -35,16 +35,11 @@ def rec_thrs():
     return np.linspace(0, 1, 101)
 
 
-def _ptr(x):
-    return None if x is None else x.data_ptr()
-
-
 def _as_masks(masks, dev=None):
     m = masks if torch.is_tensor(masks) else torch.as_tensor(np.asarray(masks))
     if dev is not None:
         m = m.to(dev)
-    if not m.is_cuda:
-        raise RuntimeError("checkerpose_amd.coco_eval: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("coco_eval", m)
     if m.dim() == 2:
         m = m[None]
     if m.dim() != 3 or 0 in m.shape:
@@ -81,9 +76,7 @@ def pack_masks(masks, device=None):
     bits = torch.empty((N, H, (W + 31) // 32), dtype=torch.int32, device=dev)
     area = torch.empty((N,), dtype=torch.int32, device=dev)
     box = torch.empty((N, 4), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        _abi.check(_abi.load().cp_coco_pack(torch.cuda.current_stream(dev).cuda_stream, m.data_ptr(), N, H, W, bits.data_ptr(),
-                                            area.data_ptr(), box.data_ptr()), "cp_coco_pack")
+    _abi.call("cp_coco_pack", dev, m, N, H, W, bits, area, box)
     return PackedMasks(bits, area, box, H, W)
 
 
@@ -91,17 +84,13 @@ def rle_encode(packed):
     """pycoco_utils.binary_mask_to_rle of every packed mask -> (counts int32 (total,), offsets int64 (N + 1,)) on the device: mask n's
     run lengths are counts[offsets[n]:offsets[n + 1]]"""
     N, dev = len(packed), packed.device
-    lib = _abi.load()
     n_runs = torch.empty((N,), dtype=torch.int32, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_coco_rle_count(st, packed.bits.data_ptr(), N, packed.H, packed.W, n_runs.data_ptr()), "cp_coco_rle_count")
-        offsets = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
-        offsets[1:] = torch.cumsum(n_runs, 0)
-        total = int(offsets[-1])
-        counts = torch.empty((total,), dtype=torch.int32, device=dev)
-        _abi.check(lib.cp_coco_rle_write(st, packed.bits.data_ptr(), N, packed.H, packed.W, offsets.data_ptr(), counts.data_ptr(), total),
-                   "cp_coco_rle_write")
+    _abi.call("cp_coco_rle_count", dev, packed.bits, N, packed.H, packed.W, n_runs)
+    offsets = torch.zeros((N + 1,), dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(n_runs, 0)
+    total = int(offsets[-1])
+    counts = torch.empty((total,), dtype=torch.int32, device=dev)
+    _abi.call("cp_coco_rle_write", dev, packed.bits, N, packed.H, packed.W, offsets, counts, total)
     return counts, offsets
 
 
@@ -194,18 +183,14 @@ def mask_ious(dets, gts, pairs):
     out = torch.empty((P,), dtype=torch.float64, device=dev)
     if P == 0:
         return out
-    with torch.cuda.device(dev):
-        _abi.check(_abi.load().cp_coco_mask_iou(torch.cuda.current_stream(dev).cuda_stream, d.bits.data_ptr(), d.area.data_ptr(),
-                                                d.box.data_ptr(), len(d), g.bits.data_ptr(), g.area.data_ptr(), g.box.data_ptr(), len(g),
-                                                d.H, d.W, p.data_ptr(), P, out.data_ptr()), "cp_coco_mask_iou")
+    _abi.call("cp_coco_mask_iou", dev, d.bits, d.area, d.box, len(d), g.bits, g.area, g.box, len(g), d.H, d.W, p, P, out)
     return out
 
 
 def _boxes(b, dev=None):
     t = torch.as_tensor(b)
     t = t.to(device=dev if dev is not None else t.device, dtype=torch.float64).reshape(-1, 4).contiguous()
-    if not t.is_cuda:
-        raise RuntimeError("checkerpose_amd.coco_eval: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("coco_eval", t)
     return t
 
 
@@ -219,9 +204,7 @@ def box_ious(dets, gts, pairs):
     out = torch.empty((P,), dtype=torch.float64, device=dev)
     if P == 0:
         return out
-    with torch.cuda.device(dev):
-        _abi.check(_abi.load().cp_coco_box_iou(torch.cuda.current_stream(dev).cuda_stream, d.data_ptr(), int(d.shape[0]), g.data_ptr(),
-                                               int(g.shape[0]), p.data_ptr(), P, out.data_ptr()), "cp_coco_box_iou")
+    _abi.call("cp_coco_box_iou", dev, d, int(d.shape[0]), g, int(g.shape[0]), p, P, out)
     return out
 
 
@@ -348,8 +331,7 @@ def evaluate(cocoset, dets, ann_type="segm", return_tables=False):
     if ann_type not in ("segm", "bbox"):
         raise ValueError("ann_type must be 'segm' or 'bbox', got %r" % (ann_type,))
     cs, dev = cocoset, cocoset.device
-    if dev.type != "cuda":
-        raise RuntimeError("checkerpose_amd.coco_eval: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("coco_eval", device=dev)
     K = len(cs.category_ids)
     if K == 0:
         raise ValueError("the set has no categories")
@@ -393,16 +375,12 @@ def evaluate(cocoset, dets, ann_type="segm", return_tables=False):
     recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
     rank, order = i32(plan["det_rank"]).to(dev), i32(plan["order"]).to(dev)
     max_dets = i32(np.asarray(MAX_DETS))
-    nz = lambda t: _ptr(t) if t.numel() else None      # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        if n_groups:
-            _abi.check(lib.cp_coco_match(st, nz(ious), moff_h.data_ptr(), moff_d.data_ptr(), n_groups, ND, NG, P, nz(det_area), nz(gt_area),
-                                         nz(gt_flag), thrs.data_ptr(), rng.data_ptr(), nz(dt_match), nz(dt_ignore), nz(gt_ignore),
-                                         scratch.data_ptr() if NG else None), "cp_coco_match")
-        _abi.check(lib.cp_coco_accumulate(st, nz(dt_match), nz(dt_ignore), nz(gt_ignore), nz(rank), nz(order), aoff_h.data_ptr(),
-                                          aoff_d.data_ptr(), K, ND, NG, max_dets.data_ptr(), recs.data_ptr(), precision.data_ptr(),
-                                          recall.data_ptr()), "cp_coco_accumulate")
+    nz = lambda t: t if t.numel() else None      # noqa: E731  (an empty table goes in as a null pointer)
+    if n_groups:
+        _abi.call("cp_coco_match", dev, nz(ious), moff_h, moff_d, n_groups, ND, NG, P, nz(det_area), nz(gt_area), nz(gt_flag), thrs, rng,
+                  nz(dt_match), nz(dt_ignore), nz(gt_ignore), scratch if NG else None)
+    _abi.call("cp_coco_accumulate", dev, nz(dt_match), nz(dt_ignore), nz(gt_ignore), nz(rank), nz(order), aoff_h, aoff_d, K, ND, NG,
+              max_dets, recs, precision, recall)
     out = {"precision": precision.cpu().numpy(), "recall": recall.cpu().numpy()}
     out.update(summarize(out["precision"], out["recall"]))
     if return_tables:

@@ -3,7 +3,8 @@
 What bop_toolkit's scripts/calc_gt_info.py and scripts/calc_gt_masks.py write for every ground-truth pose of a scene -- the pixel
 counts, visib_fract, bbox_obj, bbox_visib of scene_gt_info.json and the mask / mask_visib images -- computed for a batch of poses
 in one call.  The reference renders each pose through OpenGL on a 3W x 3H canvas and makes full-frame numpy passes; here the
-canvas is rendered tile by tile by metric.render_depth's rasteriser and counted in the same kernel.
+canvas is rendered tile by tile by metric.render_depth's rasteriser and counted in the same kernel.  Poses, camera, mesh and image ids
+are handled by checkerpose_amd/scene.py, as for metric.vsd_errors.
 
   gt_info(...)              poses + meshes + sensor depth -> counts, fraction, boxes (+ masks, + the in-frame render)
   gt_info_from_depth(...)   the same counting on a caller's canvas render (B,3H,3W)
@@ -18,15 +19,25 @@ import json
 import numpy as np
 import torch
 
-from . import _abi
-from .metric import _vsd_common, _vsd_images
+from . import _abi, scene
 
 KEYS = ("px_count_all", "px_count_valid", "px_count_visib", "visib_fract", "bbox_obj", "bbox_visib")
 
 
-def _result(counts, fract, boxes, ok):
-    return {"px_count_all": counts[:, 0], "px_count_valid": counts[:, 1], "px_count_visib": counts[:, 2], "visib_fract": fract,
-            "bbox_obj": boxes[:, 0], "bbox_visib": boxes[:, 1], "ok": ok.to(torch.bool)}
+def _outputs(B, H, W, dev, return_masks):
+    """the output tensors both entry points fill: counts, fraction, boxes, ok (+ the two masks)"""
+    u8 = lambda *shape: torch.empty(shape, dtype=torch.uint8, device=dev)      # noqa: E731
+    return (torch.empty((B, 3), dtype=torch.int32, device=dev), torch.empty((B,), dtype=torch.float64, device=dev),
+            torch.empty((B, 2, 4), dtype=torch.int32, device=dev), u8(B), u8(B, H, W) if return_masks else None,
+            u8(B, H, W) if return_masks else None)
+
+
+def _result(counts, fract, boxes, ok, mask, visib):
+    out = {"px_count_all": counts[:, 0], "px_count_valid": counts[:, 1], "px_count_visib": counts[:, 2], "visib_fract": fract,
+           "bbox_obj": boxes[:, 0], "bbox_visib": boxes[:, 1], "ok": ok.to(torch.bool)}
+    if mask is not None:
+        out["mask"], out["mask_visib"] = mask, visib
+    return out
 
 
 def gt_info(R, t, cam_K, meshes, depth, image_ids=None, mesh_ids=None, delta=15.0, return_masks=False, return_depth=False):
@@ -34,7 +45,7 @@ def gt_info(R, t, cam_K, meshes, depth, image_ids=None, mesh_ids=None, delta=15.
       R, t: (B,3,3) / (B,3,1) CUDA tensors; cam_K: (3,3) or (B,3,3); meshes: a MeshSet built with faces (with several meshes, mesh_ids
       (B,) names each pose's); depth: (H,W) or (I,H,W) sensor depth in the vertices' units (mm; 0 = no measurement), image_ids (B,)
       names each pose's image (default: the one image, or image b for pose b when I == B); delta: the visibility tolerance (15 mm;
-      5 for itodd) -- the argument handling is metric.vsd_errors'.
+      5 for itodd) -- the argument handling is metric.vsd_errors' (scene.py).
     -> dict of CUDA tensors: px_count_all (the silhouette on the 3W x 3H canvas, truncated part included), px_count_valid,
     px_count_visib int32 (B,); visib_fract float64 (B,); bbox_obj (the canvas silhouette in frame coordinates, not clipped: may be
     negative or exceed the frame), bbox_visib int32 (B,4) = x, y, xmax - xmin, ymax - ymin, BOTH -1 unless px_count_visib > 0;
@@ -43,30 +54,19 @@ def gt_info(R, t, cam_K, meshes, depth, image_ids=None, mesh_ids=None, delta=15.
     mask files' content);  with return_depth "depth" float32 (B,H,W), the in-frame render -- the same bits as metric.render_depth
     at (W,H).  The other outputs are the same bits with or without the images.
     mask_visib, mask and bbox_visib are what targets.make_training_batch takes as masks_visib, masks_full and Bboxes."""
-    dev, poses, B, K, k_stride, M, ids, vmax = _vsd_common(R, t, cam_K, meshes, mesh_ids)
-    d, img, n_img = _vsd_images(depth, image_ids, B, dev)
+    dev, poses, B = scene.mesh_poses(R, t, meshes)
+    K, k_stride = scene.camera(cam_K, B, dev)
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, meshes.sizes)
+    d, img, n_img = scene.depth_images(depth, image_ids, B, dev)
     H, W = int(d.shape[1]), int(d.shape[2])
     verts, v_off = meshes.on(dev)
     faces, f_off, _ = meshes.faces_on(dev)
-    lib = _abi.load()
-    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    fract = torch.empty((B,), dtype=torch.float64, device=dev)
-    boxes = torch.empty((B, 2, 4), dtype=torch.int32, device=dev)
-    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
-    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_masks else None
-    visib = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_masks else None
+    counts, fract, boxes, ok, mask, visib = _outputs(B, H, W, dev, return_masks)
     render = torch.empty((B, H, W), dtype=torch.float32, device=dev) if return_depth else None
-    scratch = torch.empty(lib.cp_gt_info_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
-    ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_gt_info(st, poses.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(), faces.data_ptr(),
-                                  f_off.data_ptr(), M, ptr(ids), d.data_ptr(), ptr(img), n_img, H, W, float(delta), B, vmax,
-                                  counts.data_ptr(), fract.data_ptr(), boxes.data_ptr(), ok.data_ptr(), ptr(mask), ptr(visib), ptr(render),
-                                  scratch.data_ptr()), "cp_gt_info")
-    out = _result(counts, fract, boxes, ok)
-    if return_masks:
-        out["mask"], out["mask_visib"] = mask, visib
+    scratch = torch.empty(_abi.load().cp_gt_info_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
+    _abi.call("cp_gt_info", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, d, img, n_img, H, W, float(delta), B, vmax,
+              counts, fract, boxes, ok, mask, visib, render, scratch)
+    out = _result(counts, fract, boxes, ok, mask, visib)
     if return_depth:
         out["depth"] = render
     return out
@@ -76,42 +76,22 @@ def gt_info_from_depth(depth_gt_large, depth, cam_K, image_ids=None, delta=15.0,
     """gt_info's counting on caller-supplied canvas renders (cp_gt_info_from_depth): depth_gt_large (B,3H,3W) float32 CUDA tensor, the
     object on the 3W x 3H canvas with the principal point moved by (W, H) -- frame pixel (x, y) is [y + H, x + W]; depth: (H,W) or
     (I,H,W) sensor depth.  -> gt_info's dict (ok is False only for a non-finite K or a device-side image id out of range)."""
-    if not (torch.is_tensor(depth_gt_large) and depth_gt_large.is_cuda):
-        raise RuntimeError("checkerpose_amd.gt_info: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("gt_info", depth_gt_large)
     if depth_gt_large.dim() != 3 or depth_gt_large.shape[0] == 0:
         raise ValueError("depth_gt_large must be (B,3H,3W) with B >= 1, got %r" % (tuple(depth_gt_large.shape),))
     dev = depth_gt_large.device
     large = depth_gt_large.to(torch.float32).contiguous()
     B = int(large.shape[0])
-    d, img, n_img = _vsd_images(depth, image_ids, B, dev)
+    d, img, n_img = scene.depth_images(depth, image_ids, B, dev)
     H, W = int(d.shape[1]), int(d.shape[2])
     if tuple(large.shape[1:]) != (3 * H, 3 * W):
         raise ValueError("depth is %r, so depth_gt_large must be %r; got %r" % ((H, W), (3 * H, 3 * W), tuple(large.shape[1:])))
-    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
-    if tuple(K.shape) == (3, 3):
-        K, k_stride = K.reshape(9).contiguous(), 0
-    elif tuple(K.shape) == (B, 3, 3):
-        K, k_stride = K.reshape(B, 9).contiguous(), 9
-    else:
-        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
-    lib = _abi.load()
-    counts = torch.empty((B, 3), dtype=torch.int32, device=dev)
-    fract = torch.empty((B,), dtype=torch.float64, device=dev)
-    boxes = torch.empty((B, 2, 4), dtype=torch.int32, device=dev)
-    ok = torch.empty((B,), dtype=torch.uint8, device=dev)
-    mask = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_masks else None
-    visib = torch.empty((B, H, W), dtype=torch.uint8, device=dev) if return_masks else None
-    scratch = torch.empty(lib.cp_gt_info_scratch_bytes(B, 0), dtype=torch.uint8, device=dev)
-    ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_gt_info_from_depth(st, large.data_ptr(), K.data_ptr(), k_stride, d.data_ptr(), ptr(img), n_img, H, W, float(delta),
-                                             B, counts.data_ptr(), fract.data_ptr(), boxes.data_ptr(), ok.data_ptr(), ptr(mask), ptr(visib),
-                                             scratch.data_ptr()), "cp_gt_info_from_depth")
-    out = _result(counts, fract, boxes, ok)
-    if return_masks:
-        out["mask"], out["mask_visib"] = mask, visib
-    return out
+    K, k_stride = scene.camera(cam_K, B, dev)
+    counts, fract, boxes, ok, mask, visib = _outputs(B, H, W, dev, return_masks)
+    scratch = torch.empty(_abi.load().cp_gt_info_scratch_bytes(B, 0), dtype=torch.uint8, device=dev)
+    _abi.call("cp_gt_info_from_depth", dev, large, K, k_stride, d, img, n_img, H, W, float(delta), B, counts, fract, boxes, ok, mask, visib,
+              scratch)
+    return _result(counts, fract, boxes, ok, mask, visib)
 
 
 def scene_gt_info(scene_gt, scene_camera, depths, meshes, obj_index, delta=15.0, device="cuda:0", return_masks=False, _call=None):

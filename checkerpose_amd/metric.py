@@ -3,200 +3,29 @@ scripts (test.py:378-427, test_lm.py:300-321, compute_auc_posecnn test.py:37-57)
 
   pose_errors(...)                       batched ADD / ADD-S (ADI) on device tensors -- takes what solve_pnp_ransac returns
   Calculate_ADD_Error_BOP / _ADI_        the reference's names and numpy-in, float-out signatures (one pose; B = 1 of the above)
-  MeshSet                                the packed vertex table of several objects, uploaded once, with their diameters
   compute_auc_posecnn, summarize         pass rates at 2 / 5 / 10 % of the diameter and the PoseCNN AUC (host: one float per image)
-  bop_errors, mssd / mspd / proj, SymmetrySet, bop_recall, summarize_bop      BOP's MSSD / MSPD / projection error (row N7): below
-  vsd_errors, vsd, render_depth, vsd_from_depth                               BOP's VSD with its depth rasteriser (row N8): below
+  bop_errors, mssd / mspd / proj, bop_recall, summarize_bop                   BOP's MSSD / MSPD / projection error (row N7): below
+  vsd_errors, vsd, render_depth, vsd_from_depth, vsd_taus                     BOP's VSD with its depth rasteriser (row N8): below
   mask_errors, mask_overlap, box_overlap, cus / cou_bb_proj / cou_mask / cou_bb   BOP's overlap errors (row N12): at the end
+
+This module holds the error functions, the recall and summary functions and the one-pose wrappers under the reference's names.  The
+containers (MeshSet, SymmetrySet, symmetry_transformations, the host calc_pts_diameter) live in checkerpose_amd/scene.py and are
+importable from here as before; the handling of poses, camera, mesh / image ids, frame size and kinds is scene's too, and every
+launch goes through _abi.call.
 
 ADI is an all-pairs search: V^2 distance evaluations per pose and no spatial index.  Measured on one MI355X (tools/pose_error_bench.py,
 profiles/pose_error_bench.json): one pose takes 0.16 / 0.36 / 1.44 ms at 4 096 / 20 480 / 61 440 vertices, 256 poses 0.60 / 11.6 / 101 ms
 (about 9e12 pairs/s when the chip is full); beyond about 1e5 vertices subsample the mesh (the reference's own LM tables are 4 096
 farthest-point samples per object).  There is no CPU fallback."""
-import weakref
+import ctypes as C
 
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, scene
+from .scene import MeshSet, SymmetrySet, calc_pts_diameter, symmetry_transformations   # noqa: F401  (their public home was here)
 
 KINDS = {"add": _abi.POSE_ERR_ADD, "adi": _abi.POSE_ERR_ADI}
-
-
-def calc_pts_diameter(pts):
-    """largest pairwise distance of a point set (bop_toolkit_lib.misc.calc_pts_diameter restated): exact, in float64.
-    Only points that can be an end of the longest pair are compared: with c the centroid and L a distance that IS attained,
-    |p_i - p_j| <= |p_i - c| + max_k |p_k - c|, so a point whose bound falls below L is dropped before the all-pairs pass.
-    The pass over the K points kept is K^2 (chunked: about 100 MB of temporaries whatever K); a sphere-like cloud keeps most of its
-    points, so for real BOP meshes of 1e5+ vertices pass the `diameter` of models_info.json to MeshSet instead of computing it."""
-    p = np.ascontiguousarray(np.asarray(pts, dtype=np.float64).reshape(-1, 3))
-    if p.shape[0] == 0:
-        raise ValueError("calc_pts_diameter: empty point set")
-    r = np.linalg.norm(p - p.mean(0), axis=1)
-    a = p[int(r.argmax())]
-    for _ in range(3):                                  # a few farthest-point hops: a lower bound that is an actual distance
-        d = np.linalg.norm(p - a, axis=1)
-        a, low = p[int(d.argmax())], float(d.max())
-    keep = p[r + r.max() >= low * (1.0 - 1e-9)]
-    best = 0.0
-    rows = max(1, (1 << 21) // keep.shape[0])              # rows x K x 3 doubles per chunk: 48 MB, + the products
-    for i0 in range(0, keep.shape[0], rows):
-        d = keep[i0:i0 + rows, None, :] - keep[None, :, :]
-        best = max(best, float((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]).max()))
-    return float(np.sqrt(best))
-
-
-class MeshSet:
-    """The vertices of M objects packed into one (sumV, 3) fp32 table + (M + 1) int32 offsets (cp_pose_errors' layout), and their
-    diameters.  Built on the host; the device copies are made once per device on first use."""
-
-    def __init__(self, verts, offsets, diameters, faces=None, face_offsets=None, colors=None, normals=None):
-        self.verts = verts                  # (sumV, 3) float32 CPU tensor
-        self.offsets = offsets              # (M + 1,) int32 CPU tensor
-        self.diameters = diameters          # (M,) float64 numpy
-        self.sizes = np.diff(offsets.numpy()).astype(np.int64)
-        self.faces = faces                  # (sumF, 3) int32 CPU tensor, vertex indices local to each mesh, or None (VSD needs them)
-        self.face_offsets = face_offsets    # (M + 1,) int32 CPU tensor, or None
-        self.colors = colors                # (sumV, 3) float32 CPU tensor in [0, 1], rows as verts, or None (render.render_rgb)
-        self.normals = normals              # (sumV, 3) float32 CPU tensor, or None (phong shading needs them)
-        self._dev = {}
-        self._dev_faces = {}
-        self._dev_shading = {}
-
-    @classmethod
-    def from_arrays(cls, arrays, diameters=None, faces=None, device=None, colors=None, normals=None):
-        """arrays: a list of (V_m, 3) arrays / tensors (or ONE such array); diameters: one per mesh, or None = computed as the
-        reference does (largest pairwise distance of the vertices) -- on the host, or with `device` on that device
-        (prepare.pts_diameters: the same bits); faces: None, or one (F_m, 3) integer array of vertex indices
-        per mesh (or ONE such array with one mesh) -- the triangles vsd_errors / render_depth rasterise;
-        colors: None, or per mesh a (V_m, 3) uint8 / float array of vertex colours or None (that mesh is 0.5 grey) -- as
-        renderer_py's add_object takes them: a mesh whose largest value is > 1 is divided by 255 (in float32);
-        normals: None, or one (V_m, 3) float array per mesh (every mesh): render.render_rgb's phong shading.
-        With both None the object is what it was before these arguments existed."""
-        if torch.is_tensor(arrays) or isinstance(arrays, np.ndarray):
-            arrays = [arrays]
-            if faces is not None and (torch.is_tensor(faces) or isinstance(faces, np.ndarray)):
-                faces = [faces]
-            if colors is not None and (torch.is_tensor(colors) or isinstance(colors, np.ndarray)):
-                colors = [colors]
-            if normals is not None and (torch.is_tensor(normals) or isinstance(normals, np.ndarray)):
-                normals = [normals]
-        host = []
-        for a in arrays:
-            a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
-            if a.ndim != 2 or a.shape[1] != 3 or a.shape[0] == 0:
-                raise ValueError("every mesh must be a non-empty (V, 3) array, got %r" % (a.shape,))
-            host.append(np.ascontiguousarray(a, dtype=np.float32))
-        if not host:
-            raise ValueError("MeshSet needs at least one mesh")
-        off = np.zeros(len(host) + 1, dtype=np.int64)
-        off[1:] = np.cumsum([a.shape[0] for a in host])
-        if off[-1] >= 2 ** 31:
-            raise ValueError("vertex table too large for int32 offsets")
-        if diameters is None and device is not None:
-            from .prepare import pts_diameters
-            diameters = pts_diameters(host, device).cpu().numpy()
-        elif diameters is None:
-            diameters = [calc_pts_diameter(a) for a in host]
-        diameters = np.asarray(diameters, dtype=np.float64).reshape(-1)
-        if diameters.shape[0] != len(host):
-            raise ValueError("need one diameter per mesh")
-        ftab = foff = None
-        if faces is not None:
-            faces = list(faces)
-            if len(faces) != len(host):
-                raise ValueError("need one face array per mesh")
-            fhost = []
-            for f, a in zip(faces, host):
-                f = f.detach().cpu().numpy() if torch.is_tensor(f) else np.asarray(f)
-                if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
-                    raise ValueError("faces must be (F, 3) integer arrays, got %r %s" % (f.shape, f.dtype))
-                if f.shape[0] and (f.min() < 0 or f.max() >= a.shape[0]):
-                    raise ValueError("a face names a vertex outside 0..%d" % (a.shape[0] - 1))
-                fhost.append(np.ascontiguousarray(f, dtype=np.int32))
-            fo = np.zeros(len(fhost) + 1, dtype=np.int64)
-            fo[1:] = np.cumsum([f.shape[0] for f in fhost])
-            if fo[-1] >= 2 ** 31 // 3:
-                raise ValueError("face table too large for int32 offsets")
-            ftab = torch.from_numpy(np.concatenate(fhost, 0).reshape(-1, 3)) if fo[-1] else torch.zeros((1, 3), dtype=torch.int32)
-            foff = torch.from_numpy(fo.astype(np.int32))
-        ctab = ntab = None
-        if colors is not None:
-            colors = list(colors)
-            if len(colors) != len(host):
-                raise ValueError("need one colour array (or None) per mesh")
-            chost = []
-            for c, a in zip(colors, host):
-                if c is None:
-                    chost.append(np.full(a.shape, 0.5, dtype=np.float32))
-                    continue
-                c = c.detach().cpu().numpy() if torch.is_tensor(c) else np.asarray(c)
-                if c.shape != a.shape:
-                    raise ValueError("colors must be (V, 3) like the vertices, got %r" % (c.shape,))
-                c = np.array(c, dtype=np.float32)
-                if not np.isfinite(c).all():
-                    raise ValueError("colors must be finite")
-                if c.max() > 1.0:
-                    c /= np.float32(255.0)
-                chost.append(c)
-            ctab = torch.from_numpy(np.ascontiguousarray(np.concatenate(chost, 0)))
-        if normals is not None:
-            normals = list(normals)
-            if len(normals) != len(host) or any(n is None for n in normals):
-                raise ValueError("need one normal array per mesh")
-            nhost = []
-            for n, a in zip(normals, host):
-                n = n.detach().cpu().numpy() if torch.is_tensor(n) else np.asarray(n)
-                if n.shape != a.shape:
-                    raise ValueError("normals must be (V, 3) like the vertices, got %r" % (n.shape,))
-                nhost.append(np.ascontiguousarray(n, dtype=np.float32))
-            ntab = torch.from_numpy(np.ascontiguousarray(np.concatenate(nhost, 0)))
-        return cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters, ftab, foff, ctab, ntab)
-
-    def __len__(self):
-        return int(self.offsets.numel()) - 1
-
-    def _key(self, device):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
-        return (device.type, device.index if device.index is not None else torch.cuda.current_device())
-
-    def on(self, device):
-        """(verts, offsets) on `device`, uploaded on the first call"""
-        key = self._key(device)
-        if key not in self._dev:
-            self._dev[key] = (self.verts.to(device), self.offsets.to(device))
-        return self._dev[key]
-
-    def faces_on(self, device):
-        """(faces, face offsets, diameters) on `device`, uploaded on the first call; ValueError without a face table"""
-        if self.faces is None:
-            raise ValueError("this MeshSet has no faces: build it with MeshSet.from_arrays(..., faces=...) to render it")
-        key = self._key(device)
-        if key not in self._dev_faces:
-            self._dev_faces[key] = (self.faces.to(device), self.face_offsets.to(device),
-                                    torch.from_numpy(np.ascontiguousarray(self.diameters, dtype=np.float64)).to(device))
-        return self._dev_faces[key]
-
-
-    def shading_on(self, device):
-        """(colors or None, normals or None) on `device`, uploaded on the first call"""
-        key = self._key(device)
-        if key not in self._dev_shading:
-            self._dev_shading[key] = (None if self.colors is None else self.colors.to(device),
-                                      None if self.normals is None else self.normals.to(device))
-        return self._dev_shading[key]
-
-
-def _as_poses(R, t, B=None):
-    """(B,3,3) + (B,3,1) / (B,3) float64 -> contiguous (B,12) [R row-major | t]"""
-    if R.dim() == 2:
-        R = R[None]
-    B = R.shape[0] if B is None else B
-    if tuple(R.shape) != (B, 3, 3) or t.numel() != 3 * B:
-        raise ValueError("poses must be R (B,3,3) and t (B,3,1) / (B,3); got %r and %r" % (tuple(R.shape), tuple(t.shape)))
-    return torch.cat([R.reshape(B, 9).to(torch.float64), t.reshape(B, 3).to(torch.float64)], 1).contiguous()
 
 
 def pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add", "adi")):
@@ -209,74 +38,28 @@ def pose_errors(R_est, t_est, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add",
     relative pose I + R_est^T (R_gt - R_est), which is the reference's rigid change of frame only then -- with a sheared or scaled
     estimate neither the reference's ADD nor R_est^T R_gt is what comes out.  A pose with a NaN / inf entry scores NaN in both errors.
     -> dict kind -> (B,) float64 CUDA tensor, in the vertices' units.  ADI costs V^2 per pose (module docstring)."""
-    if not (torch.is_tensor(R_est) and torch.is_tensor(t_est) and R_est.is_cuda and t_est.is_cuda):
-        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("metric", R_est, t_est)
     dev = R_est.device
-    mask = 0
-    for k in ([kinds] if isinstance(kinds, str) else kinds):
-        if k not in KINDS:
-            raise ValueError("kinds must be among %s, got %r" % (sorted(KINDS), k))
-        mask |= KINDS[k]
-    if not mask:
-        raise ValueError("kinds is empty: ask for \"add\", \"adi\" or both")
-    est = _as_poses(R_est, t_est)
+    mask = scene.kinds_mask(kinds, KINDS, "kinds is empty: ask for \"add\", \"adi\" or both")
+    est = scene.pack_poses(R_est, t_est)
     B = est.shape[0]
     if B == 0:
         raise ValueError("no poses")
-    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
-    ms = vertices if isinstance(vertices, MeshSet) else _cached_meshset(vertices)
+    gt = scene.pack_poses(R_gt, t_gt, B, dev)
+    ms = scene.as_meshset(vertices)
     verts, offsets = ms.on(dev)
-    M = len(ms)
-    if mesh_ids is None:
-        if M != 1:
-            raise ValueError("several meshes need mesh_ids")
-        ids, vmax = None, int(ms.sizes[0])
-    elif torch.is_tensor(mesh_ids) and mesh_ids.is_cuda:      # stays on the device: an id outside 0..M-1 scores NaN (cp_pose_errors)
-        if mesh_ids.numel() != B:
-            raise ValueError("mesh_ids must be (B,)")
-        ids, vmax = mesh_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous(), int(ms.sizes.max())
-    else:
-        ids_host = np.asarray(mesh_ids).reshape(-1).astype(np.int64)
-        if ids_host.shape[0] != B or ids_host.min() < 0 or ids_host.max() >= M:
-            raise ValueError("mesh_ids must be (B,) with values in 0..%d" % (M - 1))
-        ids, vmax = torch.from_numpy(ids_host.astype(np.int32)).to(dev), int(ms.sizes[np.unique(ids_host)].max())
-    lib = _abi.load()
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, ms.sizes)
     out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k, bit in KINDS.items() if mask & bit}
     scratch = None
     if mask & KINDS["adi"]:
-        scratch = torch.empty(lib.cp_pose_errors_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_pose_errors(st, est.data_ptr(), gt.data_ptr(), verts.data_ptr(), offsets.data_ptr(), M,
-                                      None if ids is None else ids.data_ptr(), B, vmax, mask,
-                                      out["add"].data_ptr() if "add" in out else None, out["adi"].data_ptr() if "adi" in out else None,
-                                      None if scratch is None else scratch.data_ptr()), "cp_pose_errors")
+        scratch = torch.empty(_abi.load().cp_pose_errors_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
+    _abi.call("cp_pose_errors", dev, est, gt, verts, offsets, len(ms), ids, B, vmax, mask, out.get("add"), out.get("adi"), scratch)
     return out
 
 
-_MESH_CACHE = {}        # id(array) -> (weak reference to the array, MeshSet): the upload of a mesh happens once per array
-
-
-def _cached_meshset(vertices):
-    """MeshSet of a bare (V,3) array / tensor or a list of them; cached per array OBJECT (test.py's loop passes the same `vertices`
-    for every image), dropped when the array is collected.  The array is taken as constant: edit it in place and the cache is stale."""
-    if isinstance(vertices, (list, tuple)):
-        return MeshSet.from_arrays(list(vertices), diameters=np.full(len(vertices), np.nan))
-    key = id(vertices)
-    hit = _MESH_CACHE.get(key)
-    if hit is not None and hit[0]() is vertices:
-        return hit[1]
-    ms = MeshSet.from_arrays([vertices], diameters=[np.nan])
-    _MESH_CACHE[key] = (weakref.ref(vertices, lambda _r, k=key: _MESH_CACHE.pop(k, None)), ms)
-    return ms
-
-
 def _one_pose(kind, R_GT, t_GT, R_predict, t_predict, vertices, device):
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
-    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
-    out = pose_errors(f(R_predict, (1, 3, 3)), f(t_predict, (1, 3, 1)), f(R_GT, (1, 3, 3)), f(t_GT, (1, 3, 1)), vertices, kinds=(kind,))
+    dev = scene.cuda_device("metric", device)
+    out = pose_errors(*scene.upload_pose(R_predict, t_predict, dev), *scene.upload_pose(R_GT, t_GT, dev), vertices, kinds=(kind,))
     return float(out[kind][0])
 
 
@@ -361,108 +144,13 @@ def summarize(errors, diameters, symmetric=None, mesh_ids=None):
 
 
 # ---- BOP's MSSD / MSPD / projection error (cp_bop_errors) ---------------------------------------------------------
-# The twin of the three renderer-free functions of bop_toolkit_lib/pose_error.py (mssd :96-118, mspd :121-144, proj :217-232), of
-# misc.get_symmetry_transformations (:43-90) and of the recall eval_bop19_pose.py / eval_calc_scores.py compute from them.
+# The twin of the three renderer-free functions of bop_toolkit_lib/pose_error.py (mssd :96-118, mspd :121-144, proj :217-232) and of
+# the recall eval_bop19_pose.py / eval_calc_scores.py compute from them (misc.get_symmetry_transformations: scene.SymmetrySet).
 #   bop_errors(...)                        batched, on device tensors -- takes what solve_pnp_ransac returns
 #   mssd / mspd / proj                     bop_toolkit's names and numpy-in, float-out signatures (B = 1 of the above)
-#   SymmetrySet                            the packed symmetry transformations of several objects, uploaded once
 #   bop_recall, summarize_bop              recall per threshold and its mean (AR_MSSD / AR_MSPD); host: one float per pose
 BOP_KINDS = {"mssd": _abi.BOP_ERR_MSSD, "mspd": _abi.BOP_ERR_MSPD, "proj": _abi.BOP_ERR_PROJ}
 _BOP_MAPS = {None: 0, "small": _abi.BOP_MAP_SMALL, "large": _abi.BOP_MAP_LARGE}
-
-
-def _rotation_about(angle, axis):
-    """rotation by `angle` about `axis` through the origin (bop_toolkit_lib.transform.rotation_matrix restated, 3x3 part): the
-    axis is normalised first; R = cos I + (1 - cos) a a^T + sin [a]_x, summed in that order"""
-    import math
-    sina, cosa = math.sin(angle), math.cos(angle)
-    a = np.array(np.asarray(axis, dtype=np.float64).reshape(-1)[:3], dtype=np.float64, copy=True)
-    a /= math.sqrt(np.dot(a, a))
-    R = np.diag([cosa, cosa, cosa])
-    R += np.outer(a, a) * (1.0 - cosa)
-    a *= sina
-    R += np.array([[0.0, -a[2], a[1]], [a[2], 0.0, -a[0]], [-a[1], a[0], 0.0]])
-    return R
-
-
-def symmetry_transformations(model_info, max_sym_disc_step=0.01):
-    """The symmetry set of one models_info.json entry as a list of {"R": (3,3), "t": (3,1)} (misc.get_symmetry_transformations
-    restated).  Discrete symmetries: the identity plus every 4x4 of "symmetries_discrete".  Each continuous symmetry is sampled at
-    count = ceil(pi / max_sym_disc_step) steps of 2 pi / count, i = 1 .. count - 1 -- so WITH a continuous symmetry the identity is
-    not in the set, which then has (count - 1) * (1 + number of discrete symmetries) members per continuous axis: every
-    discretised rotation composed with every discrete one."""
-    disc = [{"R": np.eye(3), "t": np.zeros((3, 1))}]
-    for sym in model_info.get("symmetries_discrete", ()):
-        m = np.reshape(np.asarray(sym, dtype=np.float64), (4, 4))
-        disc.append({"R": m[:3, :3], "t": m[:3, 3].reshape(3, 1)})
-    cont = []
-    for sym in model_info.get("symmetries_continuous", ()):
-        offset = np.asarray(sym["offset"], dtype=np.float64).reshape(3, 1)
-        count = int(np.ceil(np.pi / max_sym_disc_step))
-        step = 2.0 * np.pi / count
-        for i in range(1, count):
-            R = _rotation_about(i * step, sym["axis"])
-            cont.append({"R": R, "t": -R.dot(offset) + offset})
-    if not cont:
-        return disc
-    return [{"R": c["R"].dot(d["R"]), "t": c["R"].dot(d["t"]) + c["t"]} for d in disc for c in cont]
-
-
-class SymmetrySet:
-    """The symmetry transformations of M objects packed into one (sumS, 12) fp64 table [R row-major | t] + (M + 1) int32 offsets
-    (cp_bop_errors' layout), in MeshSet order.  Built on the host; the device copies are made once per device on first use."""
-
-    def __init__(self, table, offsets):
-        self.table = table                  # (sumS, 12) float64 CPU tensor
-        self.offsets = offsets              # (M + 1,) int32 CPU tensor
-        self.sizes = np.diff(offsets.numpy()).astype(np.int64)
-        self._dev = {}
-
-    @classmethod
-    def from_transforms(cls, sets):
-        """sets: one list of {"R": (3,3), "t": (3,) / (3,1)} per mesh (what bop_toolkit passes as `syms`)"""
-        rows, off = [], [0]
-        for syms in sets:
-            if len(syms) == 0:
-                raise ValueError("every mesh needs at least one symmetry transformation (the identity for an asymmetric object)")
-            for s in syms:
-                rows.append(np.concatenate([np.asarray(s["R"], dtype=np.float64).reshape(9), np.asarray(s["t"], dtype=np.float64).reshape(3)]))
-            off.append(len(rows))
-        if not rows:
-            raise ValueError("SymmetrySet needs at least one mesh")
-        return cls(torch.from_numpy(np.ascontiguousarray(np.stack(rows, 0))), torch.tensor(off, dtype=torch.int32))
-
-    @classmethod
-    def from_models_info(cls, infos, max_sym_disc_step=0.01):
-        """infos: one models_info.json entry (dict) per mesh, in MeshSet order -> misc.get_symmetry_transformations of each"""
-        if isinstance(infos, dict):
-            raise ValueError("pass a LIST of models_info entries, one per mesh in MeshSet order")
-        return cls.from_transforms([symmetry_transformations(i, max_sym_disc_step) for i in infos])
-
-    @classmethod
-    def identity(cls, M):
-        return cls.from_transforms([[{"R": np.eye(3), "t": np.zeros(3)}]] * int(M))
-
-    def transforms(self, m):
-        """mesh m's set back as bop_toolkit's list of {"R", "t"}"""
-        t = self.table.numpy()[int(self.offsets[m]):int(self.offsets[m + 1])]
-        return [{"R": r[:9].reshape(3, 3).copy(), "t": r[9:].reshape(3, 1).copy()} for r in t]
-
-    def __len__(self):
-        return int(self.offsets.numel()) - 1
-
-    def on(self, device):
-        """(table, offsets) on `device`, uploaded on the first call"""
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
-        key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
-        if key not in self._dev:
-            self._dev[key] = (self.table.to(device), self.offsets.to(device))
-        return self._dev[key]
-
-
-_IDENTITY_SETS = {}     # M -> SymmetrySet of M identities (symmetries=None)
 
 
 def bop_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, symmetries=None, mesh_ids=None, kinds=("mssd", "mspd", "proj"), _mapping=None):
@@ -476,76 +164,33 @@ def bop_errors(R_est, t_est, R_gt, t_gt, cam_K, vertices, symmetries=None, mesh_
     device-side mesh id outside 0..M-1, scores NaN in every kind.  `_mapping` ("small" / "large") forces one of the kernel's two
     mappings (measurement and tests: results are bit-identical).
     -> dict kind -> (B,) float64 CUDA tensor."""
-    if not (torch.is_tensor(R_est) and torch.is_tensor(t_est) and R_est.is_cuda and t_est.is_cuda):
-        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("metric", R_est, t_est)
     dev = R_est.device
-    mask = 0
-    for k in ([kinds] if isinstance(kinds, str) else kinds):
-        if k not in BOP_KINDS:
-            raise ValueError("kinds must be among %s, got %r" % (sorted(BOP_KINDS), k))
-        mask |= BOP_KINDS[k]
-    if not mask:
-        raise ValueError("kinds is empty: ask for \"mssd\", \"mspd\" and / or \"proj\"")
+    mask = scene.kinds_mask(kinds, BOP_KINDS, "kinds is empty: ask for \"mssd\", \"mspd\" and / or \"proj\"")
     if _mapping not in _BOP_MAPS:
         raise ValueError("_mapping must be None, \"small\" or \"large\"")
-    est = _as_poses(R_est, t_est)
+    est = scene.pack_poses(R_est, t_est)
     B = est.shape[0]
     if B == 0:
         raise ValueError("no poses")
-    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
-    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
-    if tuple(K.shape) == (3, 3):
-        K, k_stride = K.reshape(9).contiguous(), 0
-    elif tuple(K.shape) == (B, 3, 3):
-        K, k_stride = K.reshape(B, 9).contiguous(), 9
-    else:
-        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
-    ms = vertices if isinstance(vertices, MeshSet) else _cached_meshset(vertices)
+    gt = scene.pack_poses(R_gt, t_gt, B, dev)
+    K, k_stride = scene.camera(cam_K, B, dev)
+    ms = scene.as_meshset(vertices)
     M = len(ms)
-    if symmetries is None:
-        if M not in _IDENTITY_SETS:
-            _IDENTITY_SETS[M] = SymmetrySet.identity(M)
-        ss = _IDENTITY_SETS[M]
-    else:
-        ss = symmetries if isinstance(symmetries, SymmetrySet) else SymmetrySet.from_transforms(symmetries)
-    if len(ss) != M:
-        raise ValueError("%d symmetry sets for %d meshes" % (len(ss), M))
+    ss = scene.as_symmetries(symmetries, M)
     verts, v_off = ms.on(dev)
     table, s_off = ss.on(dev)
-    if mesh_ids is None:
-        if M != 1:
-            raise ValueError("several meshes need mesh_ids")
-        ids, vmax, smax = None, int(ms.sizes[0]), int(ss.sizes[0])
-    elif torch.is_tensor(mesh_ids) and mesh_ids.is_cuda:      # stays on the device: an id outside 0..M-1 scores NaN (cp_bop_errors)
-        if mesh_ids.numel() != B:
-            raise ValueError("mesh_ids must be (B,)")
-        ids = mesh_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-        vmax, smax = int(ms.sizes.max()), int(ss.sizes.max())
-    else:
-        ids_host = np.asarray(mesh_ids).reshape(-1).astype(np.int64)
-        if ids_host.shape[0] != B or ids_host.min() < 0 or ids_host.max() >= M:
-            raise ValueError("mesh_ids must be (B,) with values in 0..%d" % (M - 1))
-        used = np.unique(ids_host)
-        ids, vmax, smax = torch.from_numpy(ids_host.astype(np.int32)).to(dev), int(ms.sizes[used].max()), int(ss.sizes[used].max())
-    lib = _abi.load()
+    ids, (vmax, smax) = scene.mesh_ids_on(mesh_ids, B, dev, ms.sizes, ss.sizes)
     out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k, bit in BOP_KINDS.items() if mask & bit}
-    scratch = torch.empty(lib.cp_bop_errors_map_scratch_bytes(B, smax, vmax, _BOP_MAPS[_mapping]), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    ptr = lambda k: out[k].data_ptr() if k in out else None   # noqa: E731
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_bop_errors(st, est.data_ptr(), gt.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(),
-                                     table.data_ptr(), s_off.data_ptr(), M, None if ids is None else ids.data_ptr(), B, vmax, smax,
-                                     mask | _BOP_MAPS[_mapping], ptr("mssd"), ptr("mspd"), ptr("proj"), scratch.data_ptr()),
-                   "cp_bop_errors")
+    scratch = torch.empty(_abi.load().cp_bop_errors_map_scratch_bytes(B, smax, vmax, _BOP_MAPS[_mapping]), dtype=torch.uint8, device=dev)
+    _abi.call("cp_bop_errors", dev, est, gt, K, k_stride, verts, v_off, table, s_off, M, ids, B, vmax, smax, mask | _BOP_MAPS[_mapping],
+              out.get("mssd"), out.get("mspd"), out.get("proj"), scratch)
     return out
 
 
 def _one_bop(kind, R_est, t_est, R_gt, t_gt, K, pts, syms, device):
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
-    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
-    out = bop_errors(f(R_est, (1, 3, 3)), f(t_est, (1, 3, 1)), f(R_gt, (1, 3, 3)), f(t_gt, (1, 3, 1)),
+    dev = scene.cuda_device("metric", device)
+    out = bop_errors(*scene.upload_pose(R_est, t_est, dev), *scene.upload_pose(R_gt, t_gt, dev),
                      np.eye(3) if K is None else np.asarray(K, dtype=np.float64).reshape(3, 3), pts,
                      symmetries=None if syms is None else [list(syms)], kinds=(kind,))
     return float(out[kind][0])
@@ -703,71 +348,8 @@ def score_poses(R_est, t_est, R_gt, t_gt, cam_K, vertices, mesh_ids=None, kinds=
 #   vsd                                    bop_toolkit's name and signature (one pose; `renderer` is a MeshSet with faces)
 #   render_depth                           the rasteriser alone
 #   bop_recall(.., "vsd"), summarize_bop   recall per (tau, threshold) pair, AR_VSD and BOP'19's AR
-def _vsd_common(R, t, cam_K, meshes, mesh_ids):
-    if not (torch.is_tensor(R) and torch.is_tensor(t) and R.is_cuda and t.is_cuda):
-        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
-    if not isinstance(meshes, MeshSet):
-        raise ValueError("VSD renders triangles: pass a MeshSet built with faces")
-    if meshes.faces is None:
-        raise ValueError("this MeshSet has no faces: build it with MeshSet.from_arrays(..., faces=...) to render it")
-    dev = R.device
-    poses = _as_poses(R, t)
-    B = poses.shape[0]
-    if B == 0:
-        raise ValueError("no poses")
-    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
-    if tuple(K.shape) == (3, 3):
-        K, k_stride = K.reshape(9).contiguous(), 0
-    elif tuple(K.shape) == (B, 3, 3):
-        K, k_stride = K.reshape(B, 9).contiguous(), 9
-    else:
-        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
-    M = len(meshes)
-    if mesh_ids is None:
-        if M != 1:
-            raise ValueError("several meshes need mesh_ids")
-        ids, vmax = None, int(meshes.sizes[0])
-    elif torch.is_tensor(mesh_ids) and mesh_ids.is_cuda:
-        if mesh_ids.numel() != B:
-            raise ValueError("mesh_ids must be (B,)")
-        ids, vmax = mesh_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous(), int(meshes.sizes.max())
-    else:
-        ids_host = np.asarray(mesh_ids).reshape(-1).astype(np.int64)
-        if ids_host.shape[0] != B or ids_host.min() < 0 or ids_host.max() >= M:
-            raise ValueError("mesh_ids must be (B,) with values in 0..%d" % (M - 1))
-        ids, vmax = torch.from_numpy(ids_host.astype(np.int32)).to(dev), int(meshes.sizes[np.unique(ids_host)].max())
-    return dev, poses, B, K, k_stride, M, ids, vmax
-
-
-def _vsd_images(depth_test, image_ids, B, dev):
-    d = torch.as_tensor(depth_test)
-    if d.dim() == 2:
-        d = d[None]
-    if d.dim() != 3:
-        raise ValueError("depth_test must be (H,W) or (I,H,W), got %r" % (tuple(d.shape),))
-    d = d.to(device=dev, dtype=torch.float32).contiguous()
-    n_img = int(d.shape[0])
-    if image_ids is None:
-        if n_img == 1:
-            img = None
-        elif n_img == B:
-            img = torch.arange(B, dtype=torch.int32, device=dev)
-        else:
-            raise ValueError("%d depth images for %d poses need image_ids" % (n_img, B))
-    elif torch.is_tensor(image_ids) and image_ids.is_cuda:        # stays on the device: an id outside 0..I-1 scores NaN
-        if image_ids.numel() != B:
-            raise ValueError("image_ids must be (B,)")
-        img = image_ids.reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
-    else:
-        host = np.asarray(image_ids).reshape(-1).astype(np.int64)
-        if host.shape[0] != B or host.min() < 0 or host.max() >= n_img:
-            raise ValueError("image_ids must be (B,) with values in 0..%d" % (n_img - 1))
-        img = torch.from_numpy(host.astype(np.int32)).to(dev)
-    return d, img, n_img
-
-
-def _vsd_taus(taus):
-    import ctypes as C
+def vsd_taus(taus):
+    """the misalignment tolerances of VSD (default bop_thresholds("vsd")) -> (float64 (T,) array, the same as a ctypes double[T])"""
     tv = bop_thresholds("vsd") if taus is None else np.asarray(taus, dtype=np.float64).reshape(-1)
     if not 1 <= tv.shape[0] <= 16 or not np.isfinite(tv).all():
         raise ValueError("taus: 1 to 16 finite values")
@@ -786,27 +368,22 @@ def vsd_errors(R_est, t_est, R_gt, t_gt, cam_K, meshes, depth_test, image_ids=No
     A pose with a NaN / inf entry, a device-side mesh / image id out of range, or any vertex at Z <= 0 scores NaN (a miss).
     -> {"vsd": (B,T) float64 CUDA tensor} (+ "counts": (B,T+2) int32 = union, inter, cost count per tau; + "depth": (B,2,H,W)
     float32 = the estimate's and the ground truth's render).  The counts are the same bits with or without the depth output."""
-    dev, est, B, K, k_stride, M, ids, vmax = _vsd_common(R_est, t_est, cam_K, meshes, mesh_ids)
-    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
-    d, img, n_img = _vsd_images(depth_test, image_ids, B, dev)
+    dev, est, B = scene.mesh_poses(R_est, t_est, meshes)
+    K, k_stride = scene.camera(cam_K, B, dev)
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, meshes.sizes)
+    gt = scene.pack_poses(R_gt, t_gt, B, dev)
+    d, img, n_img = scene.depth_images(depth_test, image_ids, B, dev)
     H, W = int(d.shape[1]), int(d.shape[2])
-    tv, ctaus = _vsd_taus(taus)
+    tv, ctaus = vsd_taus(taus)
     T = tv.shape[0]
     verts, v_off = meshes.on(dev)
     faces, f_off, diam = meshes.faces_on(dev)
-    lib = _abi.load()
     err = torch.empty((B, T), dtype=torch.float64, device=dev)
     counts = torch.empty((B, T + 2), dtype=torch.int32, device=dev)
     depth = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev) if return_depth else None
-    scratch = torch.empty(lib.cp_vsd_errors_scratch_bytes(B, vmax, H, W), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_vsd_errors(st, est.data_ptr(), gt.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(),
-                                     faces.data_ptr(), f_off.data_ptr(), M, None if ids is None else ids.data_ptr(), d.data_ptr(),
-                                     None if img is None else img.data_ptr(), n_img, H, W, float(delta), diam.data_ptr(), ctaus, T,
-                                     1 if normalized_by_diameter else 0, 1 if sphere_check else 0, B, vmax, err.data_ptr(),
-                                     counts.data_ptr(), None if depth is None else depth.data_ptr(), scratch.data_ptr()),
-                   "cp_vsd_errors")
+    scratch = torch.empty(_abi.load().cp_vsd_errors_scratch_bytes(B, vmax, H, W), dtype=torch.uint8, device=dev)
+    _abi.call("cp_vsd_errors", dev, est, gt, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, d, img, n_img, H, W, float(delta),
+              diam, ctaus, T, 1 if normalized_by_diameter else 0, 1 if sphere_check else 0, B, vmax, err, counts, depth, scratch)
     out = {"vsd": err}
     if return_counts:
         out["counts"] = counts
@@ -818,8 +395,7 @@ def vsd_errors(R_est, t_est, R_gt, t_gt, cam_K, meshes, depth_test, image_ids=No
 def vsd_from_depth(depth_est, depth_gt, depth_test, cam_K, diameters, image_ids=None, delta=15.0, taus=None, normalized_by_diameter=True):
     """vsd_errors' counting on caller-supplied renders (cp_vsd_from_depth): depth_est, depth_gt (B,H,W) float32 CUDA tensors;
     diameters: a float or one per pose.  -> {"vsd": (B,T) f64, "counts": (B,T+2) int32}"""
-    if not (torch.is_tensor(depth_est) and torch.is_tensor(depth_gt) and depth_est.is_cuda and depth_gt.is_cuda):
-        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("metric", depth_est, depth_gt)
     if depth_est.dim() != 3 or depth_est.shape != depth_gt.shape:
         raise ValueError("depth_est and depth_gt must both be (B,H,W)")
     dev = depth_est.device
@@ -828,32 +404,21 @@ def vsd_from_depth(depth_est, depth_gt, depth_test, cam_K, diameters, image_ids=
     B, H, W = (int(v) for v in de.shape)
     if B == 0:
         raise ValueError("no poses")
-    d, img, n_img = _vsd_images(depth_test, image_ids, B, dev)
+    d, img, n_img = scene.depth_images(depth_test, image_ids, B, dev)
     if tuple(d.shape[1:]) != (H, W):
         raise ValueError("depth_test is %r, the renders are %r" % (tuple(d.shape[1:]), (H, W)))
-    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
-    if tuple(K.shape) == (3, 3):
-        K, k_stride = K.reshape(9).contiguous(), 0
-    elif tuple(K.shape) == (B, 3, 3):
-        K, k_stride = K.reshape(B, 9).contiguous(), 9
-    else:
-        raise ValueError("cam_K must be (3,3) or (B,3,3), got %r" % (tuple(K.shape),))
+    K, k_stride = scene.camera(cam_K, B, dev)
     diam = np.asarray(diameters, dtype=np.float64).reshape(-1)
     if diam.shape[0] not in (1, B):
         raise ValueError("diameters: a float or one per pose")
     diam = torch.from_numpy(np.array(np.broadcast_to(diam, (B,)), dtype=np.float64)).to(dev)
-    tv, ctaus = _vsd_taus(taus)
+    tv, ctaus = vsd_taus(taus)
     T = tv.shape[0]
-    lib = _abi.load()
     err = torch.empty((B, T), dtype=torch.float64, device=dev)
     counts = torch.empty((B, T + 2), dtype=torch.int32, device=dev)
-    scratch = torch.empty(lib.cp_vsd_errors_scratch_bytes(B, 0, H, W), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_vsd_from_depth(st, de.data_ptr(), dg.data_ptr(), K.data_ptr(), k_stride, d.data_ptr(),
-                                         None if img is None else img.data_ptr(), n_img, H, W, float(delta), diam.data_ptr(), ctaus, T,
-                                         1 if normalized_by_diameter else 0, B, err.data_ptr(), counts.data_ptr(), scratch.data_ptr()),
-                   "cp_vsd_from_depth")
+    scratch = torch.empty(_abi.load().cp_vsd_errors_scratch_bytes(B, 0, H, W), dtype=torch.uint8, device=dev)
+    _abi.call("cp_vsd_from_depth", dev, de, dg, K, k_stride, d, img, n_img, H, W, float(delta), diam, ctaus, T,
+              1 if normalized_by_diameter else 0, B, err, counts, scratch)
     return {"vsd": err, "counts": counts}
 
 
@@ -862,20 +427,15 @@ def render_depth(R, t, cam_K, meshes, size, mesh_ids=None):
     eye-space Z of the front-most surface on the ray through image point (x + 0.5, y + 0.5), 0 where there is none -- what
     bop_toolkit's renderer.render_object(...)['depth'] holds.  size: (width, height), as bop_toolkit's renderers take it.
     A pose with a non-finite entry or any vertex at Z <= 0 renders nothing (zeros).  -> (B,H,W) float32 CUDA tensor"""
-    dev, poses, B, K, k_stride, M, ids, vmax = _vsd_common(R, t, cam_K, meshes, mesh_ids)
-    W, H = int(size[0]), int(size[1])
-    if W <= 0 or H <= 0:
-        raise ValueError("size must be (width, height), both positive")
+    dev, poses, B = scene.mesh_poses(R, t, meshes)
+    K, k_stride = scene.camera(cam_K, B, dev)
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, meshes.sizes)
+    W, H = scene.frame_size(size)
     verts, v_off = meshes.on(dev)
     faces, f_off, _ = meshes.faces_on(dev)
-    lib = _abi.load()
     depth = torch.empty((B, H, W), dtype=torch.float32, device=dev)
-    scratch = torch.empty(lib.cp_vsd_errors_scratch_bytes(B, vmax, H, W), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_render_depth(st, poses.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(), faces.data_ptr(),
-                                       f_off.data_ptr(), M, None if ids is None else ids.data_ptr(), H, W, B, vmax, depth.data_ptr(),
-                                       scratch.data_ptr()), "cp_render_depth")
+    scratch = torch.empty(_abi.load().cp_vsd_errors_scratch_bytes(B, vmax, H, W), dtype=torch.uint8, device=dev)
+    _abi.call("cp_render_depth", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, H, W, B, vmax, depth, scratch)
     return depth
 
 
@@ -886,9 +446,7 @@ def vsd(R_est, t_est, R_gt, t_gt, depth_test, K, delta, taus, normalized_by_diam
     normalised by (it replaces the MeshSet's for this call).  Only the 'step' cost exists.  No sphere shortcut: that is the caller's."""
     if cost_type != "step":
         raise ValueError("only the 'step' pixel-wise matching cost is implemented")
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
+    dev = scene.cuda_device("metric", device)
     if not isinstance(renderer, MeshSet) or renderer.faces is None:
         raise ValueError("renderer must be a MeshSet built with faces")
     m = int(obj_id)
@@ -897,8 +455,7 @@ def vsd(R_est, t_est, R_gt, t_gt, depth_test, K, delta, taus, normalized_by_diam
     v0, v1 = int(renderer.offsets[m]), int(renderer.offsets[m + 1])
     f0, f1 = int(renderer.face_offsets[m]), int(renderer.face_offsets[m + 1])
     one = MeshSet.from_arrays([renderer.verts[v0:v1]], diameters=[float(diameter)], faces=[renderer.faces[f0:f1]])
-    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
-    out = vsd_errors(f(R_est, (1, 3, 3)), f(t_est, (1, 3, 1)), f(R_gt, (1, 3, 3)), f(t_gt, (1, 3, 1)),
+    out = vsd_errors(*scene.upload_pose(R_est, t_est, dev), *scene.upload_pose(R_gt, t_gt, dev),
                      np.asarray(K, dtype=np.float64).reshape(3, 3), one, np.asarray(depth_test, dtype=np.float32), delta=delta, taus=taus,
                      normalized_by_diameter=normalized_by_diameter, sphere_check=False)
     return [float(v) for v in out["vsd"][0].cpu()]
@@ -935,35 +492,24 @@ def mask_errors(R_est, t_est, R_gt, t_gt, cam_K, meshes, size, mesh_ids=None, ki
     counts 0, boxes -1 and empty masks.  The errors are the same bits with or without the optional outputs.
     return_masks forfeits the early leave: every tile of every pair then walks its pixels to store them (zeros where nothing is
     rendered), which is the stored-image cost the fused call otherwise avoids -- ask for masks only when they are wanted."""
-    names = [kinds] if isinstance(kinds, str) else list(kinds)
-    for k in names:
-        if k not in MASK_KINDS:
-            raise ValueError("kinds must be among %s, got %r" % (list(MASK_KINDS), k))
-    if not names:
-        raise ValueError("kinds is empty: ask for \"cus\", \"cou_bb_proj\" or both")
-    dev, est, B, K, k_stride, M, ids, vmax = _vsd_common(R_est, t_est, cam_K, meshes, mesh_ids)
-    gt = _as_poses(torch.as_tensor(R_gt, dtype=torch.float64).to(dev), torch.as_tensor(t_gt, dtype=torch.float64).to(dev), B)
+    mask = scene.kinds_mask(kinds, MASK_KINDS, "kinds is empty: ask for \"cus\", \"cou_bb_proj\" or both")
+    dev, est, B = scene.mesh_poses(R_est, t_est, meshes)
+    K, k_stride = scene.camera(cam_K, B, dev)
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, meshes.sizes)
+    gt = scene.pack_poses(R_gt, t_gt, B, dev)
     if size is None:
         raise ValueError("size=(width, height) is required: a MeshSet has no frame")
-    W, H = int(size[0]), int(size[1])
-    if W <= 0 or H <= 0:
-        raise ValueError("size must be (width, height), both positive")
+    W, H = scene.frame_size(size)
     verts, v_off = meshes.on(dev)
     faces, f_off, diam = meshes.faces_on(dev)
-    lib = _abi.load()
-    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in MASK_KINDS if k in names}
+    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for n, k in enumerate(MASK_KINDS) if mask >> n & 1}
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if return_counts else None
     ok = torch.empty(B, dtype=torch.uint8, device=dev) if return_counts else None
     boxes = torch.empty((B, 2, 4), dtype=torch.int32, device=dev) if return_boxes else None
     masks = torch.empty((B, 2, H, W), dtype=torch.uint8, device=dev) if return_masks else None
-    scratch = torch.empty(lib.cp_mask_errors_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
-    ptr = lambda x: None if x is None else x.data_ptr()     # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_mask_errors(st, est.data_ptr(), gt.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(),
-                                      faces.data_ptr(), f_off.data_ptr(), M, ptr(ids), diam.data_ptr(), H, W, 1 if sphere_check else 0,
-                                      B, vmax, ptr(out.get("cus")), ptr(out.get("cou_bb_proj")), ptr(counts), ptr(boxes), ptr(ok),
-                                      ptr(masks), scratch.data_ptr()), "cp_mask_errors")
+    scratch = torch.empty(_abi.load().cp_mask_errors_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
+    _abi.call("cp_mask_errors", dev, est, gt, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, diam, H, W, 1 if sphere_check else 0,
+              B, vmax, out.get("cus"), out.get("cou_bb_proj"), counts, boxes, ok, masks, scratch)
     if return_counts:
         out["counts"], out["ok"] = counts, ok.view(torch.bool)
     if return_boxes:
@@ -995,14 +541,9 @@ def mask_overlap(mask_est, mask_gt, kinds=("cou_mask", "cou_bb"), return_counts=
     cou_mask = 1 - inter / union, 1.0 when the union is empty;  cou_bb = 1 - iou of the boxes (xmin, ymin, xmax - xmin, ymax - ymin)
     of the two masks, NaN where a mask is empty (misc.calc_2d_bbox raises there).
     -> dict kind -> (B,) float64 CUDA tensor (+ "counts": (B,4) int32 = inter, union, n_est, n_gt; + "boxes": (B,2,4) int32, -1 where empty)"""
-    names = [kinds] if isinstance(kinds, str) else list(kinds)
-    for k in names:
-        if k not in OVERLAP_KINDS:
-            raise ValueError("kinds must be among %s, got %r" % (list(OVERLAP_KINDS), k))
-    if not names and not return_counts and not return_boxes:
-        raise ValueError("kinds is empty: ask for \"cou_mask\", \"cou_bb\" or both")
-    if not (torch.is_tensor(mask_est) and mask_est.is_cuda):
-        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    mask = scene.kinds_mask(kinds, OVERLAP_KINDS, None if return_counts or return_boxes else
+                            "kinds is empty: ask for \"cou_mask\", \"cou_bb\" or both")
+    scene.require_cuda("metric", mask_est)
     dev = mask_est.device
     me, mg = _as_masks(mask_est), _as_masks(mask_gt, dev)
     if me.shape != mg.shape:
@@ -1010,15 +551,10 @@ def mask_overlap(mask_est, mask_gt, kinds=("cou_mask", "cou_bb"), return_counts=
     B, H, W = (int(v) for v in me.shape)
     if B == 0 or H == 0 or W == 0:
         raise ValueError("no masks")
-    lib = _abi.load()
-    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for k in OVERLAP_KINDS if k in names}
+    out = {k: torch.empty(B, dtype=torch.float64, device=dev) for n, k in enumerate(OVERLAP_KINDS) if mask >> n & 1}
     counts = torch.empty((B, 4), dtype=torch.int32, device=dev) if return_counts else None
     boxes = torch.empty((B, 2, 4), dtype=torch.int32, device=dev) if return_boxes else None
-    ptr = lambda x: None if x is None else x.data_ptr()     # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_mask_overlap(st, me.data_ptr(), mg.data_ptr(), H, W, B, ptr(out.get("cou_mask")), ptr(out.get("cou_bb")),
-                                       ptr(counts), ptr(boxes)), "cp_mask_overlap")
+    _abi.call("cp_mask_overlap", dev, me, mg, H, W, B, out.get("cou_mask"), out.get("cou_bb"), counts, boxes)
     if return_counts:
         out["counts"] = counts
     if return_boxes:
@@ -1029,8 +565,7 @@ def mask_overlap(mask_est, mask_gt, kinds=("cou_mask", "cou_bb"), return_counts=
 def box_overlap(bb_est, bb_gt):
     """pose_error.cou_bb = 1 - misc.iou of B box pairs (x, y, w, h), on the device (cp_box_overlap): bb_est (B,4) CUDA tensor (any
     real dtype; computed in float64), bb_gt the same shape (tensor or host array).  -> (B,) float64 CUDA tensor"""
-    if not (torch.is_tensor(bb_est) and bb_est.is_cuda):
-        raise RuntimeError("checkerpose_amd.metric: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("metric", bb_est)
     dev = bb_est.device
     a = bb_est.reshape(-1, 4).to(torch.float64).contiguous()
     c = torch.as_tensor(bb_gt).to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous()
@@ -1038,35 +573,26 @@ def box_overlap(bb_est, bb_gt):
         raise ValueError("bb_est and bb_gt must both be (B,4), B > 0")
     B = int(a.shape[0])
     out = torch.empty(B, dtype=torch.float64, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(_abi.load().cp_box_overlap(st, a.data_ptr(), c.data_ptr(), B, out.data_ptr()), "cp_box_overlap")
+    _abi.call("cp_box_overlap", dev, a, c, B, out)
     return out
-
-
-def _one_device(device):
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("checkerpose_amd.metric: a CUDA/HIP device is required (no CPU fallback)")
-    return dev
 
 
 def cou_mask(mask_est, mask_gt, device="cuda:0"):
     """bop_toolkit_lib.pose_error.cou_mask (two hxw arrays -> float), counted on the device"""
-    dev = _one_device(device)
+    dev = scene.cuda_device("metric", device)
     f = lambda m: torch.from_numpy(np.ascontiguousarray(np.asarray(m).astype(bool))).to(dev)   # noqa: E731
     return float(mask_overlap(f(mask_est), f(mask_gt), kinds=("cou_mask",))["cou_mask"][0])
 
 
 def cou_bb(bb_est, bb_gt, device="cuda:0"):
     """bop_toolkit_lib.pose_error.cou_bb (two boxes x, y, w, h -> float), on the device"""
-    dev = _one_device(device)
+    dev = scene.cuda_device("metric", device)
     f = lambda b: torch.from_numpy(np.asarray(b, dtype=np.float64).reshape(1, 4)).to(dev)   # noqa: E731
     return float(box_overlap(f(bb_est), f(bb_gt))[0])
 
 
 def _one_mask_error(kind, R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size, device):
-    dev = _one_device(device)
+    dev = scene.cuda_device("metric", device)
     if not isinstance(renderer, MeshSet) or renderer.faces is None:
         raise ValueError("renderer must be a MeshSet built with faces")
     if size is None:
@@ -1074,8 +600,7 @@ def _one_mask_error(kind, R_est, t_est, R_gt, t_gt, K, renderer, obj_id, size, d
     m = int(obj_id)
     if not 0 <= m < len(renderer):
         raise ValueError("obj_id must be a mesh index in 0..%d" % (len(renderer) - 1))
-    f = lambda a, s: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(s))).to(dev)   # noqa: E731
-    out = mask_errors(f(R_est, (1, 3, 3)), f(t_est, (1, 3, 1)), f(R_gt, (1, 3, 3)), f(t_gt, (1, 3, 1)),
+    out = mask_errors(*scene.upload_pose(R_est, t_est, dev), *scene.upload_pose(R_gt, t_gt, dev),
                       np.asarray(K, dtype=np.float64).reshape(3, 3), renderer, size, mesh_ids=None if len(renderer) == 1 else [m],
                       kinds=(kind,))
     return float(out[kind][0])

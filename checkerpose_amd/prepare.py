@@ -16,19 +16,12 @@ import pickle
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, scene
 from .aux_utils.pointnet2_utils import pc_normalize
-from .metric import MeshSet
+from .scene import MeshSet
 
 
-def _device(device):
-    dev = torch.device(device)
-    if dev.type != "cuda" or not torch.cuda.is_available():
-        raise RuntimeError("checkerpose_amd.prepare: a CUDA/HIP device is required (no CPU fallback)")
-    return dev
-
-
-def _pack(clouds):
+def pack_clouds(clouds):
     """one (V,3) array / tensor or a list of them -> (fp64 host table (sumV,3), int32 host offsets (M+1)); the reference promotes
     the PLY's floats to float64 the same way (get_fps_points.py:112-115)"""
     if torch.is_tensor(clouds) or isinstance(clouds, np.ndarray):
@@ -54,8 +47,8 @@ def _pack(clouds):
 
 
 def _upload(clouds, device):
-    dev = _device(device)
-    table, off = _pack(clouds)
+    dev = scene.cuda_device("prepare", device)
+    table, off = pack_clouds(clouds)
     return dev, torch.from_numpy(table).to(dev), torch.from_numpy(off).to(dev), off
 
 
@@ -64,32 +57,24 @@ def _fps(dev, pts, off_dev, off, npoint, slices=0):
     if npoint < 1:
         raise ValueError("npoint must be at least 1")
     M, sizes = off.shape[0] - 1, np.diff(off)
-    lib = _abi.load()
-    nbytes = lib.cp_fps_scratch_bytes(M, int(off[-1]), int(sizes.max()), int(slices))
+    nbytes = _abi.load().cp_fps_scratch_bytes(M, int(off[-1]), int(sizes.max()), int(slices))
     if nbytes == 0:
         raise ValueError("cp_fps: bad shape (M = %d, slices = %r)" % (M, slices))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     ids = torch.empty((M, npoint), dtype=torch.int32, device=dev)
     xyz = torch.empty((M, npoint, 3), dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _abi.check(lib.cp_fps(st, pts.data_ptr(), off_dev.data_ptr(), off.ctypes.data, M, npoint, int(slices), ids.data_ptr(),
-                              xyz.data_ptr(), scratch.data_ptr()), "cp_fps")
+    _abi.call("cp_fps", dev, pts, off_dev, off.ctypes.data, M, npoint, int(slices), ids, xyz, scratch)
     return ids, xyz
 
 
 def _diameters(dev, pts, off_dev, off):
     M, sizes = off.shape[0] - 1, np.diff(off)
-    lib = _abi.load()
-    nbytes = lib.cp_pts_diameter_scratch_bytes(M, int(sizes.max()))
+    nbytes = _abi.load().cp_pts_diameter_scratch_bytes(M, int(sizes.max()))
     if nbytes == 0:
         raise ValueError("cp_pts_diameter: a cloud of %d points is too large (at most 5792 * 1024)" % int(sizes.max()))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     out = torch.empty(M, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _abi.check(lib.cp_pts_diameter(st, pts.data_ptr(), off_dev.data_ptr(), off.ctypes.data, M, out.data_ptr(), scratch.data_ptr()),
-                   "cp_pts_diameter")
+    _abi.call("cp_pts_diameter", dev, pts, off_dev, off.ctypes.data, M, out, scratch)
     return out
 
 

@@ -24,38 +24,17 @@ UNPINNED: (1) OpenGL's own output -- the shaders are GLSL and run nowhere this p
 read from them (tests/render_rgb_stages.py, float64), as the depth render of row N8 is; (2) cv2's INTER_AREA -- cv2 is not
 available to the tests, as for the resize of row N3; (3) textured models (`texture_file` / `texture_uv`) are out of scope: GL's
 sampler rule cannot be read from the shader.  Specular terms, the C++ and vispy renderers, PLY reading and PNG writing are not here.
+
+The MeshSet and the handling of poses, camera, mesh ids, frame size and the light are checkerpose_amd/scene.py's (shared with
+vis.vis_poses); the depth rasteriser alone is metric.render_depth.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _abi, metric
-
-SHADINGS = {"flat": 0, "phong": 1}
-
-
-def _pose_tensors(R, t):
-    """solve_pnp_ransac's device tensors as they are; host arrays / CPU tensors go to the current device (96 bytes per pose)"""
-    if torch.is_tensor(R) and R.is_cuda:
-        dev = R.device
-    elif torch.is_tensor(t) and t.is_cuda:
-        dev = t.device
-    else:
-        if not torch.cuda.is_available():
-            raise RuntimeError("checkerpose_amd.render: a CUDA/HIP device is required (no CPU fallback)")
-        dev = torch.device("cuda", torch.cuda.current_device())
-    R = torch.as_tensor(R).to(device=dev, dtype=torch.float64)
-    t = torch.as_tensor(t).to(device=dev, dtype=torch.float64)
-    return R, t
-
-
-def _vec3(x, name):
-    v = np.asarray(x, dtype=np.float64).reshape(-1)
-    if v.shape[0] != 3 or not np.isfinite(v).all():
-        raise ValueError("%s must be 3 finite values, got %r" % (name, x))
-    return (C.c_double * 3)(*v.tolist())
+from . import _abi, metric, scene
+from .scene import SHADINGS   # noqa: F401  (public here since row N14)
 
 
 def render_rgb(R, t, cam_K, meshes, size, mesh_ids=None, shading="phong", ambient_weight=0.5, light_cam_pos=(0, 0, 0),
@@ -75,43 +54,30 @@ def render_rgb(R, t, cam_K, meshes, size, mesh_ids=None, shading="phong", ambien
     -1 where the mask is empty.
     A pose with a non-finite entry, a singular R or any vertex at Z <= 0 is not rendered: ok = 0, background only.
     -> {"rgb": uint8 (B,H,W,3), "ok": uint8 (B,)} (+ "depth", "mask", "boxes"), all on the device.  Four launches whatever the data."""
-    if shading not in SHADINGS:
-        raise ValueError("shading must be \"flat\" or \"phong\", got %r" % (shading,))
+    shade, amb, light_c = scene.lighting(shading, ambient_weight, light_cam_pos)
     ssaa = int(ssaa)
     if ssaa not in (1, 2, 4):
         raise ValueError("ssaa must be 1, 2 or 4, got %r" % (ssaa,))
     if ssaa != 1 and (return_depth or return_mask or return_boxes):
         raise ValueError("depth, mask and boxes are made at ssaa=1 only: render them in a call of their own")
-    amb = float(ambient_weight)
-    if not math.isfinite(amb):
-        raise ValueError("ambient_weight must be finite")
-    light = np.asarray(light_cam_pos, dtype=np.float64).reshape(-1)
-    if light.shape[0] != 3:
-        raise ValueError("light_cam_pos must be 3 values")
-    light_c = _vec3(light * np.array([1.0, -1.0, -1.0]), "light_cam_pos")       # OpenGL's camera frame -> the poses'
-    bg_c = _vec3(bg_color, "bg_color")
-    if not isinstance(meshes, metric.MeshSet):
-        raise ValueError("render_rgb renders triangles: pass a MeshSet built with faces")
-    if shading == "phong" and meshes.normals is None:
-        raise ValueError("phong shading needs vertex normals: MeshSet.from_arrays(..., normals=...)")
-    W, H = int(size[0]), int(size[1])
-    if W <= 0 or H <= 0:
-        raise ValueError("size must be (width, height), both positive")
-    R, t = _pose_tensors(R, t)
-    dev, poses, B, K, k_stride, M, ids, vmax = metric._vsd_common(R, t, cam_K, meshes, mesh_ids)
+    bg_c = scene.vec3(bg_color, "bg_color")
+    scene.check_shaded_meshes(meshes, shading, "render_rgb")
+    W, H = scene.frame_size(size)
+    dev, poses, B = scene.mesh_poses(*scene.poses_to_device("render", R, t), meshes)
+    K, k_stride = scene.camera(cam_K, B, dev)
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, meshes.sizes)
     verts, v_off = meshes.on(dev)
     faces, f_off, _ = meshes.faces_on(dev)
     colors, normals = meshes.shading_on(dev)
     if surf_color is not None:
-        surf_c, colors = _vec3(surf_color, "surf_color"), None
+        surf_c, colors = scene.vec3(surf_color, "surf_color"), None
     else:
-        surf_c = _vec3((0.5, 0.5, 0.5), "surf_color")
+        surf_c = scene.vec3((0.5, 0.5, 0.5), "surf_color")
     if out is None:
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
     elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (B, H, W, 3)
               and out.is_contiguous()):
         raise ValueError("out must be a contiguous uint8 (%d,%d,%d,3) tensor on %s" % (B, H, W, dev))
-    lib = _abi.load()
     res = {"rgb": out, "ok": torch.empty(B, dtype=torch.uint8, device=dev)}
     if return_depth:
         res["depth"] = torch.empty((B, H, W), dtype=torch.float32, device=dev)
@@ -119,16 +85,9 @@ def render_rgb(R, t, cam_K, meshes, size, mesh_ids=None, shading="phong", ambien
         res["mask"] = torch.empty((B, H, W), dtype=torch.uint8, device=dev)
     if return_boxes:
         res["boxes"] = torch.empty((B, 4), dtype=torch.int32, device=dev)
-    scratch = torch.empty(lib.cp_render_rgb_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
-    ptr = lambda k: res[k].data_ptr() if k in res else None      # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_render_rgb(st, poses.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(), faces.data_ptr(),
-                                     f_off.data_ptr(), M, None if ids is None else ids.data_ptr(),
-                                     None if colors is None else colors.data_ptr(), None if normals is None else normals.data_ptr(),
-                                     surf_c, light_c, amb, bg_c, SHADINGS[shading], ssaa, 1 if bgr else 0, H, W, B, vmax,
-                                     out.data_ptr(), ptr("depth"), ptr("mask"), ptr("boxes"), res["ok"].data_ptr(), scratch.data_ptr()),
-                   "cp_render_rgb")
+    scratch = torch.empty(_abi.load().cp_render_rgb_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
+    _abi.call("cp_render_rgb", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, colors, normals, surf_c, light_c, amb,
+              bg_c, shade, ssaa, 1 if bgr else 0, H, W, B, vmax, out, res.get("depth"), res.get("mask"), res.get("boxes"), res["ok"], scratch)
     return res
 
 
@@ -292,7 +251,7 @@ def synthetic_batch(meshes, mesh_ids, R, t, cam_K, size, p3d_xyz, augment=None, 
     for k in ("return_depth", "return_mask", "return_boxes", "out"):
         if k in render_kw:
             raise ValueError("synthetic_batch sets %s itself" % k)
-    Rt, tt = _pose_tensors(R, t)
+    Rt, tt = scene.poses_to_device("render", R, t)
     r = render_rgb(Rt, tt, cam_K, meshes, size, mesh_ids=mesh_ids, return_mask=True, return_boxes=True, **render_kw)
     boxes = r["boxes"].cpu().numpy()
     if (boxes[:, 0] < 0).any():

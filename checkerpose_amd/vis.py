@@ -24,15 +24,17 @@ holds fewer than three distinct values gets diff_ok = 0 and zeros (the reference
 
 UNPINNED / out of scope: the text the reference writes on both pictures (its font call does not exist in the Pillow at hand; `boxes`
 are returned for a caller who annotates), JPEG / PNG writing, dataset folders, textures, SSAA in the composite.  OpenGL's own output
-is unpinned as for render_rgb.  There is no CPU fallback."""
+is unpinned as for render_rgb.  There is no CPU fallback.
+
+Poses, camera (per IMAGE here), mesh ids, the grouping of the poses by image (scene.group_by_image) and the light are handled by
+checkerpose_amd/scene.py, which render.render_rgb shares."""
 import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _abi, metric
-from .render import SHADINGS, _pose_tensors, _vec3
+from . import _abi, scene
 
 _S = 1.0 - 0.2      # depth_for_vis' valid_end - valid_start, as Python forms it
 
@@ -44,25 +46,6 @@ def _frames_checked(frames):
     if f.dtype != torch.uint8 or f.dim() != 4 or f.shape[3] != 3 or min(f.shape[:3]) <= 0:
         raise ValueError("frames must be uint8 (I,H,W,3), got %s %r" % (f.dtype, tuple(f.shape)))
     return f
-
-
-def _image_ids(image_ids, P, n_img):
-    """-> (image of pose (P,) int32, img_off (I+1,) int32, pose_order (P,) int32): the stable grouping of the poses by image"""
-    if image_ids is None:
-        if n_img == 1:
-            ids = np.zeros(P, dtype=np.int64)
-        elif n_img == P:
-            ids = np.arange(P, dtype=np.int64)
-        else:
-            raise ValueError("%d frames for %d poses need image_ids" % (n_img, P))
-    else:
-        ids = (image_ids.cpu().numpy() if torch.is_tensor(image_ids) else np.asarray(image_ids)).reshape(-1).astype(np.int64)
-        if ids.shape[0] != P or (P and (ids.min() < 0 or ids.max() >= n_img)):
-            raise ValueError("image_ids must be (P,) with values in 0..%d" % (n_img - 1))
-    order = np.argsort(ids, kind="stable").astype(np.int32)
-    off = np.zeros(n_img + 1, dtype=np.int32)
-    off[1:] = np.cumsum(np.bincount(ids, minlength=n_img))
-    return ids.astype(np.int32), off, order
 
 
 def _depth_checked(depth, shape):
@@ -98,20 +81,15 @@ def depth_diff_vis(ren_depth, depth, image_ids=None, delta=15.0):
     dshape = tuple(torch.as_tensor(depth).shape)
     if len(dshape) not in (2, 3) or tuple(dshape[-2:]) != (H, W):
         raise ValueError("depth must be (H,W) or (I,H,W) with H, W = %d, %d; got %r" % (H, W, dshape))
-    if not r.is_cuda:
-        raise RuntimeError("checkerpose_amd.vis: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("vis", r)
     dev = r.device
     r = r.to(torch.float32).contiguous()
-    d, img, n_img = metric._vsd_images(depth, image_ids, B, dev)
-    lib = _abi.load()
+    d, img, n_img = scene.depth_images(depth, image_ids, B, dev)
     out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
     stats = torch.empty((B, 3), dtype=torch.float64, device=dev)
     ok = torch.empty((B,), dtype=torch.uint8, device=dev)
-    scratch = torch.empty(lib.cp_depth_diff_vis_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_depth_diff_vis(st, r.data_ptr(), d.data_ptr(), None if img is None else img.data_ptr(), n_img, float(delta), _S,
-                                         H, W, B, out.data_ptr(), stats.data_ptr(), ok.data_ptr(), scratch.data_ptr()), "cp_depth_diff_vis")
+    scratch = torch.empty(_abi.load().cp_depth_diff_vis_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
+    _abi.call("cp_depth_diff_vis", dev, r, d, img, n_img, float(delta), _S, H, W, B, out, stats, ok, scratch)
     return {"depth_diff": out, "diff_stats": stats, "diff_ok": ok}
 
 
@@ -129,26 +107,15 @@ def vis_poses(R, t, cam_K, meshes, frames, image_ids=None, mesh_ids=None, surf_c
     -> {"vis", "ren_rgb": uint8 (I,H,W,3), "ren_depth": float32 (I,H,W), "boxes": int32 (P,4) x, y, w, h (-1 without a coloured
     pixel), "ok": uint8 (P,)} on the device; with depth_diff also depth_diff_vis' "depth_diff", "diff_stats", "diff_ok" of ren_depth.
     Four launches whatever the data (cp_vis_poses); bit-identical from call to call, for an image alone or in a batch."""
-    if shading not in SHADINGS:
-        raise ValueError("shading must be \"flat\" or \"phong\", got %r" % (shading,))
-    amb = float(ambient_weight)
-    if not math.isfinite(amb):
-        raise ValueError("ambient_weight must be finite")
-    light = np.asarray(light_cam_pos, dtype=np.float64).reshape(-1)
-    if light.shape[0] != 3:
-        raise ValueError("light_cam_pos must be 3 values")
-    light_c = _vec3(light * np.array([1.0, -1.0, -1.0]), "light_cam_pos")       # OpenGL's camera frame -> the poses'
-    box_c = _vec3(box_color, "box_color")
+    shade, amb, light_c = scene.lighting(shading, ambient_weight, light_cam_pos)
+    box_c = scene.vec3(box_color, "box_color")
     fr = _frames_checked(frames)
     n_img, H, W = (int(v) for v in fr.shape[:3])
-    if not isinstance(meshes, metric.MeshSet):
-        raise ValueError("vis_poses renders triangles: pass a MeshSet built with faces")
-    if shading == "phong" and meshes.normals is None:
-        raise ValueError("phong shading needs vertex normals: MeshSet.from_arrays(..., normals=...)")
+    scene.check_shaded_meshes(meshes, shading, "vis_poses")
     P = int((R.shape if hasattr(R, "shape") else np.asarray(R).shape)[0])
     if P <= 0:
         raise ValueError("no poses")
-    ids, off, order = _image_ids(image_ids, P, n_img)
+    ids, off, order = scene.group_by_image(image_ids, P, n_img)
     surf = None
     if surf_colors is not None:
         surf = np.asarray(surf_colors.cpu() if torch.is_tensor(surf_colors) else surf_colors, dtype=np.float64)
@@ -160,40 +127,26 @@ def vis_poses(R, t, cam_K, meshes, frames, image_ids=None, mesh_ids=None, surf_c
         if depth is None:
             raise ValueError("depth_diff needs the sensor depth")
         depth = _depth_checked(depth, (n_img, H, W))
-    if not fr.is_cuda:
-        raise RuntimeError("checkerpose_amd.vis: CUDA/HIP tensors required (no CPU fallback)")
+    scene.require_cuda("vis", fr)
     dev = fr.device
     fr = fr.contiguous()
-    R, t = _pose_tensors(torch.as_tensor(R).to(dev), torch.as_tensor(t).to(dev))
-    _, poses, _, _, _, M, mids, vmax = metric._vsd_common(R, t, np.eye(3), meshes, mesh_ids)
-    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
-    if tuple(K.shape) == (3, 3):
-        K, k_stride = K.reshape(9).contiguous(), 0
-    elif tuple(K.shape) == (n_img, 3, 3):
-        K, k_stride = K.reshape(n_img, 9).contiguous(), 9
-    else:
-        raise ValueError("cam_K must be (3,3) or (I,3,3), got %r" % (tuple(K.shape),))
+    _, poses, B = scene.mesh_poses(*scene.poses_to_device("vis", torch.as_tensor(R).to(dev), torch.as_tensor(t).to(dev)), meshes)
+    mids, (vmax,) = scene.mesh_ids_on(mesh_ids, B, dev, meshes.sizes)
+    K, k_stride = scene.camera(cam_K, n_img, dev, "I")
     verts, v_off = meshes.on(dev)
     faces, f_off, _ = meshes.faces_on(dev)
     colors, normals = meshes.shading_on(dev)
     surf_d = None if surf is None else torch.from_numpy(np.ascontiguousarray(surf)).to(dev)
     ids_d, off_d, order_d = (torch.from_numpy(a).to(dev) for a in (ids, off, order))
-    lib = _abi.load()
     res = {"vis": torch.empty((n_img, H, W, 3), dtype=torch.uint8, device=dev),
            "ren_rgb": torch.empty((n_img, H, W, 3), dtype=torch.uint8, device=dev),
            "ren_depth": torch.empty((n_img, H, W), dtype=torch.float32, device=dev),
            "boxes": torch.empty((P, 4), dtype=torch.int32, device=dev), "ok": torch.empty((P,), dtype=torch.uint8, device=dev)}
-    scratch = torch.empty(lib.cp_vis_poses_scratch_bytes(P, vmax, n_img), dtype=torch.uint8, device=dev)
-    ptr = lambda x: None if x is None else x.data_ptr()      # noqa: E731
-    st = torch.cuda.current_stream(dev).cuda_stream
-    with torch.cuda.device(dev):
-        _abi.check(lib.cp_vis_poses(st, poses.data_ptr(), K.data_ptr(), k_stride, verts.data_ptr(), v_off.data_ptr(), faces.data_ptr(),
-                                    f_off.data_ptr(), M, ptr(mids), ptr(colors), ptr(normals), ptr(surf_d), ids_d.data_ptr(),
-                                    off_d.data_ptr(), order_d.data_ptr(), off.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p),
-                                    fr.data_ptr(), SHADINGS[shading], amb, light_c, box_c, 1 if resolve_visib else 0,
-                                    1 if draw_boxes else 0, H, W, P, n_img, vmax, res["vis"].data_ptr(), res["ren_rgb"].data_ptr(),
-                                    res["ren_depth"].data_ptr(), res["boxes"].data_ptr(), res["ok"].data_ptr(), scratch.data_ptr()),
-                   "cp_vis_poses")
+    scratch = torch.empty(_abi.load().cp_vis_poses_scratch_bytes(P, vmax, n_img), dtype=torch.uint8, device=dev)
+    _abi.call("cp_vis_poses", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), mids, colors, normals, surf_d, ids_d, off_d,
+              order_d, off.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), fr, shade, amb, light_c, box_c,
+              1 if resolve_visib else 0, 1 if draw_boxes else 0, H, W, P, n_img, vmax, res["vis"], res["ren_rgb"], res["ren_depth"],
+              res["boxes"], res["ok"], scratch)
     if depth_diff:
         res.update(depth_diff_vis(res["ren_depth"], depth.to(dev), delta=delta))
     return res

@@ -13,15 +13,15 @@ The DEFAULT VIEW SET of overall_visibility is UNPINNED: the reference reads its 
 a file it does not ship; with R=None the views are the rotations of render.sample_views(min_n_views) (hinter_sampling's 2 562 at the
 default).  Pass the pickle's rotations as R to reproduce a published figure.
 Not rebuilt: the reference's V = 3 case (qhull accepts three points plus the viewpoint; V < 4 raises ValueError here), clouds of
-float32 computed in float32 (everything is promoted to float64, as prepare._pack does) and reading PLY files.
+float32 computed in float32 (everything is promoted to float64, as prepare.pack_clouds does) and reading PLY files.
 There is no CPU fallback."""
 import math
 
 import numpy as np
 import torch
 
-from . import _abi
-from .prepare import _device, _pack
+from . import _abi, scene
+from .prepare import pack_clouds
 
 STATUS = {1: "degenerate cloud: the flipped points are coincident, collinear or coplanar",
           2: "the horizon of an insertion is not a simple cycle",
@@ -39,7 +39,7 @@ def _radius_param(radius_param):
 
 
 def _cloud(vertices):
-    table, _ = _pack([vertices])
+    table, _ = pack_clouds([vertices])
     if table.shape[0] < 4:
         raise ValueError("need at least 4 vertices, got %d (the reference's V = 3 case is not rebuilt)" % table.shape[0])
     if table.shape[0] > 2 ** 22:
@@ -108,10 +108,9 @@ def hpr_visibility(vertices, R, t=(0, 0, 400.0), radius_param=2.0, device="cuda:
     hit = _vertex_at_viewpoint(v, R, t)
     if hit is not None:
         raise ValueError("a vertex lies at the viewpoint in view %d (norm 0: the flip is undefined)" % hit)
-    dev = _device(device)
+    dev = scene.cuda_device("prepare", device)
     n, V = R.shape[0], v.shape[0]
-    lib = _abi.load()
-    nbytes = lib.cp_hpr_visibility_scratch_bytes(n, V, wg)
+    nbytes = _abi.load().cp_hpr_visibility_scratch_bytes(n, V, wg)
     if nbytes == 0:
         raise ValueError("cp_hpr_visibility: bad shape (n_views = %d, V = %d, workgroups = %d)" % (n, V, wg))
     pts, Rd, td = torch.from_numpy(v).to(dev), torch.from_numpy(R).to(dev), torch.from_numpy(t).to(dev)
@@ -119,11 +118,7 @@ def hpr_visibility(vertices, R, t=(0, 0, 400.0), radius_param=2.0, device="cuda:
     mask = torch.empty((n, V), dtype=torch.uint8, device=dev) if return_mask else None
     status = torch.empty(n, dtype=torch.int32, device=dev)
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev).cuda_stream
-        _abi.check(lib.cp_hpr_visibility(st, pts.data_ptr(), Rd.data_ptr(), td.data_ptr(), 0 if t.ndim == 1 else 3, n, V, rp, wg,
-                                         counts.data_ptr(), None if mask is None else mask.data_ptr(), status.data_ptr(),
-                                         scratch.data_ptr()), "cp_hpr_visibility")
+    _abi.call("cp_hpr_visibility", dev, pts, Rd, td, 0 if t.ndim == 1 else 3, n, V, rp, wg, counts, mask, status, scratch)
     codes = status.cpu().numpy()
     bad = np.nonzero(codes)[0]
     if bad.size:

@@ -92,17 +92,17 @@ def test_model_info_and_normalisation_against_direct_numpy(g):
 
 def test_python_layer_refuses_bad_clouds_without_a_device():
     with pytest.raises(ValueError):
-        prepare._pack([np.zeros((0, 3))])
+        prepare.pack_clouds([np.zeros((0, 3))])
     with pytest.raises(ValueError):
-        prepare._pack([np.zeros((4, 2))])
+        prepare.pack_clouds([np.zeros((4, 2))])
     with pytest.raises(ValueError):
-        prepare._pack([])
+        prepare.pack_clouds([])
     for bad in (np.nan, np.inf, -np.inf):
         a = np.zeros((5, 3))
         a[3, 1] = bad
         with pytest.raises(ValueError):
-            prepare._pack([np.ones((2, 3)), a])
-    table, off = prepare._pack([np.ones((2, 3), dtype=np.float32), torch.zeros(5, 3)])
+            prepare.pack_clouds([np.ones((2, 3)), a])
+    table, off = prepare.pack_clouds([np.ones((2, 3), dtype=np.float32), torch.zeros(5, 3)])
     assert table.dtype == np.float64 and table.shape == (7, 3) and off.dtype == np.int32 and off.tolist() == [0, 2, 7]
     with pytest.raises(RuntimeError):
         prepare.fps_batch([np.ones((2, 3))], 2, device="cpu")                            # no CPU fallback

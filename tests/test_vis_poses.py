@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from checkerpose_amd import vis
+from checkerpose_amd import scene, vis
 from tests import vis_stages as VS
 from tests.common import GOLDEN
 
@@ -160,9 +160,9 @@ def test_package_names_and_csr():
     import checkerpose_amd
     for n in ("vis_poses", "depth_diff_vis", "select_estimates", "vis_est_poses", "vis_gt_poses"):
         assert getattr(checkerpose_amd, n) is getattr(vis, n)
-    ids, off, order = vis._image_ids([2, 0, 2, 3, 0, 2], 6, 5)
+    ids, off, order = scene.group_by_image([2, 0, 2, 3, 0, 2], 6, 5)
     assert ids.tolist() == [2, 0, 2, 3, 0, 2] and off.tolist() == [0, 2, 2, 5, 6, 6] and order.tolist() == [1, 4, 0, 2, 5, 3]      # stable
-    assert vis._image_ids(None, 3, 1)[1].tolist() == [0, 3] and vis._image_ids(None, 3, 3)[2].tolist() == [0, 1, 2]
+    assert scene.group_by_image(None, 3, 1)[1].tolist() == [0, 3] and scene.group_by_image(None, 3, 3)[2].tolist() == [0, 1, 2]
 
 
 def _mesh_set():
