@@ -24,7 +24,8 @@ def is_deterministic():
     return bool(_abi.load().cp_get_deterministic())
 
 
-_RENDER_NAMES = ("render_rgb", "sample_views", "render_views", "synthetic_batch")
+_RENDER_NAMES = ("render_rgb", "sample_views", "render_views", "synthetic_batch", "render_scene", "scene_masks", "scene_training_batch",
+                 "sample_scene_poses")
 _COCO_NAMES = ("annotate_masks", "calc_gt_coco", "mask_ious", "box_ious", "CocoSet", "eval_bop22_coco", "check_coco_results",
                "save_coco_results")
 _VISIBILITY_NAMES = ("compute_vis_hpr", "hpr_visibility", "overall_visibility")
@@ -33,7 +34,8 @@ _VIS_NAMES = ("vis_poses", "depth_diff_vis", "select_estimates", "vis_est_poses"
 
 def __getattr__(name):
     """row N14's entry points, imported on first use (render.py pulls in torch): checkerpose_amd.render_rgb, .sample_views,
-    .render_views, .synthetic_batch; row N15's likewise (coco_eval.py): .annotate_masks, .calc_gt_coco, .mask_ious, .box_ious, .CocoSet,
+    .render_views, .synthetic_batch (and row N19's .render_scene, .scene_masks, .scene_training_batch, .sample_scene_poses);
+    row N15's likewise (coco_eval.py): .annotate_masks, .calc_gt_coco, .mask_ious, .box_ious, .CocoSet,
     .eval_bop22_coco, .check_coco_results, .save_coco_results (coco_eval.evaluate is reached through the module); row N16's likewise
     (visibility.py): .compute_vis_hpr, .hpr_visibility, .overall_visibility; row N18's likewise (vis.py): .vis_poses, .depth_diff_vis,
     .select_estimates, .vis_est_poses, .vis_gt_poses"""

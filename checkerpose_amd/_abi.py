@@ -220,6 +220,9 @@ SIGNATURES = {
                           _I, _P, _P, _P, _P, _P, _P]),
     "cp_depth_diff_vis_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_depth_diff_vis": (_I, [_P, _P, _P, _P, _I, C.c_double, C.c_double, _I, _I, _I, _P, _P, _P, _P]),
+    "cp_render_scene_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "cp_render_scene": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, C.c_double, _P, C.c_double,
+                             _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cp_coco_pack": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "cp_coco_rle_count": (_I, [_P, _P, _I, _I, _I, _P]),
     "cp_coco_rle_write": (_I, [_P, _P, _I, _I, _I, _P, _P, _L]),
@@ -307,6 +310,7 @@ SIGNATURES = {
     "cp_nchw_to_nhwc": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I]),
     "cp_u8hwc_to_nhwc_norm": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cp_crop_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I]),
+    "cp_crop_mask_bits": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I]),
     "cp_augment_plan_bytes": (C.c_size_t, [_I]),
     "cp_augment_frames": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "cp_nhwc_to_nchw_f32": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I]),

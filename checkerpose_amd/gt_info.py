@@ -32,7 +32,8 @@ def _outputs(B, H, W, dev, return_masks):
             u8(B, H, W) if return_masks else None)
 
 
-def _result(counts, fract, boxes, ok, mask, visib):
+def label_dict(counts, fract, boxes, ok, mask, visib):
+    """the result dict of the entry points from their output tensors (render.render_scene fills the same ones: mask, visib None)"""
     out = {"px_count_all": counts[:, 0], "px_count_valid": counts[:, 1], "px_count_visib": counts[:, 2], "visib_fract": fract,
            "bbox_obj": boxes[:, 0], "bbox_visib": boxes[:, 1], "ok": ok.to(torch.bool)}
     if mask is not None:
@@ -66,7 +67,7 @@ def gt_info(R, t, cam_K, meshes, depth, image_ids=None, mesh_ids=None, delta=15.
     scratch = torch.empty(_abi.load().cp_gt_info_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
     _abi.call("cp_gt_info", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, d, img, n_img, H, W, float(delta), B, vmax,
               counts, fract, boxes, ok, mask, visib, render, scratch)
-    out = _result(counts, fract, boxes, ok, mask, visib)
+    out = label_dict(counts, fract, boxes, ok, mask, visib)
     if return_depth:
         out["depth"] = render
     return out
@@ -91,7 +92,7 @@ def gt_info_from_depth(depth_gt_large, depth, cam_K, image_ids=None, delta=15.0,
     scratch = torch.empty(_abi.load().cp_gt_info_scratch_bytes(B, 0), dtype=torch.uint8, device=dev)
     _abi.call("cp_gt_info_from_depth", dev, large, K, k_stride, d, img, n_img, H, W, float(delta), B, counts, fract, boxes, ok, mask, visib,
               scratch)
-    return _result(counts, fract, boxes, ok, mask, visib)
+    return label_dict(counts, fract, boxes, ok, mask, visib)
 
 
 def scene_gt_info(scene_gt, scene_camera, depths, meshes, obj_index, delta=15.0, device="cuda:0", return_masks=False, _call=None):

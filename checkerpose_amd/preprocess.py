@@ -61,6 +61,27 @@ def get_final_Bbox(Bbox, resize_method, max_x, max_y):
     return np.array([x1, y1, x2 - x1, y2 - y1])
 
 
+def _windows(Bboxes, resize_method, W, H):
+    """roi_window of every box -> (B,6) int32; a None entry keeps the all-zero window (an empty roi: a zero crop)"""
+    win = np.zeros((len(Bboxes), 6), dtype=np.int32)
+    for b, box in enumerate(Bboxes):
+        if box is not None:
+            win[b] = roi_window([int(v) for v in box], resize_method, W, H)
+    return win
+
+
+def _img_index_on(img_index, B, n_img, dev):
+    """the image of each box as an int32 tensor on dev, or None where the kernels' default holds (image b, or the only image)"""
+    if img_index is None:
+        if n_img not in (1, B):
+            raise RuntimeError("checkerpose_amd.preprocess: img_index is needed when %d boxes come from %d images" % (B, n_img))
+        return None
+    idx_np = np.asarray(img_index, dtype=np.int32).reshape(-1)
+    if idx_np.shape[0] != B or (B and (idx_np.min() < 0 or idx_np.max() >= n_img)):
+        raise RuntimeError("checkerpose_amd.preprocess: img_index must hold one valid image number per box")
+    return torch.from_numpy(idx_np).to(dev)
+
+
 def get_roi_batch(images, Bboxes, crop_size, interpolation=INTER_LINEAR, resize_method="crop_square_resize", img_index=None, out=None):
     """`get_roi` (bop_dataset_pytorch.py:132-145) for a batch, on the GPU.
     images: uint8 CUDA tensor (n_img, H, W, C) or (H, W, C) (C <= 4, the loader's cv2.imread layout); Bboxes: (B, 4) boxes
@@ -77,19 +98,7 @@ def get_roi_batch(images, Bboxes, crop_size, interpolation=INTER_LINEAR, resize_
         raise NotImplementedError("interpolation %r: cv2.INTER_NEAREST (0) and cv2.INTER_LINEAR (1) are built" % (interpolation,))
     n_img, H, W, C_ = (int(v) for v in images.shape)
     B = len(Bboxes)
-    win = np.zeros((B, 6), dtype=np.int32)
-    for b, box in enumerate(Bboxes):
-        if box is not None:
-            win[b] = roi_window([int(v) for v in box], resize_method, W, H)
-    if img_index is None:
-        if n_img not in (1, B):
-            raise RuntimeError("checkerpose_amd.preprocess: img_index is needed when %d boxes come from %d images" % (B, n_img))
-        idx_t = None
-    else:
-        idx_np = np.asarray(img_index, dtype=np.int32).reshape(-1)
-        if idx_np.shape[0] != B or (B and (idx_np.min() < 0 or idx_np.max() >= n_img)):
-            raise RuntimeError("checkerpose_amd.preprocess: img_index must hold one valid image number per box")
-        idx_t = torch.from_numpy(idx_np).to(images.device)
+    win, idx_t = _windows(Bboxes, resize_method, W, H), _img_index_on(img_index, B, n_img, images.device)
     if out is None:
         out = torch.empty(B, crop_size, crop_size, C_, dtype=torch.uint8, device=images.device)
     elif tuple(out.shape) != (B, crop_size, crop_size, C_) or out.dtype != torch.uint8 or not out.is_contiguous() or out.device != images.device:
@@ -102,3 +111,29 @@ def get_roi_batch(images, Bboxes, crop_size, interpolation=INTER_LINEAR, resize_
     _abi.check(lib.cp_crop_resize_u8(st, images.data_ptr(), n_img, H, W, C_, win_t.data_ptr(), idx_t.data_ptr() if idx_t is not None else None,
                                      out.data_ptr(), B, int(crop_size), int(interpolation)), "cp_crop_resize_u8")
     return out                                # (win_t / idx_t may be freed: torch's allocator reuses a block in stream order)
+
+
+def get_roi_mask_bits(bits, bit, Bboxes, crop_size, resize_method="crop_square_resize", img_index=None):
+    """`get_roi_batch(..., INTER_NEAREST)` of the 0 / 255 mask images that ONE BIT of a bit plane stands for, without expanding them
+    (cp_crop_mask_bits: the same window, zero-padding and index arithmetic, so the same bytes).
+    bits: int32 CUDA tensor (n_img, H, W) or (H, W) -- render.render_scene's "full_bits" / "visib_bits"; bit: (B,) for each box the
+    bit of its mask (render_scene's "slot"; a value outside 0..31 gives a zero crop); Bboxes, resize_method, img_index: get_roi_batch's.
+    -> uint8 CUDA tensor (B, crop_size, crop_size, 1), the shape get_roi_batch gives for a mask."""
+    if not (torch.is_tensor(bits) and bits.is_cuda and bits.dtype == torch.int32):
+        raise RuntimeError("checkerpose_amd.preprocess: bits must be an int32 CUDA tensor (no CPU path)")
+    if bits.dim() == 2:
+        bits = bits.unsqueeze(0)
+    if bits.dim() != 3 or not bits.is_contiguous():
+        raise RuntimeError("checkerpose_amd.preprocess: bits (n_img, H, W), contiguous")
+    n_img, H, W = (int(v) for v in bits.shape)
+    B = len(Bboxes)
+    bit_np = np.asarray(bit.detach().cpu() if torch.is_tensor(bit) else bit).reshape(-1).astype(np.int32)
+    if bit_np.shape[0] != B:
+        raise ValueError("bit must hold one bit number per box")
+    win, idx_t = _windows(Bboxes, resize_method, W, H), _img_index_on(img_index, B, n_img, bits.device)
+    out = torch.empty(B, int(crop_size), int(crop_size), 1, dtype=torch.uint8, device=bits.device)
+    if B == 0:
+        return out
+    win_t, bit_t = torch.from_numpy(win).to(bits.device), torch.from_numpy(bit_np).to(bits.device)
+    _abi.call("cp_crop_mask_bits", bits.device, bits, n_img, H, W, win_t, idx_t, bit_t, out, B, int(crop_size))
+    return out

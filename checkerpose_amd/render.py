@@ -4,6 +4,11 @@
   sample_views      the host twin of bop_toolkit_lib.view_sampler.sample_views (float64 numpy; both modes)
   render_views      the loop of bop_toolkit's scripts/render_train_imgs.py:128-214 without the files
   synthetic_batch   render_rgb -> targets.make_training_batch: a training batch of an object nobody photographed
+  render_scene      P poses on I images -> per image the occluded composite over a background, per pose gt_info's labels, the masks
+                    as two bit planes per image (row N19; csrc/scene_labels.hip, cp_render_scene)
+  scene_masks       a bit plane back as the uint8 (P,H,W) mask images it stands for (plain torch)
+  scene_training_batch   render_scene -> bop_io's visibility filter -> the loader's tuple, the mask crops cut from the bit planes
+  sample_scene_poses     the project's own placement of several objects per image (host, UNPINNED)
 
 Render rule (renderer_py.py:24-105, 422-518 and renderer.py:23-29 read as a rule; stated per sample in csrc/render_rgb.hip):
 coverage and the front-most surface are metric.render_depth's; over the winning triangle (the smallest face index among equal
@@ -28,12 +33,13 @@ sampler rule cannot be read from the shader.  Specular terms, the C++ and vispy 
 The MeshSet and the handling of poses, camera, mesh ids, frame size and the light are checkerpose_amd/scene.py's (shared with
 vis.vis_poses); the depth rasteriser alone is metric.render_depth.
 """
+import ctypes as C
 import math
 
 import numpy as np
 import torch
 
-from . import _abi, metric, scene
+from . import _abi, gt_info, metric, scene
 from .scene import SHADINGS   # noqa: F401  (public here since row N14)
 
 
@@ -246,7 +252,8 @@ def synthetic_batch(meshes, mesh_ids, R, t, cam_K, size, p3d_xyz, augment=None, 
     with frame b for sample b, the mask as both masks_visib and masks_full (one object, nothing occludes it) and the boxes as the
     ground-truth boxes -- exactly that composition, bit for bit.  render_kw goes to render_rgb (ssaa must stay 1: the mask belongs to
     the sample grid); every sample must be rendered with a non-empty mask (ValueError otherwise: a sample needs its box).
-    The boxes (16 bytes per sample) pass through the host, where make_training_batch grows them; no frame does."""
+    The boxes (16 bytes per sample) pass through the host, where make_training_batch grows them; no frame does.
+    Several objects in one frame, hiding each other, with visible and full masks that differ: scene_training_batch."""
     from . import targets
     for k in ("return_depth", "return_mask", "return_boxes", "out"):
         if k in render_kw:
@@ -259,3 +266,202 @@ def synthetic_batch(meshes, mesh_ids, R, t, cam_K, size, p3d_xyz, augment=None, 
     B = boxes.shape[0]
     return targets.make_training_batch(r["rgb"], r["mask"], r["mask"], Rt, tt, cam_K, boxes, p3d_xyz, img_index=np.arange(B),
                                        augment=augment, backgrounds=backgrounds)
+
+
+# ---- occluded scenes of several objects (row N19) --------------------------------------------------------------------------------------
+MAX_SCENE_POSES = 32        # per image: one bit of the planes each
+
+
+def _scene_backgrounds(backgrounds, bg_index, n_img, H, W):
+    """the checks of render_scene's background arguments that need no device -> (backgrounds or None, host int32 ids or None)"""
+    if backgrounds is None:
+        if bg_index is not None:
+            raise ValueError("bg_index without backgrounds")
+        return None, None
+    if not (torch.is_tensor(backgrounds) and backgrounds.dtype == torch.uint8 and backgrounds.dim() in (3, 4)):
+        raise ValueError("backgrounds must be a uint8 (n_bg,H,W,3) tensor")
+    bg = backgrounds.unsqueeze(0) if backgrounds.dim() == 3 else backgrounds
+    if tuple(bg.shape[1:]) != (H, W, 3) or bg.shape[0] < 1:
+        raise ValueError("backgrounds must be (n_bg,%d,%d,3), at the frame size; got %r" % (H, W, tuple(bg.shape)))
+    n_bg = int(bg.shape[0])
+    if bg_index is None:
+        if n_bg not in (1, n_img):
+            raise ValueError("%d backgrounds for %d images need bg_index" % (n_bg, n_img))
+        return bg, None
+    idx = np.asarray(bg_index.cpu() if torch.is_tensor(bg_index) else bg_index).reshape(-1).astype(np.int64)
+    if idx.shape[0] != n_img or (n_img and (idx.min() < 0 or idx.max() >= n_bg)):
+        raise ValueError("bg_index must be (I,) = (%d,) with values in 0..%d" % (n_img, n_bg - 1))
+    return bg, idx.astype(np.int32)
+
+
+def render_scene(R, t, cam_K, meshes, size, image_ids, mesh_ids=None, n_images=None, surf_colors=None, shading="phong",
+                 ambient_weight=0.5, light_cam_pos=(0, 0, 0), bg_color=(0, 0, 0), backgrounds=None, bg_index=None, delta=15.0, bgr=False):
+    """Occluded scenes of several objects with their labels, on the device (cp_render_scene): what vis.vis_poses(resolve_visib=True)
+    followed by gt_info.gt_info(depth=ren_depth, return_masks=True) computes, bit for bit, in four launches, over a background.
+      R, t: (P,3,3) / (P,3,1) or (P,3) -- device tensors, or host arrays; cam_K: (3,3) or (I,3,3), PER IMAGE; meshes: a MeshSet built
+      with faces (colors / normals as the shading needs them), mesh_ids (P,) with several meshes; size: (width, height);
+      image_ids (P,): each pose's image -- the poses of an image are composed in the order given, at most 32 of them (ValueError);
+      n_images: I (default: the largest image id + 1; an image may have no pose);  surf_colors, shading, ambient_weight,
+      light_cam_pos: vis_poses';  backgrounds: uint8 (n_bg,H,W,3) CUDA tensor behind the objects, image i showing row bg_index[i]
+      (default: row i, or the only row), or None: bg_color, RGB in [0, 1];  delta: gt_info's visibility tolerance;  bgr: store the
+      channels reversed (what cv2.imread gives the loaders).
+    The slot of a pose is its rank among the poses of its image, in the order given; a pose that is not rendered keeps its slot.
+    -> dict of device tensors: "rgb" uint8 (I,H,W,3) and "depth" float32 (I,H,W) -- vis_poses' ren_rgb (where depth > 0; the
+    background elsewhere) and ren_depth; "full_bits", "visib_bits" int32 (I,H,W): bit s is set where the mask / mask_visib image of
+    the pose at slot s would be 255 (scene_masks expands them; preprocess.get_roi_mask_bits crops them) -- 8 bytes per pixel whatever
+    P is, against 2 P; "slot" int32 (P,); gt_info.KEYS as gt_info gives them with "depth" as the sensor depth; "ok" bool (P,) --
+    False for a pose vis_poses does not render (a non-finite entry, a singular R, any vertex at Z <= 0): counts 0, boxes -1, no bit.
+    Bit-identical from call to call, for an image alone or in a batch; the labels with or without backgrounds."""
+    shade, amb, light_c = scene.lighting(shading, ambient_weight, light_cam_pos)
+    bg_c = scene.vec3(bg_color, "bg_color")
+    scene.check_shaded_meshes(meshes, shading, "render_scene")
+    W, H = scene.frame_size(size)
+    if not math.isfinite(float(delta)):
+        raise ValueError("delta must be finite")
+    P = int((R.shape if hasattr(R, "shape") else np.asarray(R).shape)[0])
+    if P <= 0:
+        raise ValueError("no poses")
+    if image_ids is None:
+        raise ValueError("render_scene needs image_ids: each pose's image")
+    flat = np.asarray(image_ids.cpu() if torch.is_tensor(image_ids) else image_ids).reshape(-1)
+    n_img = int(n_images) if n_images is not None else (int(flat.max()) + 1 if flat.size else 0)
+    if n_img <= 0:
+        raise ValueError("n_images must be positive")
+    ids, off, order = scene.group_by_image(flat, P, n_img)
+    if int(np.diff(off).max()) > MAX_SCENE_POSES:
+        raise ValueError("image %d holds %d poses: at most %d per image (one bit of the planes each)"
+                         % (int(np.diff(off).argmax()), int(np.diff(off).max()), MAX_SCENE_POSES))
+    surf = scene.surf_colors_host(surf_colors, P)
+    bg, bg_idx = _scene_backgrounds(backgrounds, bg_index, n_img, H, W)
+    if bg is not None:
+        scene.require_cuda("render", bg)
+    dev, poses, _ = scene.mesh_poses(*scene.poses_to_device("render", R, t), meshes)
+    if bg is not None and bg.device != dev:
+        raise ValueError("backgrounds must live on the poses' device")
+    mids, (vmax,) = scene.mesh_ids_on(mesh_ids, P, dev, meshes.sizes)
+    K, k_stride = scene.camera(cam_K, n_img, dev, "I")
+    verts, v_off = meshes.on(dev)
+    faces, f_off, _ = meshes.faces_on(dev)
+    colors, normals = meshes.shading_on(dev)
+    surf_d = None if surf is None else torch.from_numpy(np.ascontiguousarray(surf)).to(dev)
+    ids_d, off_d, order_d = (torch.from_numpy(a).to(dev) for a in (ids, off, order))
+    bg_d = None if bg is None else bg.contiguous()
+    bg_idx_d = None if bg_idx is None else torch.from_numpy(bg_idx).to(dev)
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)      # noqa: E731
+    rgb, depth = torch.empty((n_img, H, W, 3), dtype=torch.uint8, device=dev), torch.empty((n_img, H, W), dtype=torch.float32, device=dev)
+    full, visib, slot, counts, boxes = i32(n_img, H, W), i32(n_img, H, W), i32(P), i32(P, 3), i32(P, 2, 4)
+    fract, ok = torch.empty((P,), dtype=torch.float64, device=dev), torch.empty((P,), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_abi.load().cp_render_scene_scratch_bytes(P, vmax, n_img), dtype=torch.uint8, device=dev)
+    _abi.call("cp_render_scene", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), mids, colors, normals, surf_d, ids_d, off_d,
+              order_d, off.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), bg_d, 0 if bg_d is None else int(bg_d.shape[0]),
+              bg_idx_d, bg_c, shade, amb, light_c, float(delta), 1 if bgr else 0, H, W, P, n_img, vmax, rgb, depth, full, visib, slot, counts,
+              fract, boxes, ok, scratch)
+    out = {"rgb": rgb, "depth": depth, "full_bits": full, "visib_bits": visib, "slot": slot}
+    out.update(gt_info.label_dict(counts, fract, boxes, ok, None, None))
+    return out
+
+
+def scene_masks(bits, image_ids, slot):
+    """The mask images a bit plane of render_scene stands for: bits int32 (I,H,W) ("full_bits" or "visib_bits"), image_ids (P,) and
+    slot (P,) ("slot") -> uint8 (P,H,W) holding 0 / 255, gt_info's "mask" / "mask_visib".  A slot outside 0..31 gives zeros.
+    Plain torch on the planes' device (a CPU tensor works): for callers and tests; the training path crops the planes directly."""
+    bits = torch.as_tensor(bits)
+    if bits.dim() != 3 or bits.dtype != torch.int32:
+        raise ValueError("bits must be an int32 (I,H,W) tensor, got %s %r" % (bits.dtype, tuple(bits.shape)))
+    ids = torch.as_tensor(image_ids).reshape(-1).to(device=bits.device, dtype=torch.int64)
+    s = torch.as_tensor(slot).reshape(-1).to(device=bits.device, dtype=torch.int32)
+    if ids.numel() != s.numel():
+        raise ValueError("image_ids and slot must both be (P,)")
+    if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= bits.shape[0]):
+        raise ValueError("image_ids must name planes 0..%d" % (bits.shape[0] - 1))
+    have = ((s >= 0) & (s < 32))[:, None, None]
+    bit = torch.bitwise_right_shift(bits[ids], s.clamp(0, 31)[:, None, None]) & 1        # (arithmetic shift: the bit asked for is kept)
+    return ((bit != 0) & have).to(torch.uint8) * 255
+
+
+def _no_swap(augment):
+    if augment is not None and (np.asarray(augment.bg_index) >= 0).any():
+        raise ValueError("scene_training_batch: the plan swaps backgrounds (bg_index >= 0), which would erase the occluders -- "
+                         "render_scene composites the background itself: pass backgrounds / bg_index to it")
+
+
+def scene_training_batch(meshes, mesh_ids, R, t, cam_K, size, image_ids, p3d_xyz, visib_threshold=0.1, obj_ids=None, is_train=True,
+                         padding_ratio=1.5, crop_size_img=256, crop_size_gt=64, resize_method="crop_square_resize", augment=None,
+                         **scene_kw):
+    """A training batch of occluded synthetic scenes: render_scene(R, t, cam_K, meshes, size, image_ids, mesh_ids, **scene_kw), the
+    loader's filter visib_fract > visib_threshold (tools_for_BOP/bop_io.py:173-180, strict) over the rendered poses, then
+    targets.make_training_batch's body for the poses kept -- sample b's frame is its image's "rgb", its box its "bbox_visib", and the
+    two mask crops are cut from the bit planes (preprocess.get_roi_mask_bits): exactly make_training_batch on the expanded masks,
+    bit for bit, without the 2 P mask images.
+      cam_K (3,3) or (I,3,3) PER IMAGE; p3d_xyz (N,3) shared, (P,N,3) per pose, or with obj_ids (P,) the object table (n_obj,N,3);
+      augment: an augment.AugmentPlan of P samples, one per POSE (rows of the poses kept are used), whose samples ask for no
+      background swap (ValueError otherwise: the scene call composites the background itself -- scene_kw's backgrounds / bg_index);
+      is_train, padding_ratio, crop sizes, resize_method: make_training_batch's (is_train draws the box jitter from np.random).
+    -> (batch, kept): make_training_batch's 11 / 12 entries for the poses kept, and their indices (int64 numpy, ascending).
+    Only the per-pose ok, fractions and boxes pass through the host."""
+    from . import preprocess as PP
+    from . import targets
+    _no_swap(augment)
+    P = int((R.shape if hasattr(R, "shape") else np.asarray(R).shape)[0])
+    if augment is not None and augment.B != P:
+        raise ValueError("augment: a plan of one sample per pose (%d), got %d" % (P, augment.B))
+    Rt, tt = scene.poses_to_device("render", R, t)
+    sc = render_scene(Rt, tt, cam_K, meshes, size, image_ids, mesh_ids=mesh_ids, **scene_kw)
+    kept = scene_kept(sc["ok"].cpu().numpy(), sc["visib_fract"].cpu().numpy(), visib_threshold)
+    img = np.asarray(image_ids.cpu() if torch.is_tensor(image_ids) else image_ids).reshape(-1).astype(np.int64)[kept]
+    boxes = sc["bbox_visib"].cpu().numpy()[kept]
+    slot = sc["slot"].cpu().numpy()[kept]
+    dev, kept_d = Rt.device, torch.from_numpy(kept).to(Rt.device)
+    K = torch.as_tensor(cam_K).to(device=dev, dtype=torch.float64)
+    if K.dim() == 3:
+        K = K[torch.from_numpy(img).to(dev)]
+    p3 = p3d_xyz
+    if obj_ids is None and torch.as_tensor(p3d_xyz).dim() == 3:
+        p3 = torch.as_tensor(p3d_xyz)[kept_d.to(torch.as_tensor(p3d_xyz).device)]
+    oid = None if obj_ids is None else np.asarray(obj_ids.cpu() if torch.is_tensor(obj_ids) else obj_ids).reshape(-1)[kept]
+    plan = None if augment is None else augment.select(kept)
+    crop_masks = lambda grown: (PP.get_roi_mask_bits(sc["visib_bits"], slot, grown, crop_size_gt, resize_method, img_index=img),      # noqa: E731
+                                PP.get_roi_mask_bits(sc["full_bits"], slot, grown, crop_size_gt, resize_method, img_index=img))
+    batch = targets.batch_from_frames(sc["rgb"], crop_masks, Rt[kept_d], tt[kept_d], K, list(boxes), p3, is_train, padding_ratio,
+                                      crop_size_img, crop_size_gt, resize_method, img, oid, plan, None, None)
+    return batch, kept
+
+
+def scene_kept(ok, visib_fract, visib_threshold):
+    """bop_io's sample filter on render_scene's host-side labels: the ascending int64 indices of the poses that were rendered (ok) and
+    whose visib_fract is STRICTLY above the threshold (`visib_fract > train_obj_visible_theshold`, bop_io.py:173-180)"""
+    ok, fract = np.asarray(ok).reshape(-1).astype(bool), np.asarray(visib_fract, dtype=np.float64).reshape(-1)
+    return np.nonzero(ok & (fract > float(visib_threshold)))[0].astype(np.int64)
+
+
+def sample_scene_poses(rng, n_images, objects_per_image, cam_K, size, z_range, n_meshes):
+    """Poses for render_scene: objects_per_image objects in each of n_images images.
+    UNPINNED -- this is the project's OWN placement rule, not a restatement of any reference code (the reference trains on scenes that
+    BlenderProc / the BOP datasets placed): per pose, independently, the projected centre (u, v) is uniform in the frame [0, W) x
+    [0, H), Z is uniform in z_range = (near, far), t = Z K^-1 (u, v, 1), the rotation is uniform on SO(3) (a normalised Gaussian
+    quaternion), the mesh uniform among n_meshes.  Nothing keeps the objects from intersecting: the composite resolves depth per pixel.
+      rng: a numpy.random.Generator; cam_K (3,3) shared or (n_images,3,3); size: (width, height).
+    -> R (P,3,3), t (P,3,1) float64, image_ids (P,), mesh_ids (P,) int32 numpy arrays, P = n_images * objects_per_image, poses
+    interleaved across images (pose j lies in image j % n_images) -- the same seed gives the same arrays."""
+    n_img, per, M = int(n_images), int(objects_per_image), int(n_meshes)
+    W, H = scene.frame_size(size)
+    if n_img <= 0 or M <= 0 or not 1 <= per <= MAX_SCENE_POSES:
+        raise ValueError("n_images and n_meshes must be positive, objects_per_image in 1..%d" % MAX_SCENE_POSES)
+    z0, z1 = (float(v) for v in z_range)
+    if not (0.0 < z0 <= z1 and math.isfinite(z1)):
+        raise ValueError("z_range must be (near, far) with 0 < near <= far")
+    K = np.asarray(cam_K, dtype=np.float64)
+    if K.shape not in ((3, 3), (n_img, 3, 3)):
+        raise ValueError("cam_K must be (3,3) or (n_images,3,3)")
+    P = n_img * per
+    image_ids = (np.arange(P) % n_img).astype(np.int32)
+    Kp = np.broadcast_to(K, (n_img, 3, 3))[image_ids]
+    q = rng.normal(size=(P, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    R = np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w), 2 * (x * y + z * w), 1 - 2 * (x * x + z * z),
+                  2 * (y * z - x * w), 2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], 1).reshape(P, 3, 3)
+    u, v, Z = rng.uniform(0.0, W, size=P), rng.uniform(0.0, H, size=P), rng.uniform(z0, z1, size=P)
+    t = Z[:, None] * np.linalg.solve(Kp, np.stack([u, v, np.ones(P)], 1)[:, :, None])[:, :, 0]
+    mesh_ids = rng.integers(0, M, size=P).astype(np.int32)
+    return R, t.reshape(P, 3, 1), image_ids, mesh_ids

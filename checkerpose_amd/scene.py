@@ -8,7 +8,7 @@ into what a device call takes.  metric, gt_info, render, vis, bop_eval, coco_eva
   pack_poses, poses_to_device, upload_pose         R, t -> (B,12) float64; host poses to the device; one numpy pose to (1,3,3)
   camera, mesh_ids_on, image_ids_host / image_ids_on / depth_images / group_by_image, frame_size, kinds_mask      the shape helpers
   mesh_poses, as_meshset, as_symmetries            the pose + mesh prologue of the rendering calls; bare arrays / lists -> the containers
-  lighting, check_shaded_meshes, vec3              the shading arguments of render.render_rgb and vis.vis_poses
+  lighting, check_shaded_meshes, vec3, surf_colors_host      the shading arguments of render.render_rgb, vis.vis_poses and render.render_scene
 
 The shape helpers are plain tensor plumbing: they never ask whether a tensor is on a GPU (require_cuda is a call of its own), so
 they run on CPU tensors."""
@@ -515,3 +515,15 @@ def check_shaded_meshes(meshes, shading, who):
         raise ValueError("%s renders triangles: pass a MeshSet built with faces" % who)
     if shading == "phong" and meshes.normals is None:
         raise ValueError("phong shading needs vertex normals: MeshSet.from_arrays(..., normals=...)")
+
+
+def surf_colors_host(surf_colors, P):
+    """one colour per pose, or one for all, RGB in [0, 1] -> float64 (P,3) on the host; None stays None (the mesh's own colours)"""
+    if surf_colors is None:
+        return None
+    surf = np.asarray(surf_colors.cpu() if torch.is_tensor(surf_colors) else surf_colors, dtype=np.float64)
+    if surf.size == 3:
+        surf = np.tile(surf.reshape(1, 3), (P, 1))
+    if surf.shape != (P, 3) or not np.isfinite(surf).all():
+        raise ValueError("surf_colors must be (P,3) or one colour, all finite")
+    return surf

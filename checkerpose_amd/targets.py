@@ -8,6 +8,7 @@ per crop in Python (`test.py:388-389,432-457`).  Here:
 
   encode_targets       keypoints + K, R, t + the crops' final boxes -> roi_mask_bits / pixel_x_codes / pixel_y_codes (cp_encode_targets)
   make_training_batch  frames + masks + GT poses + boxes -> the loader's tuple for a batch (get_roi_batch x 3 + encode_targets)
+  batch_from_frames    its body, with the two mask crops as an argument (render.scene_training_batch cuts them from bit planes)
   code_report          network outputs + labels + GT mask crops -> test.py's per-crop code / mask figures and their integer counts
   pose_re_te           bop_toolkit_lib.pose_error.re / te, batched
   evaluate_batch       frames + boxes + GT -> everything test.py scores per crop; summarize_report -> its score lines
@@ -186,6 +187,19 @@ def make_training_batch(frames, masks_visib, masks_full, R, t, cam_K, Bboxes, p3
     mv, mf = _mask_images(masks_visib), _mask_images(masks_full)
     if tuple(mv.shape[1:3]) != (H, W) or tuple(mf.shape[1:3]) != (H, W):
         raise ValueError("masks must have the frames' height and width")
+    crop_masks = lambda grown: (PP.get_roi_batch(mv, grown, crop_size_gt, PP.INTER_NEAREST, resize_method, img_index=img_index),      # noqa: E731
+                                PP.get_roi_batch(mf, grown, crop_size_gt, PP.INTER_NEAREST, resize_method, img_index=img_index))
+    return batch_from_frames(frames, crop_masks, R, t, cam_K, Bboxes, p3d_xyz, is_train, padding_ratio, crop_size_img, crop_size_gt,
+                             resize_method, img_index, obj_ids, augment, backgrounds, mv[..., 0])
+
+
+def batch_from_frames(frames, crop_masks, R, t, cam_K, Bboxes, p3d_xyz, is_train, padding_ratio, crop_size_img, crop_size_gt,
+                      resize_method, img_index, obj_ids, augment, backgrounds, swap_masks):
+    """The body of make_training_batch, shared with render.scene_training_batch: everything but where the two mask crops come from.
+    frames: uint8 (n_img,H,W,3) on the device; crop_masks(grown boxes) -> (roi_mask, roi_entire), uint8 (B,S,S,1) INTER_NEAREST crops
+    of the visible and the full masks, called after the image crop; swap_masks: uint8 (n_img,H,W) for a plan's background swap, or
+    None when the plan asks for none.  The other arguments and the result are make_training_batch's."""
+    H, W = int(frames.shape[1]), int(frames.shape[2])
     if is_train:
         if any(b is None for b in Bboxes):
             raise ValueError("a training sample needs its ground-truth box")
@@ -200,10 +214,9 @@ def make_training_batch(frames, masks_visib, masks_full, R, t, cam_K, Bboxes, p3
         for b, box in enumerate(grown):
             if box is not None:                  # the window the crop reads (cp_crop_resize_u8): [x1, x2) x [y1, y2) inside the frame
                 wins[b] = PP.roi_window([int(v) for v in box], resize_method, W, H)[:4]
-        aug = AUG.augment_frames(frames, augment, masks=mv[..., 0], backgrounds=backgrounds, img_index=img_index, rects=wins)
+        aug = AUG.augment_frames(frames, augment, masks=swap_masks, backgrounds=backgrounds, img_index=img_index, rects=wins)
         roi_x = PP.get_roi_batch(aug, grown, crop_size_img, PP.INTER_LINEAR, resize_method, img_index=np.arange(len(grown)))
-    roi_mask = PP.get_roi_batch(mv, grown, crop_size_gt, PP.INTER_NEAREST, resize_method, img_index=img_index)
-    roi_entire = PP.get_roi_batch(mf, grown, crop_size_gt, PP.INTER_NEAREST, resize_method, img_index=img_index)
+    roi_mask, roi_entire = crop_masks(grown)
     final = [None if b is None else PP.get_final_Bbox(b, resize_method, W, H) for b in grown]
     lab = encode_targets(p3d_xyz, cam_K, R, t, final, crop_size_gt, obj_ids=obj_ids)
     dev = frames.device

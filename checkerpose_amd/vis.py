@@ -116,13 +116,7 @@ def vis_poses(R, t, cam_K, meshes, frames, image_ids=None, mesh_ids=None, surf_c
     if P <= 0:
         raise ValueError("no poses")
     ids, off, order = scene.group_by_image(image_ids, P, n_img)
-    surf = None
-    if surf_colors is not None:
-        surf = np.asarray(surf_colors.cpu() if torch.is_tensor(surf_colors) else surf_colors, dtype=np.float64)
-        if surf.size == 3:
-            surf = np.tile(surf.reshape(1, 3), (P, 1))
-        if surf.shape != (P, 3) or not np.isfinite(surf).all():
-            raise ValueError("surf_colors must be (P,3) or one colour, all finite")
+    surf = scene.surf_colors_host(surf_colors, P)
     if depth_diff:
         if depth is None:
             raise ValueError("depth_diff needs the sensor depth")

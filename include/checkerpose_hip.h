@@ -798,6 +798,44 @@ size_t cp_depth_diff_vis_scratch_bytes(int I, int H, int W);
 int cp_depth_diff_vis(cp_stream_t stream, const float* ren_depth, const float* depth, const int32_t* image_ids, int n_depth,
                       double delta, double s, int H, int W, int I, uint8_t* out, double* stats, uint8_t* diff_ok, void* scratch);
 
+/* Occluded multi-object training scenes with their labels on the device (next-row N19; csrc/scene_labels.hip): for I images and P poses
+ * at once, the composite colour and depth of every image over a background, and for every pose the content of scene_gt_info.json
+ * with that composite as the sensor depth, the 2 P mask images held as two bit planes per image.  Inputs follow cp_vis_poses (poses,
+ * per-IMAGE cam_K / k_stride, the mesh tables, colors, normals, surf_colors, image_of_pose, the img_off / pose_order CSR on the device
+ * and on the host); there are no frames.
+ * Slots.  The slot s of a pose is its rank among the poses of its image, in the order given (pose_order within [img_off[i],
+ *   img_off[i + 1])).  Poses that are not rendered keep their slot.  At most 32 poses per image (CP_ERR_RANGE otherwise).
+ * Composite.  depth fp32 (I,H,W) and the colour are exactly what cp_vis_poses produces with resolve != 0: per pose cp_render_rgb's frame
+ *   (ssaa 1); the front-most pose wins under the strict m_depth < ren_depth test: of equal depths the earlier pose keeps the pixel.
+ *   rgb uint8 (I,H,W,3) = the winner's colour where depth > 0; elsewhere backgrounds[bg_index[img]] (backgrounds uint8 (n_bg,H,W,3),
+ *   bg_index int32 (I); bg_index NULL: row img when n_bg == I, row 0 when n_bg == 1; a row outside [0, n_bg) falls back to bg_color), or,
+ *   with backgrounds NULL (then n_bg == 0 and bg_index NULL), the quantised bg_color (3 doubles ON THE HOST, cp_render_rgb's rounding).
+ *   bgr != 0 stores every pixel's channels reversed.
+ * Labels.  Exactly cp_gt_info's for every pose with the image's composite depth as the sensor depth: the same canvas x in [-W, 2W),
+ *   y in [-H, 2H) on the same tile origin, the same depth_im_to_dist_im_fast arithmetic, the same 'bop19' test
+ *   f32(dist_gt) - f32(dist_im) <= (float)delta.  counts int32 (P,3) = px_count_all, _valid, _visib; visib_fract fp64 (P); boxes int32
+ *   (P,2,4) = bbox_obj, bbox_visib as x, y, w, h, BOTH -1 unless px_count_visib > 0; ok uint8 (P).
+ *   A pose that cp_vis_poses does not render (a non-finite entry, a singular R, any vertex at Z <= 0, a bad mesh or image id, a
+ *   non-finite surface colour) has ok = 0, counts 0, fraction 0, boxes -1 and no bit.
+ * Bit planes.  full_bits and visib_bits uint32 (I,H,W): bit s of a pixel is set where the mask / mask_visib image of the pose at slot s
+ *   of that image would be 255: 8 bytes per pixel whatever P is.  slot int32 (P): each pose's slot (-1: its image id is out of range).
+ * Four launches whatever the data (pose, vertex, tile: a workgroup per (image, 32 x 32 canvas tile) -- margin tiles count coverage only,
+ * in-frame tiles make the composite depth in a first walk over the image's poses and the labels, bits and the owner's colour in a
+ * second --, finish).  Integer reductions only, no floating-point atomics; nothing allocates or synchronises; every output is
+ * bit-identical from call to call, for an image alone or in a batch, with or without backgrounds (the labels).
+ * CP_ERR_RANGE: more than 32 poses in an image, 2^24 workgroups or more in a launch, I * H * W * 3 or n_bg * H * W * 3 >= 2^31.
+ * scratch: cp_render_scene_scratch_bytes(P, Vmax, I) bytes -- P headers of 64 4-byte words, then cp_render_rgb's four float4 tables of
+ * (P, Vmax) --, 16-byte aligned. */
+size_t cp_render_scene_scratch_bytes(int P, int Vmax, int I);
+int cp_render_scene(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                    const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                    const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                    const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host, const int32_t* pose_order_host,
+                    const uint8_t* backgrounds, int n_bg, const int32_t* bg_index, const double* bg_color, int shading,
+                    double ambient_weight, const double* light_pos, double delta, int bgr, int H, int W, int P, int I, int Vmax,
+                    uint8_t* rgb, float* depth, uint32_t* full_bits, uint32_t* visib_bits, int32_t* slot, int32_t* counts,
+                    double* visib_fract, int32_t* boxes, uint8_t* ok, void* scratch);
+
 /* BOP's overlap errors on the device (next-row N12; csrc/mask_error.hip; reference bop_toolkit_lib/pose_error.py:235-330 cou_mask, cus,
  * cou_bb, cou_bb_proj with misc.calc_2d_bbox / misc.iou, misc.py:202-263): the four functions that close pose_error.py.
  * cp_mask_errors: for B pairs (estimate, ground truth) of one mesh each under one K, on a W x H frame,
@@ -1273,6 +1311,13 @@ int cp_u8hwc_to_nhwc_norm(cp_stream_t stream, int dtype, const uint8_t* in, void
  * out: (B, crop, crop, C) uint8, the operand of cp_u8hwc_to_nhwc_norm.  An empty roi gives a zero crop. */
 int cp_crop_resize_u8(cp_stream_t stream, const uint8_t* images, int n_img, int H, int W, int C, const int32_t* windows,
                       const int32_t* img_idx, uint8_t* out, int B, int crop, int interpolation);
+
+/* The same crop of ONE BIT of a uint32 plane (next-row N19: cp_render_scene's full_bits / visib_bits): out uint8 (B,crop,crop) is
+ * cp_crop_resize_u8's INTER_NEAREST crop -- its window, zero-padding and index arithmetic -- of the mask image
+ * (plane[img] >> bit[b]) & 1 ? 255 : 0, which is never stored.  plane uint32 (n_img,H,W); windows, img_idx as above; bit int32 (B) on
+ * the device.  An empty roi, or a bit outside 0..31, gives zeros. */
+int cp_crop_mask_bits(cp_stream_t stream, const uint32_t* plane, int n_img, int H, int W, const int32_t* windows,
+                      const int32_t* img_idx, const int32_t* bit, uint8_t* out, int B, int crop);
 
 /* Training-frame augmentation on the device (next-row N13; csrc/augment.hip; reference lm_dataset_pytorch.py:523-541 replace_bg and
  * GDR_Net_Augmentation.py:161-178 build_augmentations): background swap, salt-and-pepper, 5 x 5 motion blur, coarse dropout, 5-tap
