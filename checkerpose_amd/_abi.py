@@ -215,14 +215,20 @@ SIGNATURES = {
     "cp_gt_info_from_depth": (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, C.c_double, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_render_rgb_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_render_rgb": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_double, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "cp_render_rgb_tex": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_double, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P,
+                               _P, _P, _P, _P, _I]),
     "cp_vis_poses_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_vis_poses": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, C.c_double, _P, _P, _I, _I, _I, _I, _I, _I,
                           _I, _P, _P, _P, _P, _P, _P]),
+    "cp_vis_poses_tex": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, C.c_double, _P, _P, _I, _I, _I, _I, _I, _I,
+                              _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "cp_depth_diff_vis_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_depth_diff_vis": (_I, [_P, _P, _P, _P, _I, C.c_double, C.c_double, _I, _I, _I, _P, _P, _P, _P]),
     "cp_render_scene_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_render_scene": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, C.c_double, _P, C.c_double,
                              _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_render_scene_tex": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, C.c_double, _P, C.c_double,
+                                 _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "cp_coco_pack": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     "cp_coco_rle_count": (_I, [_P, _P, _I, _I, _I, _P]),
     "cp_coco_rle_write": (_I, [_P, _P, _I, _I, _I, _P, _P, _L]),

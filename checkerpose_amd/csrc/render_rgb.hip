@@ -22,6 +22,10 @@
 // the same arithmetic on it: the two are equal bit for bit.  The samples meet in LDS as integer sums (integer atomics: any order);
 // no high-resolution image is ever stored.
 //
+// Textures (row N20): with the texture tables of cp_render_rgb_tex the colour of a textured mesh's sample is its texel -- the rule at the
+// top of render_shade.h --; the tile launch is then rgb_tile_kernel<true> (the mesh, hence the colour source, is uniform over a
+// workgroup), and without them rgb_tile_kernel<false>: instruction for instruction the kernel this file always had.
+//
 // Launches (four, whatever the data and the options):
 //   rgb_pose_kernel     per pose: P = (K f)' [R | t] (vs_side_init), [R | t] and the normal matrix in fp32, validity, accumulators.
 //   rgb_vertex_kernel   per (pose, 256 vertices): the screen record and the rectangle (vs_vertex_chunk), the eye position, v_L, for
@@ -56,6 +60,7 @@ struct RrParams {
   float surf[3];
   int bg[3];                  // the quantised background
   int k_stride, M, B, Vmax, H, W, f, bgr, tx, ty, vchunks;
+  RrTex X;                    // the texture tables, all null without textures (last: the older fields keep their offsets)
 };
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_pose_kernel(RrParams p) {
@@ -81,6 +86,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_vertex_kernel(RrParams p) {
                   h + RrH::BAD(0), shading_records);
 }
 
+template <bool TEX>
 __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];
   __shared__ int s_n;
@@ -109,6 +115,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
   vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
   const int32_t* __restrict__ faces = p.faces + 3 * (size_t)ffirst;
   const size_t vbase = (size_t)b * p.Vmax;
+  const RrTexMesh tm = rr_tex_mesh(p.X, m, (size_t)vfirst, TEX);      // (uniform: one mesh per workgroup)
   float best[VS_PPL];
   int face[VS_PPL];
   vs_raster_tile<true>(s_tri, &s_n, p.T.sv + vbase, faces, F, V, c, best, face);
@@ -129,7 +136,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
     if (sx >= f * p.W || sy >= f * p.H) continue;
     int col[3] = {p.bg[0], p.bg[1], p.bg[2]};
     const bool cov = best[k] > 0.f;
-    if (cov) rr_shade(p.T, p.colors, p.surf, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, col);
+    if (cov) rr_shade<TEX>(p.T, p.colors, p.surf, tm, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, col);
     if (f == 1) {
       const size_t at = ((size_t)b * p.H + sy) * p.W + sx;
       p.rgb[3 * at + c0] = (uint8_t)col[0]; p.rgb[3 * at + 1] = (uint8_t)col[1]; p.rgb[3 * at + c2] = (uint8_t)col[2];
@@ -183,11 +190,12 @@ extern "C" size_t cp_render_rgb_scratch_bytes(int B, int Vmax) {
   return cp_align16_up((size_t)B * RR_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)B * Vmax * sizeof(float4));
 }
 
-extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
-                             const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
-                             const float* colors, const float* normals, const double* surf_color, const double* light_pos,
-                             double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B, int Vmax,
-                             uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch) {
+extern "C" int cp_render_rgb_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                                 const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                                 const float* colors, const float* normals, const double* surf_color, const double* light_pos,
+                                 double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B,
+                                 int Vmax, uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch,
+                                 const float* uv, const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter) {
   if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !surf_color || !light_pos || !bg_color || !rgb || !ok || !scratch)
     return CP_ERR_INVALID;
   if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
@@ -197,6 +205,7 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   if (shading == RR_PHONG && !normals) return CP_ERR_INVALID;
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (!(ambient_weight == ambient_weight) || __builtin_isinf(ambient_weight)) return CP_ERR_INVALID;
+  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
   for (int k = 0; k < 3; ++k)
     if (!__builtin_isfinite(surf_color[k]) || !__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(bg_color[k])) return CP_ERR_INVALID;
   if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(verts, 3) ||
@@ -208,6 +217,7 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   p.M = M; p.mesh_id = mesh_ids; p.colors = colors; p.normals = normals; p.rgb = rgb; p.depth = depth; p.mask = mask; p.boxes = boxes;
   p.ok = ok; p.B = B; p.Vmax = Vmax; p.H = H; p.W = W; p.f = ssaa; p.T.shading = shading; p.bgr = bgr ? 1 : 0;
   p.T.ambient = (float)ambient_weight;
+  p.X.uv = uv; p.X.texels = texels; p.X.off = tex_off; p.X.dims = tex_dims; p.X.filter = filter;
   for (int k = 0; k < 3; ++k) { p.surf[k] = (float)surf_color[k]; p.T.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
   const long long sw = (long long)ssaa * W, sh = (long long)ssaa * H;
   if (sw >= (1LL << 24) || sh >= (1LL << 24) || (long long)H * W >= (1LL << 31) / 3) return CP_ERR_RANGE;
@@ -224,7 +234,17 @@ extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const doub
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(rgb_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(rgb_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(rgb_tile_kernel, dim3(g.tile_blocks), dim3(VS_THREADS), 0, st, p);
+  RR_LAUNCH_TILE(rgb_tile_kernel, texels != nullptr, dim3(g.tile_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(rgb_finish_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   return cp_check_launch();
+}
+
+extern "C" int cp_render_rgb(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                             const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                             const float* colors, const float* normals, const double* surf_color, const double* light_pos,
+                             double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B, int Vmax,
+                             uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch) {
+  return cp_render_rgb_tex(stream, poses, cam_K, k_stride, verts, v_offsets, faces, f_offsets, M, mesh_ids, colors, normals, surf_color,
+                           light_pos, ambient_weight, bg_color, shading, ssaa, bgr, H, W, B, Vmax, rgb, depth, mask, boxes, ok, scratch,
+                           nullptr, nullptr, nullptr, nullptr, RR_NEAREST);
 }

@@ -7,7 +7,25 @@
 //   rr_pose_record                  a pose kernel's body: P = (K scale)' [R | t], [R | t] and the normal matrix in fp32, validity
 //   rr_vertex_record                per vertex, beside the screen record: the eye position, v_L and, for phong, v_normal
 //   RrTables, rr_shade              the shaded, quantised colour of one sample on one face.  The colour source is an argument: the
-//                                   mesh's vertex colours (interpolated), or one surface colour when `colors` is null
+//                                   mesh's texture (row N20: rr_texel, in rr_shade<true> only -- the tile kernels' <true> instantiations), its vertex colours
+//                                   (interpolated), or one surface colour when `colors` is null
+//   RrTex, RrTexMesh, rr_tex_mesh   the texture tables of a MeshSet and one mesh's view of them;  rr_tex_args: their host-side checks
+//
+// Texture rule (row N20; bop_toolkit_lib/renderer_py.py:309-352 add_object + the fragment shaders' texture2D(u_texture, v_texcoord), the
+// sampler pinned to the OpenGL specification's "Texture Minification / Magnification" rule, NOT to a driver's output).  Per mesh a
+// texture T, uint8 (Ht, Wt, 3) with rows in the image FILE's order (row 0 on top), held as one RGBX word per texel (r | g << 8 |
+// b << 16), and UVs fp32 (V, 2) = (texture_u, texture_v).  The reference uploads np.flipud(image) / 255: GL's texel row j is the file's
+// row Ht - 1 - j; the table stays in file order and the flip is in the index.  Per covered sample, on the winning face:
+//   (u, v) interpolated perspective-correctly with v_color's weights and v_color's expression, a + (w1 (c - a) + w2 (d - a));
+//   nearest:  i = clamp(floor(u * Wt), 0, Wt - 1),  j = clamp(floor(v * Ht), 0, Ht - 1),  texel = T[Ht - 1 - j, i];
+//   linear, clamp-to-edge:  a = u * Wt - 0.5,  i0 = floor(a),  alpha = a - i0,  i1 = i0 + 1, both clamped to [0, Wt - 1]; the same in
+//             v gives j0, j1, beta.  In fp32, per channel, on the BYTES as floats (no fused multiply-add), with t_ij = T[Ht - 1 - j, i]:
+//               lo = t_i0j0 + alpha * (t_i1j0 - t_i0j0);   hi = t_i0j1 + alpha * (t_i1j1 - t_i0j1);   texel = lo + beta * (hi - lo)
+//             (four equal texels give that texel exactly);
+//   colour = light_w * (texel / 255), the quotient a correctly rounded fp32 division; then rr_quant.
+// Wrap is clamp-to-edge only, there are no mipmaps, one filter per MeshSet.  The clamps are taken on the floats (NaN -> 0), so every
+// index lies inside the mesh's texture whatever the UVs hold.  Priority: a surface colour, then the texture, then the vertex colours,
+// then 0.5 grey.  UNPINNED: which filter vispy selects, a driver's fixed-point filtering, OpenGL's own output.
 #pragma once
 #include "vsd_raster.h"
 
@@ -18,6 +36,8 @@ using RrH = VsHdr<1>;
 constexpr int RR_HDR = 48;
 constexpr int RR_RT = RrH::USER, RR_NM = RR_RT + 12, RR_BOX = RR_NM + 12, RR_SK = RR_BOX + 4;
 enum { RR_FLAT = 0, RR_PHONG = 1 };
+enum { RR_NEAREST = 0, RR_LINEAR = 1 };
+constexpr int RR_TEX_SIDE = 16384;               // the largest side of a texture
 
 // round-half-even(255 v) of an fp32 colour value, clamped to 0..255 (NaN -> 0)
 __device__ __forceinline__ int rr_quant(float v) {
@@ -92,6 +112,77 @@ __device__ __forceinline__ void rr_vertex_record(const RrTables& T, const int32_
   }
 }
 
+// the texture tables of a MeshSet (all null without textures) and one mesh's view of them
+struct RrTex {
+  const float* uv;            // (sumV, 2), rows as verts
+  const uint32_t* texels;     // (sum Wt Ht) RGBX words, file row order
+  const int32_t* off;         // (M + 1) texel offsets
+  const int32_t* dims;        // (M, 2) = Wt, Ht; 0 0: the mesh has no texture
+  int filter;
+};
+struct RrTexMesh {
+  const float* uv;            // the mesh's first row
+  const uint32_t* tex;        // the mesh's first texel
+  int Wt, Ht, filter;         // Wt == 0: no texture
+};
+
+// mesh m's (first vertex row vfirst) view; `use` false (a surface colour overrides the texture) or no tables: Wt == 0
+__device__ __forceinline__ RrTexMesh rr_tex_mesh(const RrTex& X, int m, size_t vfirst, bool use) {
+  RrTexMesh t = {nullptr, nullptr, 0, 0, X.filter};
+  if (!use || !X.texels) return t;
+  const int Wt = X.dims[2 * m], Ht = X.dims[2 * m + 1];
+  if (Wt <= 0 || Ht <= 0 || Wt > RR_TEX_SIDE || Ht > RR_TEX_SIDE || X.off[m] < 0) return t;
+  t.uv = X.uv + 2 * vfirst; t.tex = X.texels + (size_t)X.off[m]; t.Wt = Wt; t.Ht = Ht;
+  return t;
+}
+
+// the host-side checks of the texture arguments of the three _tex entry points: all four tables or none, a known filter
+inline int rr_tex_args(const float* uv, const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter) {
+  if (filter != RR_NEAREST && filter != RR_LINEAR) return CP_ERR_INVALID;
+  const int given = (uv ? 1 : 0) + (texels ? 1 : 0) + (tex_off ? 1 : 0) + (tex_dims ? 1 : 0);
+  if (given != 0 && given != 4) return CP_ERR_INVALID;
+  if (cp_misaligned(uv, 3) || cp_misaligned(texels, 3) || cp_misaligned(tex_off, 3) || cp_misaligned(tex_dims, 3)) return CP_ERR_ALIGN;
+  return CP_OK;
+}
+
+// The tile launch of a shaded call: the kernel's <true> instantiation when the call has texture tables, else its <false> one -- the
+// code the rows N14 / N18 / N19 always had (identical instructions; the tables sit at the END of the params structs so that not even an
+// offset moves) -- recorded under the plain name the launch lists always showed.
+#define RR_LAUNCH_TILE(kernel, textured, ...)                                                          \
+  do {                                                                                                 \
+    if (textured) { cp_mark_kernel("%s", #kernel "<true>"); hipLaunchKernelGGL(kernel<true>, __VA_ARGS__); } \
+    else { cp_mark_kernel("%s", #kernel); hipLaunchKernelGGL(kernel<false>, __VA_ARGS__); }            \
+  } while (0)
+
+// an index of a texture axis of n texels from its float position: clamped to [0, n - 1] on the float (NaN -> 0)
+__device__ __forceinline__ int rr_tex_index(float f, int n) { return (int)fminf(fmaxf(f, 0.f), (float)(n - 1)); }
+
+// the texel of mesh texture t at (u, v) by the rule at the top of this file, as bytes in float (0..255), per channel
+__device__ __forceinline__ void rr_texel(const RrTexMesh& t, float u, float v, float (&rgb)[3]) {
+#pragma clang fp contract(off)
+  const float su = u * (float)t.Wt, sv = v * (float)t.Ht;
+  if (t.filter == RR_NEAREST) {                                        // (uniform)
+    const int i = rr_tex_index(floorf(su), t.Wt), j = rr_tex_index(floorf(sv), t.Ht);
+    const uint32_t w = t.tex[(size_t)(t.Ht - 1 - j) * t.Wt + i];
+    rgb[0] = (float)(w & 255u); rgb[1] = (float)((w >> 8) & 255u); rgb[2] = (float)((w >> 16) & 255u);
+    return;
+  }
+  const float a = su - 0.5f, b = sv - 0.5f;
+  const float fa = floorf(a), fb = floorf(b);
+  const float alpha = a - fa, beta = b - fb;
+  const int i0 = rr_tex_index(fa, t.Wt), i1 = rr_tex_index(fa + 1.0f, t.Wt);
+  const int j0 = rr_tex_index(fb, t.Ht), j1 = rr_tex_index(fb + 1.0f, t.Ht);
+  const size_t r0 = (size_t)(t.Ht - 1 - j0) * t.Wt, r1 = (size_t)(t.Ht - 1 - j1) * t.Wt;
+  const uint32_t w00 = t.tex[r0 + i0], w10 = t.tex[r0 + i1], w01 = t.tex[r1 + i0], w11 = t.tex[r1 + i1];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float t00 = (float)((w00 >> (8 * c)) & 255u), t10 = (float)((w10 >> (8 * c)) & 255u);
+    const float t01 = (float)((w01 >> (8 * c)) & 255u), t11 = (float)((w11 >> (8 * c)) & 255u);
+    const float lo = t00 + alpha * (t10 - t00), hi = t01 + alpha * (t11 - t01);
+    rgb[c] = lo + beta * (hi - lo);
+  }
+}
+
 __device__ __forceinline__ float rr_mix(float w0, float w1, float w2, float a, float c, float d) {
 #pragma clang fp contract(off)
   return (w0 * a + w1 * c) + w2 * d;
@@ -104,9 +195,11 @@ __device__ __forceinline__ float rr_mix_col(float w1, float w2, float a, float c
   return a + (w1 * (c - a) + w2 * (d - a));
 }
 
-// the shaded, quantised colour of the sample (qx, qy) (tile-relative indices) on face fidx; the colour is `colors` (rows from cbase,
-// interpolated) or, with colors == nullptr, the one colour `surf`
-__device__ __forceinline__ void rr_shade(const RrTables& T, const float* __restrict__ colors, const float (&surf)[3],
+// the shaded, quantised colour of the sample (qx, qy) (tile-relative indices) on face fidx; the colour is the texture `tm` (TEX and
+// tm.Wt > 0: uniform over the caller's workgroup), else `colors` (rows from cbase, interpolated) or, with colors == nullptr, the one
+// colour `surf`.  rr_shade<false> is the code the rows N14 / N18 / N19 always had.
+template <bool TEX>
+__device__ __forceinline__ void rr_shade(const RrTables& T, const float* __restrict__ colors, const float (&surf)[3], const RrTexMesh& tm,
                                          const int32_t* __restrict__ h, const int32_t* __restrict__ faces, size_t vbase, size_t cbase,
                                          int fidx, float fx0, float fy0, float qx, float qy, int (&out)[3]) {
 #pragma clang fp contract(off)
@@ -122,6 +215,13 @@ __device__ __forceinline__ void rr_shade(const RrTables& T, const float* __restr
   const float p0 = e0 * a.w, p1 = e1 * c.w, p2 = e2 * d.w;
   const float ps = (p0 + p1) + p2;
   const float w0 = p0 / ps, w1 = p1 / ps, w2 = p2 / ps;
+  float tx[3] = {0.f, 0.f, 0.f};
+  if (TEX && tm.Wt > 0) {                                              // (the texel first: three values live through the lighting)
+    const float* __restrict__ ua = tm.uv + 2 * (size_t)i0;
+    const float* __restrict__ uc = tm.uv + 2 * (size_t)i1;
+    const float* __restrict__ ud = tm.uv + 2 * (size_t)i2;
+    rr_texel(tm, rr_mix_col(w1, w2, ua[0], uc[0], ud[0]), rr_mix_col(w1, w2, ua[1], uc[1], ud[1]), tx);
+  }
   const float4 la = T.vl[vbase + i0], lc = T.vl[vbase + i1], ld = T.vl[vbase + i2];
   const float lx = rr_mix(w0, w1, w2, la.x, lc.x, ld.x), ly = rr_mix(w0, w1, w2, la.y, lc.y, ld.y), lz = rr_mix(w0, w1, w2, la.z, lc.z, ld.z);
   float nx, ny, nz;
@@ -140,7 +240,9 @@ __device__ __forceinline__ void rr_shade(const RrTables& T, const float* __restr
   float lw = T.ambient + (dt > 0.f ? dt : 0.f);                        // (NaN from a zero-length vector: no diffuse term)
   if (lw > 1.0f) lw = 1.0f;
   float r = surf[0], g = surf[1], bl = surf[2];
-  if (colors) {
+  if (TEX && tm.Wt > 0) {
+    r = tx[0] / 255.0f; g = tx[1] / 255.0f; bl = tx[2] / 255.0f;
+  } else if (colors) {
     const float* __restrict__ ca = colors + 3 * (cbase + i0);
     const float* __restrict__ cc = colors + 3 * (cbase + i1);
     const float* __restrict__ cd = colors + 3 * (cbase + i2);

@@ -15,6 +15,10 @@
 //   A pose that cp_vis_poses does not render (a non-finite entry, a singular R, any vertex at Z <= 0, a bad mesh or image id, a
 //   non-finite surface colour) is skipped: ok = 0, counts 0, fraction 0, boxes -1, its bits 0.
 //
+// Textures (row N20, cp_render_scene_tex): the owner's colour is its mesh's texel by render_shade.h's rule; the tile launch is then
+// scene_tile_kernel<true> (the colour source is uniform per iteration of the pose loop), without textures scene_tile_kernel<false>:
+// instruction for instruction the kernel this file always had.
+//
 // Launches (four, whatever the data):
 //   scene_pose_kernel     per pose: render_shade.h's header under the pose's IMAGE's K, validity, its slot, the accumulators initialised.
 //   scene_vertex_kernel   per (pose, 256 vertices): cp_render_rgb's records; the pixel rectangle clamped to the CANVAS (gt_info's).
@@ -74,6 +78,7 @@ struct SlParams {
   float delta;
   int bg[3];                  // the quantised bg_color
   int k_stride, M, P, I, Vmax, H, W, n_bg, bgr, tx, ty, x0, y0, vchunks;
+  RrTex X;                    // the texture tables, all null without textures (last: the older fields keep their offsets)
 };
 
 // the image's rows of the CSR, clamped to [0, P] and to SL_MAX_POSES rows (the host checked them; the clamps bound the loops and the
@@ -140,7 +145,10 @@ __device__ __forceinline__ uint32_t sl_hits(const SlParams& p, int j0, int j1, i
 
 // (held to 3 waves per SIMD: left alone hipcc takes 174 VGPRs, 6 above what 3 waves allow; with the bound it takes 161, still without
 // scratch, and a full device measured the call at 1.37 ms against 1.80 ms -- profiles/scene_bench.json)
-__global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) void scene_tile_kernel(SlParams p) {
+// (the <true> instantiation needs the texel's words and blend weights on top: held to 3 waves it takes 168 VGPRs and 28 to 40 bytes of
+// scratch per lane, so it is allowed 2 waves and takes them without scratch; the <false> one keeps its bound and its 161 VGPRs)
+template <bool TEX>
+__global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(TEX ? 2 : 3, 3))) void scene_tile_kernel(SlParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];
   __shared__ int s_n;
   __shared__ int s_canvas[VS_WAVES][SL_NCANVAS];
@@ -224,6 +232,7 @@ __global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       colors = nullptr;
       for (int k = 0; k < 3; ++k) surf[k] = (float)p.surf[3 * (size_t)b + k];
     }
+    const RrTexMesh tm = rr_tex_mesh(p.X, m, (size_t)vfirst, TEX && !p.surf);      // (uniform: one mesh per iteration)
     int acc_c[SL_NCANVAS], acc_f[SL_NFRAME];
 #pragma unroll
     for (int k = 0; k < SL_NCANVAS; ++k) acc_c[k] = vs_acc_identity<1>(k);
@@ -253,7 +262,7 @@ __global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       if (dg == ren[k] && !((owned >> k) & 1u)) {                    // the first pose in order at the composite's depth
         owned |= 1u << k;
         int q[3];
-        rr_shade(p.T, colors, surf, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, q);
+        rr_shade<TEX>(p.T, colors, surf, tm, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, q);
         col[k] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16);
       }
     }
@@ -312,15 +321,16 @@ extern "C" size_t cp_render_scene_scratch_bytes(int P, int Vmax, int I) {
   return cp_align16_up((size_t)P * SL_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)P * Vmax * sizeof(float4));
 }
 
-extern "C" int cp_render_scene(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
-                               const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
-                               const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
-                               const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host,
-                               const int32_t* pose_order_host, const uint8_t* backgrounds, int n_bg, const int32_t* bg_index,
-                               const double* bg_color, int shading, double ambient_weight, const double* light_pos, double delta, int bgr,
-                               int H, int W, int P, int I, int Vmax, uint8_t* rgb, float* depth, uint32_t* full_bits,
-                               uint32_t* visib_bits, int32_t* slot, int32_t* counts, double* visib_fract, int32_t* boxes, uint8_t* ok,
-                               void* scratch) {
+extern "C" int cp_render_scene_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                                   const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                                   const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                                   const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host,
+                                   const int32_t* pose_order_host, const uint8_t* backgrounds, int n_bg, const int32_t* bg_index,
+                                   const double* bg_color, int shading, double ambient_weight, const double* light_pos, double delta,
+                                   int bgr, int H, int W, int P, int I, int Vmax, uint8_t* rgb, float* depth, uint32_t* full_bits,
+                                   uint32_t* visib_bits, int32_t* slot, int32_t* counts, double* visib_fract, int32_t* boxes, uint8_t* ok,
+                                   void* scratch, const float* uv, const uint32_t* texels, const int32_t* tex_off,
+                                   const int32_t* tex_dims, int filter) {
   if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !image_of_pose || !img_off || !pose_order || !img_off_host ||
       !pose_order_host || !bg_color || !light_pos || !rgb || !depth || !full_bits || !visib_bits || !slot || !counts || !visib_fract ||
       !boxes || !ok || !scratch)
@@ -332,6 +342,7 @@ extern "C" int cp_render_scene(cp_stream_t stream, const double* poses, const do
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (backgrounds ? (n_bg <= 0 || (!bg_index && n_bg != 1 && n_bg != I)) : (n_bg != 0 || bg_index)) return CP_ERR_INVALID;
   if (!__builtin_isfinite(ambient_weight)) return CP_ERR_INVALID;
+  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
   for (int k = 0; k < 3; ++k)
     if (!__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(bg_color[k])) return CP_ERR_INVALID;
   if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(surf_colors, 7) ||
@@ -361,6 +372,7 @@ extern "C" int cp_render_scene(cp_stream_t stream, const double* poses, const do
   p.depth = depth; p.full_bits = full_bits; p.visib_bits = visib_bits; p.slot = slot; p.counts = counts; p.fract = visib_fract;
   p.boxes = boxes; p.ok = ok; p.P = P; p.I = I; p.Vmax = Vmax; p.H = H; p.W = W; p.bgr = bgr; p.delta = (float)delta;
   p.T.shading = shading; p.T.ambient = (float)ambient_weight;
+  p.X.uv = uv; p.X.texels = texels; p.X.off = tex_off; p.X.dims = tex_dims; p.X.filter = filter;
   for (int k = 0; k < 3; ++k) { p.T.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
   p.tx = gi.tx; p.ty = gi.ty; p.x0 = gi.x0; p.y0 = gi.y0; p.vchunks = gp.vchunks;
   char* at = (char*)scratch;
@@ -373,7 +385,22 @@ extern "C" int cp_render_scene(cp_stream_t stream, const double* poses, const do
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(scene_pose_kernel, dim3(gp.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(scene_vertex_kernel, dim3(gp.vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(scene_tile_kernel, dim3(gi.tile_blocks), dim3(VS_THREADS), 0, st, p);
+  RR_LAUNCH_TILE(scene_tile_kernel, texels != nullptr, dim3(gi.tile_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(scene_finish_kernel, dim3(gp.pose_blocks), dim3(VS_THREADS), 0, st, p);
   return cp_check_launch();
+}
+
+extern "C" int cp_render_scene(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                               const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                               const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                               const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host,
+                               const int32_t* pose_order_host, const uint8_t* backgrounds, int n_bg, const int32_t* bg_index,
+                               const double* bg_color, int shading, double ambient_weight, const double* light_pos, double delta, int bgr,
+                               int H, int W, int P, int I, int Vmax, uint8_t* rgb, float* depth, uint32_t* full_bits,
+                               uint32_t* visib_bits, int32_t* slot, int32_t* counts, double* visib_fract, int32_t* boxes, uint8_t* ok,
+                               void* scratch) {
+  return cp_render_scene_tex(stream, poses, cam_K, k_stride, verts, v_offsets, faces, f_offsets, M, mesh_ids, colors, normals, surf_colors,
+                             image_of_pose, img_off, pose_order, img_off_host, pose_order_host, backgrounds, n_bg, bg_index, bg_color,
+                             shading, ambient_weight, light_pos, delta, bgr, H, W, P, I, Vmax, rgb, depth, full_bits, visib_bits, slot,
+                             counts, visib_fract, boxes, ok, scratch, nullptr, nullptr, nullptr, nullptr, RR_NEAREST);
 }

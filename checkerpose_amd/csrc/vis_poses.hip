@@ -6,7 +6,8 @@
 // The rule, per image, poses in the order given (pose_order within [img_off[i], img_off[i + 1])):
 //   m_rgb, m_depth of a pose = cp_render_rgb(ssaa 1, background 0 0 0, depth asked) of that pose alone, bit for bit: vsd_raster.h's
 //   walk (vs_raster_tile<true>) on the same tile grid and render_shade.h's rr_shade, with the pose's own surface colour (surf_colors
-//   row) or the mesh's colours;
+//   row), the mesh's texture (row N20, cp_vis_poses_tex: render_shade.h's rule; the tile launch is then vis_scene_tile_kernel<true>, the
+//   colour source uniform per iteration of the pose loop) or the mesh's colours;
 //   ren_rgb = 0, ren_depth = 0;  m = m_depth != 0 and (ren_depth == 0 or m_depth < ren_depth) on the fp32 depths (strict: of two
 //   equal depths the earlier pose keeps the pixel);  ren_depth[m] = m_depth;
 //   resolve != 0: ren_rgb[m] = m_rgb;   resolve == 0: ren_rgb = min(255, ren_rgb + m_rgb) as integers;
@@ -65,6 +66,7 @@ struct VpParams {
   RrTables T;
   int box_q[3];               // int(c * 255) of box_color
   int k_stride, M, P, I, Vmax, H, W, resolve, draw_boxes, tx, ty, vchunks;
+  RrTex X;                    // the texture tables, all null without textures (last: the older fields keep their offsets)
 };
 
 __global__ __launch_bounds__(VS_THREADS) void vis_pose_kernel(VpParams p) {
@@ -100,6 +102,7 @@ __device__ __forceinline__ void vp_image_rows(const VpParams& p, int img, int& j
   j1 = min(max(p.img_off[img + 1], j0), p.P);
 }
 
+template <bool TEX>
 __global__ __launch_bounds__(VS_THREADS) void vis_scene_tile_kernel(VpParams p) {
   __shared__ float4 s_tri[VS_CHUNK][4];
   __shared__ int s_n;
@@ -131,6 +134,7 @@ __global__ __launch_bounds__(VS_THREADS) void vis_scene_tile_kernel(VpParams p) 
       colors = nullptr;
       for (int k = 0; k < 3; ++k) surf[k] = (float)p.surf[3 * (size_t)b + k];
     }
+    const RrTexMesh tm = rr_tex_mesh(p.X, m, (size_t)vfirst, TEX && !p.surf);      // (uniform: one mesh per iteration)
     int acc[4] = {INT_MAX, INT_MAX, INT_MIN, INT_MIN};
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k) {
@@ -138,7 +142,7 @@ __global__ __launch_bounds__(VS_THREADS) void vis_scene_tile_kernel(VpParams p) 
       const int sx = ox + lx, sy = oy + ly;
       if (sx >= p.W || sy >= p.H || !(best[k] > 0.f)) continue;
       int q[3];
-      rr_shade(p.T, colors, surf, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, q);
+      rr_shade<TEX>(p.T, colors, surf, tm, h, faces, vbase, (size_t)vfirst, face[k], fx0, fy0, (float)lx, (float)ly, q);
       const float md = vs_depth_of(best[k]);
       const bool front = md != 0.f && (dep[k] == 0.f || md < dep[k]);
       if (front) dep[k] = md;
@@ -388,13 +392,14 @@ extern "C" size_t cp_vis_poses_scratch_bytes(int P, int Vmax, int I) {
   return cp_align16_up((size_t)P * RR_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)P * Vmax * sizeof(float4));
 }
 
-extern "C" int cp_vis_poses(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
-                            const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
-                            const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
-                            const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host,
-                            const int32_t* pose_order_host, const uint8_t* frames, int shading, double ambient_weight,
-                            const double* light_pos, const double* box_color, int resolve, int draw_boxes, int H, int W, int P, int I,
-                            int Vmax, uint8_t* vis, uint8_t* ren_rgb, float* ren_depth, int32_t* boxes, uint8_t* ok, void* scratch) {
+extern "C" int cp_vis_poses_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                                const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                                const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                                const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host,
+                                const int32_t* pose_order_host, const uint8_t* frames, int shading, double ambient_weight,
+                                const double* light_pos, const double* box_color, int resolve, int draw_boxes, int H, int W, int P, int I,
+                                int Vmax, uint8_t* vis, uint8_t* ren_rgb, float* ren_depth, int32_t* boxes, uint8_t* ok, void* scratch,
+                                const float* uv, const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter) {
   if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !image_of_pose || !img_off || !pose_order || !img_off_host ||
       !pose_order_host || !frames || !light_pos || !box_color || !vis || !ren_rgb || !ren_depth || !boxes || !ok || !scratch)
     return CP_ERR_INVALID;
@@ -404,6 +409,7 @@ extern "C" int cp_vis_poses(cp_stream_t stream, const double* poses, const doubl
   if ((resolve != 0 && resolve != 1) || (draw_boxes != 0 && draw_boxes != 1)) return CP_ERR_INVALID;
   if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (!__builtin_isfinite(ambient_weight)) return CP_ERR_INVALID;
+  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
   for (int k = 0; k < 3; ++k)
     if (!__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(box_color[k])) return CP_ERR_INVALID;
   if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(surf_colors, 7) ||
@@ -430,6 +436,7 @@ extern "C" int cp_vis_poses(cp_stream_t stream, const double* poses, const doubl
   p.img_off = img_off; p.pose_order = pose_order; p.frames = frames; p.vis = vis; p.ren_rgb = ren_rgb; p.ren_depth = ren_depth;
   p.boxes = boxes; p.ok = ok; p.P = P; p.I = I; p.Vmax = Vmax; p.H = H; p.W = W; p.resolve = resolve; p.draw_boxes = draw_boxes;
   p.T.shading = shading; p.T.ambient = (float)ambient_weight;
+  p.X.uv = uv; p.X.texels = texels; p.X.off = tex_off; p.X.dims = tex_dims; p.X.filter = filter;
   for (int k = 0; k < 3; ++k) {
     p.T.light[k] = (float)light_pos[k];
     const double q = box_color[k] * 255.0;                            // int(c * 255): truncation, then the uint8 range
@@ -446,9 +453,22 @@ extern "C" int cp_vis_poses(cp_stream_t stream, const double* poses, const doubl
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(vis_pose_kernel, dim3(gp.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(vis_vertex_kernel, dim3(gp.vert_blocks), dim3(VS_THREADS), 0, st, p);
-  CP_LAUNCH(vis_scene_tile_kernel, dim3(gi.tile_blocks), dim3(VS_THREADS), 0, st, p);
+  RR_LAUNCH_TILE(vis_scene_tile_kernel, texels != nullptr, dim3(gi.tile_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(vis_finish_kernel, dim3((unsigned)finish_blocks), dim3(VS_THREADS), 0, st, p);
   return cp_check_launch();
+}
+
+extern "C" int cp_vis_poses(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                            const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                            const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                            const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host,
+                            const int32_t* pose_order_host, const uint8_t* frames, int shading, double ambient_weight,
+                            const double* light_pos, const double* box_color, int resolve, int draw_boxes, int H, int W, int P, int I,
+                            int Vmax, uint8_t* vis, uint8_t* ren_rgb, float* ren_depth, int32_t* boxes, uint8_t* ok, void* scratch) {
+  return cp_vis_poses_tex(stream, poses, cam_K, k_stride, verts, v_offsets, faces, f_offsets, M, mesh_ids, colors, normals, surf_colors,
+                          image_of_pose, img_off, pose_order, img_off_host, pose_order_host, frames, shading, ambient_weight, light_pos,
+                          box_color, resolve, draw_boxes, H, W, P, I, Vmax, vis, ren_rgb, ren_depth, boxes, ok, scratch, nullptr, nullptr,
+                          nullptr, nullptr, RR_NEAREST);
 }
 
 extern "C" size_t cp_depth_diff_vis_scratch_bytes(int I, int H, int W) {

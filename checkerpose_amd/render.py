@@ -27,8 +27,16 @@ project's statement of cv2.resize(INTER_AREA)'s integer-factor path on 8-bit ima
 
 UNPINNED: (1) OpenGL's own output -- the shaders are GLSL and run nowhere this project runs, so the shading is pinned to the rule
 read from them (tests/render_rgb_stages.py, float64), as the depth render of row N8 is; (2) cv2's INTER_AREA -- cv2 is not
-available to the tests, as for the resize of row N3; (3) textured models (`texture_file` / `texture_uv`) are out of scope: GL's
-sampler rule cannot be read from the shader.  Specular terms, the C++ and vispy renderers, PLY reading and PNG writing are not here.
+available to the tests, as for the resize of row N3.  Specular terms, the C++ and vispy renderers, PLY reading and PNG writing are
+not here.
+
+Textures (row N20; stated in csrc/render_shade.h): a MeshSet built with textures= / uvs= colours a textured mesh's sample by its
+texel -- (u, v) interpolated perspective-correctly like v_color, then the OpenGL specification's sampler rule with clamp-to-edge and no
+mipmaps: "nearest" texel = T[Ht - 1 - clamp(floor(v Ht))][clamp(floor(u Wt))] (the reference uploads np.flipud(image)), "linear" the
+bilinear blend about (u Wt - 0.5, v Ht - 0.5) -- and colour = light_w * (texel / 255).  add_object's order holds: surf_color, then the
+texture, then vertex colours, then grey.  The filter lives on the MeshSet.  UNPINNED: which filter vispy selects for its Texture2D,
+a driver's fixed-point filtering (GL implementations blend with a few fractional bits), OpenGL's own output, and the quantisation
+of float textures to bytes (MeshSet.from_arrays).
 
 The MeshSet and the handling of poses, camera, mesh ids, frame size and the light are checkerpose_amd/scene.py's (shared with
 vis.vis_poses); the depth rasteriser alone is metric.render_depth.
@@ -79,6 +87,7 @@ def render_rgb(R, t, cam_K, meshes, size, mesh_ids=None, shading="phong", ambien
         surf_c, colors = scene.vec3(surf_color, "surf_color"), None
     else:
         surf_c = scene.vec3((0.5, 0.5, 0.5), "surf_color")
+    tex = meshes.textures_on(dev, use=surf_color is None)
     if out is None:
         out = torch.empty((B, H, W, 3), dtype=torch.uint8, device=dev)
     elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.uint8 and tuple(out.shape) == (B, H, W, 3)
@@ -92,8 +101,9 @@ def render_rgb(R, t, cam_K, meshes, size, mesh_ids=None, shading="phong", ambien
     if return_boxes:
         res["boxes"] = torch.empty((B, 4), dtype=torch.int32, device=dev)
     scratch = torch.empty(_abi.load().cp_render_rgb_scratch_bytes(B, vmax), dtype=torch.uint8, device=dev)
-    _abi.call("cp_render_rgb", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, colors, normals, surf_c, light_c, amb,
-              bg_c, shade, ssaa, 1 if bgr else 0, H, W, B, vmax, out, res.get("depth"), res.get("mask"), res.get("boxes"), res["ok"], scratch)
+    _abi.call("cp_render_rgb_tex", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, colors, normals, surf_c, light_c, amb,
+              bg_c, shade, ssaa, 1 if bgr else 0, H, W, B, vmax, out, res.get("depth"), res.get("mask"), res.get("boxes"), res["ok"], scratch,
+              *tex)
     return res
 
 
@@ -352,10 +362,10 @@ def render_scene(R, t, cam_K, meshes, size, image_ids, mesh_ids=None, n_images=N
     full, visib, slot, counts, boxes = i32(n_img, H, W), i32(n_img, H, W), i32(P), i32(P, 3), i32(P, 2, 4)
     fract, ok = torch.empty((P,), dtype=torch.float64, device=dev), torch.empty((P,), dtype=torch.uint8, device=dev)
     scratch = torch.empty(_abi.load().cp_render_scene_scratch_bytes(P, vmax, n_img), dtype=torch.uint8, device=dev)
-    _abi.call("cp_render_scene", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), mids, colors, normals, surf_d, ids_d, off_d,
+    _abi.call("cp_render_scene_tex", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), mids, colors, normals, surf_d, ids_d, off_d,
               order_d, off.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), bg_d, 0 if bg_d is None else int(bg_d.shape[0]),
               bg_idx_d, bg_c, shade, amb, light_c, float(delta), 1 if bgr else 0, H, W, P, n_img, vmax, rgb, depth, full, visib, slot, counts,
-              fract, boxes, ok, scratch)
+              fract, boxes, ok, scratch, *meshes.textures_on(dev, use=surf is None))
     out = {"rgb": rgb, "depth": depth, "full_bits": full, "visib_bits": visib, "slot": slot}
     out.update(gt_info.label_dict(counts, fract, boxes, ok, None, None))
     return out

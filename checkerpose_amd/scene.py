@@ -130,6 +130,77 @@ def _normal_rule(n, a):
     return np.ascontiguousarray(n, dtype=np.float32)
 
 
+TEX_FILTERS = {"nearest": 0, "linear": 1}
+TEX_MAX_SIDE = 16384
+
+
+def _texture_rule(t, _):
+    """one mesh's texture -> uint8 (Ht, Wt, 3) in the file's row order, or None"""
+    if t is None:
+        return None
+    if t.ndim != 3 or t.shape[2] not in (3, 4):
+        raise ValueError("a texture must be an (Ht, Wt, 3 | 4) array, got %r" % (t.shape,))
+    if min(t.shape[:2]) < 1 or max(t.shape[:2]) > TEX_MAX_SIDE:
+        raise ValueError("a texture's sides must lie in 1..%d, got %r" % (TEX_MAX_SIDE, t.shape[:2]))
+    t = t[:, :, :3]
+    if t.dtype == np.uint8:
+        return np.ascontiguousarray(t)
+    if not np.issubdtype(t.dtype, np.floating) and not np.issubdtype(t.dtype, np.integer):
+        raise ValueError("a texture must hold uint8 or float values, got %s" % t.dtype)
+    f = t.astype(np.float64)
+    if not np.isfinite(f).all() or f.min() < 0.0:
+        raise ValueError("a texture must hold finite values >= 0")
+    if f.max() > 1.0:
+        if f.max() > 255.0 or (f != np.rint(f)).any():
+            raise ValueError("a texture whose largest value is > 1 must hold whole numbers in 0..255")
+        return np.ascontiguousarray(f.astype(np.uint8))
+    return np.ascontiguousarray(np.rint(255.0 * f).astype(np.uint8))     # UNPINNED: the project's own quantisation (half to even)
+
+
+def _uv_rule(u, a):
+    if u is None:
+        return None
+    if u.ndim != 2 or u.shape != (a.shape[0], 2):
+        raise ValueError("uvs must be (V, 2) like the vertices, got %r" % (u.shape,))
+    u = np.ascontiguousarray(u, dtype=np.float32)
+    if not np.isfinite(u).all():
+        raise ValueError("uvs must be finite")
+    return u
+
+
+def _texture_tables(textures, uvs, tex_filter, single, host):
+    """MeshSet.from_arrays' texture arguments -> (uv (sumV,2) float32, texels (sum Wt Ht,) int32 RGBX words, offsets (M+1,) int32,
+    dims (M,2) int32 = Wt, Ht) as CPU tensors, or None without textures"""
+    if tex_filter not in TEX_FILTERS:
+        raise ValueError("tex_filter must be \"nearest\" or \"linear\", got %r" % (tex_filter,))
+    M = len(host)
+    if textures is None:
+        if uvs is not None and any(u is not None for u in ([uvs] if single and _is_array(uvs) else list(uvs))):
+            raise ValueError("uvs without a texture")
+        return None
+    tex = _per_mesh(textures, single and _is_array(textures) and np.ndim(textures) == 3, _texture_rule, host,
+                    "need one texture (or None) per mesh", none_ok=True)
+    uv = _per_mesh([None] * M if uvs is None else uvs, single, _uv_rule, host, "need one uv array (or None) per mesh", none_ok=True)
+    for m in range(M):
+        if (tex[m] is None) != (uv[m] is None):
+            raise ValueError("mesh %d: %s" % (m, "a texture without uvs" if uv[m] is None else "uvs without a texture"))
+    if all(t is None for t in tex):
+        return None
+    off = np.zeros(M + 1, dtype=np.int64)
+    off[1:] = np.cumsum([0 if t is None else t.shape[0] * t.shape[1] for t in tex])
+    if off[-1] >= 2 ** 31:
+        raise ValueError("the textures hold %d texels: 2^31 or more" % off[-1])
+    dims = np.array([(0, 0) if t is None else (t.shape[1], t.shape[0]) for t in tex], dtype=np.int32)
+    words = np.zeros(int(off[-1]), dtype=np.uint32)
+    for m, t in enumerate(tex):
+        if t is not None:
+            w = t.astype(np.uint32)
+            words[off[m]:off[m + 1]] = (w[:, :, 0] | (w[:, :, 1] << 8) | (w[:, :, 2] << 16)).reshape(-1)
+    uvt = np.concatenate([np.zeros((a.shape[0], 2), dtype=np.float32) if uv[m] is None else uv[m] for m, a in enumerate(host)], 0)
+    return (torch.from_numpy(np.ascontiguousarray(uvt)), torch.from_numpy(words.view(np.int32)), torch.from_numpy(off.astype(np.int32)),
+            torch.from_numpy(dims))
+
+
 def _table(arrays):
     return torch.from_numpy(np.ascontiguousarray(np.concatenate(arrays, 0)))
 
@@ -150,9 +221,13 @@ class MeshSet:
         self._dev = {}
         self._dev_faces = {}
         self._dev_shading = {}
+        self.uvs = self.texels = self.tex_offsets = self.tex_dims = None     # the texture tables (row N20), set by from_arrays
+        self.tex_filter = "nearest"         # lives on the MeshSet, as GL keeps it on the texture object
+        self._dev_tex = {}
 
     @classmethod
-    def from_arrays(cls, arrays, diameters=None, faces=None, device=None, colors=None, normals=None):
+    def from_arrays(cls, arrays, diameters=None, faces=None, device=None, colors=None, normals=None, uvs=None, textures=None,
+                    tex_filter="nearest"):
         """arrays: a list of (V_m, 3) arrays / tensors (or ONE such array); diameters: one per mesh, or None = computed as the
         reference does (largest pairwise distance of the vertices) -- on the host, or with `device` on that device
         (prepare.pts_diameters: the same bits); faces: None, or one (F_m, 3) integer array of vertex indices
@@ -160,7 +235,14 @@ class MeshSet:
         colors: None, or per mesh a (V_m, 3) uint8 / float array of vertex colours or None (that mesh is 0.5 grey) -- as
         renderer_py's add_object takes them: a mesh whose largest value is > 1 is divided by 255 (in float32);
         normals: None, or one (V_m, 3) float array per mesh (every mesh): render.render_rgb's phong shading.
-        With both None the object is what it was before these arguments existed."""
+        With both None the object is what it was before these arguments existed.
+        textures: None, or per mesh None or an (Ht, Wt, 3 | 4) image in the FILE's row order (row 0 on top, as inout.load_im gives it;
+        alpha is dropped; sides 1..16384, fewer than 2^31 texels in all): uint8 as it is; floats whose largest value is > 1 must be
+        whole numbers in 0..255; floats <= 1 are quantised round-half-even(255 x) (UNPINNED: the project's own choice -- the reference
+        keeps image / 255 in float32);  uvs: per mesh None or a finite (V_m, 2) float array (texture_u, texture_v), given exactly for
+        the meshes that have a texture;  tex_filter "nearest" or "linear": GL's sampler rule with clamp-to-edge, no mipmaps
+        (csrc/render_shade.h).  A textured mesh is coloured by its texture, its vertex colours are ignored (add_object's order).
+        With textures None the MeshSet is what it is without these arguments."""
         single = _is_array(arrays)
         host = _per_mesh(arrays, single, _vertex_rule)
         if not host:
@@ -187,7 +269,12 @@ class MeshSet:
             if len(normals) != len(host) or any(n is None for n in normals):
                 raise ValueError("need one normal array per mesh")
             ntab = _table(_per_mesh(normals, False, _normal_rule, host))
-        return cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters, ftab, foff, ctab, ntab)
+        tex = _texture_tables(textures, uvs, tex_filter, single, host)
+        ms = cls(torch.from_numpy(np.concatenate(host, 0)), torch.from_numpy(off.astype(np.int32)), diameters, ftab, foff, ctab, ntab)
+        if tex is not None:
+            ms.uvs, ms.texels, ms.tex_offsets, ms.tex_dims = tex
+            ms.tex_filter = tex_filter
+        return ms
 
     def __len__(self):
         return int(self.offsets.numel()) - 1
@@ -207,6 +294,14 @@ class MeshSet:
         """(colors or None, normals or None) on `device`, uploaded on the first call"""
         return on_device(self._dev_shading, device, lambda d: (None if self.colors is None else self.colors.to(d),
                                                                None if self.normals is None else self.normals.to(d)))
+
+    def textures_on(self, device, use=True):
+        """the texture arguments of the _tex entry points: (uvs, texels, offsets, dims, filter code) on `device`, uploaded on the first
+        call; four Nones and 0 without textures or with `use` false (a surface colour overrides them)"""
+        if self.texels is None or not use:
+            return None, None, None, None, 0
+        return on_device(self._dev_tex, device, lambda d: (self.uvs.to(d), self.texels.to(d), self.tex_offsets.to(d), self.tex_dims.to(d))) + (
+            TEX_FILTERS[self.tex_filter],)
 
 
 _MESH_CACHE = {}        # id(array) -> (weak reference to the array, MeshSet): the upload of a mesh happens once per array

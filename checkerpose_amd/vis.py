@@ -23,7 +23,7 @@ n = (x - min x) / (max (x - min x) / (1.0 - 0.2)) + 0.2; green = blue = uint8(25
 holds fewer than three distinct values gets diff_ok = 0 and zeros (the reference raises or divides 0 by 0).
 
 UNPINNED / out of scope: the text the reference writes on both pictures (its font call does not exist in the Pillow at hand; `boxes`
-are returned for a caller who annotates), JPEG / PNG writing, dataset folders, textures, SSAA in the composite.  OpenGL's own output
+are returned for a caller who annotates), JPEG / PNG writing, dataset folders, SSAA in the composite.  A textured MeshSet (row N20) is drawn with its textures, by render_rgb's rule.  OpenGL's own output
 is unpinned as for render_rgb.  There is no CPU fallback.
 
 Poses, camera (per IMAGE here), mesh ids, the grouping of the poses by image (scene.group_by_image) and the light are handled by
@@ -137,10 +137,10 @@ def vis_poses(R, t, cam_K, meshes, frames, image_ids=None, mesh_ids=None, surf_c
            "ren_depth": torch.empty((n_img, H, W), dtype=torch.float32, device=dev),
            "boxes": torch.empty((P, 4), dtype=torch.int32, device=dev), "ok": torch.empty((P,), dtype=torch.uint8, device=dev)}
     scratch = torch.empty(_abi.load().cp_vis_poses_scratch_bytes(P, vmax, n_img), dtype=torch.uint8, device=dev)
-    _abi.call("cp_vis_poses", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), mids, colors, normals, surf_d, ids_d, off_d,
+    _abi.call("cp_vis_poses_tex", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), mids, colors, normals, surf_d, ids_d, off_d,
               order_d, off.ctypes.data_as(C.c_void_p), order.ctypes.data_as(C.c_void_p), fr, shade, amb, light_c, box_c,
               1 if resolve_visib else 0, 1 if draw_boxes else 0, H, W, P, n_img, vmax, res["vis"], res["ren_rgb"], res["ren_depth"],
-              res["boxes"], res["ok"], scratch)
+              res["boxes"], res["ok"], scratch, *meshes.textures_on(dev, use=surf is None))
     if depth_diff:
         res.update(depth_diff_vis(res["ren_depth"], depth.to(dev), delta=delta))
     return res

@@ -756,6 +756,50 @@ int cp_render_rgb(cp_stream_t stream, const double* poses, const double* cam_K, 
                   double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B, int Vmax,
                   uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch);
 
+/* Textured meshes (next-row N20; csrc/render_shade.h states the rule; reference bop_toolkit_lib/renderer_py.py:309-352 add_object and the
+ * fragment shaders' texture2D(u_texture, v_texcoord), the sampler pinned to the OpenGL specification's NEAREST / LINEAR rule with
+ * CLAMP_TO_EDGE and no mipmaps -- which filter vispy selects, a driver's fixed-point filtering and OpenGL's output are NOT pinned).
+ * cp_render_rgb_tex, cp_vis_poses_tex and cp_render_scene_tex take their plain call's arguments plus five:
+ *   uv fp32 (sumV,2) = (texture_u, texture_v), rows as verts (zeros for a mesh without a texture);
+ *   texels uint32 (sum Wt Ht): one word r | g << 8 | b << 16 per texel, every texture row-major in the image FILE's row order (row 0 on
+ *   top; GL's texel row j is the file's row Ht - 1 - j: the flip is in the index), textures in mesh order;
+ *   tex_off int32 (M+1): each mesh's first texel;  tex_dims int32 (M,2) = Wt, Ht, both in 1..16384, or 0 0: the mesh has no texture;
+ *   filter 0 (nearest) or 1 (linear).
+ * Per covered sample of a textured mesh (u, v) is interpolated perspective-correctly with v_color's weights and expression form;
+ *   nearest: i = clamp(floor(u Wt), 0, Wt - 1), j = clamp(floor(v Ht), 0, Ht - 1), texel = T[Ht - 1 - j][i];
+ *   linear:  a = u Wt - 0.5, i0 = floor(a), alpha = a - i0, i1 = i0 + 1, both clamped; likewise j0, j1, beta; per channel in fp32 on the
+ *            bytes  lo = t00 + alpha (t10 - t00), hi = t01 + alpha (t11 - t01), texel = lo + beta (hi - lo);
+ *   colour = light_w * (texel / 255) (a correctly rounded fp32 division), quantised as every other colour.
+ * Priority: a surface colour (cp_vis_poses / cp_render_scene: surf_colors non-NULL) ignores the texture; else a textured mesh uses its
+ * texture and its vertex colours are ignored; else the vertex colours; else the surface colour / 0.5 grey.  (cp_render_rgb_tex's
+ * surf_color is never NULL: it colours the untextured meshes when colors is NULL; a caller who wants it to override passes no tables.)
+ * The four tables are given together or all NULL (CP_ERR_INVALID otherwise, and for an unknown filter); all NULL is the plain call,
+ * bit for bit and launch for launch -- the plain entry points forward so.  With tables the tile launch is the tile kernel's textured
+ * instantiation (rgb_tile_kernel<true>, vis_scene_tile_kernel<true>, scene_tile_kernel<true>: same launch count, same scratch).  The tables are trusted as verts and v_offsets are: the caller checks them (scene.MeshSet does). */
+int cp_render_rgb_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                      const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                      const float* colors, const float* normals, const double* surf_color, const double* light_pos,
+                      double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B, int Vmax,
+                      uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch, const float* uv,
+                      const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter);
+int cp_vis_poses_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                     const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                     const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                     const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host, const int32_t* pose_order_host,
+                     const uint8_t* frames, int shading, double ambient_weight, const double* light_pos, const double* box_color,
+                     int resolve, int draw_boxes, int H, int W, int P, int I, int Vmax, uint8_t* vis, uint8_t* ren_rgb, float* ren_depth,
+                     int32_t* boxes, uint8_t* ok, void* scratch, const float* uv, const uint32_t* texels, const int32_t* tex_off,
+                     const int32_t* tex_dims, int filter);
+int cp_render_scene_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                        const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                        const float* colors, const float* normals, const double* surf_colors, const int32_t* image_of_pose,
+                        const int32_t* img_off, const int32_t* pose_order, const int32_t* img_off_host, const int32_t* pose_order_host,
+                        const uint8_t* backgrounds, int n_bg, const int32_t* bg_index, const double* bg_color, int shading,
+                        double ambient_weight, const double* light_pos, double delta, int bgr, int H, int W, int P, int I, int Vmax,
+                        uint8_t* rgb, float* depth, uint32_t* full_bits, uint32_t* visib_bits, int32_t* slot, int32_t* counts,
+                        double* visib_fract, int32_t* boxes, uint8_t* ok, void* scratch, const float* uv, const uint32_t* texels,
+                        const int32_t* tex_off, const int32_t* tex_dims, int filter);
+
 /* Poses drawn over the photograph on the device (next-row N18; csrc/vis_poses.hip; reference bop_toolkit_lib/visualization.py:90-235
  * vis_object_poses as scripts/vis_est_poses.py and vis_gt_poses.py drive it, text excluded): for I images and P poses at once,
  * the composite of every image's poses, their 2-D boxes, and the half-and-half blend with the frame.
