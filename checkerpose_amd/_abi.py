@@ -317,6 +317,8 @@ SIGNATURES = {
     "cp_u8hwc_to_nhwc_norm": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "cp_crop_resize_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I]),
     "cp_crop_mask_bits": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I]),
+    "cp_warp_affine_u8": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I]),
+    "cp_warp_mask_bits": (_I, [_P, _P, _I, _I, _I, _P, _P, _P, _P, _I, _I, _I]),
     "cp_augment_plan_bytes": (C.c_size_t, [_I]),
     "cp_augment_frames": (_I, [_P, _P, _I, _I, _I, _P, _P, _I, _P, _I, _P]),
     "cp_nhwc_to_nchw_f32": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I]),

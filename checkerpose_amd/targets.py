@@ -212,8 +212,8 @@ def batch_from_frames(frames, crop_masks, R, t, cam_K, Bboxes, p3d_xyz, is_train
         from . import augment as AUG
         wins = np.zeros((len(grown), 4), dtype=np.int64)
         for b, box in enumerate(grown):
-            if box is not None:                  # the window the crop reads (cp_crop_resize_u8): [x1, x2) x [y1, y2) inside the frame
-                wins[b] = PP.roi_window([int(v) for v in box], resize_method, W, H)[:4]
+            if box is not None:                  # the window the crop reads (cp_crop_resize_u8 / cp_warp_affine_u8): [x1, x2) x [y1, y2) inside the frame
+                wins[b] = PP.roi_window([int(v) for v in box], resize_method, W, H, crop_size_img)[:4]
         aug = AUG.augment_frames(frames, augment, masks=swap_masks, backgrounds=backgrounds, img_index=img_index, rects=wins)
         roi_x = PP.get_roi_batch(aug, grown, crop_size_img, PP.INTER_LINEAR, resize_method, img_index=np.arange(len(grown)))
     roi_mask, roi_entire = crop_masks(grown)

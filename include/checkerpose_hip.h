@@ -1363,6 +1363,24 @@ int cp_crop_resize_u8(cp_stream_t stream, const uint8_t* images, int n_img, int 
 int cp_crop_mask_bits(cp_stream_t stream, const uint32_t* plane, int n_img, int H, int W, const int32_t* windows,
                       const int32_t* img_idx, const int32_t* bit, uint8_t* out, int B, int crop);
 
+/* The loader's third resize_method on the device (next-row N21; csrc/warp_affine.hip; reference bop_dataset_pytorch.py:39-52, 111-145
+ * crop_resize_by_warp_affine -> GDR_Net_Augmentation.py:199-240 get_affine_transform -> cv2.warpAffine): B warps of full uint8 images
+ * (n_img, H, W, C <= 4) in ONE launch.  inv_mats (device, B x 6 float64): the INVERSE map a00 a01 b0 a10 a11 b1 of each crop -- output
+ * pixel (x, y) samples the source at A . (x, y) + b -- inverted on the host as invertAffineTransform does; a row that holds a NaN means
+ * "no box": a zero crop.  interpolation: cv2's 8-bit INTER_NEAREST (0) / INTER_LINEAR (1) arithmetic of warpAffine -- coordinates in
+ * fixed point (AB_BITS 10, quantised to 1/32 pixel), four taps with 15-bit weights, every tap outside the frame zero on its own
+ * (BORDER_CONSTANT 0); the rule is stated in the kernel file's header, the numpy restatement is tests/warp_stages.py.  The caller keeps
+ * every output corner's source point within 2^20 pixels of the origin (the int32 fixed point wraps beyond; the Python wrapper refuses).
+ * img_idx (device, B) or NULL when n_img is 1 or B.  out: (B, out_h, out_w, C) uint8.  Nothing allocates or synchronises. */
+int cp_warp_affine_u8(cp_stream_t stream, const uint8_t* images, int n_img, int H, int W, int C, const double* inv_mats,
+                      const int32_t* img_idx, uint8_t* out, int B, int out_h, int out_w, int interpolation);
+
+/* The same warp of ONE BIT of a uint32 plane (cp_render_scene's full_bits / visib_bits): out uint8 (B,out_h,out_w) is
+ * cp_warp_affine_u8's INTER_NEAREST warp of the mask image (plane[img] >> bit[b]) & 1 ? 255 : 0, which is never stored.  bit int32 (B)
+ * on the device; a NaN row, or a bit outside 0..31, gives zeros. */
+int cp_warp_mask_bits(cp_stream_t stream, const uint32_t* plane, int n_img, int H, int W, const double* inv_mats,
+                      const int32_t* img_idx, const int32_t* bit, uint8_t* out, int B, int out_h, int out_w);
+
 /* Training-frame augmentation on the device (next-row N13; csrc/augment.hip; reference lm_dataset_pytorch.py:523-541 replace_bg and
  * GDR_Net_Augmentation.py:161-178 build_augmentations): background swap, salt-and-pepper, 5 x 5 motion blur, coarse dropout, 5-tap
  * separable Gaussian and one 256-entry table per channel (Add, Invert, Multiply, Multiply, Contrast composed) for B samples in ONE
