@@ -31,13 +31,9 @@ constexpr int GI_ACC = GiH::USER, GI_NSUM = 3, GI_NACC = 11;
 enum { GI_MODE_RENDER = 0, GI_MODE_DEPTH = 1 };
 
 struct GiParams {
+  VsMesh mesh;                // (Vmax 0 in DEPTH mode: no vertices)
   const double* poses;        // (B, 12)
   const double* K;
-  const float* verts;
-  const int32_t* v_off;
-  const int32_t* faces;       // (sumF, 3), indices local to the mesh
-  const int32_t* f_off;
-  const int32_t* mesh_id;
   const float* depth;         // (I, H, W): the sensor's
   const int32_t* image_id;    // nullptr: image 0
   const float* large;         // DEPTH mode: (B, 3H, 3W)
@@ -51,7 +47,7 @@ struct GiParams {
   int32_t* hdr;               // (B, GI_HDR)
   float4* sv;                 // (B, Vmax)
   float delta;
-  int k_stride, M, B, Vmax, H, W, I, mode, tx, ty, x0, y0, vchunks;
+  int k_stride, B, I, H, W, mode, tx, ty, x0, y0, vchunks;      // (H .. vchunks side by side: one scalar load in the tile kernel)
 };
 
 __global__ __launch_bounds__(VS_THREADS) void gt_info_pose_kernel(GiParams p) {
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_pose_kernel(GiParams p) {
     vs_rect_set(h + GiH::RECT(0), -p.W, -p.H, 2 * p.W - 1, 2 * p.H - 1);
   } else {
     int vfirst, V, ffirst, F, m;
-    ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m) && ok;
+    ok = vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m) && ok;
     const double* __restrict__ q = p.poses + 12 * (size_t)b;
     ok = ok && vs_finite(q, 12);
     vs_side_init(K, 1.0, q, (float*)h + GiH::P(0), h + GiH::RECT(0));
@@ -85,9 +81,9 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_vertex_kernel(GiParams p) 
   int32_t* __restrict__ h = p.hdr + (size_t)b * GI_HDR;
   if (!h[GiH::OK]) return;                                           // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
-  vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+  vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
   const float4 canvas = make_float4(-(float)p.W - 2.f, 2.f * (float)p.W + 1.f, -(float)p.H - 2.f, 2.f * (float)p.H + 1.f);
-  vs_vertex_chunk((const float*)h + GiH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, canvas, p.sv + (size_t)b * p.Vmax, h + GiH::RECT(0),
+  vs_vertex_chunk((const float*)h + GiH::P(0), p.mesh.verts + 3 * (size_t)vfirst, V, vc, canvas, p.sv + (size_t)b * p.mesh.Vmax, h + GiH::RECT(0),
                   h + GiH::BAD(0));
 }
 
@@ -115,9 +111,10 @@ __global__ __launch_bounds__(VS_THREADS) void gt_info_tile_kernel(GiParams p) {
         if (x >= -p.W && x < 2 * p.W && y >= -p.H && y < 2 * p.H) dep[k] = p.large[((size_t)b * 3 * p.H + (y + p.H)) * 3 * p.W + (x + p.W)];
       }
     } else {
+      const VsMesh mesh = p.mesh;                                   // (a copy on purpose: read through p, the kernel takes 6 more VGPRs)
       int vfirst, V, ffirst, F, m;
-      vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-      vs_depth_tile(s_tri, &s_n, p.sv + (size_t)b * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep);
+      vs_mesh_rows(mesh, b, vfirst, V, ffirst, F, m);
+      vs_depth_tile(s_tri, &s_n, p.sv + (size_t)b * mesh.Vmax, mesh.faces + 3 * (size_t)ffirst, F, V, c, dep);
     }
   }
 
@@ -193,7 +190,7 @@ void gi_carve(GiParams& p, void* scratch) {
 
 int gi_launch(GiParams& p, hipStream_t st) {
   VsGrid g;
-  if ((long long)p.H * p.W >= (1LL << 31) / 9 || !vs_grid(p.W, p.H, 1, true, p.B, 1, p.Vmax, g)) return CP_ERR_RANGE;
+  if ((long long)p.H * p.W >= (1LL << 31) / 9 || !vs_grid(p.W, p.H, 1, true, p.B, 1, p.mesh.Vmax, g)) return CP_ERR_RANGE;
   p.tx = g.tx; p.ty = g.ty; p.x0 = g.x0; p.y0 = g.y0; p.vchunks = g.vchunks;
   CP_LAUNCH(gt_info_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   if (p.mode == GI_MODE_RENDER) CP_LAUNCH(gt_info_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
@@ -214,22 +211,19 @@ extern "C" int cp_gt_info(cp_stream_t stream, const double* poses, const double*
                           const float* depth, const int32_t* image_ids, int I, int H, int W, double delta, int B, int Vmax,
                           int32_t* counts, double* visib_fract, int32_t* boxes, uint8_t* ok, uint8_t* mask, uint8_t* mask_visib,
                           float* depth_gt, void* scratch) {
-  if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !depth || !counts || !visib_fract || !boxes || !ok || !scratch)
+  GiParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!poses || !depth || !counts || !visib_fract || !boxes || !ok || !scratch) return CP_ERR_INVALID;
+  if (vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, B) || vs_images_invalid(image_ids, I) || !(delta == delta) ||
+      (mask == nullptr) != (mask_visib == nullptr))
     return CP_ERR_INVALID;
-  if (B <= 0 || M <= 0 || Vmax <= 0 || I <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9) || !(delta == delta))
-    return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (!image_ids && I != 1) return CP_ERR_INVALID;
-  if ((mask == nullptr) != (mask_visib == nullptr)) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(visib_fract, 7) ||
-      cp_misaligned(verts, 3) || cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) ||
-      cp_misaligned(mesh_ids, 3) || cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) ||
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || vs_view_misaligned(cam_K) || cp_misaligned(visib_fract, 7) ||
+      vs_mesh_misaligned(p.mesh) || cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) ||
       cp_misaligned(boxes, 3) || cp_misaligned(depth_gt, 3))
     return CP_ERR_ALIGN;
-  GiParams p = {};
-  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
-  p.M = M; p.mesh_id = mesh_ids; p.depth = depth; p.image_id = image_ids; p.I = I; p.H = H; p.W = W; p.delta = (float)delta; p.B = B;
-  p.Vmax = Vmax; p.counts = counts; p.fract = visib_fract; p.boxes = boxes; p.ok = ok; p.mask = mask; p.mask_visib = mask_visib;
+  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.depth = depth; p.image_id = image_ids; p.I = I; p.H = H; p.W = W;
+  p.delta = (float)delta; p.B = B; p.counts = counts; p.fract = visib_fract; p.boxes = boxes; p.ok = ok; p.mask = mask;
+  p.mask_visib = mask_visib;
   p.depth_gt = depth_gt; p.mode = GI_MODE_RENDER;
   gi_carve(p, scratch);
   return gi_launch(p, (hipStream_t)stream);
@@ -239,16 +233,16 @@ extern "C" int cp_gt_info_from_depth(cp_stream_t stream, const float* depth_gt_l
                                      const float* depth, const int32_t* image_ids, int I, int H, int W, double delta, int B,
                                      int32_t* counts, double* visib_fract, int32_t* boxes, uint8_t* ok, uint8_t* mask,
                                      uint8_t* mask_visib, void* scratch) {
-  if (!depth_gt_large || !cam_K || !depth || !counts || !visib_fract || !boxes || !ok || !scratch) return CP_ERR_INVALID;
-  if (B <= 0 || I <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9) || !(delta == delta)) return CP_ERR_INVALID;
-  if (!image_ids && I != 1) return CP_ERR_INVALID;
-  if ((mask == nullptr) != (mask_visib == nullptr)) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(cam_K, 7) || cp_misaligned(visib_fract, 7) || cp_misaligned(depth_gt_large, 3) ||
+  if (!depth_gt_large || !depth || !counts || !visib_fract || !boxes || !ok || !scratch) return CP_ERR_INVALID;
+  if (vs_view_invalid(cam_K, k_stride, H, W, B) || vs_images_invalid(image_ids, I) || !(delta == delta) ||
+      (mask == nullptr) != (mask_visib == nullptr))
+    return CP_ERR_INVALID;
+  if (cp_misaligned(scratch, 15) || vs_view_misaligned(cam_K) || cp_misaligned(visib_fract, 7) || cp_misaligned(depth_gt_large, 3) ||
       cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
   GiParams p = {};
   p.large = depth_gt_large; p.K = cam_K; p.k_stride = k_stride; p.depth = depth; p.image_id = image_ids; p.I = I; p.H = H; p.W = W;
-  p.delta = (float)delta; p.B = B; p.Vmax = 0; p.counts = counts; p.fract = visib_fract; p.boxes = boxes; p.ok = ok; p.mask = mask;
+  p.delta = (float)delta; p.B = B; p.counts = counts; p.fract = visib_fract; p.boxes = boxes; p.ok = ok; p.mask = mask;
   p.mask_visib = mask_visib; p.mode = GI_MODE_DEPTH;
   gi_carve(p, scratch);
   return gi_launch(p, (hipStream_t)stream);

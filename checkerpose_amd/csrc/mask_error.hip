@@ -34,14 +34,10 @@ constexpr int ME_SKIP = MeH::USER, ME_RENDER = ME_SKIP + 1, ME_ACC = ME_SKIP + 2
 constexpr int MO_THREADS = 512;
 
 struct MeParams {
+  VsMesh mesh;
   const double* est;          // (B, 12)
   const double* gt;
   const double* K;
-  const float* verts;
-  const int32_t* v_off;
-  const int32_t* faces;       // (sumF, 3), indices local to the mesh
-  const int32_t* f_off;
-  const int32_t* mesh_id;
   const double* diameters;    // per mesh (the sphere shortcut) or nullptr
   double* cus;                // (B) or nullptr
   double* bbp;                // (B) or nullptr
@@ -51,7 +47,7 @@ struct MeParams {
   uint8_t* masks;             // (B, 2, H, W) or nullptr
   int32_t* hdr;               // (B, ME_HDR)
   float4* sv;                 // (B, 2, Vmax)
-  int k_stride, M, B, Vmax, H, W, sphere, tx, ty, vchunks;
+  int k_stride, B, H, W, sphere, tx, ty, vchunks;
 };
 
 // 1 - misc.iou of two boxes x, y, w, h; T = long long (exact) or double (the caller's values): one quotient at the end
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(VS_THREADS) void mask_error_pose_kernel(MeParams p)
   int32_t* __restrict__ h = p.hdr + (size_t)b * ME_HDR;
   const double* __restrict__ K = p.K + (size_t)p.k_stride * b;
   int vfirst, V, ffirst, F, m;
-  bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+  bool ok = vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
   const double* __restrict__ e = p.est + 12 * (size_t)b;
   const double* __restrict__ g = p.gt + 12 * (size_t)b;
   ok = ok && vs_pose_finite(K, e) && vs_finite(g, 12);
@@ -116,9 +112,9 @@ __global__ __launch_bounds__(VS_THREADS) void mask_error_vertex_kernel(MeParams 
   int32_t* __restrict__ h = p.hdr + (size_t)b * ME_HDR;
   if (!h[ME_RENDER]) return;                                         // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
-  vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  vs_vertex_chunk((const float*)h + MeH::P(s), p.verts + 3 * (size_t)vfirst, V, vc, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f),
-                  p.sv + ((size_t)b * 2 + s) * p.Vmax, h + MeH::RECT(s), h + MeH::BAD(s));
+  vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+  vs_vertex_chunk((const float*)h + MeH::P(s), p.mesh.verts + 3 * (size_t)vfirst, V, vc, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f),
+                  p.sv + ((size_t)b * 2 + s) * p.mesh.Vmax, h + MeH::RECT(s), h + MeH::BAD(s));
 }
 
 __global__ __launch_bounds__(VS_THREADS) void mask_error_tile_kernel(MeParams p) {
@@ -141,11 +137,11 @@ __global__ __launch_bounds__(VS_THREADS) void mask_error_tile_kernel(MeParams p)
     for (int k = 0; k < VS_PPL; ++k) dep[s][k] = 0.f;
   if (hit[0] || hit[1]) {
     int vfirst, V, ffirst, F, m;
-    vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+    vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
       if (hit[s])                                                    // (uniform)
-        vs_depth_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep[s]);
+        vs_depth_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.mesh.Vmax, p.mesh.faces + 3 * (size_t)ffirst, F, V, c, dep[s]);
   }
 
   int acc[ME_NACC];
@@ -265,20 +261,16 @@ extern "C" int cp_mask_errors(cp_stream_t stream, const double* pose_est, const 
                               const int32_t* mesh_ids, const double* diameters, int H, int W, int sphere_check, int B, int Vmax,
                               double* cus, double* cou_bb_proj, int32_t* counts, int32_t* boxes, uint8_t* ok, uint8_t* masks,
                               void* scratch) {
-  if (!pose_est || !pose_gt || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !scratch) return CP_ERR_INVALID;
-  if (!cus && !cou_bb_proj) return CP_ERR_INVALID;
-  if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (sphere_check && !diameters) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(pose_est, 7) || cp_misaligned(pose_gt, 7) || cp_misaligned(cam_K, 7) ||
-      cp_misaligned(diameters, 7) || cp_misaligned(cus, 7) || cp_misaligned(cou_bb_proj, 7) || cp_misaligned(verts, 3) ||
-      cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) ||
+  MeParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!pose_est || !pose_gt || !scratch || (!cus && !cou_bb_proj) || (sphere_check && !diameters)) return CP_ERR_INVALID;
+  if (vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, B)) return CP_ERR_INVALID;
+  if (cp_misaligned(scratch, 15) || cp_misaligned(pose_est, 7) || cp_misaligned(pose_gt, 7) || vs_view_misaligned(cam_K) ||
+      cp_misaligned(diameters, 7) || cp_misaligned(cus, 7) || cp_misaligned(cou_bb_proj, 7) || vs_mesh_misaligned(p.mesh) ||
       cp_misaligned(counts, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
-  MeParams p = {};
-  p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
-  p.f_off = f_offsets; p.M = M; p.mesh_id = mesh_ids; p.diameters = diameters; p.H = H; p.W = W; p.sphere = sphere_check ? 1 : 0;
-  p.B = B; p.Vmax = Vmax; p.cus = cus; p.bbp = cou_bb_proj; p.counts = counts; p.boxes = boxes; p.ok = ok; p.masks = masks;
+  p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.diameters = diameters; p.H = H; p.W = W;
+  p.sphere = sphere_check ? 1 : 0; p.B = B; p.cus = cus; p.bbp = cou_bb_proj; p.counts = counts; p.boxes = boxes; p.ok = ok; p.masks = masks;
   p.hdr = (int32_t*)scratch;
   p.sv = (float4*)((char*)scratch + cp_align16_up((size_t)B * ME_HDR * sizeof(int32_t)));
   VsGrid g;

@@ -24,7 +24,9 @@
 //
 // Textures (row N20): with the texture tables of cp_render_rgb_tex the colour of a textured mesh's sample is its texel -- the rule at the
 // top of render_shade.h --; the tile launch is then rgb_tile_kernel<true> (the mesh, hence the colour source, is uniform over a
-// workgroup), and without them rgb_tile_kernel<false>: instruction for instruction the kernel this file always had.
+// workgroup), and without them rgb_tile_kernel<false>, which holds no texture code: the kernel this file had before textures, with the
+// same registers, LDS, output bits and measured time; NOT the same instructions any more: the params struct's layout moved the argument
+// loads and hipcc's schedule with them (profiles/raster_args_ab.json).
 //
 // Launches (four, whatever the data and the options):
 //   rgb_pose_kernel     per pose: P = (K f)' [R | t] (vs_side_init), [R | t] and the normal matrix in fp32, validity, accumulators.
@@ -41,13 +43,9 @@
 namespace {
 
 struct RrParams {
+  VsMesh mesh;
   const double* poses;        // (B, 12)
   const double* K;
-  const float* verts;
-  const int32_t* v_off;
-  const int32_t* faces;       // (sumF, 3), indices local to the mesh
-  const int32_t* f_off;
-  const int32_t* mesh_id;
   const float* colors;        // (sumV, 3) in [0, 1], or nullptr: surf
   const float* normals;       // (sumV, 3), phong
   uint8_t* rgb;               // (B, H, W, 3)
@@ -59,31 +57,20 @@ struct RrParams {
   RrTables T;                 // the (B, Vmax) tables, the light, the ambient weight, the shading (render_shade.h)
   float surf[3];
   int bg[3];                  // the quantised background
-  int k_stride, M, B, Vmax, H, W, f, bgr, tx, ty, vchunks;
-  RrTex X;                    // the texture tables, all null without textures (last: the older fields keep their offsets)
+  int k_stride, B, H, W, f, bgr, tx, ty, vchunks;
+  RrTex X;                    // the texture tables, all null without textures
 };
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_pose_kernel(RrParams p) {
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.B) return;
   int vfirst, V, ffirst, F, m;
-  const bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+  const bool ok = vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
   rr_pose_record(p.K + (size_t)p.k_stride * b, p.poses + 12 * (size_t)b, (double)p.f, ok, p.hdr + (size_t)b * RR_HDR);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void rgb_vertex_kernel(RrParams p) {
-  int b, s, vc;
-  vs_vertex_block(p.vchunks, 1, b, s, vc);
-  int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
-  if (!h[RrH::OK]) return;                                           // (uniform; no barrier in this kernel)
-  int vfirst, V, ffirst, F, m;
-  vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const float4 grid = make_float4(-2.f, (float)(p.f * p.W) + 1.f, -2.f, (float)(p.f * p.H) + 1.f);      // the sample grid
-  const auto shading_records = [&](int i, const float* __restrict__ vt) {
-    rr_vertex_record(p.T, h, (size_t)b * p.Vmax + i, vt, p.normals ? p.normals + 3 * ((size_t)vfirst + i) : nullptr);
-  };
-  vs_vertex_chunk((const float*)h + RrH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, grid, p.T.sv + (size_t)b * p.Vmax, h + RrH::RECT(0),
-                  h + RrH::BAD(0), shading_records);
+  rr_vertex_body(p, RR_HDR, make_float4(-2.f, (float)(p.f * p.W) + 1.f, -2.f, (float)(p.f * p.H) + 1.f));      // the sample grid
 }
 
 template <bool TEX>
@@ -112,9 +99,9 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_tile_kernel(RrParams p) {
     return;
   }
   int vfirst, V, ffirst, F, m;
-  vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const int32_t* __restrict__ faces = p.faces + 3 * (size_t)ffirst;
-  const size_t vbase = (size_t)b * p.Vmax;
+  vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+  const int32_t* __restrict__ faces = p.mesh.faces + 3 * (size_t)ffirst;
+  const size_t vbase = (size_t)b * p.mesh.Vmax;
   const RrTexMesh tm = rr_tex_mesh(p.X, m, (size_t)vfirst, TEX);      // (uniform: one mesh per workgroup)
   float best[VS_PPL];
   int face[VS_PPL];
@@ -187,7 +174,7 @@ __global__ __launch_bounds__(VS_THREADS) void rgb_finish_kernel(RrParams p) {
 
 extern "C" size_t cp_render_rgb_scratch_bytes(int B, int Vmax) {
   if (B <= 0 || Vmax < 0) return 0;
-  return cp_align16_up((size_t)B * RR_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)B * Vmax * sizeof(float4));
+  return rr_scratch_bytes(B, Vmax, RR_HDR);
 }
 
 extern "C" int cp_render_rgb_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
@@ -196,41 +183,26 @@ extern "C" int cp_render_rgb_tex(cp_stream_t stream, const double* poses, const 
                                  double ambient_weight, const double* bg_color, int shading, int ssaa, int bgr, int H, int W, int B,
                                  int Vmax, uint8_t* rgb, float* depth, uint8_t* mask, int32_t* boxes, uint8_t* ok, void* scratch,
                                  const float* uv, const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter) {
-  if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !surf_color || !light_pos || !bg_color || !rgb || !ok || !scratch)
-    return CP_ERR_INVALID;
-  if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
+  RrParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!poses || !surf_color || !bg_color || !rgb || !ok || !scratch) return CP_ERR_INVALID;
+  if (vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, B)) return CP_ERR_INVALID;
   if (ssaa != 1 && ssaa != 2 && ssaa != 4) return CP_ERR_INVALID;
   if (ssaa != 1 && (depth || mask || boxes)) return CP_ERR_INVALID;   // depth, mask and boxes belong to the ssaa = 1 sample grid
-  if (shading != RR_FLAT && shading != RR_PHONG) return CP_ERR_INVALID;
-  if (shading == RR_PHONG && !normals) return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (!(ambient_weight == ambient_weight) || __builtin_isinf(ambient_weight)) return CP_ERR_INVALID;
-  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
-  for (int k = 0; k < 3; ++k)
-    if (!__builtin_isfinite(surf_color[k]) || !__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(bg_color[k])) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(verts, 3) ||
-      cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) ||
+  if (const int e = rr_shading_args(shading, normals, ambient_weight, light_pos, uv, texels, tex_off, tex_dims, filter, p.T, p.X)) return e;
+  if (!rr_finite3(surf_color) || !rr_finite3(bg_color)) return CP_ERR_INVALID;
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || vs_view_misaligned(cam_K) || vs_mesh_misaligned(p.mesh) ||
       cp_misaligned(colors, 3) || cp_misaligned(normals, 3) || cp_misaligned(depth, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
-  RrParams p = {};
-  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
-  p.M = M; p.mesh_id = mesh_ids; p.colors = colors; p.normals = normals; p.rgb = rgb; p.depth = depth; p.mask = mask; p.boxes = boxes;
-  p.ok = ok; p.B = B; p.Vmax = Vmax; p.H = H; p.W = W; p.f = ssaa; p.T.shading = shading; p.bgr = bgr ? 1 : 0;
-  p.T.ambient = (float)ambient_weight;
-  p.X.uv = uv; p.X.texels = texels; p.X.off = tex_off; p.X.dims = tex_dims; p.X.filter = filter;
-  for (int k = 0; k < 3; ++k) { p.surf[k] = (float)surf_color[k]; p.T.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
+  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.colors = colors; p.normals = normals; p.rgb = rgb; p.depth = depth; p.mask = mask;
+  p.boxes = boxes; p.ok = ok; p.B = B; p.H = H; p.W = W; p.f = ssaa; p.bgr = bgr ? 1 : 0;
+  for (int k = 0; k < 3; ++k) { p.surf[k] = (float)surf_color[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
   const long long sw = (long long)ssaa * W, sh = (long long)ssaa * H;
   if (sw >= (1LL << 24) || sh >= (1LL << 24) || (long long)H * W >= (1LL << 31) / 3) return CP_ERR_RANGE;
   VsGrid g;
   if (!vs_grid(W, H, ssaa, false, B, 1, Vmax, g)) return CP_ERR_RANGE;
   p.tx = g.tx; p.ty = g.ty; p.vchunks = g.vchunks;
-  char* at = (char*)scratch;
-  const size_t rec = cp_align16_up((size_t)B * Vmax * sizeof(float4));
-  p.hdr = (int32_t*)at; at += cp_align16_up((size_t)B * RR_HDR * sizeof(int32_t));
-  p.T.sv = (float4*)at; at += rec;
-  p.T.eye = (float4*)at; at += rec;
-  p.T.vl = (float4*)at; at += rec;
-  p.T.vn = (float4*)at;
+  rr_carve(scratch, B, Vmax, RR_HDR, p.hdr, p.T);
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(rgb_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(rgb_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);

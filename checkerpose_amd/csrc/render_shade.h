@@ -10,6 +10,9 @@
 //                                   mesh's texture (row N20: rr_texel, in rr_shade<true> only -- the tile kernels' <true> instantiations), its vertex colours
 //                                   (interpolated), or one surface colour when `colors` is null
 //   RrTex, RrTexMesh, rr_tex_mesh   the texture tables of a MeshSet and one mesh's view of them;  rr_tex_args: their host-side checks
+//   rr_vertex_body, rr_scene_pose_head    the three vertex kernels' body; what vis_pose_kernel and scene_pose_kernel start with
+//   rr_shading_args, rr_scratch_bytes, rr_carve     (host) the shading, light and texture arguments checked and filled in; the scratch
+//                                   of a shaded call -- a header per pose and the four tables -- sized and carved
 //
 // Texture rule (row N20; bop_toolkit_lib/renderer_py.py:309-352 add_object + the fragment shaders' texture2D(u_texture, v_texcoord), the
 // sampler pinned to the OpenGL specification's "Texture Minification / Magnification" rule, NOT to a driver's output).  Per mesh a
@@ -112,6 +115,38 @@ __device__ __forceinline__ void rr_vertex_record(const RrTables& T, const int32_
   }
 }
 
+// The body of the three shaded vertex kernels (p: RrParams, VpParams or SlParams), for ALL threads of the workgroup: the screen record
+// and the rectangle (vs_vertex_chunk, the sample's pixels clamped to `clip`) and the shading records, under the pose's header of
+// hdr_words words.
+template <typename Params>
+__device__ __forceinline__ void rr_vertex_body(const Params& p, int hdr_words, float4 clip) {
+  int b, s, vc;
+  vs_vertex_block(p.vchunks, 1, b, s, vc);
+  int32_t* __restrict__ h = p.hdr + (size_t)b * hdr_words;
+  if (!h[RrH::OK]) return;                                           // (uniform; no barrier in this kernel)
+  int vfirst, V, ffirst, F, m;
+  vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+  const auto shading_records = [&](int i, const float* __restrict__ vt) {
+    rr_vertex_record(p.T, h, (size_t)b * p.mesh.Vmax + i, vt, p.normals ? p.normals + 3 * ((size_t)vfirst + i) : nullptr);
+  };
+  vs_vertex_chunk((const float*)h + RrH::P(0), p.mesh.verts + 3 * (size_t)vfirst, V, vc, clip, p.T.sv + (size_t)b * p.mesh.Vmax,
+                  h + RrH::RECT(0), h + RrH::BAD(0), shading_records);
+}
+
+// What the pose kernels of an image's poses (p: VpParams or SlParams) start with: pose b's mesh rows, its image (img; false: no such
+// image), its surface colour finite, and the header h under the IMAGE's K.
+template <typename Params>
+__device__ __forceinline__ bool rr_scene_pose_head(const Params& p, int b, int32_t* __restrict__ h, int& img) {
+  int vfirst, V, ffirst, F, m;
+  bool ok = vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+  img = p.image_of_pose[b];
+  const bool img_ok = img >= 0 && img < p.I;
+  ok = ok && img_ok;
+  if (p.surf) ok = ok && vs_finite(p.surf + 3 * (size_t)b, 3);
+  rr_pose_record(p.K + (size_t)p.k_stride * (img_ok ? img : 0), p.poses + 12 * (size_t)b, 1.0, ok, h);
+  return img_ok;
+}
+
 // the texture tables of a MeshSet (all null without textures) and one mesh's view of them
 struct RrTex {
   const float* uv;            // (sumV, 2), rows as verts
@@ -145,9 +180,40 @@ inline int rr_tex_args(const float* uv, const uint32_t* texels, const int32_t* t
   return CP_OK;
 }
 
+// The host-side checks of a shaded call's shading, light and texture arguments, which they fill into T and X: a known shading, normals
+// for phong, a finite ambient weight, rr_tex_args (its own code: the one ALIGN among an entry point's INVALID rules), a finite light.
+inline int rr_shading_args(int shading, const float* normals, double ambient_weight, const double* light_pos, const float* uv,
+                           const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter, RrTables& T, RrTex& X) {
+  if (!light_pos || (shading != RR_FLAT && shading != RR_PHONG) || (shading == RR_PHONG && !normals) || !__builtin_isfinite(ambient_weight))
+    return CP_ERR_INVALID;
+  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
+  for (int k = 0; k < 3; ++k)
+    if (!__builtin_isfinite(light_pos[k])) return CP_ERR_INVALID;
+  T.shading = shading; T.ambient = (float)ambient_weight;
+  for (int k = 0; k < 3; ++k) T.light[k] = (float)light_pos[k];
+  X.uv = uv; X.texels = texels; X.off = tex_off; X.dims = tex_dims; X.filter = filter;
+  return CP_OK;
+}
+// a[0 .. 3) are finite (a colour of an entry point's own)
+inline bool rr_finite3(const double* a) { return __builtin_isfinite(a[0]) && __builtin_isfinite(a[1]) && __builtin_isfinite(a[2]); }
+
+// the scratch of a shaded call over n poses: n headers of hdr_words words, then the four (n, Vmax) tables
+inline size_t rr_scratch_bytes(int n, int Vmax, int hdr_words) {
+  return cp_align16_up((size_t)n * hdr_words * sizeof(int32_t)) + 4 * cp_align16_up((size_t)n * Vmax * sizeof(float4));
+}
+inline void rr_carve(void* scratch, int n, int Vmax, int hdr_words, int32_t*& hdr, RrTables& T) {
+  char* at = (char*)scratch;
+  const size_t rec = cp_align16_up((size_t)n * Vmax * sizeof(float4));
+  hdr = (int32_t*)at; at += cp_align16_up((size_t)n * hdr_words * sizeof(int32_t));
+  T.sv = (float4*)at; at += rec;
+  T.eye = (float4*)at; at += rec;
+  T.vl = (float4*)at; at += rec;
+  T.vn = (float4*)at;
+}
+
 // The tile launch of a shaded call: the kernel's <true> instantiation when the call has texture tables, else its <false> one -- the
-// code the rows N14 / N18 / N19 always had (identical instructions; the tables sit at the END of the params structs so that not even an
-// offset moves) -- recorded under the plain name the launch lists always showed.
+// code the rows N14 / N18 / N19 always had (no texture code in it: the same registers, LDS and output bits; the params structs' layout
+// only moves the argument loads) -- recorded under the plain name the launch lists always showed.
 #define RR_LAUNCH_TILE(kernel, textured, ...)                                                          \
   do {                                                                                                 \
     if (textured) { cp_mark_kernel("%s", #kernel "<true>"); hipLaunchKernelGGL(kernel<true>, __VA_ARGS__); } \

@@ -16,8 +16,8 @@
 //   non-finite surface colour) is skipped: ok = 0, counts 0, fraction 0, boxes -1, its bits 0.
 //
 // Textures (row N20, cp_render_scene_tex): the owner's colour is its mesh's texel by render_shade.h's rule; the tile launch is then
-// scene_tile_kernel<true> (the colour source is uniform per iteration of the pose loop), without textures scene_tile_kernel<false>:
-// instruction for instruction the kernel this file always had.
+// scene_tile_kernel<true> (the colour source is uniform per iteration of the pose loop), without textures scene_tile_kernel<false>,
+// which holds no texture code: the kernel this file had before textures, with the same registers, LDS and output bits.
 //
 // Launches (four, whatever the data):
 //   scene_pose_kernel     per pose: render_shade.h's header under the pose's IMAGE's K, validity, its slot, the accumulators initialised.
@@ -49,13 +49,9 @@ constexpr int SL_SLOT = SL_FRAME + SL_NFRAME;
 constexpr int SL_MAX_POSES = 32;                         // per image: one bit each
 
 struct SlParams {
+  VsMesh mesh;
   const double* poses;        // (P, 12)
   const double* K;            // (9) or (I, 9)
-  const float* verts;
-  const int32_t* v_off;
-  const int32_t* faces;
-  const int32_t* f_off;
-  const int32_t* mesh_id;
   const float* colors;        // (sumV, 3) or nullptr
   const float* normals;
   const double* surf;         // (P, 3) or nullptr
@@ -77,34 +73,22 @@ struct SlParams {
   RrTables T;
   float delta;
   int bg[3];                  // the quantised bg_color
-  int k_stride, M, P, I, Vmax, H, W, n_bg, bgr, tx, ty, x0, y0, vchunks;
-  RrTex X;                    // the texture tables, all null without textures (last: the older fields keep their offsets)
+  int k_stride, P, I, H, W, n_bg, bgr, tx, ty, x0, y0, vchunks;
+  RrTex X;                    // the texture tables, all null without textures
 };
-
-// the image's rows of the CSR, clamped to [0, P] and to SL_MAX_POSES rows (the host checked them; the clamps bound the loops and the
-// shifts whatever the memory holds)
-__device__ __forceinline__ void sl_image_rows(const SlParams& p, int img, int& j0, int& j1) {
-  j0 = min(max(p.img_off[img], 0), p.P);
-  j1 = min(min(max(p.img_off[img + 1], j0), p.P), j0 + SL_MAX_POSES);
-}
 
 __global__ __launch_bounds__(VS_THREADS) void scene_pose_kernel(SlParams p) {
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.P) return;
-  int vfirst, V, ffirst, F, m;
-  bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const int img = p.image_of_pose[b];
-  const bool img_ok = img >= 0 && img < p.I;
-  ok = ok && img_ok;
-  if (p.surf) ok = ok && vs_finite(p.surf + 3 * (size_t)b, 3);
   int32_t* __restrict__ h = p.hdr + (size_t)b * SL_HDR;
-  rr_pose_record(p.K + (size_t)p.k_stride * (img_ok ? img : 0), p.poses + 12 * (size_t)b, 1.0, ok, h);
+  int img;
+  const bool img_ok = rr_scene_pose_head(p, b, h, img);
   for (int k = 0; k < SL_NCANVAS; ++k) h[SL_CANVAS + k] = vs_acc_identity<1>(k);
   for (int k = 0; k < SL_NFRAME; ++k) h[SL_FRAME + k] = vs_acc_identity<2>(k);
   int slot = -1;
   if (img_ok) {
     int j0, j1;
-    sl_image_rows(p, img, j0, j1);
+    vs_image_rows(p.img_off, p.P, img, SL_MAX_POSES, j0, j1);
     for (int j = j0; j < j1; ++j)
       if (slot < 0 && p.pose_order[j] == b) slot = j - j0;
   }
@@ -112,19 +96,8 @@ __global__ __launch_bounds__(VS_THREADS) void scene_pose_kernel(SlParams p) {
   for (int k = SL_SLOT + 1; k < SL_HDR; ++k) h[k] = 0;
 }
 
-__global__ __launch_bounds__(VS_THREADS) void scene_vertex_kernel(SlParams p) {
-  int b, s, vc;
-  vs_vertex_block(p.vchunks, 1, b, s, vc);
-  int32_t* __restrict__ h = p.hdr + (size_t)b * SL_HDR;
-  if (!h[RrH::OK]) return;                                           // (uniform; no barrier in this kernel)
-  int vfirst, V, ffirst, F, m;
-  vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const float4 canvas = make_float4(-(float)p.W - 2.f, 2.f * (float)p.W + 1.f, -(float)p.H - 2.f, 2.f * (float)p.H + 1.f);
-  const auto shading_records = [&](int i, const float* __restrict__ vt) {
-    rr_vertex_record(p.T, h, (size_t)b * p.Vmax + i, vt, p.normals ? p.normals + 3 * ((size_t)vfirst + i) : nullptr);
-  };
-  vs_vertex_chunk((const float*)h + RrH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, canvas, p.T.sv + (size_t)b * p.Vmax, h + RrH::RECT(0),
-                  h + RrH::BAD(0), shading_records);
+__global__ __launch_bounds__(VS_THREADS) void scene_vertex_kernel(SlParams p) {      // the rectangle clamped to the canvas
+  rr_vertex_body(p, SL_HDR, make_float4(-(float)p.W - 2.f, 2.f * (float)p.W + 1.f, -(float)p.H - 2.f, 2.f * (float)p.H + 1.f));
 }
 
 // bit s: the pose at slot s of image img (rows [j0, j1) of the CSR, at most 32) is rendered and its rectangle meets the tile at (ox, oy).
@@ -158,7 +131,7 @@ __global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(TEX 
   const bool in_frame = ox >= 0 && ox < p.W && oy >= 0 && oy < p.H;  // the grid is anchored at frame pixel (0, 0)
   const int x = ox + lx;
   int j0, j1;
-  sl_image_rows(p, img, j0, j1);
+  vs_image_rows(p.img_off, p.P, img, SL_MAX_POSES, j0, j1);
 
   const uint32_t hits = sl_hits(p, j0, j1, img, ox, oy);
 
@@ -166,9 +139,9 @@ __global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(TEX 
     for (uint32_t left = hits; left; left &= left - 1) {
       const int b = p.pose_order[j0 + __ffs((int)left) - 1];
       int vfirst, V, ffirst, F, m;
-      vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+      vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
       float dep[VS_PPL];
-      vs_depth_tile(s_tri, &s_n, p.T.sv + (size_t)b * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep);
+      vs_depth_tile(s_tri, &s_n, p.T.sv + (size_t)b * p.mesh.Vmax, p.mesh.faces + 3 * (size_t)ffirst, F, V, c, dep);
       int acc[SL_NCANVAS];
 #pragma unroll
       for (int k = 0; k < SL_NCANVAS; ++k) acc[k] = vs_acc_identity<1>(k);
@@ -195,9 +168,9 @@ __global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(TEX 
   for (uint32_t left = alone ? 0u : hits; left; left &= left - 1) {
     const int b = p.pose_order[j0 + __ffs((int)left) - 1];
     int vfirst, V, ffirst, F, m;
-    vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
+    vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
     float dep[VS_PPL];
-    vs_depth_tile(s_tri, &s_n, p.T.sv + (size_t)b * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep);
+    vs_depth_tile(s_tri, &s_n, p.T.sv + (size_t)b * p.mesh.Vmax, p.mesh.faces + 3 * (size_t)ffirst, F, V, c, dep);
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k)
       if (dep[k] != 0.f && (ren[k] == 0.f || dep[k] < ren[k])) ren[k] = dep[k];
@@ -216,9 +189,9 @@ __global__ __launch_bounds__(VS_THREADS) __attribute__((amdgpu_waves_per_eu(TEX 
     const int b = p.pose_order[j0 + __ffs((int)left) - 1];
     int32_t* __restrict__ h = p.hdr + (size_t)b * SL_HDR;
     int vfirst, V, ffirst, F, m;
-    vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-    const int32_t* __restrict__ faces = p.faces + 3 * (size_t)ffirst;
-    const size_t vbase = (size_t)b * p.Vmax;
+    vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+    const int32_t* __restrict__ faces = p.mesh.faces + 3 * (size_t)ffirst;
+    const size_t vbase = (size_t)b * p.mesh.Vmax;
     float best[VS_PPL];
     int face[VS_PPL];
     vs_raster_tile<true>(s_tri, &s_n, p.T.sv + vbase, faces, F, V, c, best, face);
@@ -318,7 +291,7 @@ __global__ __launch_bounds__(VS_THREADS) void scene_finish_kernel(SlParams p) {
 
 extern "C" size_t cp_render_scene_scratch_bytes(int P, int Vmax, int I) {
   if (P <= 0 || Vmax < 0 || I <= 0) return 0;
-  return cp_align16_up((size_t)P * SL_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)P * Vmax * sizeof(float4));
+  return rr_scratch_bytes(P, Vmax, SL_HDR);
 }
 
 extern "C" int cp_render_scene_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
@@ -331,57 +304,36 @@ extern "C" int cp_render_scene_tex(cp_stream_t stream, const double* poses, cons
                                    uint32_t* visib_bits, int32_t* slot, int32_t* counts, double* visib_fract, int32_t* boxes, uint8_t* ok,
                                    void* scratch, const float* uv, const uint32_t* texels, const int32_t* tex_off,
                                    const int32_t* tex_dims, int filter) {
-  if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !image_of_pose || !img_off || !pose_order || !img_off_host ||
-      !pose_order_host || !bg_color || !light_pos || !rgb || !depth || !full_bits || !visib_bits || !slot || !counts || !visib_fract ||
-      !boxes || !ok || !scratch)
+  SlParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!poses || !image_of_pose || !img_off || !pose_order || !img_off_host || !pose_order_host || !bg_color || !rgb || !depth ||
+      !full_bits || !visib_bits || !slot || !counts || !visib_fract || !boxes || !ok || !scratch)
     return CP_ERR_INVALID;
-  if (P <= 0 || I <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
-  if (shading != RR_FLAT && shading != RR_PHONG) return CP_ERR_INVALID;
-  if (shading == RR_PHONG && !normals) return CP_ERR_INVALID;
+  if (vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, P) || I <= 0) return CP_ERR_INVALID;
   if ((bgr != 0 && bgr != 1) || !(delta == delta)) return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
   if (backgrounds ? (n_bg <= 0 || (!bg_index && n_bg != 1 && n_bg != I)) : (n_bg != 0 || bg_index)) return CP_ERR_INVALID;
-  if (!__builtin_isfinite(ambient_weight)) return CP_ERR_INVALID;
-  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
-  for (int k = 0; k < 3; ++k)
-    if (!__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(bg_color[k])) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(surf_colors, 7) ||
-      cp_misaligned(visib_fract, 7) || cp_misaligned(verts, 3) || cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) ||
-      cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) || cp_misaligned(colors, 3) || cp_misaligned(normals, 3) ||
+  if (const int e = rr_shading_args(shading, normals, ambient_weight, light_pos, uv, texels, tex_off, tex_dims, filter, p.T, p.X)) return e;
+  if (!rr_finite3(bg_color)) return CP_ERR_INVALID;
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || vs_view_misaligned(cam_K) || cp_misaligned(surf_colors, 7) ||
+      cp_misaligned(visib_fract, 7) || vs_mesh_misaligned(p.mesh) || cp_misaligned(colors, 3) || cp_misaligned(normals, 3) ||
       cp_misaligned(image_of_pose, 3) || cp_misaligned(img_off, 3) || cp_misaligned(pose_order, 3) || cp_misaligned(img_off_host, 3) ||
       cp_misaligned(pose_order_host, 3) || cp_misaligned(bg_index, 3) || cp_misaligned(depth, 3) || cp_misaligned(full_bits, 3) ||
       cp_misaligned(visib_bits, 3) || cp_misaligned(slot, 3) || cp_misaligned(counts, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
-  // the CSR: a monotone partition of [0, P), every entry of pose_order a pose; then one bit per pose of an image
-  if (img_off_host[0] != 0 || img_off_host[I] != P) return CP_ERR_INVALID;
-  for (int i = 0; i < I; ++i)
-    if (img_off_host[i + 1] < img_off_host[i]) return CP_ERR_INVALID;
-  for (int j = 0; j < P; ++j)
-    if (pose_order_host[j] < 0 || pose_order_host[j] >= P) return CP_ERR_INVALID;
-  for (int i = 0; i < I; ++i)
-    if (img_off_host[i + 1] - img_off_host[i] > SL_MAX_POSES) return CP_ERR_RANGE;
+  if (vs_csr_invalid(img_off_host, pose_order_host, I, P)) return CP_ERR_INVALID;
+  if (vs_csr_over(img_off_host, I, SL_MAX_POSES)) return CP_ERR_RANGE;                  // one bit per pose of an image
   if (W >= (1 << 24) || H >= (1 << 24) || (long long)I * H * W >= (1LL << 31) / 3 || (long long)H * W >= (1LL << 31) / 9)
     return CP_ERR_RANGE;
   if (backgrounds && (long long)n_bg * H * W >= (1LL << 31) / 3) return CP_ERR_RANGE;
   VsGrid gp, gi;
   if (!vs_grid(W, H, 1, false, P, 1, Vmax, gp) || !vs_grid(W, H, 1, true, I, 1, Vmax, gi)) return CP_ERR_RANGE;      // gp: its pose and vertex blocks
-  SlParams p = {};
-  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
-  p.M = M; p.mesh_id = mesh_ids; p.colors = colors; p.normals = normals; p.surf = surf_colors; p.image_of_pose = image_of_pose;
-  p.img_off = img_off; p.pose_order = pose_order; p.backgrounds = backgrounds; p.n_bg = n_bg; p.bg_index = bg_index; p.rgb = rgb;
-  p.depth = depth; p.full_bits = full_bits; p.visib_bits = visib_bits; p.slot = slot; p.counts = counts; p.fract = visib_fract;
-  p.boxes = boxes; p.ok = ok; p.P = P; p.I = I; p.Vmax = Vmax; p.H = H; p.W = W; p.bgr = bgr; p.delta = (float)delta;
-  p.T.shading = shading; p.T.ambient = (float)ambient_weight;
-  p.X.uv = uv; p.X.texels = texels; p.X.off = tex_off; p.X.dims = tex_dims; p.X.filter = filter;
-  for (int k = 0; k < 3; ++k) { p.T.light[k] = (float)light_pos[k]; p.bg[k] = rr_quant_host(bg_color[k]); }
+  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.colors = colors; p.normals = normals; p.surf = surf_colors;
+  p.image_of_pose = image_of_pose; p.img_off = img_off; p.pose_order = pose_order; p.backgrounds = backgrounds; p.n_bg = n_bg;
+  p.bg_index = bg_index; p.rgb = rgb; p.depth = depth; p.full_bits = full_bits; p.visib_bits = visib_bits; p.slot = slot; p.counts = counts;
+  p.fract = visib_fract; p.boxes = boxes; p.ok = ok; p.P = P; p.I = I; p.H = H; p.W = W; p.bgr = bgr; p.delta = (float)delta;
+  for (int k = 0; k < 3; ++k) p.bg[k] = rr_quant_host(bg_color[k]);
   p.tx = gi.tx; p.ty = gi.ty; p.x0 = gi.x0; p.y0 = gi.y0; p.vchunks = gp.vchunks;
-  char* at = (char*)scratch;
-  const size_t rec = cp_align16_up((size_t)P * Vmax * sizeof(float4));
-  p.hdr = (int32_t*)at; at += cp_align16_up((size_t)P * SL_HDR * sizeof(int32_t));
-  p.T.sv = (float4*)at; at += rec;
-  p.T.eye = (float4*)at; at += rec;
-  p.T.vl = (float4*)at; at += rec;
-  p.T.vn = (float4*)at;
+  rr_carve(scratch, P, Vmax, SL_HDR, p.hdr, p.T);
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(scene_pose_kernel, dim3(gp.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(scene_vertex_kernel, dim3(gp.vert_blocks), dim3(VS_THREADS), 0, st, p);

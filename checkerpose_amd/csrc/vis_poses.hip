@@ -43,13 +43,9 @@
 namespace {
 
 struct VpParams {
+  VsMesh mesh;
   const double* poses;        // (P, 12)
   const double* K;            // (9) or (I, 9)
-  const float* verts;
-  const int32_t* v_off;
-  const int32_t* faces;
-  const int32_t* f_off;
-  const int32_t* mesh_id;
   const float* colors;        // (sumV, 3) or nullptr
   const float* normals;
   const double* surf;         // (P, 3) or nullptr: the mesh's colours (0.5 grey without any)
@@ -65,41 +61,19 @@ struct VpParams {
   int32_t* hdr;               // (P, RR_HDR)
   RrTables T;
   int box_q[3];               // int(c * 255) of box_color
-  int k_stride, M, P, I, Vmax, H, W, resolve, draw_boxes, tx, ty, vchunks;
-  RrTex X;                    // the texture tables, all null without textures (last: the older fields keep their offsets)
+  int k_stride, P, I, H, W, resolve, draw_boxes, tx, ty, vchunks;
+  RrTex X;                    // the texture tables, all null without textures
 };
 
 __global__ __launch_bounds__(VS_THREADS) void vis_pose_kernel(VpParams p) {
   const int b = blockIdx.x * VS_THREADS + threadIdx.x;
   if (b >= p.P) return;
-  int vfirst, V, ffirst, F, m;
-  bool ok = vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const int img = p.image_of_pose[b];
-  const bool img_ok = img >= 0 && img < p.I;
-  ok = ok && img_ok;
-  if (p.surf) ok = ok && vs_finite(p.surf + 3 * (size_t)b, 3);
-  rr_pose_record(p.K + (size_t)p.k_stride * (img_ok ? img : 0), p.poses + 12 * (size_t)b, 1.0, ok, p.hdr + (size_t)b * RR_HDR);
+  int img;
+  rr_scene_pose_head(p, b, p.hdr + (size_t)b * RR_HDR, img);
 }
 
 __global__ __launch_bounds__(VS_THREADS) void vis_vertex_kernel(VpParams p) {
-  int b, s, vc;
-  vs_vertex_block(p.vchunks, 1, b, s, vc);
-  int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
-  if (!h[RrH::OK]) return;                                           // (uniform; no barrier in this kernel)
-  int vfirst, V, ffirst, F, m;
-  vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-  const float4 grid = make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f);
-  const auto shading_records = [&](int i, const float* __restrict__ vt) {
-    rr_vertex_record(p.T, h, (size_t)b * p.Vmax + i, vt, p.normals ? p.normals + 3 * ((size_t)vfirst + i) : nullptr);
-  };
-  vs_vertex_chunk((const float*)h + RrH::P(0), p.verts + 3 * (size_t)vfirst, V, vc, grid, p.T.sv + (size_t)b * p.Vmax, h + RrH::RECT(0),
-                  h + RrH::BAD(0), shading_records);
-}
-
-// the image's rows of the CSR, clamped to [0, P] (the host checked them; the clamp bounds the loops whatever the memory holds)
-__device__ __forceinline__ void vp_image_rows(const VpParams& p, int img, int& j0, int& j1) {
-  j0 = min(max(p.img_off[img], 0), p.P);
-  j1 = min(max(p.img_off[img + 1], j0), p.P);
+  rr_vertex_body(p, RR_HDR, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f));
 }
 
 template <bool TEX>
@@ -115,16 +89,16 @@ __global__ __launch_bounds__(VS_THREADS) void vis_scene_tile_kernel(VpParams p) 
 #pragma unroll
   for (int k = 0; k < VS_PPL; ++k) { col[k] = 0u; dep[k] = 0.f; }
   int j0, j1;
-  vp_image_rows(p, img, j0, j1);
+  vs_image_rows(p.img_off, p.P, img, j0, j1);
   for (int j = j0; j < j1; ++j) {                                     // (every test below is uniform over the workgroup)
     const int b = p.pose_order[j];
     if (b < 0 || b >= p.P || p.image_of_pose[b] != img) continue;
     int32_t* __restrict__ h = p.hdr + (size_t)b * RR_HDR;
     if (!h[RrH::OK] || h[RrH::BAD(0)] || !vs_tile_hit(h + RrH::RECT(0), ox, oy)) continue;
     int vfirst, V, ffirst, F, m;
-    vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-    const int32_t* __restrict__ faces = p.faces + 3 * (size_t)ffirst;
-    const size_t vbase = (size_t)b * p.Vmax;
+    vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+    const int32_t* __restrict__ faces = p.mesh.faces + 3 * (size_t)ffirst;
+    const size_t vbase = (size_t)b * p.mesh.Vmax;
     float best[VS_PPL];
     int face[VS_PPL];
     vs_raster_tile<true>(s_tri, &s_n, p.T.sv + vbase, faces, F, V, c, best, face);
@@ -184,7 +158,7 @@ __global__ __launch_bounds__(VS_THREADS) void vis_finish_kernel(VpParams p) {
   bool on = false;
   if (p.draw_boxes) {
     int j0, j1;
-    vp_image_rows(p, img, j0, j1);
+    vs_image_rows(p.img_off, p.P, img, j0, j1);
     for (int j = j0; j < j1; ++j) {
       const int b = p.pose_order[j];
       if (b < 0 || b >= p.P || p.image_of_pose[b] != img) continue;
@@ -389,7 +363,7 @@ inline long long dd_tiles(int H, int W) { return ((long long)H * W + DD_TILE - 1
 
 extern "C" size_t cp_vis_poses_scratch_bytes(int P, int Vmax, int I) {
   if (P <= 0 || Vmax < 0 || I <= 0) return 0;
-  return cp_align16_up((size_t)P * RR_HDR * sizeof(int32_t)) + 4 * cp_align16_up((size_t)P * Vmax * sizeof(float4));
+  return rr_scratch_bytes(P, Vmax, RR_HDR);
 }
 
 extern "C" int cp_vis_poses_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
@@ -400,56 +374,36 @@ extern "C" int cp_vis_poses_tex(cp_stream_t stream, const double* poses, const d
                                 const double* light_pos, const double* box_color, int resolve, int draw_boxes, int H, int W, int P, int I,
                                 int Vmax, uint8_t* vis, uint8_t* ren_rgb, float* ren_depth, int32_t* boxes, uint8_t* ok, void* scratch,
                                 const float* uv, const uint32_t* texels, const int32_t* tex_off, const int32_t* tex_dims, int filter) {
-  if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !image_of_pose || !img_off || !pose_order || !img_off_host ||
-      !pose_order_host || !frames || !light_pos || !box_color || !vis || !ren_rgb || !ren_depth || !boxes || !ok || !scratch)
+  VpParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!poses || !image_of_pose || !img_off || !pose_order || !img_off_host || !pose_order_host || !frames || !box_color || !vis ||
+      !ren_rgb || !ren_depth || !boxes || !ok || !scratch)
     return CP_ERR_INVALID;
-  if (P <= 0 || I <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
-  if (shading != RR_FLAT && shading != RR_PHONG) return CP_ERR_INVALID;
-  if (shading == RR_PHONG && !normals) return CP_ERR_INVALID;
+  if (vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, P) || I <= 0) return CP_ERR_INVALID;
   if ((resolve != 0 && resolve != 1) || (draw_boxes != 0 && draw_boxes != 1)) return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (!__builtin_isfinite(ambient_weight)) return CP_ERR_INVALID;
-  if (const int e = rr_tex_args(uv, texels, tex_off, tex_dims, filter)) return e;
-  for (int k = 0; k < 3; ++k)
-    if (!__builtin_isfinite(light_pos[k]) || !__builtin_isfinite(box_color[k])) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(surf_colors, 7) ||
-      cp_misaligned(verts, 3) || cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) ||
-      cp_misaligned(mesh_ids, 3) || cp_misaligned(colors, 3) || cp_misaligned(normals, 3) || cp_misaligned(image_of_pose, 3) ||
+  if (const int e = rr_shading_args(shading, normals, ambient_weight, light_pos, uv, texels, tex_off, tex_dims, filter, p.T, p.X)) return e;
+  if (!rr_finite3(box_color)) return CP_ERR_INVALID;
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || vs_view_misaligned(cam_K) || cp_misaligned(surf_colors, 7) ||
+      vs_mesh_misaligned(p.mesh) || cp_misaligned(colors, 3) || cp_misaligned(normals, 3) || cp_misaligned(image_of_pose, 3) ||
       cp_misaligned(img_off, 3) || cp_misaligned(pose_order, 3) || cp_misaligned(img_off_host, 3) || cp_misaligned(pose_order_host, 3) ||
       cp_misaligned(ren_depth, 3) || cp_misaligned(boxes, 3))
     return CP_ERR_ALIGN;
-  // the CSR: a monotone partition of [0, P), every entry of pose_order a pose
-  if (img_off_host[0] != 0 || img_off_host[I] != P) return CP_ERR_INVALID;
-  for (int i = 0; i < I; ++i)
-    if (img_off_host[i + 1] < img_off_host[i]) return CP_ERR_INVALID;
-  for (int j = 0; j < P; ++j)
-    if (pose_order_host[j] < 0 || pose_order_host[j] >= P) return CP_ERR_INVALID;
+  if (vs_csr_invalid(img_off_host, pose_order_host, I, P)) return CP_ERR_INVALID;
   if (W >= (1 << 24) || H >= (1 << 24) || (long long)I * H * W >= (1LL << 31) / 3) return CP_ERR_RANGE;
   VsGrid gp, gi;
   if (!vs_grid(W, H, 1, false, P, 1, Vmax, gp) || !vs_grid(W, H, 1, false, I, 1, Vmax, gi)) return CP_ERR_RANGE;
   const long long npix = (long long)I * H * W;
   const long long finish_blocks = ((npix > P ? npix : (long long)P) + VS_THREADS - 1) / VS_THREADS;
   if (finish_blocks >= (1LL << 24)) return CP_ERR_RANGE;
-  VpParams p = {};
-  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces; p.f_off = f_offsets;
-  p.M = M; p.mesh_id = mesh_ids; p.colors = colors; p.normals = normals; p.surf = surf_colors; p.image_of_pose = image_of_pose;
-  p.img_off = img_off; p.pose_order = pose_order; p.frames = frames; p.vis = vis; p.ren_rgb = ren_rgb; p.ren_depth = ren_depth;
-  p.boxes = boxes; p.ok = ok; p.P = P; p.I = I; p.Vmax = Vmax; p.H = H; p.W = W; p.resolve = resolve; p.draw_boxes = draw_boxes;
-  p.T.shading = shading; p.T.ambient = (float)ambient_weight;
-  p.X.uv = uv; p.X.texels = texels; p.X.off = tex_off; p.X.dims = tex_dims; p.X.filter = filter;
+  p.poses = poses; p.K = cam_K; p.k_stride = k_stride; p.colors = colors; p.normals = normals; p.surf = surf_colors;
+  p.image_of_pose = image_of_pose; p.img_off = img_off; p.pose_order = pose_order; p.frames = frames; p.vis = vis; p.ren_rgb = ren_rgb;
+  p.ren_depth = ren_depth; p.boxes = boxes; p.ok = ok; p.P = P; p.I = I; p.H = H; p.W = W; p.resolve = resolve; p.draw_boxes = draw_boxes;
   for (int k = 0; k < 3; ++k) {
-    p.T.light[k] = (float)light_pos[k];
     const double q = box_color[k] * 255.0;                            // int(c * 255): truncation, then the uint8 range
     p.box_q[k] = q >= 255.0 ? 255 : (q > 0.0 ? (int)q : 0);
   }
   p.tx = gi.tx; p.ty = gi.ty; p.vchunks = gp.vchunks;
-  char* at = (char*)scratch;
-  const size_t rec = cp_align16_up((size_t)P * Vmax * sizeof(float4));
-  p.hdr = (int32_t*)at; at += cp_align16_up((size_t)P * RR_HDR * sizeof(int32_t));
-  p.T.sv = (float4*)at; at += rec;
-  p.T.eye = (float4*)at; at += rec;
-  p.T.vl = (float4*)at; at += rec;
-  p.T.vn = (float4*)at;
+  rr_carve(scratch, P, Vmax, RR_HDR, p.hdr, p.T);
   hipStream_t st = (hipStream_t)stream;
   CP_LAUNCH(vis_pose_kernel, dim3(gp.pose_blocks), dim3(VS_THREADS), 0, st, p);
   CP_LAUNCH(vis_vertex_kernel, dim3(gp.vert_blocks), dim3(VS_THREADS), 0, st, p);

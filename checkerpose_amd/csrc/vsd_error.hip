@@ -32,14 +32,10 @@ constexpr int VS_HDR = 40;                       // 4-byte words per pose (the r
 enum { VS_MODE_VSD = 0, VS_MODE_RENDER = 1, VS_MODE_DEPTH = 2 };
 
 struct VsParams {
+  VsMesh mesh;                // (Vmax 0 in DEPTH mode: no vertices)
   const double* est;          // (B, 12)
   const double* gt;
   const double* K;
-  const float* verts;
-  const int32_t* v_off;
-  const int32_t* faces;       // (sumF, 3), indices local to the mesh
-  const int32_t* f_off;
-  const int32_t* mesh_id;
   const float* depth_test;    // (I, H, W)
   const int32_t* image_id;    // nullptr: image 0
   const double* diameters;    // per mesh (VSD) / per pose (DEPTH)
@@ -53,12 +49,11 @@ struct VsParams {
   int32_t* rows;              // (B, tiles, VS_ROW)
   double taus[VS_TMAX];
   float delta;
-  int k_stride, M, B, Vmax, H, W, I, T, normalise, sphere, mode, nsides, tx, ty, vchunks;
+  // (tx and ty stand apart on purpose: vsd_tile_kernel's speed depends on where its walk loops lie -- a loop start on a 64-byte boundary
+  // costs it 3 %, every instruction the same -- and with the two in one scalar load the first loop starts on one.  After a change to
+  // this struct or to the kernel's prologue, compare tools/vsd_bench.py with the commit before.)
+  int k_stride, B, H, W, I, T, normalise, sphere, mode, tx, nsides, vchunks, ty;
 };
-
-__device__ inline bool vs_mesh(const VsParams& p, int b, int& vfirst, int& V, int& ffirst, int& F, int& m) {
-  return vs_mesh_rows(p.mesh_id, p.v_off, p.f_off, p.M, p.Vmax, b, vfirst, V, ffirst, F, m);
-}
 
 __global__ __launch_bounds__(VS_THREADS) void vsd_pose_kernel(VsParams p) {
 #pragma clang fp contract(off)
@@ -76,7 +71,7 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_pose_kernel(VsParams p) {
     for (int s = 0; s < 2; ++s) vs_rect_set(h + VsH::RECT(s), 0, 0, p.W - 1, p.H - 1);
   } else {
     int vfirst, V, ffirst, F, m;
-    ok = vs_mesh(p, b, vfirst, V, ffirst, F, m) && ok;
+    ok = vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m) && ok;
     const double* __restrict__ e = p.est + 12 * (size_t)b;
     const double* __restrict__ g = p.gt + 12 * (size_t)b;
     ok = ok && vs_finite(e, 12) && vs_finite(g, 12);
@@ -96,9 +91,9 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_vertex_kernel(VsParams p) {
   int32_t* __restrict__ h = p.hdr + (size_t)b * VS_HDR;
   if (!h[VsH::OK] || h[VS_SKIP]) return;                             // (uniform; no barrier in this kernel)
   int vfirst, V, ffirst, F, m;
-  vs_mesh(p, b, vfirst, V, ffirst, F, m);
-  vs_vertex_chunk((const float*)h + VsH::P(s), p.verts + 3 * (size_t)vfirst, V, vc, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f),
-                  p.sv + ((size_t)b * 2 + s) * p.Vmax, h + VsH::RECT(s), h + VsH::BAD(s));
+  vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
+  vs_vertex_chunk((const float*)h + VsH::P(s), p.mesh.verts + 3 * (size_t)vfirst, V, vc, make_float4(-2.f, (float)p.W + 1.f, -2.f, (float)p.H + 1.f),
+                  p.sv + ((size_t)b * 2 + s) * p.mesh.Vmax, h + VsH::RECT(s), h + VsH::BAD(s));
 }
 
 __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
@@ -131,11 +126,11 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
     }
   } else {
     int vfirst, V, ffirst, F, m;
-    vs_mesh(p, b, vfirst, V, ffirst, F, m);
+    vs_mesh_rows(p.mesh, b, vfirst, V, ffirst, F, m);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
       if (hit[s])                                                    // (uniform)
-        vs_depth_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.Vmax, p.faces + 3 * (size_t)ffirst, F, V, c, dep[s]);
+        vs_depth_tile(s_tri, &s_n, p.sv + ((size_t)b * 2 + s) * p.mesh.Vmax, p.mesh.faces + 3 * (size_t)ffirst, F, V, c, dep[s]);
   }
 
   if (p.depth_out) {
@@ -159,7 +154,7 @@ __global__ __launch_bounds__(VS_THREADS) void vsd_tile_kernel(VsParams p) {
     const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
     const int img = p.image_id ? p.image_id[b] : 0;
     const float* __restrict__ test = p.depth_test + (size_t)img * p.H * p.W;
-    const double diam = p.diameters[p.mode == VS_MODE_DEPTH ? b : (p.mesh_id ? p.mesh_id[b] : 0)];
+    const double diam = p.diameters[p.mode == VS_MODE_DEPTH ? b : (p.mesh.mesh_id ? p.mesh.mesh_id[b] : 0)];
 #pragma unroll
     for (int k = 0; k < VS_PPL; ++k) {
       const int x = ox + lx, y = oy + c.y(k);
@@ -240,13 +235,13 @@ void vs_carve(VsParams& p, void* scratch) {
   p.hdr = (int32_t*)at;
   at += cp_align16_up((size_t)p.B * VS_HDR * sizeof(int32_t));
   p.sv = (float4*)at;
-  at += (size_t)p.B * 2 * p.Vmax * sizeof(float4);
+  at += (size_t)p.B * 2 * p.mesh.Vmax * sizeof(float4);
   p.rows = (int32_t*)at;
 }
 
 int vs_launch(VsParams& p, hipStream_t st) {
   VsGrid g;
-  if (!vs_grid(p.W, p.H, 1, false, p.B, p.nsides, p.Vmax, g) || (long long)p.H * p.W >= (1LL << 31)) return CP_ERR_RANGE;
+  if (!vs_grid(p.W, p.H, 1, false, p.B, p.nsides, p.mesh.Vmax, g) || (long long)p.H * p.W >= (1LL << 31)) return CP_ERR_RANGE;
   p.tx = g.tx; p.ty = g.ty; p.vchunks = g.vchunks;
   CP_LAUNCH(vsd_pose_kernel, dim3(g.pose_blocks), dim3(VS_THREADS), 0, st, p);
   if (p.mode != VS_MODE_DEPTH) CP_LAUNCH(vsd_vertex_kernel, dim3(g.vert_blocks), dim3(VS_THREADS), 0, st, p);
@@ -269,24 +264,19 @@ extern "C" int cp_vsd_errors(cp_stream_t stream, const double* pose_est, const d
                              const int32_t* mesh_ids, const float* depth_test, const int32_t* image_ids, int I, int H, int W,
                              double delta, const double* diameters, const double* taus, int T, int normalized_by_diameter,
                              int sphere_check, int B, int Vmax, double* errors, int32_t* counts, float* depth_out, void* scratch) {
-  if (!pose_est || !pose_gt || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !depth_test || !diameters || !taus || !errors ||
-      !counts || !scratch)
-    return CP_ERR_INVALID;
-  if (B <= 0 || M <= 0 || Vmax <= 0 || I <= 0 || H <= 0 || W <= 0 || T < 1 || T > VS_TMAX || (k_stride != 0 && k_stride != 9) ||
+  VsParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!pose_est || !pose_gt || !depth_test || !diameters || !taus || !errors || !counts || !scratch) return CP_ERR_INVALID;
+  if (vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, B) || vs_images_invalid(image_ids, I) || T < 1 || T > VS_TMAX ||
       !(delta == delta))
     return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (!image_ids && I != 1) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(pose_est, 7) || cp_misaligned(pose_gt, 7) || cp_misaligned(cam_K, 7) ||
-      cp_misaligned(diameters, 7) || cp_misaligned(errors, 7) || cp_misaligned(verts, 3) || cp_misaligned(v_offsets, 3) ||
-      cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) || cp_misaligned(depth_test, 3) ||
+  if (cp_misaligned(scratch, 15) || cp_misaligned(pose_est, 7) || cp_misaligned(pose_gt, 7) || vs_view_misaligned(cam_K) ||
+      cp_misaligned(diameters, 7) || cp_misaligned(errors, 7) || vs_mesh_misaligned(p.mesh) || cp_misaligned(depth_test, 3) ||
       cp_misaligned(image_ids, 3) || cp_misaligned(counts, 3) || cp_misaligned(depth_out, 3))
     return CP_ERR_ALIGN;
-  VsParams p = {};
-  p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
-  p.f_off = f_offsets; p.M = M; p.mesh_id = mesh_ids; p.depth_test = depth_test; p.image_id = image_ids; p.I = I; p.H = H; p.W = W;
-  p.delta = (float)delta; p.diameters = diameters; p.T = T; p.normalise = normalized_by_diameter ? 1 : 0; p.sphere = sphere_check ? 1 : 0;
-  p.B = B; p.Vmax = Vmax; p.errors = errors; p.counts = counts; p.depth_out = depth_out; p.mode = VS_MODE_VSD; p.nsides = 2;
+  p.est = pose_est; p.gt = pose_gt; p.K = cam_K; p.k_stride = k_stride; p.depth_test = depth_test; p.image_id = image_ids; p.I = I; p.H = H;
+  p.W = W; p.delta = (float)delta; p.diameters = diameters; p.T = T; p.normalise = normalized_by_diameter ? 1 : 0;
+  p.sphere = sphere_check ? 1 : 0; p.B = B; p.errors = errors; p.counts = counts; p.depth_out = depth_out; p.mode = VS_MODE_VSD; p.nsides = 2;
   for (int k = 0; k < T; ++k) p.taus[k] = taus[k];
   vs_carve(p, scratch);
   return vs_launch(p, (hipStream_t)stream);
@@ -296,18 +286,17 @@ extern "C" int cp_vsd_from_depth(cp_stream_t stream, const float* depth_est, con
                                  const float* depth_test, const int32_t* image_ids, int I, int H, int W, double delta,
                                  const double* diameters, const double* taus, int T, int normalized_by_diameter, int B, double* errors,
                                  int32_t* counts, void* scratch) {
-  if (!depth_est || !depth_gt || !cam_K || !depth_test || !diameters || !taus || !errors || !counts || !scratch) return CP_ERR_INVALID;
-  if (B <= 0 || I <= 0 || H <= 0 || W <= 0 || T < 1 || T > VS_TMAX || (k_stride != 0 && k_stride != 9) || !(delta == delta))
+  if (!depth_est || !depth_gt || !depth_test || !diameters || !taus || !errors || !counts || !scratch) return CP_ERR_INVALID;
+  if (vs_view_invalid(cam_K, k_stride, H, W, B) || vs_images_invalid(image_ids, I) || T < 1 || T > VS_TMAX || !(delta == delta))
     return CP_ERR_INVALID;
-  if (!image_ids && I != 1) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(cam_K, 7) || cp_misaligned(diameters, 7) || cp_misaligned(errors, 7) ||
+  if (cp_misaligned(scratch, 15) || vs_view_misaligned(cam_K) || cp_misaligned(diameters, 7) || cp_misaligned(errors, 7) ||
       cp_misaligned(depth_est, 3) || cp_misaligned(depth_gt, 3) || cp_misaligned(depth_test, 3) || cp_misaligned(image_ids, 3) ||
       cp_misaligned(counts, 3))
     return CP_ERR_ALIGN;
   VsParams p = {};
   p.in_est = depth_est; p.in_gt = depth_gt; p.K = cam_K; p.k_stride = k_stride; p.depth_test = depth_test; p.image_id = image_ids;
   p.I = I; p.H = H; p.W = W; p.delta = (float)delta; p.diameters = diameters; p.T = T; p.normalise = normalized_by_diameter ? 1 : 0;
-  p.B = B; p.Vmax = 0; p.errors = errors; p.counts = counts; p.mode = VS_MODE_DEPTH; p.nsides = 2;
+  p.B = B; p.errors = errors; p.counts = counts; p.mode = VS_MODE_DEPTH; p.nsides = 2;
   for (int k = 0; k < T; ++k) p.taus[k] = taus[k];
   vs_carve(p, scratch);
   return vs_launch(p, (hipStream_t)stream);
@@ -316,16 +305,13 @@ extern "C" int cp_vsd_from_depth(cp_stream_t stream, const float* depth_est, con
 extern "C" int cp_render_depth(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
                                const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
                                int H, int W, int B, int Vmax, float* depth_out, void* scratch) {
-  if (!poses || !cam_K || !verts || !v_offsets || !faces || !f_offsets || !depth_out || !scratch) return CP_ERR_INVALID;
-  if (B <= 0 || M <= 0 || Vmax <= 0 || H <= 0 || W <= 0 || (k_stride != 0 && k_stride != 9)) return CP_ERR_INVALID;
-  if (!mesh_ids && M != 1) return CP_ERR_INVALID;
-  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || cp_misaligned(cam_K, 7) || cp_misaligned(verts, 3) ||
-      cp_misaligned(v_offsets, 3) || cp_misaligned(faces, 3) || cp_misaligned(f_offsets, 3) || cp_misaligned(mesh_ids, 3) ||
+  VsParams p = {};
+  p.mesh = {verts, v_offsets, faces, f_offsets, mesh_ids, M, Vmax};
+  if (!poses || !depth_out || !scratch || vs_mesh_invalid(p.mesh) || vs_view_invalid(cam_K, k_stride, H, W, B)) return CP_ERR_INVALID;
+  if (cp_misaligned(scratch, 15) || cp_misaligned(poses, 7) || vs_view_misaligned(cam_K) || vs_mesh_misaligned(p.mesh) ||
       cp_misaligned(depth_out, 3))
     return CP_ERR_ALIGN;
-  VsParams p = {};
-  p.est = poses; p.gt = poses; p.K = cam_K; p.k_stride = k_stride; p.verts = verts; p.v_off = v_offsets; p.faces = faces;
-  p.f_off = f_offsets; p.M = M; p.mesh_id = mesh_ids; p.H = H; p.W = W; p.B = B; p.Vmax = Vmax; p.depth_out = depth_out;
+  p.est = poses; p.gt = poses; p.K = cam_K; p.k_stride = k_stride; p.H = H; p.W = W; p.B = B; p.depth_out = depth_out;
   p.mode = VS_MODE_RENDER; p.nsides = 1; p.T = 1;
   vs_carve(p, scratch);
   return vs_launch(p, (hipStream_t)stream);

@@ -24,6 +24,10 @@
 //   vs_dist         misc.depth_im_to_dist_im_fast at a pixel; vs_visible: visibility.py's 'bop19' test
 //   vs_acc_identity, vs_acc_combine, vs_acc_waves, vs_acc_reduce     NSUM integer sums, then groups of min min max max
 //   vs_box_xywh     xmin ymin xmax ymax -> x, y, w, h, or -1 four times
+//   VsMesh, vs_mesh_rows                                      the mesh table of a call and one pose's rows of it
+//   vs_image_rows   an image's rows of the image-to-poses CSR (vis_poses.hip, scene_labels.hip)
+//   vs_mesh_invalid / _misaligned, vs_view_invalid / _misaligned, vs_images_invalid, vs_csr_invalid / _over     (host) the entry
+//                   points' argument rules, by error class
 //   vs_grid         (host) the tile grid, the vertex chunks and the block counts of a call
 #pragma once
 #include "common.h"
@@ -95,19 +99,41 @@ __device__ inline int vs_sphere_skip(const double* __restrict__ e, const double*
   return overlap ? 0 : 1;
 }
 
-// mesh m = mesh_id[b] (0 without ids): its rows of the vertex and face tables; false when the id or the tables are out of range
-__device__ inline bool vs_mesh_rows(const int32_t* __restrict__ mesh_id, const int32_t* __restrict__ v_off,
-                                    const int32_t* __restrict__ f_off, int M, int Vmax, int b, int& vfirst, int& V, int& ffirst, int& F,
-                                    int& m) {
+// The mesh table of a call.  It must stay the FIRST member of every raster row's params struct: where the member stands changes
+// hipcc's register allocation of the tile kernels.  Checked on the host by vs_mesh_invalid / vs_mesh_misaligned below.
+struct VsMesh {
+  const float* verts;         // (sumV, 3)
+  const int32_t* v_off;       // (M + 1)
+  const int32_t* faces;       // (sumF, 3), indices local to the mesh
+  const int32_t* f_off;       // (M + 1)
+  const int32_t* mesh_id;     // per pose, or nullptr: mesh 0
+  int M, Vmax;
+};
+
+// mesh m = mesh_id[b] (0 without ids): its rows of the vertex and face tables; false when the id or the tables are out of range.
+// (M and Vmax are read first, together: one scalar load of the kernel's arguments.)
+__device__ inline bool vs_mesh_rows(const VsMesh& t, int b, int& vfirst, int& V, int& ffirst, int& F, int& m) {
   vfirst = 0; V = 0; ffirst = 0; F = 0;
-  m = mesh_id ? mesh_id[b] : 0;
+  const int M = t.M, Vmax = t.Vmax;
+  m = t.mesh_id ? t.mesh_id[b] : 0;
   if (m < 0 || m >= M) return false;
-  vfirst = v_off[m];
-  V = v_off[m + 1] - vfirst;
-  ffirst = f_off[m];
-  F = f_off[m + 1] - ffirst;
+  vfirst = t.v_off[m];
+  V = t.v_off[m + 1] - vfirst;
+  ffirst = t.f_off[m];
+  F = t.f_off[m + 1] - ffirst;
   if (vfirst < 0 || V <= 0 || V > Vmax || ffirst < 0 || F < 0) { V = 0; F = 0; return false; }
   return true;
+}
+
+// image img's rows [j0, j1) of the image-to-poses CSR, clamped to [0, P] and, with `cap`, to that many rows (the host checked them --
+// vs_csr_invalid, vs_csr_over --; the clamps bound the loops, and scene_labels' shifts, whatever the memory holds)
+__device__ __forceinline__ void vs_image_rows(const int32_t* __restrict__ img_off, int P, int img, int& j0, int& j1) {
+  j0 = min(max(img_off[img], 0), P);
+  j1 = min(max(img_off[img + 1], j0), P);
+}
+__device__ __forceinline__ void vs_image_rows(const int32_t* __restrict__ img_off, int P, int img, int cap, int& j0, int& j1) {
+  vs_image_rows(img_off, P, img, j0, j1);
+  j1 = min(j1, j0 + cap);
 }
 
 // row . (x, y, z, 1): one fma chain
@@ -365,6 +391,41 @@ __device__ __forceinline__ void vs_box_xywh(const int32_t* __restrict__ r, bool 
 }
 
 // ---- host side
+// An entry point's argument rules by error class, as predicates: every entry point returns CP_ERR_INVALID when one of the *_invalid
+// (and its own INVALID rules) holds, then CP_ERR_ALIGN for the *_misaligned (and its own), then, with an image-to-poses CSR,
+// CP_ERR_INVALID for vs_csr_invalid, then CP_ERR_RANGE for its size rules (vs_csr_over, vs_grid, its own pixel bound).
+
+// the mesh table: a table missing, no mesh or no vertex row, no ids although there are several meshes;  then its alignment
+inline bool vs_mesh_invalid(const VsMesh& t) {
+  return !t.verts || !t.v_off || !t.faces || !t.f_off || t.M <= 0 || t.Vmax <= 0 || (!t.mesh_id && t.M != 1);
+}
+inline bool vs_mesh_misaligned(const VsMesh& t) {
+  return cp_misaligned(t.verts, 3) || cp_misaligned(t.v_off, 3) || cp_misaligned(t.faces, 3) || cp_misaligned(t.f_off, 3) ||
+         cp_misaligned(t.mesh_id, 3);
+}
+// the camera (one K: k_stride 0, or one per pose or image: k_stride 9) and the frame: H, W and the count of poses positive
+inline bool vs_view_invalid(const double* K, int k_stride, int H, int W, int count) {
+  return !K || (k_stride != 0 && k_stride != 9) || H <= 0 || W <= 0 || count <= 0;
+}
+inline bool vs_view_misaligned(const double* K) { return cp_misaligned(K, 7); }
+// the images that poses are scored against: none, or no ids although there are several
+inline bool vs_images_invalid(const int32_t* image_ids, int I) { return I <= 0 || (!image_ids && I != 1); }
+// the image-to-poses CSR (host copies) is no monotone partition of [0, P), or an entry of pose_order is no pose;  vs_csr_over: an image
+// has more than `cap` poses
+inline bool vs_csr_invalid(const int32_t* img_off, const int32_t* pose_order, int I, int P) {
+  if (img_off[0] != 0 || img_off[I] != P) return true;
+  for (int i = 0; i < I; ++i)
+    if (img_off[i + 1] < img_off[i]) return true;
+  for (int j = 0; j < P; ++j)
+    if (pose_order[j] < 0 || pose_order[j] >= P) return true;
+  return false;
+}
+inline bool vs_csr_over(const int32_t* img_off, int I, int cap) {
+  for (int i = 0; i < I; ++i)
+    if (img_off[i + 1] - img_off[i] > cap) return true;
+  return false;
+}
+
 // The launch plan of B poses with `nsides` sides on a W x H frame sampled f x f per pixel: tx x ty tiles starting at pixel (x0, y0),
 // vchunks vertex chunks.  canvas: gt_info's grid over [-W, 2W) x [-H, 2H), anchored so that frame pixel (0, 0) is a tile corner.
 // False when a kernel's block count would reach 2^24.  (The callers bound W, H, f first: nothing overflows here.)

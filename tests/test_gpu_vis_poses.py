@@ -220,6 +220,27 @@ def test_outputs_do_not_depend_on_the_call_the_batch_or_the_order():
     assert on.any() and (white["vis"][on][:, 0] == 255).all()
 
 
+def test_an_image_may_hold_more_than_32_poses():
+    """cp_render_scene clamps an image's rows of the image-to-poses CSR to 32 (one bit per pose); cp_vis_poses, which reads the rows
+    through the same accessor, must not.  33 tetrahedra (tests/test_gpu_scene.py's) in ONE 48 x 40 image at 33 distinct depths,
+    overlapping near the centre, the nearest one LAST in the order: ren_depth is, bit for bit, the per-pixel smallest positive value
+    of render_depth's 33 images (the rule at the top of vis_poses.hip: m_depth is cp_render_depth's, the update a strict minimum)."""
+    from checkerpose_amd import metric, vis
+    from tests import test_gpu_scene as SC
+    s, n, dev = SC.fixture(), 33, torch.device("cuda:0")
+    R = np.stack([SC._rot((1, 2, 3), 0.19 * j) for j in range(n)])
+    t = np.array([[3.0 * np.cos(1.3 * j), 3.0 * np.sin(1.3 * j), 476.0 - 3.0 * j] for j in range(n)]).reshape(n, 3, 1)      # pose 32: Z = 380
+    Rd, td = torch.from_numpy(R).to(dev), torch.from_numpy(t).to(dev)
+    each = metric.render_depth(Rd, td, s.K, s.ms, (SC.W, SC.H), mesh_ids=[0] * n).cpu().numpy()
+    assert each.shape == (n, SC.H, SC.W) and all(e.any() for e in each)
+    want = np.where(each > 0, each, np.float32(np.inf)).min(axis=0)
+    want[np.isinf(want)] = 0.0
+    r = host(vis.vis_poses(Rd, td, s.K, s.ms, torch.zeros(1, SC.H, SC.W, 3, dtype=torch.uint8, device=dev), image_ids=[0] * n, mesh_ids=[0] * n))
+    assert r["ok"].tolist() == [1] * n
+    assert np.array_equal(r["ren_depth"][0].view(np.int32), want.view(np.int32))
+    assert ((each[n - 1] > 0) & (r["ren_depth"][0] == each[n - 1])).any()            # the last pose, past row 32, owns pixels
+
+
 def test_the_launch_list_does_not_depend_on_the_poses():
     from checkerpose_amd import _abi
     lib = _abi.load()

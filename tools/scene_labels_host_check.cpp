@@ -83,7 +83,16 @@ int main() {
     a = good; a.P = 34; a.I = 2; a.n_bg = 2; a.pose_order_host = order33; a.img_off_host = off33; EXPECT(call(a), CP_ERR_RANGE);
     // 32 pass that check: the call goes on to the size checks (a frame side of 2^24 refuses it there, still before any launch)
     a.img_off_host = off32; a.W = 1 << 24; EXPECT(call(a), CP_ERR_RANGE);
+    // 33 poses in one image and an entry of pose_order that is no pose: the CSR's INVALID comes before the limit's RANGE
+    static int32_t order33_bad[34];
+    for (int j = 0; j < 34; ++j) order33_bad[j] = j == 33 ? 34 : j;
+    a = good; a.P = 34; a.I = 2; a.n_bg = 2; a.pose_order_host = order33_bad; a.img_off_host = off33; EXPECT(call(a), CP_ERR_INVALID);
   }
+  // two rules broken at once: INVALID before ALIGN, ALIGN before the CSR's INVALID, the CSR before RANGE
+  a = good; a.rgb = nullptr; a.verts = (const float*)(buf + 2); EXPECT(call(a), CP_ERR_INVALID);
+  a = good; a.slot = (int32_t*)(buf + 2); a.W = 1 << 24; EXPECT(call(a), CP_ERR_ALIGN);
+  a = good; a.fract = (double*)(buf + 4); a.img_off_host = off_back; EXPECT(call(a), CP_ERR_ALIGN);
+  a = good; a.pose_order_host = order_hi; a.W = 1 << 24; EXPECT(call(a), CP_ERR_INVALID);
   // sizes: a frame side of 2^24, a batch of 2^31 / 3 bytes, a canvas of 2^31 / 9 pixels, 2^24 workgroups
   WITH(W, 1 << 24, CP_ERR_RANGE);
   a = good; a.H = 4096; a.W = 4096; a.I = 64; a.n_bg = 1; { static int32_t big_off[65]; for (int i = 0; i < 65; ++i) big_off[i] = i == 0 ? 0 : P; a.img_off_host = big_off; EXPECT(call(a), CP_ERR_RANGE); }

@@ -74,6 +74,11 @@ int main() {
     a = good; a.P = 1 << 20; a.I = 1; a.Vmax = 1 << 13; a.img_off_host = one_off; a.pose_order_host = many_order;
     EXPECT(call(a), CP_ERR_RANGE);
   }
+  // two rules broken at once: INVALID before ALIGN, ALIGN before the CSR's INVALID, the CSR before RANGE
+  a = good; a.frames = nullptr; a.verts = (const float*)(buf + 2); EXPECT(call(a), CP_ERR_INVALID);
+  a = good; a.boxes = (int32_t*)(buf + 2); a.W = 1 << 24; EXPECT(call(a), CP_ERR_ALIGN);
+  a = good; a.poses = (const double*)(buf + 4); a.img_off_host = off_back; EXPECT(call(a), CP_ERR_ALIGN);
+  a = good; a.pose_order_host = order_hi; a.W = 1 << 24; EXPECT(call(a), CP_ERR_INVALID);
   // scratch: P headers of 48 words, four float4 tables of (P, Vmax)
   EXPECT(cp_vis_poses_scratch_bytes(5, 12, 3), 5 * 48 * 4 + 4 * 5 * 12 * 16);
   EXPECT(cp_vis_poses_scratch_bytes(3, 7, 1), 3 * 48 * 4 + 4 * 3 * 7 * 16);
