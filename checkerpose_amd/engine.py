@@ -104,68 +104,57 @@ class WeightStore:
             raise RuntimeError("parameter %s must be an fp32 tensor on %s" % (key, self.device))
         return t.detach().contiguous()
 
+    def cached(self, key, make):
+        """cache[key], made by make() the first time it is asked for"""
+        if key not in self.cache:
+            self.cache[key] = make()
+        return self.cache[key]
+
+    def _packed(self, nbytes, w, call, what):
+        """a packed weight image: `nbytes` device bytes filled from the fp32 source weight `w` by
+        call(stream, w pointer, image pointer) -> status, a packing launch on the current stream"""
+        out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        wc = w.contiguous()
+        self.keep.append(wc)
+        _abi.check(call(torch.cuda.current_stream(self.device).cuda_stream, wc.data_ptr(), out.data_ptr()), what)
+        return out
+
+    def _pack(self, key, nbytes, w, call, what):
+        """the same, made once per cache key"""
+        return self.cached(key, lambda: self._packed(nbytes, w, call, what))
+
     def pack(self, name, w, Cout, Cin, R, S, cin_phys, cout_rows, transposed=0, phase=0, row_map=None, dtype=None):
         dtype = self.dtype if dtype is None else dtype
-        ck = (name, cin_phys, cout_rows, transposed, phase) + (() if dtype == self.dtype else (dtype,))
-        if ck in self.cache:
-            return self.cache[ck]
-        nbytes = self.lib.cp_packed_weight_bytes(dtype, cout_rows, cin_phys, R, S)
-        out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        rm = None
-        if row_map is not None:
-            rm = torch.tensor(row_map, dtype=torch.int32, device=self.device)
-            self.keep.append(rm)
-        w = w.contiguous()
-        self.keep.append(w)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _abi.check(self.lib.cp_pack_conv_weight(st, dtype, w.data_ptr(), Cout, Cin, R, S, cin_phys, transposed, phase,
-                                                rm.data_ptr() if rm is not None else None, cout_rows, out.data_ptr()),
-                   "cp_pack_conv_weight(%s)" % name)
-        self.cache[ck] = out
-        return out
+
+        def call(st, wp, op):
+            rm = None
+            if row_map is not None:
+                rm = torch.tensor(row_map, dtype=torch.int32, device=self.device)
+                self.keep.append(rm)
+            return self.lib.cp_pack_conv_weight(st, dtype, wp, Cout, Cin, R, S, cin_phys, transposed, phase,
+                                                rm.data_ptr() if rm is not None else None, cout_rows, op)
+        return self._pack((name, cin_phys, cout_rows, transposed, phase) + (() if dtype == self.dtype else (dtype,)),
+                          self.lib.cp_packed_weight_bytes(dtype, cout_rows, cin_phys, R, S), w, call, "cp_pack_conv_weight(%s)" % name)
 
     def pack_halo(self, name, w, Cout, Cin, cin_phys):
         """3x3/s1/p1 weights in the halo kernel's image (cp_pack_conv3x3_halo_weight)."""
-        ck = ("halo", name, cin_phys)
-        if ck in self.cache:
-            return self.cache[ck]
-        out = torch.empty(self.lib.cp_packed_halo_weight_bytes(self.dtype, Cout, cin_phys), dtype=torch.uint8, device=self.device)
-        w = w.contiguous()
-        self.keep.append(w)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _abi.check(self.lib.cp_pack_conv3x3_halo_weight(st, self.dtype, w.data_ptr(), Cout, Cin, cin_phys, out.data_ptr()),
-                   "cp_pack_conv3x3_halo_weight(%s)" % name)
-        self.cache[ck] = out
-        return out
+        return self._pack(("halo", name, cin_phys), self.lib.cp_packed_halo_weight_bytes(self.dtype, Cout, cin_phys), w,
+                          lambda st, wp, op: self.lib.cp_pack_conv3x3_halo_weight(st, self.dtype, wp, Cout, Cin, cin_phys, op),
+                          "cp_pack_conv3x3_halo_weight(%s)" % name)
 
     def pack_rows3x3(self, name, w, Cout, Cin, cin_phys):
         """conv1 of the fused BasicBlock (cp_pack_conv3x3_rows_weight: small-Cout halo image, rows unpermuted)."""
-        ck = ("rows3x3", name, cin_phys)
-        if ck in self.cache:
-            return self.cache[ck]
-        out = torch.empty(self.lib.cp_packed_halo_weight_bytes(self.dtype, Cout, cin_phys), dtype=torch.uint8, device=self.device)
-        w = w.contiguous()
-        self.keep.append(w)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _abi.check(self.lib.cp_pack_conv3x3_rows_weight(st, self.dtype, w.data_ptr(), Cout, Cin, cin_phys, out.data_ptr()),
-                   "cp_pack_conv3x3_rows_weight(%s)" % name)
-        self.cache[ck] = out
-        return out
+        return self._pack(("rows3x3", name, cin_phys), self.lib.cp_packed_halo_weight_bytes(self.dtype, Cout, cin_phys), w,
+                          lambda st, wp, op: self.lib.cp_pack_conv3x3_rows_weight(st, self.dtype, wp, Cout, Cin, cin_phys, op),
+                          "cp_pack_conv3x3_rows_weight(%s)" % name)
 
     def pack_gemm(self, name, w, Cout, Cin, cin_phys, dtype=None):
         """1x1 / Linear weights in the LDS-GEMM kernel's image (cp_pack_gemm_weight)."""
         dtype = self.dtype if dtype is None else dtype
-        ck = ("gemm", name, cin_phys) + (() if dtype == self.dtype else (dtype,))
-        if ck in self.cache:
-            return self.cache[ck]
-        out = torch.empty(self.lib.cp_packed_gemm_weight_bytes(dtype, Cout, cin_phys), dtype=torch.uint8, device=self.device)
-        w = w.contiguous()
-        self.keep.append(w)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        _abi.check(self.lib.cp_pack_gemm_weight(st, dtype, w.data_ptr(), Cout, Cin, cin_phys, out.data_ptr()),
-                   "cp_pack_gemm_weight(%s)" % name)
-        self.cache[ck] = out
-        return out
+        return self._pack(("gemm", name, cin_phys) + (() if dtype == self.dtype else (dtype,)),
+                          self.lib.cp_packed_gemm_weight_bytes(dtype, Cout, cin_phys), w,
+                          lambda st, wp, op: self.lib.cp_pack_gemm_weight(st, dtype, wp, Cout, Cin, cin_phys, op),
+                          "cp_pack_gemm_weight(%s)" % name)
 
     def pack_chain(self, name, ws, affs, C_, H, W):
         """the 8 convs of an HRNet branch chain: one packed weight blob (BN scale folded in) + one [8][2][AFF] fp32 affine tensor
@@ -360,28 +349,14 @@ class Program:
                                                     R * S * x.Cphys, _rup(wCout, self.E))):
             halo = gemm = s2small = halo2 = False      # small batch: the generic kernel's split-K variant beats the tiled specialists
         if s2small:
-            ck = ("s2small", wkey, x.Cphys)
-            if ck not in self.ws.cache:
-                buf = torch.empty(self.lib.cp_conv3x3_s2_small_weight_bytes(x.Cphys, _rup(wCout, self.E)), dtype=torch.uint8, device=self.device)
-                wc = w.contiguous()
-                self.ws.keep.append(wc)
-                st_ = torch.cuda.current_stream(self.device).cuda_stream
-                _abi.check(self.lib.cp_pack_conv3x3_s2_small_weight(st_, wc.data_ptr(), wCout, wCin, x.Cphys, _rup(wCout, self.E), buf.data_ptr()),
-                           "cp_pack_conv3x3_s2_small_weight(%s)" % wkey)
-                self.ws.cache[ck] = buf
-            packed = self.ws.cache[ck]
+            packed = self.ws._pack(("s2small", wkey, x.Cphys), self.lib.cp_conv3x3_s2_small_weight_bytes(x.Cphys, _rup(wCout, self.E)), w,
+                                   lambda st, wp, op: self.lib.cp_pack_conv3x3_s2_small_weight(st, wp, wCout, wCin, x.Cphys, _rup(wCout, self.E), op),
+                                   "cp_pack_conv3x3_s2_small_weight(%s)" % wkey)
             halo = gemm = False
         elif halo2:
-            ck = ("halo2", wkey, x.Cphys)
-            if ck not in self.ws.cache:
-                buf = torch.empty(self.lib.cp_packed_conv2x2_halo_weight_bytes(self.dtype, wCout, x.Cphys), dtype=torch.uint8, device=self.device)
-                wc = w.contiguous()
-                self.ws.keep.append(wc)
-                st_ = torch.cuda.current_stream(self.device).cuda_stream
-                _abi.check(self.lib.cp_pack_conv2x2_halo_weight(st_, self.dtype, wc.data_ptr(), wCout, wCin, x.Cphys, buf.data_ptr()),
-                           "cp_pack_conv2x2_halo_weight(%s)" % wkey)
-                self.ws.cache[ck] = buf
-            packed = self.ws.cache[ck]
+            packed = self.ws._pack(("halo2", wkey, x.Cphys), self.lib.cp_packed_conv2x2_halo_weight_bytes(self.dtype, wCout, x.Cphys), w,
+                                   lambda st, wp, op: self.lib.cp_pack_conv2x2_halo_weight(st, self.dtype, wp, wCout, wCin, x.Cphys, op),
+                                   "cp_pack_conv2x2_halo_weight(%s)" % wkey)
         elif halo:
             packed = self.ws.pack_halo(wkey, w, wCout, wCin, x.Cphys)
         elif gemm:
@@ -490,13 +465,13 @@ class Program:
         packed = self.ws.pack_halo(wkey, w, wCout, wCin, x.Cphys)
         sc, sh = self.ws.affine(wkey + "#0", scale, shift, wCout)
         S = seg_w.shape[0]
-        ck = ("seg_head", seg_key, self.dtype)
-        if ck not in self.ws.cache:
+
+        def head():
             w2 = seg_w.reshape(S, wCout).float()
             if self.dtype == CP_BF16:
                 w2 = w2.to(torch.bfloat16).float()          # what the packed bf16 weights of the stand-alone head conv hold
-            self.ws.cache[ck] = (w2.contiguous().to(self.device), seg_b.float().contiguous().to(self.device))
-        sw, sb = self.ws.cache[ck]
+            return w2.contiguous().to(self.device), seg_b.float().contiguous().to(self.device)
+        sw, sb = self.ws.cached(("seg_head", seg_key, self.dtype), head)
         out = self.act(x.H, x.W, wCout)
         d = CpConvDesc()
         d.dtype, d.out_f32 = self.dtype, 0
@@ -867,19 +842,24 @@ class Program:
         return (USE_EDGE_FUSED and self.dtype == CP_BF16 and self.B >= self.edge_min
                 and bool(self.lib.cp_edgeconv_fused_supported(N, K, Cin, Cout)))
 
+    def _edge_fused_weight(self, wkey, wpq, scale, shift):
+        """(packed [W1 ; W2 - W1] image, scale, shift) of an EdgeConv layer in the keypoint side's type -- one cache entry for the
+        per-crop and the tiled launch"""
+        Co2, Cin = wpq.shape[0], wpq.shape[1]
+        gdt = self.gdt
+
+        def make():
+            buf = self.ws._packed(self.lib.cp_edgeconv_fused_weight_bytes(Cin, Co2 // 2), wpq.reshape(Co2, Cin),
+                                  lambda st, wp, op: self.lib.cp_pack_edgeconv_fused_weight_t(st, gdt, wp, Cin, Co2 // 2, op),
+                                  "cp_pack_edgeconv_fused_weight")
+            return buf, scale.contiguous(), shift.contiguous()
+        return self.ws.cached(("edge_fused", wkey, gdt), make)
+
     def edge_fused(self, x: Act, wkey, wpq, scale, shift, idx_t, gids_t, out: Act, K, G, slope):
         """whole EdgeConv layer in one launch (cp_edgeconv_fused): wpq fp32 (2 C', C) = [W1 ; W2 - W1]"""
         Co2, Cin = wpq.shape[0], wpq.shape[1]
         gdt = self.gdt
-        ck = ("edge_fused", wkey, gdt)
-        if ck not in self.ws.cache:
-            buf = torch.empty(self.lib.cp_edgeconv_fused_weight_bytes(Cin, Co2 // 2), dtype=torch.uint8, device=self.device)
-            w2 = wpq.reshape(Co2, Cin).contiguous()
-            self.ws.keep.append(w2)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _abi.check(self.lib.cp_pack_edgeconv_fused_weight_t(st, gdt, w2.data_ptr(), Cin, Co2 // 2, buf.data_ptr()), "cp_pack_edgeconv_fused_weight")
-            self.ws.cache[ck] = (buf, scale.contiguous(), shift.contiguous())
-        buf, sc, sh = self.ws.cache[ck]
+        buf, sc, sh = self._edge_fused_weight(wkey, wpq, scale, shift)
         self.keep += [buf, sc, sh]
         fn = self.lib.cp_edgeconv_fused_t
         xt, ot = x.tbuf, out.tbuf
@@ -912,24 +892,11 @@ class Program:
         the INTERNAL keypoint order of `tiled` (graph_sched.tile_schedule, device tensors)"""
         Co2, Cin = wpq.shape[0], wpq.shape[1]
         Co, N = Co2 // 2, x.W
-        st = torch.cuda.current_stream(self.device).cuda_stream
         gdt = self.gdt
-        ck = ("edge_fused", wkey, gdt)
-        if ck not in self.ws.cache:
-            buf = torch.empty(self.lib.cp_edgeconv_fused_weight_bytes(Cin, Co), dtype=torch.uint8, device=self.device)
-            w2 = wpq.reshape(Co2, Cin).contiguous()
-            self.ws.keep.append(w2)
-            _abi.check(self.lib.cp_pack_edgeconv_fused_weight_t(st, gdt, w2.data_ptr(), Cin, Co, buf.data_ptr()), "cp_pack_edgeconv_fused_weight")
-            self.ws.cache[ck] = (buf, scale.contiguous(), shift.contiguous())
-        buf, sc, sh = self.ws.cache[ck]
-        cq = ("edge_tiled_q", wkey, gdt)
-        if cq not in self.ws.cache:
-            bq = torch.empty(self.lib.cp_edgeconv_tiled_weight_bytes(Cin, Co), dtype=torch.uint8, device=self.device)
-            w2 = wpq.reshape(Co2, Cin).contiguous()
-            self.ws.keep.append(w2)
-            _abi.check(self.lib.cp_pack_edgeconv_tiled_weight_t(st, gdt, w2.data_ptr(), Cin, Co, bq.data_ptr()), "cp_pack_edgeconv_tiled_weight")
-            self.ws.cache[cq] = bq
-        bq = self.ws.cache[cq]
+        buf, sc, sh = self._edge_fused_weight(wkey, wpq, scale, shift)
+        bq = self.ws._pack(("edge_tiled_q", wkey, gdt), self.lib.cp_edgeconv_tiled_weight_bytes(Cin, Co), wpq.reshape(Co2, Cin),
+                           lambda st, wp, op: self.lib.cp_pack_edgeconv_tiled_weight_t(st, gdt, wp, Cin, Co, op),
+                           "cp_pack_edgeconv_tiled_weight")
         ktab = self.tensor(self.lib.cp_edgeconv_tiled_table_bytes(self.B, N, Co), es=1)
         self.keep += [buf, sc, sh, bq, tiled["halo"], tiled["nbr"]]
         fn = self.lib.cp_edgeconv_tiled_t
@@ -948,59 +915,37 @@ class Program:
         return (USE_MLP_FUSED and self.dtype == CP_BF16 and x.H == 1 and self.B * x.W >= self.mlp_min_rows
                 and len(dims) == 4 and bool(self.lib.cp_mlp_query_fused_supported(*[int(d) for d in dims])) and x.C == dims[0])
 
-    def mlp_query_fused(self, x: Act, keys, ws, bs, slope, out_tbuf, ostr):
-        """MLP_QueryNet (pipeline.py:168-180) in one launch: ws = the three nn.Linear weights, bs their biases; the two logits of
-        row (b, n) go to out_tbuf[ostr[0] + b * ostr[1] + n * ostr[3] + c * ostr[4]] (fp32)"""
+    def mlp_query_fused(self, x: Act, keys, ws, bs, slope, out_tbuf, ostr, ids=None):
+        """MLP_QueryNet (pipeline.py:168-180) in one launch: ws = the three nn.Linear weights, bs their biases; the nout = ws[2].shape[0]
+        logits of row (b, n) go to out_tbuf[ostr[0] + b * ostr[1] + n * ostr[3] + c * ostr[4]] (fp32).  Without ids the two-logit head of a
+        refinement stage (cp_mlp_query_fused_t); with ids = (x64, y64), (B, N) int64 torch tensors, the woProg ablation's head
+        (pipeline_lm.py:475-517, nout = 1 + 2r): the x / y codes are decoded into them in the same epilogue (cp_mlp_query_fused_n)"""
         N = x.W
         gdt = self.gdt
+        nout = int(ws[2].shape[0])
+        assert ids is not None or nout == 2
         pw1 = self.ws.pack_gemm(keys[0], ws[0].reshape(ws[0].shape[0], ws[0].shape[1], 1, 1), 256, 256, 256, dtype=gdt)
         pw2 = self.ws.pack_gemm(keys[1], ws[1].reshape(ws[1].shape[0], ws[1].shape[1], 1, 1), 64, 256, 256, dtype=gdt)
-        ck = ("mlp_query", keys[0])
-        if ck not in self.ws.cache:
-            dev = self.device
-            self.ws.cache[ck] = (torch.ones(256, dtype=torch.float32, device=dev), bs[0].float().contiguous(),
-                                 torch.ones(64, dtype=torch.float32, device=dev), bs[1].float().contiguous(),
-                                 ws[2].float().reshape(2, 64).contiguous(), bs[2].float().contiguous())
-        s1, t1, s2, t2, w3, b3 = self.ws.cache[ck]
+        dev = self.device
+        s1, t1, s2, t2, w3, b3 = self.ws.cached(("mlp_query", keys[0]), lambda: (
+            torch.ones(256, dtype=torch.float32, device=dev), bs[0].float().contiguous(),
+            torch.ones(64, dtype=torch.float32, device=dev), bs[1].float().contiguous(),
+            ws[2].float().reshape(nout, 64).contiguous(), bs[2].float().contiguous()))
         self.keep += [pw1, pw2, s1, t1, s2, t2, w3, b3]
         xt = x.tbuf
         a1 = (pw1.data_ptr(), s1.data_ptr(), t1.data_ptr(), float(slope), pw2.data_ptr(), s2.data_ptr(), t2.data_ptr(), float(slope),
               w3.data_ptr(), b3.data_ptr())
         o = (int(ostr[0]), int(ostr[1]), int(ostr[3]), int(ostr[4]))
-        self._add(self.lib.cp_mlp_query_fused_t, lambda P: (gdt, P(xt), x.cstride, x.coff, self.B, N) + a1 + (P(out_tbuf),) + o,
-                  "mlp_fused:" + keys[0], [xt], [out_tbuf])
-        M = self.B * N
-        fl = 2 * M * (256 * 256 + 256 * 64 + 64 * 2)
-        self.flops += fl
-        self.conv_log.append((keys[0], M, 256 + 64 + 2, 256, fl, "mlp_fused", M * (256 * self.es + 8) + (256 * 256 + 64 * 256) * self.es))
-
-    def mlp_query_head(self, x: Act, keys, ws, bs, slope, out_tbuf, ostr, ids):
-        """the woProg ablation's MLP_QueryNet (pipeline_lm.py:475-517) in one launch: nout = ws[2].shape[0] = 1 + 2r logits of row
-        (b, n) to out_tbuf[ostr[0] + b * ostr[1] + n * ostr[3] + c * ostr[4]] (fp32) and, in the same epilogue, the x / y codes
-        decoded into ids = (x64, y64) (B, N) int64 torch tensors (cp_mlp_query_fused_n)"""
-        N = x.W
-        gdt = self.gdt
-        nout = int(ws[2].shape[0])
-        pw1 = self.ws.pack_gemm(keys[0], ws[0].reshape(ws[0].shape[0], ws[0].shape[1], 1, 1), 256, 256, 256, dtype=gdt)
-        pw2 = self.ws.pack_gemm(keys[1], ws[1].reshape(ws[1].shape[0], ws[1].shape[1], 1, 1), 64, 256, 256, dtype=gdt)
-        ck = ("mlp_query", keys[0])
-        if ck not in self.ws.cache:
-            dev = self.device
-            self.ws.cache[ck] = (torch.ones(256, dtype=torch.float32, device=dev), bs[0].float().contiguous(),
-                                 torch.ones(64, dtype=torch.float32, device=dev), bs[1].float().contiguous(),
-                                 ws[2].float().reshape(nout, 64).contiguous(), bs[2].float().contiguous())
-        s1, t1, s2, t2, w3, b3 = self.ws.cache[ck]
-        self.keep += [pw1, pw2, s1, t1, s2, t2, w3, b3]
-        xt = x.tbuf
-        a1 = (pw1.data_ptr(), s1.data_ptr(), t1.data_ptr(), float(slope), pw2.data_ptr(), s2.data_ptr(), t2.data_ptr(), float(slope),
-              w3.data_ptr(), b3.data_ptr(), nout)
-        o = (int(ostr[0]), int(ostr[1]), int(ostr[3]), int(ostr[4]), ids[0].data_ptr(), ids[1].data_ptr(), None, None)
-        self._add(self.lib.cp_mlp_query_fused_n, lambda P: (gdt, P(xt), x.cstride, x.coff, self.B, N) + a1 + (P(out_tbuf),) + o,
-                  "mlp_fused:" + keys[0], [xt], [out_tbuf, self.raw(ids[0]), self.raw(ids[1])])
+        fn, writes = self.lib.cp_mlp_query_fused_t, [out_tbuf]
+        if ids is not None:
+            fn, a1, o = self.lib.cp_mlp_query_fused_n, a1 + (nout,), o + (ids[0].data_ptr(), ids[1].data_ptr(), None, None)
+            writes = [out_tbuf, self.raw(ids[0]), self.raw(ids[1])]
+        self._add(fn, lambda P: (gdt, P(xt), x.cstride, x.coff, self.B, N) + a1 + (P(out_tbuf),) + o, "mlp_fused:" + keys[0], [xt], writes)
         M = self.B * N
         fl = 2 * M * (256 * 256 + 256 * 64 + 64 * nout)
         self.flops += fl
-        self.conv_log.append((keys[0], M, 256 + 64 + nout, 256, fl, "mlp_fused", M * (256 * self.es + 4 * nout + 16) + (256 * 256 + 64 * 256) * self.es))
+        obytes = 4 * nout + (16 if ids is not None else 0)          # fp32 logits (+ two int64 ids) per row
+        self.conv_log.append((keys[0], M, 256 + 64 + nout, 256, fl, "mlp_fused", M * (256 * self.es + obytes) + (256 * 256 + 64 * 256) * self.es))
 
     def code_decode(self, bits_t, rows, r, x64_t, y64_t, N):
         """x / y codes of a packed logit block (rows 1..r, r+1..2r) -> int64 ids (cp_code_decode)"""
@@ -1012,16 +957,18 @@ class Program:
                 and x.C == x.Cphys and bool(self.lib.cp_mlp_pair_fused_supported(int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0])))
                 and w2.shape[1] == w1.shape[0])
 
+    def _pair_weights(self, keys, ws, bs, Cin):
+        """both packed weights + fp32 biases of a fused pre_graph_module pair, shared by the plain and the gathering launch"""
+        pw1 = self.ws.pack_gemm(keys[0], ws[0].reshape(256, Cin, 1, 1), 256, Cin, Cin, dtype=self.gdt)
+        pw2 = self.ws.pack_gemm(keys[1], ws[1].reshape(256, 256, 1, 1), 256, 256, 256, dtype=self.gdt)
+        b1, b2 = self.ws.cached(("mlp_pair", keys[0]), lambda: (bs[0].float().contiguous(), bs[1].float().contiguous()))
+        return pw1, pw2, b1, b2
+
     def mlp_pair_fused(self, x: Act, keys, ws, bs, slope, out: Act = None):
         """pre_graph_module (two nn.Linear + LeakyReLU) in one launch: the 256-channel hidden rows stay on chip"""
         N, Cin = x.W, x.C
         gdt = self.gdt
-        pw1 = self.ws.pack_gemm(keys[0], ws[0].reshape(256, Cin, 1, 1), 256, Cin, Cin, dtype=gdt)
-        pw2 = self.ws.pack_gemm(keys[1], ws[1].reshape(256, 256, 1, 1), 256, 256, 256, dtype=gdt)
-        ck = ("mlp_pair", keys[0])
-        if ck not in self.ws.cache:
-            self.ws.cache[ck] = (bs[0].float().contiguous(), bs[1].float().contiguous())
-        b1, b2 = self.ws.cache[ck]
+        pw1, pw2, b1, b2 = self._pair_weights(keys, ws, bs, Cin)
         self.keep += [pw1, pw2, b1, b2]
         if out is None:
             out = self.act(1, N, 256)
@@ -1046,16 +993,8 @@ class Program:
         Cin = L.C
         Cg = Cin - 256
         gdt = self.gdt
-        pw1 = self.ws.pack_gemm(keys[0], ws[0].reshape(256, Cin, 1, 1), 256, Cin, Cin, dtype=gdt)
-        pw2 = self.ws.pack_gemm(keys[1], ws[1].reshape(256, 256, 1, 1), 256, 256, 256, dtype=gdt)
-        ck = ("mlp_pair", keys[0])
-        if ck not in self.ws.cache:
-            self.ws.cache[ck] = (bs[0].float().contiguous(), bs[1].float().contiguous())
-        b1, b2 = self.ws.cache[ck]
-        zk = ("zeros128",)
-        if zk not in self.ws.cache:
-            self.ws.cache[zk] = torch.zeros(256, dtype=torch.uint8, device=self.device)
-        zeros = self.ws.cache[zk]
+        pw1, pw2, b1, b2 = self._pair_weights(keys, ws, bs, Cin)
+        zeros = self.ws.cached(("zeros128",), lambda: torch.zeros(256, dtype=torch.uint8, device=self.device))
         self.keep += [pw1, pw2, b1, b2, zeros]
         if out is None:
             out = self.act(1, N, 256)

@@ -2,6 +2,12 @@
 InitNet_GNN.forward (reference checkerpose/model/init.py:109-128) and PoseNet_GNNskip.forward
 (model/pipeline.py:351-384; LM twin model/pipeline_lm.py:392-425).  No arithmetic happens here: every step
 appends a C-ABI launch.  Layout: channels-last activations, graph features (B, N, C).
+
+emit_posenet and emit_posenet_woprog (the LM woProg ablation, pipeline_lm.py:480-517) share every piece the two forwards have in
+common: _plan_lowcats (which decoder concat buffers the backbone fills in place), _emit_decoder (up_net -> seg_block; PoseNet hangs
+its refinement stage behind each decoder stage through after_stage), _pre_graph_pair and _query_mlp (the keypoint-side MLPs with
+their fused / unfused choice) and _out_layer (the eval / train fork of a strided fp32 output layer).  What is left in the two
+emitters is what differs: which lanes run what, and PoseNet's progressive feedback.
 """
 import os
 
@@ -32,6 +38,12 @@ class NetEmitter:
 
     def W(self, key):
         return self.ws._w(key)
+
+    @property
+    def half_kw(self):
+        """keywords of linear() for a keypoint-side layer on the generic kernel: IEEE-half rows and weights where the eval program
+        runs its keypoint side in half (engine.USE_GNN_F16)"""
+        return {"in_half": True} if (self.tp is None and self.p.gnn_half) else {}
 
     def _unit(self, n):
         if n not in self.ones:
@@ -677,31 +689,65 @@ def _patch_tape(em, pgk, wpg, f, patches, lslice, io, N, Ech, k):
     tp.tape.append(bwd)
 
 
-def emit_posenet(em: NetEmitter, cfg, io):
-    """PoseNet_GNNskip.forward pipeline.py:351-384."""
+def _out_layer(em, x, key, w4, ostr, out_tbuf, dsrc, in_half=False):
+    """a bias layer (Linear / 1x1 conv, weight w4 (n, Cin, 1, 1)) whose fp32 output goes through the element strides `ostr` straight
+    into a caller-visible block (logits / seg).  Training program: the bias is read live, and the layer's backward starts from
+    `dsrc`, the fp32 tensor the autograd hook fills with that block's gradient."""
+    p, tp, n = em.p, em.tp, w4.shape[0]
+    if tp is None:
+        p.conv(x, key, w4, em._unit(n), em.W(key + ".bias"), 1, 1, 1, 0, n, out_f32=True, ostr=ostr, out_tbuf=out_tbuf, in_half=in_half)
+    else:
+        p.conv(x, key, w4, tp.const_vec(n, True), em._bias_vec(key, n), 1, 1, 1, 0, n, out_f32=True, ostr=ostr, out_tbuf=out_tbuf)
+        em._out_layer_bwd(key, w4, x, n, dsrc, ostr[0], ostr[1], ostr[3], ostr[4])
+
+
+def _pre_graph_pair(em, x, rp, slope, gather=None, carry=None):
+    """a refinement stage's pre_graph_module (two Linear + LeakyReLU) on the rows `x` -> its output rows: one fused launch where it
+    applies (csrc/mlp_fused.hip), else two linears.  gather = (patches, io, N, k): the caller found can_fuse_mlp_pair_gather -- Index2Feat's
+    gather x RoI bit runs inside the pair's loader and x's first 256 channels are never materialised.  carry: the channel slice the rows
+    must ALSO land in (a stage without EdgeConvs: they are the next stage's graph feature)."""
     p = em.p
-    N, B = cfg["npoint"], p.B
-    nref = cfg["res_log2"] - 3
-    active = cfg["stage"] if cfg.get("stage") is not None else nref
-    ngs = cfg["num_graph_module"]
-    ngs = (ngs,) * nref if isinstance(ngs, int) else tuple(ngs)
-    nf = cfg["num_filters"]
-    qd = cfg["query_dims"] or (nf, 256, 64)
-    k = cfg["local_k"]
-    slope = cfg["leaky_slope"]
+    pkeys = [rp + ".pre_graph_module.0", rp + ".pre_graph_module.2"]
+    pws = [em.W(k_ + ".weight") for k_ in pkeys]
+    if gather is None and not (em.tp is None and p.can_fuse_mlp_pair(x, pws[0], pws[1])):
+        h = em.linear(x, pkeys[0], ACT_LEAKY, slope, **em.half_kw)
+        return em.linear(h, pkeys[1], ACT_LEAKY, slope, out=carry, **em.half_kw)
+    bs = [em.W(k_ + ".bias") for k_ in pkeys]
+    if gather is not None:
+        patches, io, N, k = gather
+        h = p.mlp_pair_fused_gather(patches, io["xid"], io["yid"], io["mask"], x, pkeys, pws, bs, slope, N, k)
+    else:
+        h = p.mlp_pair_fused(x, pkeys, pws, bs, slope)
+    if carry is not None:      # (the fused pair launches write a dense tensor) one term, no ReLU: cp_fuse_sum_act is a
+        p.fuse_sum([h], [0], carry, relu=False)    # copy -- bit-exact for 16-bit rows of either format
+    return h
 
-    tp = em.tp
 
-    def local_buf(i):
-        gdim = 64 if i == 0 else qd[0]
-        return p.act(1, N, qd[0] + gdim)       # [local 4*E | previous graph feature]
+def _query_mlp(em, h, pfx, slope, io, ostr, ids=None):
+    """MLP_QueryNet (pipeline.py:168-180) `pfx`query_block on the rows `h`, its logits through `ostr` into the (B, 13, N) block.  Returns
+    True where it ran as ONE launch: both hidden layers stay on chip, only the logits leave -- and, with ids = (x64, y64), the ids
+    decoded from the x / y codes in the same epilogue; else two leaky linears and the output layer (no decode)."""
+    p, tp = em.p, em.tp
+    qkeys = [pfx + "query_block.mlps.%d" % j for j in (0, 2, 4)]
+    qws = [em.W(k_ + ".weight") for k_ in qkeys]
+    nout = qws[2].shape[0]
+    if tp is None and p.can_fuse_query_mlp(h, [qws[0].shape[1], qws[0].shape[0], qws[1].shape[0], nout]):
+        p.mlp_query_fused(h, qkeys, qws, [em.W(k_ + ".bias") for k_ in qkeys], slope, io["bits_tb"], ostr, ids)
+        return True
+    q = em.linear(h, qkeys[0], ACT_LEAKY, slope, **em.half_kw)
+    q = em.linear(q, qkeys[1], ACT_LEAKY, slope, **em.half_kw)
+    _out_layer(em, q, qkeys[2], qws[2].view(nout, qws[2].shape[1], 1, 1), ostr, io["bits_tb"], io.get("dbits"), in_half=bool(em.half_kw))
+    return False
 
-    L = local_buf(0) if active > 0 else None
-    # eval: up_net[i >= 1] = conv(bilinear_x2(cat[img_feat, skip])) runs as ONE launch that interpolates inside its halo loader
-    # (engine.conv_up2x); its input is the LOW-resolution concat buffer, filled in place by its two producers -- the previous
-    # stage's last conv (channels [0, nf)) and the backbone's incre module (the skip feature, channels [nf, ..))
+
+def _plan_lowcats(em, cfg, active):
+    """eval: up_net[i >= 1] = conv(bilinear_x2(cat[img_feat, skip])) runs as ONE launch that interpolates inside its halo loader
+    (engine.conv_up2x); its input is the LOW-resolution concat buffer, filled in place by its two producers -- the previous
+    stage's last conv (channels [0, nf)) and the backbone's incre module (the skip feature, channels [nf, ..)).
+    -> (lowcats {stage: that buffer}, feat_outs: where emit_init_net's backbone writes its four features, or None)"""
+    p, nf = em.p, cfg["num_filters"]
     lowcats, feat_outs = {}, None
-    if tp is None and cfg["backbone"] in HRNET_CFGS:
+    if em.tp is None and cfg["backbone"] in HRNET_CFGS:
         feat_outs = [None] * 4
         for i in range(1, active):
             j = 3 - i
@@ -711,22 +757,16 @@ def emit_posenet(em: NetEmitter, cfg, io):
             if p.can_conv_up2x(Hs, Hs, nf) and not (DECODER_SPLITK and p.would_splitk(p.B * 4 * Hs * Hs, 9 * (_rup(nf, p.E) + _rup(Cs, p.E)), nf)):
                 lowcats[i] = p.act(Hs, Hs, nf + Cs)
                 feat_outs[j] = lowcats[i].slice(_rup(nf, p.E), Cs)
-    head_later = tp is None and active > 0 and HEAD_ON_REFINE_LANE
-    feats, g = emit_init_net(em, cfg, io, "init_net.", graph_out=L.slice(qd[0], 64) if L is not None else None,
-                             feat_outs=feat_outs, defer_head=head_later)
-    dbits = io.get("decode_bits", io["bits"])      # teacher forcing (tests only): decode from supplied logits
-    if not head_later:
-        p.decode(dbits, -1, io["mask"], io["xid"], io["yid"], io["x64"], io["y64"], N)
+    return lowcats, feat_outs
+
+
+def _emit_decoder(em, cfg, io, feats, lowcats, active, after_stage=None):
+    """up_net[0..active) -> seg_block (pipeline.py:349-383, pipeline_lm.py:498-505) behind the backbone's `feats`, inside the region
+    the caller opened (none when active == 0): lane 0 the chain, lane 2 the skip upsamples, lanes 3-5 the transposed-conv phases.
+    after_stage(i, f) runs right behind stage i's launches (f: its map) and may emit on other lanes -- PoseNet's refinement stage;
+    the chain itself goes on from its own map.  Returns the last map."""
+    p, tp, nf = em.p, em.tp, cfg["num_filters"]
     f = feats[-1]
-    # lane 0: decoder chain up_net[0..2] -> seg (MFMA-bound) ; lane 1: refine stages (latency-bound graph kernels).
-    # refine[i] needs up_net[i]'s output (sync 0 -> 1) and refine[i-1]; up_net[i+1] needs only up_net[i].
-    if active > 0:
-        p.par_begin(6 if tp is None else 2)      # 0 decoder, 1 refinement, 2 skip upsamples, 3-5 transposed-conv phases
-    if head_later:     # InitNet's head needs only the backbone's last feature, like up_net[0]: it runs on the refinement lane beside it
-        p.set_lane(1)
-        g = g()
-        p.decode(dbits, -1, io["mask"], io["xid"], io["yid"], io["x64"], io["y64"], N)
-        p.set_lane(0)
     # the skip features' bilinear x2 halves of the decoder's concat buffers do not depend on the decoder: they run on a lane
     # of their own right away (lane 2 never waits for anybody) instead of on the decoder's critical path
     cats = {}
@@ -754,12 +794,11 @@ def emit_posenet(em: NetEmitter, cfg, io):
         p.set_lane(0)
         up = "up_net.%d" % i
         last = i == active - 1
+        nxt = lowcats[i + 1].slice(0, nf) if (i + 1) in lowcats else None      # this stage's map goes straight into the next one's concat buffer
         if i == 0:   # ConvTranspose2d(k3,s2,p1,op1)+BN+ReLU as 4 sub-pixel phase convs, then 2x conv3x3+BN+ReLU
             wt = em.W(up + ".0.weight")                     # (Cin, Cout, 3, 3)
-            s, t = em.ws.bn_fold(up + ".1") if tp is None else (None, None)
+            s, t = em.ws.bn_fold(up + ".1") if tp is None else (tp.const_vec(nf, True), tp.const_vec(nf, False))
             o = p.act(2 * f.H, 2 * f.W, nf)
-            if tp is not None:
-                s, t = tp.const_vec(nf, True), tp.const_vec(nf, False)
             for ph in range(4):          # the four sub-pixel phases are independent: eval runs them on lanes 0, 3, 4, 5
                 a, b = ph >> 1, ph & 1
                 if tp is None and ph > 0:
@@ -771,15 +810,15 @@ def emit_posenet(em: NetEmitter, cfg, io):
                 p.set_lane(0)
                 for ph in range(1, 4):
                     p.sync(2 + ph, 0)
-            if tp is not None:
+            else:
                 o = _convt_train_tail(em, up, wt, f, o, nf)
             f = em.conv_bn(o, up + ".3", up + ".4", 3, 1, 1)
-            f = tail_conv(f, up + ".6", up + ".7", last, out=lowcats[1].slice(0, nf) if 1 in lowcats else None)
+            f = tail_conv(f, up + ".6", up + ".7", last, out=nxt)
         elif i in lowcats:   # the same, upsample fused into conv1's loader
             s1, t1 = em.ws.bn_fold(up + ".2")
             f = p.conv_up2x(lowcats[i], up + ".1", em.W(up + ".1.weight"), s1, t1, ACT_RELU)
-            f = tail_conv(f, up + ".4", up + ".5", last, out=lowcats[i + 1].slice(0, nf) if (i + 1) in lowcats else None)
-        else:        # cat[img_feat, img_feats[-i-1]] -> bilinear x2 (align_corners) -> 2x conv3x3+BN+ReLU
+            f = tail_conv(f, up + ".4", up + ".5", last, out=nxt)
+        else:       # cat[img_feat, img_feats[-i-1]] -> bilinear x2 (align_corners) -> 2x conv3x3+BN+ReLU
             sk = feats[-i - 1]
             cat = cats[i] if i in cats else p.act(2 * f.H, 2 * f.W, f.C + sk.C)
             if i == 1 and i in cats:
@@ -791,11 +830,60 @@ def emit_posenet(em: NetEmitter, cfg, io):
                 _upsample_tape(tp, f, cat.slice(0, f.C))
                 _upsample_tape(tp, sk, cat.slice(f.Cphys, sk.C))
             f = em.conv_bn(cat, up + ".1", up + ".2", 3, 1, 1)
-            f = tail_conv(f, up + ".4", up + ".5", last, out=lowcats[i + 1].slice(0, nf) if (i + 1) in lowcats else None)
-        # ---- Refine_moduleGNN.forward pipeline.py:262-298
+            f = tail_conv(f, up + ".4", up + ".5", last, out=nxt)
+        if after_stage is not None:
+            after_stage(i, f)
+    # seg_block Conv2d(nf -> seg_dim, 1x1) on the last feature map, NCHW fp32 out (pipeline.py:349,383)
+    if active > 0:
+        p.set_lane(0)
+    if not seg_fused[0]:                      # (else: written by the last decoder conv's epilogue, engine.conv_halo_seg)
+        sd_ = wseg.shape[0]
+        _out_layer(em, f, "seg_block", wseg, (0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), io["seg_tb"], io.get("dseg"))
+    return f
+
+
+def emit_posenet(em: NetEmitter, cfg, io):
+    """PoseNet_GNNskip.forward pipeline.py:351-384."""
+    p = em.p
+    N, B = cfg["npoint"], p.B
+    nref = cfg["res_log2"] - 3
+    active = cfg["stage"] if cfg.get("stage") is not None else nref
+    ngs = cfg["num_graph_module"]
+    ngs = (ngs,) * nref if isinstance(ngs, int) else tuple(ngs)
+    nf = cfg["num_filters"]
+    qd = cfg["query_dims"] or (nf, 256, 64)
+    k = cfg["local_k"]
+    slope = cfg["leaky_slope"]
+
+    tp = em.tp
+
+    def local_buf(i):
+        gdim = 64 if i == 0 else qd[0]
+        return p.act(1, N, qd[0] + gdim)       # [local 4*E | previous graph feature]
+
+    L = local_buf(0) if active > 0 else None
+    lowcats, feat_outs = _plan_lowcats(em, cfg, active)
+    head_later = tp is None and active > 0 and HEAD_ON_REFINE_LANE
+    feats, g = emit_init_net(em, cfg, io, "init_net.", graph_out=L.slice(qd[0], 64) if L is not None else None,
+                             feat_outs=feat_outs, defer_head=head_later)
+    dbits = io.get("decode_bits", io["bits"])      # teacher forcing (tests only): decode from supplied logits
+    if not head_later:
+        p.decode(dbits, -1, io["mask"], io["xid"], io["yid"], io["x64"], io["y64"], N)
+    # lane 0: decoder chain up_net[0..2] -> seg (MFMA-bound) ; lane 1: refine stages (latency-bound graph kernels).
+    # refine[i] needs up_net[i]'s output (sync 0 -> 1) and refine[i-1]; up_net[i+1] needs only up_net[i].
+    if active > 0:
+        p.par_begin(6 if tp is None else 2)      # 0 decoder, 1 refinement, 2 skip upsamples, 3-5 transposed-conv phases
+    if head_later:     # InitNet's head needs only the backbone's last feature, like up_net[0]: it runs on the refinement lane beside it
+        p.set_lane(1)
+        g = g()
+        p.decode(dbits, -1, io["mask"], io["xid"], io["yid"], io["x64"], io["y64"], N)
+        p.set_lane(0)
+
+    def refine(i, f):
+        """Refine_moduleGNN.forward pipeline.py:262-298 on lane 1, behind decoder stage i's map f"""
+        nonlocal L
         p.sync(0, 1)
         p.set_lane(1)
-        fdec = f                                                # the decoder's own map: what the next decoder stage continues from
         if tp is None and cfg.get("export_dec"):                # attribution hooks (HipForwardMixin._run(want_dec / inject_dec)): the map
             p.to_nchw_f32(f, io["dec_feats"][i])                # the refinement stage gathers from, exported / replaced by a GIVEN one
         if tp is None and cfg.get("inject_dec"):
@@ -816,9 +904,7 @@ def emit_posenet(em: NetEmitter, cfg, io):
         # network_num_graph_module = 0 (config/lm/hr18GNN2_res6_gnn3Skip_mlpQuery_lm_woEdgeConv.txt): the pre-graph MLP's rows are the
         # stage's graph feature (pipeline.py:288-297 with an empty pre_query_block) -> they land in the next stage's input rows
         carry = Lnext.slice(qd[0], qd[0]) if (ngs[i] == 0 and Lnext is not None) else None
-        carried = False
-        pkeys = [rp + ".pre_graph_module.0", rp + ".pre_graph_module.2"]
-        pws = [em.W(k_ + ".weight") for k_ in pkeys]
+        pws = [em.W(rp + ".pre_graph_module.%d.weight" % j) for j in (0, 2)]
         gather_in_pair = tp is None and p.can_fuse_mlp_pair_gather(L, patches, pws[0], pws[1], Ech, k)
         if patches is not None and not gather_in_pair:
             p.index2feat(patches, io["xid"], io["yid"], io["mask"], L.slice(0, 4 * Ech), N, Ech, k)
@@ -829,61 +915,17 @@ def emit_posenet(em: NetEmitter, cfg, io):
                 ids_i[nm] = torch.empty_like(io[nm])
                 tp.memcpy(ids_i[nm].data_ptr(), io[nm].data_ptr(), io[nm].numel() * 4, "save_ids")
             _patch_tape(em, pgk, wpg, f, patches, L.slice(0, 4 * Ech), ids_i, N, Ech, k)
-        if gather_in_pair:      # Index2Feat's gather x RoI bit inside the pair's loader: L's first 256 channels are never materialised
-            h = p.mlp_pair_fused_gather(patches, io["xid"], io["yid"], io["mask"], L, pkeys, pws, [em.W(k_ + ".bias") for k_ in pkeys],
-                                        slope, N, k)
-        elif tp is None and p.can_fuse_mlp_pair(L, pws[0], pws[1]):
-            h = p.mlp_pair_fused(L, pkeys, pws, [em.W(k_ + ".bias") for k_ in pkeys], slope)     # csrc/mlp_fused.hip
-        else:
-            hk = {"in_half": True} if (tp is None and p.gnn_half) else {}
-            h = em.linear(L, rp + ".pre_graph_module.0", ACT_LEAKY, slope, **hk)
-            h = em.linear(h, rp + ".pre_graph_module.2", ACT_LEAKY, slope, out=carry, **hk)
-            carried = carry is not None
-        if carry is not None and not carried:      # (the fused pair launches write a dense tensor) one term, no ReLU: cp_fuse_sum_act is a
-            p.fuse_sum([h], [0], carry, relu=False)    # copy -- bit-exact for 16-bit rows of either format
+        h = _pre_graph_pair(em, L, rp, slope, gather=(patches, io, N, k) if gather_in_pair else None, carry=carry)
         for gi in range(ngs[i]):
             last = gi == ngs[i] - 1
             h = em.edgeconv("%s.pre_query_block.%d" % (rp, gi), h, io["graph"], cfg["graph_slope"],
                             out=Lnext.slice(qd[0], qd[0]) if (last and Lnext is not None) else None)
         # Linear(64 -> 2): channel 0 = new x bit -> row 4+i, channel 1 = new y bit -> row 10+i  (pipeline.py:375-378)
-        qk = rp + ".query_block.mlps.4"
-        qkeys = [rp + ".query_block.mlps.%d" % j for j in (0, 2, 4)]
-        qws = [em.W(k_ + ".weight") for k_ in qkeys]
-        if tp is None and p.can_fuse_query_mlp(h, [qws[0].shape[1], qws[0].shape[0], qws[1].shape[0], qws[2].shape[0]]):
-            # MLP_QueryNet as one launch: both hidden layers stay on chip, only the logits leave (csrc/mlp_fused.hip)
-            p.mlp_query_fused(h, qkeys, qws, [em.W(k_ + ".bias") for k_ in qkeys], slope, io["bits_tb"],
-                              ((4 + i) * N, 13 * N, 0, 1, 6 * N))
-            q = None
-        else:
-            hk = {"in_half": True} if (tp is None and p.gnn_half) else {}
-            q = em.linear(h, rp + ".query_block.mlps.0", ACT_LEAKY, slope, **hk)
-            q = em.linear(q, rp + ".query_block.mlps.2", ACT_LEAKY, slope, **hk)
-        if q is None:
-            pass
-        elif tp is None:
-            em.linear(q, qk, ACT_NONE, 0.0, out_f32=True, ostr=((4 + i) * N, 13 * N, 0, 1, 6 * N), out_tbuf=io["bits_tb"], in_half=p.gnn_half)
-        else:
-            wq = em.W(qk + ".weight")
-            wq4 = wq.view(wq.shape[0], wq.shape[1], 1, 1)
-            p.conv(q, qk, wq4, tp.const_vec(2, True), em._bias_vec(qk, 2), 1, 1, 1, 0, 2, out_f32=True,
-                   ostr=((4 + i) * N, 13 * N, 0, 1, 6 * N), out_tbuf=io["bits_tb"])
-            em._out_layer_bwd(qk, wq4, q, 2, io["dbits"], (4 + i) * N, 13 * N, 1, 6 * N)
+        _query_mlp(em, h, rp + ".", slope, io, ((4 + i) * N, 13 * N, 0, 1, 6 * N))
         p.decode(dbits, i, io["mask"], io["xid"], io["yid"], io["x64"], io["y64"], N)
         L = Lnext
-        f = fdec
-    # seg_block Conv2d(nf -> seg_dim, 1x1) on the last feature map, NCHW fp32 out (pipeline.py:349,383)
-    if active > 0:
-        p.set_lane(0)
-    sd_ = wseg.shape[0]
-    if seg_fused[0]:
-        pass                                  # written by the last decoder conv's epilogue (engine.conv_halo_seg)
-    elif tp is None:
-        p.conv(f, "seg_block", wseg, em._unit(sd_), em.W("seg_block.bias"), 1, 1, 1, 0, sd_, out_f32=True,
-               ostr=(0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), out_tbuf=io["seg_tb"])
-    else:
-        p.conv(f, "seg_block", wseg, tp.const_vec(sd_, True), em._bias_vec("seg_block", sd_), 1, 1, 1, 0, sd_, out_f32=True,
-               ostr=(0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), out_tbuf=io["seg_tb"])
-        em._out_layer_bwd("seg_block", wseg, f, sd_, io["dseg"], 0, sd_ * f.H * f.W, 1, f.H * f.W)
+
+    f = _emit_decoder(em, cfg, io, feats, lowcats, active, after_stage=refine)
     if active > 0:
         p.par_end()
     return feats, f
@@ -903,20 +945,9 @@ def emit_posenet_woprog(em: NetEmitter, cfg, io):
     assert 1 <= active <= nref
     ngs = cfg["num_graph_module"]
     ngs = (ngs,) * nref if isinstance(ngs, int) else tuple(ngs)
-    nf = cfg["num_filters"]
     slope = cfg["leaky_slope"]
     tp = em.tp
-    # decoder concat buffers filled in place by the backbone's incre modules (as in emit_posenet)
-    lowcats, feat_outs = {}, None
-    if tp is None and cfg["backbone"] in HRNET_CFGS:
-        feat_outs = [None] * 4
-        for i in range(1, active):
-            j = 3 - i
-            Cs = em.W("init_net.img_backbone.incre_modules.%d.0.conv3.weight" % j).shape[0]
-            Hs = cfg["img_size"] // (4 << j)
-            if p.can_conv_up2x(Hs, Hs, nf) and not (DECODER_SPLITK and p.would_splitk(p.B * 4 * Hs * Hs, 9 * (_rup(nf, p.E) + _rup(Cs, p.E)), nf)):
-                lowcats[i] = p.act(Hs, Hs, nf + Cs)
-                feat_outs[j] = lowcats[i].slice(_rup(nf, p.E), Cs)
+    lowcats, feat_outs = _plan_lowcats(em, cfg, active)
     head_later = tp is None
     feats, g = emit_init_net(em, cfg, io, "init_net.", feat_outs=feat_outs, defer_head=head_later, with_logits=False)
     p.par_begin(6 if tp is None else 2)      # 0 decoder, 1 keypoints, 2 skip upsamples, 3-5 transposed-conv phases
@@ -927,109 +958,15 @@ def emit_posenet_woprog(em: NetEmitter, cfg, io):
         g = g()
     for i in range(active):
         rp = "refine_net.%d" % i
-        pkeys = [rp + ".pre_graph_module.0", rp + ".pre_graph_module.2"]
-        pws = [em.W(k_ + ".weight") for k_ in pkeys]
-        if tp is None and p.can_fuse_mlp_pair(g, pws[0], pws[1]):
-            g = p.mlp_pair_fused(g, pkeys, pws, [em.W(k_ + ".bias") for k_ in pkeys], slope)     # csrc/mlp_fused.hip
-        else:
-            hk = {"in_half": True} if (tp is None and p.gnn_half) else {}
-            g = em.linear(g, pkeys[0], ACT_LEAKY, slope, **hk)
-            g = em.linear(g, pkeys[1], ACT_LEAKY, slope, **hk)
+        g = _pre_graph_pair(em, g, rp, slope)
         for gi in range(ngs[i]):
             g = em.edgeconv("%s.pre_query_block.%d" % (rp, gi), g, io["graph"], cfg["graph_slope"])
-    qkeys = ["query_block.mlps.%d" % j for j in (0, 2, 4)]
-    qws = [em.W(k_ + ".weight") for k_ in qkeys]
-    nout = qws[2].shape[0]
-    ostr = (0, 13 * N, 0, 1, N)            # logit c of (b, n) -> row c of the (B, 13, N) block: [roi | x code | y code]
-    if tp is None and p.can_fuse_query_mlp(g, [qws[0].shape[1], qws[0].shape[0], qws[1].shape[0], nout]):
-        p.mlp_query_head(g, qkeys, qws, [em.W(k_ + ".bias") for k_ in qkeys], slope, io["bits_tb"], ostr, (io["x64"], io["y64"]))
-    else:
-        hk = {"in_half": True} if (tp is None and p.gnn_half) else {}
-        q = em.linear(g, qkeys[0], ACT_LEAKY, slope, **hk)
-        q = em.linear(q, qkeys[1], ACT_LEAKY, slope, **hk)
-        if tp is None:
-            em.linear(q, qkeys[2], ACT_NONE, 0.0, out_f32=True, ostr=ostr, out_tbuf=io["bits_tb"], in_half=p.gnn_half)
-        else:
-            wq4 = qws[2].view(nout, qws[2].shape[1], 1, 1)
-            p.conv(q, qkeys[2], wq4, tp.const_vec(nout, True), em._bias_vec(qkeys[2], nout), 1, 1, 1, 0, nout, out_f32=True,
-                   ostr=ostr, out_tbuf=io["bits_tb"])
-            em._out_layer_bwd(qkeys[2], wq4, q, nout, io["dbits"], 0, 13 * N, 1, N)
+    # logit c of (b, n) -> row c of the (B, 13, N) block: [roi | x code | y code]
+    if not _query_mlp(em, g, "", slope, io, (0, 13 * N, 0, 1, N), ids=(io["x64"], io["y64"])):
         p.code_decode(io["bits"], 13, r, io["x64"], io["y64"], N)
 
-    # ---- decoder lane: up_net[0..k) -> seg_block (pipeline_lm.py:498-505), as emit_posenet runs it
+    # ---- decoder lane: up_net[0..k) -> seg_block (pipeline_lm.py:498-505)
     p.set_lane(0)
-    cats = {}
-    if tp is None:
-        for i in range(1, active):
-            if i in lowcats:
-                continue
-            sk = feats[-i - 1]
-            cats[i] = p.act(2 * sk.H, 2 * sk.W, nf + sk.C)
-            p.set_lane(2)
-            p.upsample2x(sk, cats[i].slice(_rup(nf, p.E), sk.C))
-    wseg = em.W("seg_block.weight")
-    seg_fused = False
-    f = feats[-1]
-
-    def tail_conv(x, ck, bk, last, out=None):
-        nonlocal seg_fused
-        if (last and tp is None and out is None and p.can_conv_halo_seg(x, em.W(ck + ".weight").shape[0], wseg.shape[0])
-                and not (DECODER_SPLITK and p.would_splitk(x.B * x.H * x.W, 9 * x.Cphys, em.W(ck + ".weight").shape[0]))):
-            s_, t_ = em.ws.bn_fold(bk)
-            seg_fused = True
-            return p.conv_halo_seg(x, ck, em.W(ck + ".weight"), s_, t_, ACT_RELU, "seg_block", wseg, em.W("seg_block.bias"), io["seg_tb"])
-        return em.conv_bn(x, ck, bk, 3, 1, 1, out=out)
-
-    for i in range(active):
-        p.set_lane(0)
-        up = "up_net.%d" % i
-        last = i == active - 1
-        nxt = lowcats[i + 1].slice(0, nf) if (i + 1) in lowcats else None
-        if i == 0:
-            wt = em.W(up + ".0.weight")
-            s, t = em.ws.bn_fold(up + ".1") if tp is None else (tp.const_vec(nf, True), tp.const_vec(nf, False))
-            o = p.act(2 * f.H, 2 * f.W, nf)
-            for ph in range(4):
-                a, b = ph >> 1, ph & 1
-                if tp is None and ph > 0:
-                    p.set_lane(2 + ph)
-                p.conv(f, up + ".0", wt, s, t, 1 + a, 1 + b, 1, 0, nf, ACT_RELU if tp is None else ACT_NONE, transposed=1, phase=ph,
-                       ostr=((a * o.W + b) * o.cstride, o.H * o.W * o.cstride, 2 * o.W * o.cstride, 2 * o.cstride, 1),
-                       out_tbuf=o.tbuf, out_hw=(f.H, f.W))
-            if tp is None:
-                p.set_lane(0)
-                for ph in range(1, 4):
-                    p.sync(2 + ph, 0)
-            else:
-                o = _convt_train_tail(em, up, wt, f, o, nf)
-            f = em.conv_bn(o, up + ".3", up + ".4", 3, 1, 1)
-            f = tail_conv(f, up + ".6", up + ".7", last, out=nxt)
-        elif i in lowcats:
-            s1, t1 = em.ws.bn_fold(up + ".2")
-            f = p.conv_up2x(lowcats[i], up + ".1", em.W(up + ".1.weight"), s1, t1, ACT_RELU)
-            f = tail_conv(f, up + ".4", up + ".5", last, out=nxt)
-        else:
-            sk = feats[-i - 1]
-            cat = cats[i] if i in cats else p.act(2 * f.H, 2 * f.W, f.C + sk.C)
-            if i == 1 and i in cats:
-                p.sync(2, 0)
-            p.upsample2x(f, cat.slice(0, f.C))
-            if i not in cats:
-                p.upsample2x(sk, cat.slice(f.Cphys, sk.C))
-            if tp is not None:
-                _upsample_tape(tp, f, cat.slice(0, f.C))
-                _upsample_tape(tp, sk, cat.slice(f.Cphys, sk.C))
-            f = em.conv_bn(cat, up + ".1", up + ".2", 3, 1, 1)
-            f = tail_conv(f, up + ".4", up + ".5", last, out=nxt)
-    sd_ = wseg.shape[0]
-    if seg_fused:
-        pass
-    elif tp is None:
-        p.conv(f, "seg_block", wseg, em._unit(sd_), em.W("seg_block.bias"), 1, 1, 1, 0, sd_, out_f32=True,
-               ostr=(0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), out_tbuf=io["seg_tb"])
-    else:
-        p.conv(f, "seg_block", wseg, tp.const_vec(sd_, True), em._bias_vec("seg_block", sd_), 1, 1, 1, 0, sd_, out_f32=True,
-               ostr=(0, sd_ * f.H * f.W, f.W, 1, f.H * f.W), out_tbuf=io["seg_tb"])
-        em._out_layer_bwd("seg_block", wseg, f, sd_, io["dseg"], 0, sd_ * f.H * f.W, 1, f.H * f.W)
+    f = _emit_decoder(em, cfg, io, feats, lowcats, active)
     p.par_end()
     return feats, f

@@ -192,6 +192,28 @@ def test_bf16_floors_and_program_structure(lib, B):
     assert writers == head, writers
 
 
+def test_decoder_launches_equal_posenets(lib):
+    """up_net -> seg_block comes out of ONE emitter (netbuilder._emit_decoder) for PoseNet_GNNskip and the woProg ablation: with equal
+    num_filters, backbone and stage count the decoder's launches -- the skip upsamples, every up_net conv, seg_block -- are the same
+    (lane, recorder name) sequence in both programs, whatever each pipeline runs between them on its keypoint lane"""
+    from checkerpose_amd.synthetic import build_net
+    B = 2
+    obj = torch.tensor([4, 11]).to(dev())
+    img = det_image(B, seed=4).to(dev())
+    seqs = []
+    for net in (build_net(512, lm=True), build_woprog()):
+        assert (net.cfg["num_filters"], net.init_net.backbone_name, net.num_refine_steps) == (256, "hrnet_w18", 3)
+        net = net.to(dev()).set_compute_dtype("bf16")
+        net(img, None, obj)
+        prog = net.program_for(B).progs[0]
+        launches = [(item[2], prog.calls[item[1]][2]) for item in prog.sched if item[0] == "op"]
+        seqs.append([(lane, n) for lane, n in launches if "up_net." in n or n == "upsample2x" or "seg_block" in n])
+    names = [n for _, n in seqs[0]]
+    assert sum("up_net.0.0" in n for n in names) == 4 and all(sum("up_net.%d." % i in n for n in names) >= 2 for i in (1, 2)), names
+    assert {lane for lane, _ in seqs[0]} >= {0, 3, 4, 5}              # the chain and the transposed conv's other three phases
+    assert seqs[0] == seqs[1], [(a, b) for a, b in zip(*seqs) if a != b]
+
+
 # ---- training step against torch-CPU autograd over the oracle in train mode (helpers restated from tests/test_gpu_train_step.py:
 # the EdgeConv arg-max slots and the (Leaky)ReLU branches the device took are teacher-forced into the oracle -- both are
 # discontinuous, and the ~1e-6 forward differences would otherwise route a few near-tie gradients differently)

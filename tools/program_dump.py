@@ -1,0 +1,194 @@
+"""Canonical text of the launch programs the emitters build, for A/B-ing a host-side refactor of netbuilder.py / engine.py: two trees
+emit the same programs exactly when this tool's output is byte-equal (`python tools/program_dump.py > a.txt` in each, then diff).
+
+Per matrix row (PoseNet / woProg / InitNet x dtype x batch x kernel selection, eval and one training step) and per batch slice:
+the sched list, workspace_bytes, flops, conv_log, then every call as `<C symbol> <recorder's name> lane=<k>` with its arguments --
+pointers (told from integers by fn.argtypes) as `ws+<offset>` inside the program's workspace and `p<k>` (numbered by first
+appearance) elsewhere, by-reference structs and arrays field by field under the same rules -- and the sha256 of every output
+tensor of one run on det_image(B, seed=100) (training: deterministic mode, outputs + the parameter-gradient arena).
+
+  --json FILE      also write {row: sha256 of the row's text}
+  --time-build N   instead of the dump: wall time of N program builds at B = 256 (bf16 PoseNet, first forward after invalidate())
+"""
+import argparse
+import ctypes as C
+import hashlib
+import json
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from checkerpose_amd import set_deterministic                                # noqa: E402
+from checkerpose_amd.synthetic import build_net, build_woprog, det_image     # noqa: E402
+
+
+class Canon:
+    """pointer naming of one program"""
+
+    def __init__(self, prog):
+        ws = prog.workspace
+        self.lo, self.hi, self.names = ws.data_ptr(), ws.data_ptr() + ws.numel(), {}
+
+    def ptr(self, v):
+        v = getattr(v, "value", v)
+        if not v:
+            return "null"
+        if self.lo <= v < self.hi:
+            return "ws+%d" % (v - self.lo)
+        return self.names.setdefault(v, "p%d" % len(self.names))
+
+    def value(self, v, ctype=None):
+        if hasattr(v, "_obj"):                                   # C.byref(x)
+            return self.value(v._obj)
+        if isinstance(v, C.Structure):
+            return "{%s}" % ", ".join("%s=%s" % (n, self.value(getattr(v, n), t)) for n, t in v._fields_)
+        if isinstance(v, C.Array):
+            return "[%s]" % ", ".join(self.value(e, v._type_) for e in v)
+        if ctype is C.c_void_p or isinstance(v, C.c_void_p):
+            return self.ptr(v)
+        if v is None:
+            return "null"
+        return repr(float(v)) if ctype is C.c_float or isinstance(v, float) else str(int(v))
+
+
+def dump_program(prog, out):
+    lane_of = {item[1]: item[2] for item in prog.sched if item[0] == "op"}
+    out.append("sched %r" % (prog.sched,))
+    out.append("workspace_bytes %d flops %d" % (prog.workspace_bytes, prog.flops))
+    out.append("conv_log %r" % (list(prog.conv_log),))
+    cn = Canon(prog)
+    for i, (fn, args, name) in enumerate(prog.calls):
+        types = list(fn.argtypes)[1:]                            # [0]: the stream
+        assert len(types) == len(args) - 1, (fn.__name__, len(types), len(args))
+        out.append("%s %s lane=%d (%s)" % (fn.__name__, name, lane_of[i], ", ".join(cn.value(a, t) for a, t in zip(args[1:], types))))
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def tensors_of(res):
+    if torch.is_tensor(res):
+        return [res]
+    return [t for r in res for t in tensors_of(r)] if isinstance(res, (tuple, list)) else []
+
+
+def obj_ids(B, dev):
+    return torch.tensor([(3 * i) % 13 + 1 for i in range(B)], device=dev)
+
+
+def call(net, img, lm, stage=None):
+    if not hasattr(net, "init_net"):                             # InitNet alone
+        return net(img, obj_ids(img.shape[0], img.device)) if lm else net(img)
+    if lm:
+        return net(img, None, obj_ids(img.shape[0], img.device), stage=stage)
+    return net(img, None, stage=stage)
+
+
+def eval_row(make, dtype, B, lm=False, stage=None, selection="auto"):
+    dev = torch.device("cuda:0")
+    out = []
+    with torch.no_grad():
+        net = make().to(dev)
+        net.set_compute_dtype(dtype)
+        net.set_kernel_selection(selection)
+        res = call(net, det_image(B, seed=100).to(dev), lm, stage)       # builds the program, runs it once (eagerly)
+        torch.cuda.synchronize()
+        for k, sub in enumerate(net.program_for(B, stage).progs):
+            out.append("slice %d" % k)
+            dump_program(sub, out)
+    out += ["out%d %s" % (k, sha(t)) for k, t in enumerate(tensors_of(res))]
+    return out
+
+
+def train_row(make, lm):
+    dev = torch.device("cuda:0")
+    B, out = 2, []
+    set_deterministic(True)
+    try:
+        net = make().to(dev).train()
+        with torch.enable_grad():
+            res = call(net, det_image(B, seed=100).to(dev), lm)
+            ts = [t for t in tensors_of(res) if t.requires_grad]
+            torch.autograd.backward(ts, [torch.ones_like(t) for t in ts])
+        torch.cuda.synchronize()
+        pr = list(net._train_programs.values())[-1]              # (no public accessor: program_for lists the eval programs)
+        out.append("n_fwd_ops %d" % pr["prog"].n_fwd_ops)
+        dump_program(pr["prog"], out)
+        out += ["out%d %s" % (k, sha(t)) for k, t in enumerate(tensors_of(res))]
+        out.append("pgrad %s" % sha(pr["pgrad"]))
+    finally:
+        set_deterministic(False)
+    return out
+
+
+def matrix():
+    pose, wop = (lambda: build_net(512)), build_woprog
+    rows = []
+    for B in (2, 64):
+        rows.append(("posenet bf16 B=%d" % B, lambda B=B: eval_row(pose, "bf16", B)))
+    rows.append(("posenet fp32 B=2", lambda: eval_row(pose, "fp32", 2)))
+    rows.append(("posenet bf16 B=2 stage=1", lambda: eval_row(pose, "bf16", 2, stage=1)))
+    for sel in ("per_crop", "tiled"):
+        rows.append(("posenet bf16 B=2 %s" % sel, lambda sel=sel: eval_row(pose, "bf16", 2, selection=sel)))
+    for B in (2, 64):
+        rows.append(("woprog bf16 B=%d" % B, lambda B=B: eval_row(wop, "bf16", B, lm=True)))
+    rows.append(("woprog fp32 B=2", lambda: eval_row(wop, "fp32", 2, lm=True)))
+    rows.append(("posenet graph=0 bf16 B=2", lambda: eval_row(lambda: build_net(512, graph=0), "bf16", 2)))
+    # N = 4096: the patch-ordered rows and the permutes; the tiled EdgeConv itself needs B * N / 512 workgroups to fill the chip, which
+    # at B = 2 only the pinned per-crop selection grants
+    lm4096 = []                                                  # one net for both rows: its patch schedule is host work of seconds
+
+    def lm_net():
+        if not lm4096:
+            lm4096.append(build_net(4096, lm=True))
+        return lm4096[0]
+    for sel in ("auto", "per_crop"):
+        rows.append(("posenet lm N=4096 bf16 B=2 %s" % sel, lambda sel=sel: eval_row(lm_net, "bf16", 2, lm=True, selection=sel)))
+    rows.append(("initnet bf16 B=2", lambda: eval_row(lambda: build_net(512, full=False), "bf16", 2)))
+    rows.append(("posenet train fp32 B=2", lambda: train_row(pose, False)))
+    rows.append(("woprog train fp32 B=2", lambda: train_row(wop, True)))
+    return rows
+
+
+def time_build(n):
+    dev = torch.device("cuda:0")
+    with torch.no_grad():
+        net = build_net(512).to(dev).set_compute_dtype("bf16")
+        img = det_image(256, seed=100).to(dev)
+        net(img, None)                                           # library load, allocator warm-up
+        secs = []
+        for _ in range(n):
+            net.invalidate()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            net(img, None)
+            torch.cuda.synchronize()
+            secs.append(time.perf_counter() - t0)
+            assert net.program_for(256) is not None
+    print(json.dumps({"program_build_b256_seconds": secs}))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json")
+    ap.add_argument("--time-build", type=int, default=0)
+    a = ap.parse_args()
+    if a.time_build:
+        return time_build(a.time_build)
+    digests = {}
+    for name, row in matrix():
+        text = "\n".join(["==== " + name] + row()) + "\n"
+        sys.stdout.write(text)
+        sys.stdout.flush()
+        digests[name] = hashlib.sha256(text.encode()).hexdigest()
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(digests, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
