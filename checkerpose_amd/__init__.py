@@ -30,6 +30,7 @@ _COCO_NAMES = ("annotate_masks", "calc_gt_coco", "mask_ious", "box_ious", "CocoS
                "save_coco_results")
 _VISIBILITY_NAMES = ("compute_vis_hpr", "hpr_visibility", "overall_visibility")
 _VIS_NAMES = ("vis_poses", "depth_diff_vis", "select_estimates", "vis_est_poses", "vis_gt_poses")
+_REFINE_NAMES = ("refine_poses_lm", "pose_covariance")
 
 
 def __getattr__(name):
@@ -38,7 +39,7 @@ def __getattr__(name):
     row N15's likewise (coco_eval.py): .annotate_masks, .calc_gt_coco, .mask_ious, .box_ious, .CocoSet,
     .eval_bop22_coco, .check_coco_results, .save_coco_results (coco_eval.evaluate is reached through the module); row N16's likewise
     (visibility.py): .compute_vis_hpr, .hpr_visibility, .overall_visibility; row N18's likewise (vis.py): .vis_poses, .depth_diff_vis,
-    .select_estimates, .vis_est_poses, .vis_gt_poses"""
+    .select_estimates, .vis_est_poses, .vis_gt_poses; row N22's likewise (postprocess.py): .refine_poses_lm, .pose_covariance"""
     if name in _RENDER_NAMES:
         from . import render
         return getattr(render, name)
@@ -51,4 +52,7 @@ def __getattr__(name):
     if name in _VIS_NAMES:
         from . import vis
         return getattr(vis, name)
+    if name in _REFINE_NAMES:
+        from . import postprocess
+        return getattr(postprocess, name)
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -274,9 +274,97 @@ def solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=None, column=0, re
     return out
 
 
+LM_MAX_ITERS, LM_NMAX, LM_RECORD, LM_INFO = 64, 4096, 17, 40        # csrc/pnp_refine.hip
+
+
+def refine_poses_lm(p3d_xyz, p2d, mask, cam_K, R, t, status=None, max_iters=20, step_tol=1e-10, return_records=False):
+    """Levenberg-Marquardt polish of solved poses on the device (row N22; opt-in -- the reference does not refine): minimises the
+    squared reprojection error over each crop's selected correspondences, starting from (R, t).  What cv2.solvePnPRefineLM does for
+    a cv2 user, under this project's own rule (csrc/pnp_refine.hip states it, tests/lm_stages.py restates it; parity with cv2 UNPINNED).
+      p3d_xyz (N,3) / (B,N,3), p2d (B,N,2), cam_K (3,3) / (B,3,3): as solve_pnp_ransac; mask (B,N) bool or uint8: the points to fit,
+      e.g. the `inliers` of solve_pnp_ransac / solve_pnp_gc; R (B,3,3), t (B,3,1) / (B,3): the poses to start from; status (B,) or
+      None: crops whose entry is 0 (the solvers' identity fallback) are left alone; max_iters in 1..64; step_tol > 0.
+    -> (R (B,3,3) f64, t (B,3,1) f64, refine_status (B,) int32, info[, records])
+       refine_status: 1 = stopped by the step rule, 2 = max_iters ran out, 3 = lambda passed 1e8, 0 = pass-through (the input pose,
+       bitwise: status 0 given, fewer than 6 selected points, a non-finite pose or selected pixel, a selected point behind the camera);
+       info: dict of device tensors -- cost0, cost (B,) f64: sums of squared pixels at the input / returned pose; n (B,) int64
+       selected points; iters (B,) int64; H (B,6,6) f64: the undamped J^T J at the returned pose (rotation then translation);
+       status = refine_status.  Pass-through rows hold NaN in cost0, cost and H.
+       records (return_records=True): (B, max_iters, 17) f64, [lambda, c, c', accepted, s, R' (9), t' (3)] per executed iteration,
+       NaN where none ran."""
+    max_iters = int(max_iters)
+    if not 1 <= max_iters <= LM_MAX_ITERS:
+        raise ValueError("max_iters must be in 1..%d for cp_pnp_refine_lm, got %r" % (LM_MAX_ITERS, max_iters))
+    step_tol = float(step_tol)
+    if not 0.0 < step_tol < float("inf"):
+        raise ValueError("step_tol must be a finite number > 0, got %r" % (step_tol,))
+    if p2d.dim() != 3 or p2d.shape[2] != 2:
+        raise ValueError("p2d must be (B,N,2), got %r" % (tuple(p2d.shape),))
+    B, N, _ = p2d.shape
+    if not 1 <= N <= LM_NMAX:
+        raise ValueError("p2d: N must be in 1..%d, got %d" % (LM_NMAX, N))
+    if not torch.is_tensor(mask) or tuple(mask.shape) != (B, N) or mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError("mask must be a (B,N) bool or uint8 tensor")
+    if not torch.is_tensor(R) or not torch.is_tensor(t) or tuple(R.shape) != (B, 3, 3) or tuple(t.shape) not in ((B, 3, 1), (B, 3)):
+        raise ValueError("R must be (B,3,3) and t (B,3,1) / (B,3) tensors")
+    if status is not None and (not torch.is_tensor(status) or tuple(status.shape) != (B,)):
+        raise ValueError("status must be a (B,) tensor or None")
+    if not (p2d.is_cuda and mask.is_cuda and R.is_cuda and t.is_cuda and (status is None or status.is_cuda)):
+        raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+    lib = _abi.load()
+    dev = p2d.device
+    p3 = torch.as_tensor(p3d_xyz, dtype=torch.float32, device=dev).contiguous()
+    K = torch.as_tensor(cam_K, dtype=torch.float32, device=dev).contiguous()
+    if p3.shape[-2:] != (N, 3) or K.shape[-2:] != (3, 3) or (p3.dim() == 3 and p3.shape[0] != B) or (K.dim() == 3 and K.shape[0] != B):
+        raise ValueError("p3d_xyz must be (N,3) / (B,N,3) and cam_K (3,3) / (B,3,3)")
+    p2 = p2d.contiguous().float()
+    mk = mask.contiguous().view(torch.uint8)
+    pose_in = torch.cat([R.reshape(B, 9).to(dev, torch.float64), t.reshape(B, 3).to(dev, torch.float64)], 1).contiguous()
+    st_in = None if status is None else status.to(device=dev, dtype=torch.int32).contiguous()
+    pose = torch.empty(B, 12, dtype=torch.float64, device=dev)
+    rstatus = torch.empty(B, dtype=torch.int32, device=dev)
+    info = torch.empty(B, LM_INFO, dtype=torch.float64, device=dev)
+    rec = torch.full((B, max_iters, LM_RECORD), float("nan"), dtype=torch.float64, device=dev) if return_records else None
+    with torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev).cuda_stream
+        _abi.check(lib.cp_pnp_refine_lm(st, p3.data_ptr(), 3 * N if p3.dim() == 3 else 0, p2.data_ptr(), mk.data_ptr(), 1, K.data_ptr(),
+                                        9 if K.dim() == 3 else 0, B, N, pose_in.data_ptr(), st_in.data_ptr() if st_in is not None else None,
+                                        max_iters, step_tol, pose.data_ptr(), rstatus.data_ptr(), info.data_ptr(),
+                                        rec.data_ptr() if rec is not None else None), "cp_pnp_refine_lm")
+    out_info = dict(cost0=info[:, 0], cost=info[:, 1], n=info[:, 2].long(), iters=info[:, 3].long(), H=info[:, 4:].view(B, 6, 6), status=rstatus)
+    out = (pose[:, :9].view(B, 3, 3), pose[:, 9:].view(B, 3, 1), rstatus, out_info)
+    if return_records:
+        out += (rec,)
+    return out
+
+
+def pose_covariance(info, sigma=None):
+    """First-order covariance of the refined poses' increments (w, v) from refine_poses_lm's `info`: sigma^2 inv(H), (B,6,6) f64 on
+    the device, rotation (radians) then translation (units of the model).  sigma: the pixel noise's standard deviation (a number or
+    a (B,) tensor); None = estimated per crop from the residuals, sigma^2 = cost / (2 n - 6).  Rows that were not refined (status 0)
+    or have no redundancy (2 n <= 6) are NaN.  Plain torch on the device."""
+    H, n, status = info["H"], info["n"], info["status"]
+    B = H.shape[0]
+    dof = 2 * n - 6
+    ok = (status != 0) & (dof > 0)
+    if sigma is None:
+        s2 = info["cost"] / dof.clamp(min=1).to(torch.float64)
+    else:
+        s2 = torch.as_tensor(sigma, dtype=torch.float64, device=H.device).expand(B) ** 2
+    eye = torch.eye(6, dtype=torch.float64, device=H.device).expand(B, 6, 6)
+    inv = torch.linalg.inv(torch.where(ok[:, None, None], H, eye))
+    cov = s2[:, None, None] * inv
+    return torch.where(ok[:, None, None], cov, torch.full_like(cov, float("nan")))
+
+
+def _check_refine(refine):
+    if refine not in (None, "lm"):
+        raise ValueError("refine must be None or 'lm', got %r" % (refine,))
+
+
 def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
                    resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0, solver="epnp",
-                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400):
+                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None):
     """The inner loop of the reference's test.py (:198-330) for a whole batch without leaving the GPU: detection boxes on full uint8
     frames -> padded RoI crops (`padding_Bbox` + `get_roi`, bop_dataset_pytorch.py:344-354; preprocess.get_roi_batch) -> network forward
     (uint8 input, normalised on the device) -> correspondences from the crops' final boxes (`get_final_Bbox`; N2) -> EPnP + RANSAC (N4).
@@ -284,10 +372,13 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
       p3d_xyz (N,3) / (B,N,3) model keypoints in original units; cam_K (3,3) / (B,3,3); obj_ids for the LM shared estimator.
       solver "epnp" (default): solve_pnp_ransac; "gc": solve_pnp_gc (row N17, the `--use_progressivex` path) over `graph` =
       radius_graph(p3d_xyz) with spatial_coherence_weight and prog_max_iters iterations; obj_ids then also name each crop's graph.
+      refine None (default): the solver's pose as it is; "lm" (row N22): refine_poses_lm over the solver's inliers at its defaults,
+      with either solver -- the returned R, t are then the refined ones, inliers and status still the solver's.
     -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32 (0: identity fallback), final boxes (B,4) int array)"""
     from . import preprocess as PP
     if solver not in ("epnp", "gc"):
         raise ValueError("solver must be 'epnp' or 'gc', got %r" % (solver,))
+    _check_refine(refine)
     if solver == "gc" and graph is None:
         raise ValueError("solver='gc' needs graph=radius_graph(p3d_xyz)")
     if frames.dim() == 3:
@@ -303,9 +394,11 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
         R, t, inl, status = solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=obj_ids if graph.M > 1 else None,
                                          column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
                                          spatial_coherence_weight=spatial_coherence_weight, iterations=prog_max_iters, seed=seed)
-        return R, t, inl, status, final
-    R, t, inl, status = solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
-                                         iterations=iterations, seed=seed)
+    else:
+        R, t, inl, status = solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
+                                             iterations=iterations, seed=seed)
+    if refine == "lm":
+        R, t = refine_poses_lm(p3d_xyz, p2d, inl, cam_K, R, t, status=status)[:2]
     return R, t, inl, status, final
 
 
@@ -332,7 +425,7 @@ def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, me
 def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_y_id, check_seg=False, seg_mask=None,
                     use_progressivex=False, neighborhood_ball_radius=20, spatial_coherence_weight=0.1, prog_max_iters=400,
                     discard_bd_pixel=0, return_inliers=False, reprojErr_thresh=2, cv_max_iters=150, device="cuda:0", seed=0,
-                    progx_backend=None):
+                    progx_backend=None, refine=None):
     """Same name, arguments (numpy arrays of ONE image) and returns as the reference's `from_id_to_pose`
     (test_network_with_test_data.py:32-115), with its cv2 branch running on the device (`cp_pnp_ransac`):
       the validity mask is built exactly as :50-66 (RoI bit > 0.5, optional seg mask at the predicted pixel, optional border
@@ -342,10 +435,13 @@ def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_
     progx_backend="device" asks for this project's graph-cut RANSAC (solve_pnp_gc, row N17; parity with pyprogressivex UNPINNED):
     neighborhood_ball_radius -> radius_graph, spatial_coherence_weight, prog_max_iters, reprojErr_thresh -> the solver; fewer than 6
     valid points -> the identity; inliers None, as in the reference (:99).
+    refine="lm" (row N22, not in the reference) polishes a solved pose over the solver's inliers with refine_poses_lm at its defaults,
+    on the device cv2 twin and on progx_backend="device" alike; None (default) leaves the solver's pose as it is.
     For whole batches straight from the network's outputs use correspondences() + solve_pnp_ransac() instead."""
     import numpy as np
     if progx_backend not in (None, "device"):
         raise ValueError("progx_backend must be None or 'device', got %r" % (progx_backend,))
+    _check_refine(refine)
     if use_progressivex and progx_backend is None:
         raise ValueError("use_progressivex=True needs the third-party pyprogressivex solver, which is not built; "
                          "progx_backend='device' runs this project's graph-cut RANSAC (solve_pnp_gc) in its place")
@@ -367,10 +463,12 @@ def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_
             valid[0, :, 0] = torch.from_numpy(np.ascontiguousarray(valid_mask)).to(dev)
             p2d = torch.from_numpy(np.ascontiguousarray(disc_p2d, dtype=np.float32)).to(dev)[None]
             p3 = torch.from_numpy(np.ascontiguousarray(p3d_xyz, dtype=np.float32)).to(dev)
-            R, t, inl, status = solve_pnp_gc(p3, p2d, valid, torch.from_numpy(np.ascontiguousarray(cam_K, dtype=np.float32)).to(dev),
-                                             radius_graph(p3, float(neighborhood_ball_radius)), column=0,
+            Kd = torch.from_numpy(np.ascontiguousarray(cam_K, dtype=np.float32)).to(dev)
+            R, t, inl, status = solve_pnp_gc(p3, p2d, valid, Kd, radius_graph(p3, float(neighborhood_ball_radius)), column=0,
                                              reproj_threshold=float(reprojErr_thresh), spatial_coherence_weight=float(spatial_coherence_weight),
                                              iterations=int(prog_max_iters), seed=seed)
+            if refine == "lm":
+                R, t = refine_poses_lm(p3, p2d, inl, Kd, R, t, status=status)[:2]
             if int(status[0]) == 1:
                 R_predict, t_predict = R[0].cpu().numpy(), t[0].cpu().numpy()
     elif int(valid_mask.sum()) < 4:
@@ -380,9 +478,12 @@ def from_id_to_pose(p3d_xyz, roi_xy_ori, cam_K, roi_mask_bit, pixel_x_id, pixel_
         valid = torch.zeros(1, num_all_pt, 3, dtype=torch.uint8, device=dev)
         valid[0, :, 0] = torch.from_numpy(np.ascontiguousarray(valid_mask)).to(dev)
         p2d = torch.from_numpy(np.ascontiguousarray(disc_p2d, dtype=np.float32)).to(dev)[None]
-        R, t, inl, status = solve_pnp_ransac(torch.from_numpy(np.ascontiguousarray(p3d_xyz, dtype=np.float32)).to(dev), p2d, valid,
-                                             torch.from_numpy(np.ascontiguousarray(cam_K, dtype=np.float32)).to(dev), column=0,
+        p3 = torch.from_numpy(np.ascontiguousarray(p3d_xyz, dtype=np.float32)).to(dev)
+        Kd = torch.from_numpy(np.ascontiguousarray(cam_K, dtype=np.float32)).to(dev)
+        R, t, inl, status = solve_pnp_ransac(p3, p2d, valid, Kd, column=0,
                                              reproj_threshold=float(reprojErr_thresh), iterations=int(cv_max_iters), seed=seed)
+        if refine == "lm":
+            R, t = refine_poses_lm(p3, p2d, inl, Kd, R, t, status=status)[:2]
         if int(status[0]) == 1:
             R_predict, t_predict = R[0].cpu().numpy(), t[0].cpu().numpy()
             inliers = np.nonzero(inl[0].cpu().numpy())[0]

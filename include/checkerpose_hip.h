@@ -593,6 +593,34 @@ int cp_pnp_gc(cp_stream_t stream, const float* p3d, long long p3d_bstride, const
               float reproj_threshold, int32_t w, int iterations, int min_inliers, uint32_t seed, double* pose,
               uint8_t* inliers, int32_t* status, void* scratch);
 
+/* Levenberg-Marquardt polish of solved poses (row N22): the non-linear refinement of the reprojection error over a crop's selected
+ * correspondences -- the inliers of cp_pnp_ransac or cp_pnp_gc -- that a cv2 user gets from solvePnPRefineLM.  The reference does not
+ * refine; opt-in, the rule is this project's own (stated in full at the top of csrc/pnp_refine.hip, restated in numpy by
+ * tests/lm_stages.py); parity with cv2 is UNPINNED.  One launch, one workgroup per crop, fp64 without contraction.
+ *   p3d, p3d_bstride, p2d, cam_K, K_bstride, B, N as cp_pnp_ransac (N <= 4096; B == 0 returns without a launch);
+ *   mask uint8, `mask_stride` bytes between keypoints, (b * N + i) * mask_stride: non-zero = selected;
+ *   pose_in fp64 (B,12) = [R row-major | t]; status_in int32 (B) or NULL: 0 = leave this crop's pose alone;
+ *   max_iters in 1..64; step_tol > 0, finite.
+ * Per crop: cost c = sum of squared reprojection errors (pixels^2) over the n selected points; increment d = (w, v) with
+ *   R' = exp([w]x) R, t' = t + v; H = sum J^T J, g = sum J^T r.  lambda = 1e-3; an iteration solves (H + lambda diag H) d = -g by
+ *   Cholesky (not positive definite: rejected, c' = +inf, d NaN), accepts iff c' < c (c' = +inf when a selected point is not in front
+ *   of the camera or c' is not finite), then lambda = max(lambda / 10, 1e-12) or lambda * 10; s = max(|w|_inf, |v|_inf / |t|).
+ *   Stops: s <= step_tol -> status 1; lambda > 1e8 after a rejection -> 3; max_iters iterations -> 2.
+ *   Status 0 = pass-through, pose_out BITWISE pose_in: status_in 0, n < 6, a non-finite input pose or selected pixel, a selected
+ *   point with C_z <= 0 under the input pose.
+ * Outputs: pose_out fp64 (B,12) (bitwise the last accepted trial, or pose_in; pose_out == pose_in is allowed, a partial overlap is
+ *   refused), status_out int32 (B), info fp64 (B, cp_pnp_refine_lm_info_doubles() = 40) = [c at the input pose, c at the returned
+ *   pose, n, iterations run, the undamped H at the returned pose (36, row-major; order w then v)] (status 0: NaN but for n and 0
+ *   iterations); records fp64 (B, max_iters, cp_pnp_refine_lm_record_doubles() = 17) or NULL: per executed iteration [lambda used,
+ *   c, c', accepted 0/1, s, R' (9), t' (3)]; slots of iterations that did not run are never written (a caller that wants to tell
+ *   them apart fills the buffer first). */
+int cp_pnp_refine_lm_record_doubles(void);
+int cp_pnp_refine_lm_info_doubles(void);
+int cp_pnp_refine_lm(cp_stream_t stream, const float* p3d, long long p3d_bstride, const float* p2d, const uint8_t* mask,
+                     int mask_stride, const float* cam_K, long long K_bstride, int B, int N, const double* pose_in,
+                     const int32_t* status_in, int max_iters, double step_tol, double* pose_out, int32_t* status_out,
+                     double* info, double* records);
+
 /* Pose errors on the device (next-row N5; reference metric.py:8-18 -> bop_toolkit_lib/pose_error.py:147-184, called once per image
  * by test.py:378-427 / test_lm.py:300-321): ADD = mean_i |P_est(p_i) - P_gt(p_i)| and ADD-S / ADI = mean_i min_j |P_gt(p_i) - P_est(p_j)|
  * over an object's mesh vertices, for B poses at once.
