@@ -69,6 +69,10 @@ def _rup(x, m):
     return (x + m - 1) // m * m
 
 
+def _ptr(t):
+    return t.data_ptr() if t is not None else None
+
+
 class TBuf:
     """A workspace tensor: `nbytes` at `offset` of the program's workspace; live over ops [first, last]."""
     __slots__ = ("nbytes", "offset", "first", "last", "fixed")
@@ -110,13 +114,22 @@ class WeightStore:
             self.cache[key] = make()
         return self.cache[key]
 
-    def _packed(self, nbytes, w, call, what):
-        """a packed weight image: `nbytes` device bytes filled from the fp32 source weight `w` by
-        call(stream, w pointer, image pointer) -> status, a packing launch on the current stream"""
-        out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        wc = w.contiguous()
-        self.keep.append(wc)
-        _abi.check(call(torch.cuda.current_stream(self.device).cuda_stream, wc.data_ptr(), out.data_ptr()), what)
+    def _hold(self, t):
+        """pointer of `t` made contiguous and kept alive until the packing kernels ran"""
+        t = t.contiguous()
+        self.keep.append(t)
+        return t.data_ptr()
+
+    def _scale(self, s):
+        """pointer of a folded-BN scale vector that a packing launch multiplies INTO the weights"""
+        return self._hold(s.to(device=self.device, dtype=torch.float32))
+
+    def _packed(self, nbytes, w, call, what, zero=False):
+        """a packed weight image: `nbytes` device bytes (zero-filled first if `zero`) filled from the fp32 source weight `w` by
+        call(stream, w pointer, image pointer) -> status, a packing launch on the current stream.  `call` may close over further
+        pointers (_scale); an image of several pieces passes w = None and checks one launch per piece itself"""
+        out = (torch.zeros if zero else torch.empty)(nbytes, dtype=torch.uint8, device=self.device)
+        _abi.check(call(torch.cuda.current_stream(self.device).cuda_stream, self._hold(w) if w is not None else None, out.data_ptr()), what)
         return out
 
     def _pack(self, key, nbytes, w, call, what):
@@ -131,8 +144,7 @@ class WeightStore:
             if row_map is not None:
                 rm = torch.tensor(row_map, dtype=torch.int32, device=self.device)
                 self.keep.append(rm)
-            return self.lib.cp_pack_conv_weight(st, dtype, wp, Cout, Cin, R, S, cin_phys, transposed, phase,
-                                                rm.data_ptr() if rm is not None else None, cout_rows, op)
+            return self.lib.cp_pack_conv_weight(st, dtype, wp, Cout, Cin, R, S, cin_phys, transposed, phase, _ptr(rm), cout_rows, op)
         return self._pack((name, cin_phys, cout_rows, transposed, phase) + (() if dtype == self.dtype else (dtype,)),
                           self.lib.cp_packed_weight_bytes(dtype, cout_rows, cin_phys, R, S), w, call, "cp_pack_conv_weight(%s)" % name)
 
@@ -159,24 +171,21 @@ class WeightStore:
     def pack_chain(self, name, ws, affs, C_, H, W):
         """the 8 convs of an HRNet branch chain: one packed weight blob (BN scale folded in) + one [8][2][AFF] fp32 affine tensor
         (row 0: the scale, informational -- the kernel reads row 1, the shift)"""
-        ck = ("chain", name)
-        if ck in self.cache:
-            return self.cache[ck]
-        blob = torch.empty(self.lib.cp_hr_chain_weight_bytes(C_, H, W), dtype=torch.uint8, device=self.device)
-        st = torch.cuda.current_stream(self.device).cuda_stream
-        for i, w in enumerate(ws):
-            w = w.contiguous()
-            sc = affs[i][0].to(device=self.device, dtype=torch.float32).contiguous()      # folded-BN scale goes INTO the packed weights
-            self.keep += [w, sc]
-            _abi.check(self.lib.cp_pack_hr_chain_weight(st, w.data_ptr(), sc.data_ptr(), C_, H, W, i, blob.data_ptr()),
-                       "cp_pack_hr_chain_weight(%s)" % name)
-        n = self.lib.cp_hr_chain_affine_floats(C_, H, W)
-        aff = torch.zeros(8, 2, n, dtype=torch.float32, device=self.device)
-        for i, (s_, t_) in enumerate(affs):
-            aff[i, 0, :C_] = s_
-            aff[i, 1, :C_] = t_
-        self.cache[ck] = (blob, aff)
-        return self.cache[ck]
+        what = "cp_pack_hr_chain_weight(%s)" % name
+
+        def pieces(st, _, op):
+            for i, w in enumerate(ws):
+                _abi.check(self.lib.cp_pack_hr_chain_weight(st, self._hold(w), self._scale(affs[i][0]), C_, H, W, i, op), what)
+            return 0
+
+        def make():
+            blob = self._packed(self.lib.cp_hr_chain_weight_bytes(C_, H, W), None, pieces, what)
+            aff = torch.zeros(8, 2, self.lib.cp_hr_chain_affine_floats(C_, H, W), dtype=torch.float32, device=self.device)
+            for i, (s_, t_) in enumerate(affs):
+                aff[i, 0, :C_] = s_
+                aff[i, 1, :C_] = t_
+            return blob, aff
+        return self.cached(("chain", name), make)
 
     def affine(self, name, scale, shift, rows):
         """fp32 scale/shift vectors padded with zeros to a multiple of 16 entries (rows >= len)."""
@@ -272,6 +281,50 @@ class Program:
         self._rw[i] = ([t for t in reads if t is not None], [t for t in writes if t is not None])
         self.ops.append((fn, argb, name, self.lane))
 
+    def _mfma(self, fn, argb, family, key, reads, writes, M, Cout, K, flops, nbytes):
+        """Record an MFMA launch and its conv_log row together, so three things hold by construction: the launch is named
+        family:key, the row's family is that prefix (bench.py walks the calls and the log in step), and self.flops is the sum of the
+        logged flops.  flops / nbytes are algorithmic (unpadded)."""
+        self._add(fn, argb, family + ":" + key, reads, writes)
+        self.flops += flops
+        self.conv_log.append((key, M, Cout, K, flops, family, nbytes))
+
+    def _desc(self, x: Act, R, S, stride, pad, Ho, Wo, act, slope, out: Act = None, ostr=None, Cout=None, dtype=None, out_f32=0,
+              in_hw=None, cin=None):
+        """The CpConvDesc of a launch that reads `x`.  The output is the dense Act `out`, or `Cout` channels at the explicit element
+        strides ostr = (o_base, o_sb, o_sy, o_sx, o_sc).  in_hw: what d.H, d.W hold when not x's own size; cin / Cout (with `out`):
+        channel counts when not the physical ones of x / out."""
+        d = CpConvDesc()
+        d.dtype, d.out_f32 = (self.dtype if dtype is None else dtype), out_f32
+        d.B, (d.H, d.W) = x.B, in_hw or (x.H, x.W)
+        d.Cin, d.in_cstride, d.in_coff = (x.Cphys if cin is None else cin), x.cstride, x.coff
+        d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = R, S, stride, pad, Ho, Wo
+        d.act, d.slope = act, slope
+        if ostr is None:
+            ostr = (out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1)
+            Cout = out.Cphys if Cout is None else Cout
+        d.Cout = Cout
+        d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = ostr
+        self.keep.append(d)
+        return d
+
+    def _sources(self, srcs, shifts, out: Act, hw=None):
+        """Up to four source maps (whole tensors in out's channel layout; with `hw`, source i nearest-upsampled by 2^shifts[i] has that
+        size) as a launch's C arrays: (n, shift array, source TBufs, bind) -- bind(P) fills and returns the pointer array."""
+        n = len(srcs)
+        arr_p = (C.c_void_p * 4)()
+        arr_s = (C.c_int32 * 4)(*([int(v) for v in shifts] + [0] * (4 - n)))
+        self.keep += [arr_p, arr_s]
+        for s_, sh in zip(srcs, shifts):
+            assert s_.coff == 0 and s_.cstride == s_.Cphys == out.Cphys and (hw is None or (s_.H << sh, s_.W << sh) == hw)
+        tbs = [s_.tbuf for s_ in srcs]
+
+        def bind(P):
+            for i, t in enumerate(tbs):
+                arr_p[i] = P(t)
+            return arr_p
+        return n, arr_s, tbs, bind
+
     # ---- structured concurrency: independent sub-chains (HRNet branches, decoder vs GNN refinement) are launched on
     # separate lanes; under hipGraph capture each lane is its own stream joined by events, so the graph gets parallel
     # branches and the latency-bound small kernels overlap the big ones.  Eager replay ignores lanes (one stream,
@@ -311,6 +364,44 @@ class Program:
         self.lane = 0
 
     # ---- ops
+    def _conv_route(self, x: Act, R, S, stride, pad, wCout, dense, residual, out_half, in_half):
+        """The kernel conv() runs a shape on: "s2small" | "halo2" | "halo" | "gemm" (the tiled specialists, told apart by kernel
+        size and stride) or "igemm" (the generic kernel).  dense: a plain dense output -- an Act in the storage type, not transposed,
+        no row map, no explicit strides -- which every specialist needs."""
+        bf16, half, cph = self.dtype == CP_BF16, out_half or in_half, _rup(wCout, self.E)
+        k, route = (R, S, stride, pad), "igemm"
+        if not dense:
+            return route
+        if k == (3, 3, 1, 1):
+            if USE_HALO and x.W >= 16 and x.H >= 8 and not half:
+                route = "halo"
+                # small-Cout variant pads Cin to 64-byte chunks PER TAP: in fp32 (MFMA-bound) that only pays when the
+                # padding waste is small (measured: 18/36-channel convs are faster on the generic kernel in fp32)
+                if wCout <= 80 and self.dtype == CP_F32 and not _rup(x.Cphys, 16) <= 1.15 * x.Cphys:
+                    route = "igemm"
+        elif k == (1, 1, 1, 0):
+            # K >= 4 chunks; from 16384 rows the bf16 weight-stationary variant runs (weights in registers, rows streamed once), which
+            # also pays at K = 64 .. 127 (incre conv3 + shortcut of the 32^2 branch: 98 -> 72 us)
+            kmin = 16 * self.E if not (bf16 and residual is None and x.B * x.H * x.W >= 16384 and GEMM_WS_SMALL_K) else 64
+            if USE_GEMM and wCout >= 96 and x.Cphys >= kmin and not out_half:
+                route = "gemm"
+        elif k == (3, 3, 2, 1):
+            if (USE_S2_SMALL and bf16 and residual is None and x.H % 2 == 0 and x.W % 2 == 0 and x.B >= self.chain_min and not half
+                    and self.lib.cp_conv3x3_s2_small_supported(x.H, x.W, x.Cphys, cph)):
+                route = "s2small"
+        elif k == (2, 2, 1, 1):
+            # k = 2 / pad 1 (Index2Feat's patch_generator over the whole map): the small-Cout halo kernel with four taps (eval programs:
+            # the training program repacks its weights every step through the pack-item tables, which have no entry for this image)
+            if (USE_HALO2 and bf16 and not in_half and not self.ws.repacks_every_step
+                    and self.lib.cp_conv2x2_halo_supported(self.dtype, x.H, x.W, cph)):
+                route = "halo2"
+        if (route != "igemm" and self.splitk
+                and self.lib.cp_conv2d_igemm_splitk(CP_F16 if in_half else self.dtype,
+                                                    x.B * ((x.H + 2 * pad - R) // stride + 1) * ((x.W + 2 * pad - S) // stride + 1),
+                                                    R * S * x.Cphys, cph)):
+            route = "igemm"      # small batch: the generic kernel's split-K variant beats the tiled specialists
+        return route
+
     def conv(self, x: Act, wkey, w, scale, shift, R, S, stride, pad, Cout, act=ACT_NONE, slope=0.0, residual: Act = None,
              out: Act = None, transposed=0, phase=0, row_map=None, cout_rows=None, out_f32=False, ostr=None,
              out_tbuf=None, out_hw=None, w_shape=None, out_half=False, in_half=False):
@@ -324,93 +415,51 @@ class Program:
         rows = cout_rows if cout_rows is not None else wCout
         if wCin != x.C:
             raise RuntimeError("conv %s: weight expects %d input channels, activation has %d" % (wkey, wCin, x.C))
-        halo = (USE_HALO and R == 3 and S == 3 and stride == 1 and pad == 1 and ostr is None and not out_f32
-                and not transposed and row_map is None and x.W >= 16 and x.H >= 8 and not (out_half or in_half))
-        cdt = CP_F16 if in_half else self.dtype          # the launch's dtype: half rows + half weights for a keypoint-side layer
-        if halo and wCout <= 80 and self.dtype == CP_F32:
-            # small-Cout variant pads Cin to 64-byte chunks PER TAP: in fp32 (MFMA-bound) that only pays when the
-            # padding waste is small (measured: 18/36-channel convs are faster on the generic kernel in fp32)
-            halo = _rup(x.Cphys, 16) <= 1.15 * x.Cphys
-        # K >= 4 chunks; from 16384 rows the bf16 weight-stationary variant runs (weights in registers, rows streamed once), which
-        # also pays at K = 64 .. 127 (incre conv3 + shortcut of the 32^2 branch: 98 -> 72 us)
-        kmin = 16 * self.E if not (self.dtype == CP_BF16 and residual is None and x.B * x.H * x.W >= 16384 and GEMM_WS_SMALL_K) else 64
-        gemm = (USE_GEMM and R == 1 and S == 1 and stride == 1 and pad == 0 and ostr is None and not out_f32
-                and not transposed and row_map is None and wCout >= 96 and x.Cphys >= kmin and not out_half)
-        s2small = (USE_S2_SMALL and self.dtype == CP_BF16 and R == 3 and S == 3 and stride == 2 and pad == 1 and ostr is None and not out_f32
-                   and not transposed and row_map is None and residual is None and x.H % 2 == 0 and x.W % 2 == 0 and x.B >= self.chain_min
-                   and not (out_half or in_half) and bool(self.lib.cp_conv3x3_s2_small_supported(x.H, x.W, x.Cphys, _rup(wCout, self.E))))
-        # k = 2 / pad 1 (Index2Feat's patch_generator over the whole map): the small-Cout halo kernel with four taps
-        halo2 = (USE_HALO2 and self.dtype == CP_BF16 and R == 2 and S == 2 and stride == 1 and pad == 1 and ostr is None and not out_f32
-                 and not transposed and row_map is None and not in_half and not self.ws.repacks_every_step   # (eval programs:
-                 # the training program repacks its weights every step through the pack-item tables, which have no entry for this image)
-                 and bool(self.lib.cp_conv2x2_halo_supported(self.dtype, x.H, x.W, _rup(wCout, self.E))))
-        if (self.splitk and not transposed and row_map is None and (halo or gemm or s2small or halo2)
-                and self.lib.cp_conv2d_igemm_splitk(cdt, x.B * ((x.H + 2 * pad - R) // stride + 1) * ((x.W + 2 * pad - S) // stride + 1),
-                                                    R * S * x.Cphys, _rup(wCout, self.E))):
-            halo = gemm = s2small = halo2 = False      # small batch: the generic kernel's split-K variant beats the tiled specialists
-        if s2small:
-            packed = self.ws._pack(("s2small", wkey, x.Cphys), self.lib.cp_conv3x3_s2_small_weight_bytes(x.Cphys, _rup(wCout, self.E)), w,
-                                   lambda st, wp, op: self.lib.cp_pack_conv3x3_s2_small_weight(st, wp, wCout, wCin, x.Cphys, _rup(wCout, self.E), op),
-                                   "cp_pack_conv3x3_s2_small_weight(%s)" % wkey)
-            halo = gemm = False
-        elif halo2:
-            packed = self.ws._pack(("halo2", wkey, x.Cphys), self.lib.cp_packed_conv2x2_halo_weight_bytes(self.dtype, wCout, x.Cphys), w,
-                                   lambda st, wp, op: self.lib.cp_pack_conv2x2_halo_weight(st, self.dtype, wp, wCout, wCin, x.Cphys, op),
-                                   "cp_pack_conv2x2_halo_weight(%s)" % wkey)
-        elif halo:
-            packed = self.ws.pack_halo(wkey, w, wCout, wCin, x.Cphys)
-        elif gemm:
-            packed = self.ws.pack_gemm(wkey, w, wCout, wCin, x.Cphys, **({"dtype": CP_F16} if in_half else {}))
-        else:
-            packed = self.ws.pack(wkey, w, wCout, wCin, R, S, x.Cphys, rows, transposed, phase, row_map, **({"dtype": CP_F16} if in_half else {}))
+        lib, cph, cdt = self.lib, _rup(wCout, E), (CP_F16 if in_half else self.dtype)   # cdt: half rows + half weights for a keypoint-side layer
+        hkw = {"dtype": CP_F16} if in_half else {}       # (trainer.TrainWeightStore's pack / pack_gemm take no dtype: fp32 programs only)
+        route = self._conv_route(x, R, S, stride, pad, wCout, ostr is None and not out_f32 and not transposed and row_map is None,
+                                 residual, out_half, in_half)
+        # route -> (C entry point, conv_log family, packer of its weight image)
+        fn, fam, pack = {
+            "s2small": (lib.cp_conv3x3_s2_small, "conv3x3_s2_small", lambda: self.ws._pack(
+                ("s2small", wkey, x.Cphys), lib.cp_conv3x3_s2_small_weight_bytes(x.Cphys, cph), w,
+                lambda st, wp, op: lib.cp_pack_conv3x3_s2_small_weight(st, wp, wCout, wCin, x.Cphys, cph, op),
+                "cp_pack_conv3x3_s2_small_weight(%s)" % wkey)),
+            "halo2": (lib.cp_conv2x2_halo, "conv3x3_halo_s", lambda: self.ws._pack(
+                ("halo2", wkey, x.Cphys), lib.cp_packed_conv2x2_halo_weight_bytes(self.dtype, wCout, x.Cphys), w,
+                lambda st, wp, op: lib.cp_pack_conv2x2_halo_weight(st, self.dtype, wp, wCout, wCin, x.Cphys, op),
+                "cp_pack_conv2x2_halo_weight(%s)" % wkey)),
+            "halo": (lib.cp_conv3x3_halo, "conv3x3_halo_s" if wCout <= 80 else ("conv3x3_halo4" if wCout % 256 == 0 else "conv3x3_halo"),
+                     lambda: self.ws.pack_halo(wkey, w, wCout, wCin, x.Cphys)),
+            "gemm": (lib.cp_gemm_rows, "gemm_rows", lambda: self.ws.pack_gemm(wkey, w, wCout, wCin, x.Cphys, **hkw)),
+            "igemm": (lib.cp_conv2d_igemm, "conv_igemm",
+                      lambda: self.ws.pack(wkey, w, wCout, wCin, R, S, x.Cphys, rows, transposed, phase, row_map, **hkw)),
+        }[route]
+        packed = pack()
         sc, sh = self.ws.affine(wkey + "#" + str(phase), scale, shift, rows)
         Ho, Wo = out_hw if out_hw is not None else ((x.H + 2 * pad - R) // stride + 1, (x.W + 2 * pad - S) // stride + 1)
-        d = CpConvDesc()
-        d.dtype, d.out_f32 = (CP_F16 if in_half else self.dtype), (1 if out_f32 else (2 if out_half else 0))
-        d.B, d.H, d.W = x.B, x.H, x.W
-        d.Cin, d.in_cstride, d.in_coff = x.Cphys, x.cstride, x.coff
-        d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = R, S, stride, pad, Ho, Wo
-        d.act, d.slope = act, slope
+        if ostr is None and out is None:
+            out = self.act(Ho, Wo, Cout)
+        d = self._desc(x, R, S, stride, pad, Ho, Wo, act, slope, out, ostr, Cout if ostr is not None else None, cdt,
+                       1 if out_f32 else (2 if out_half else 0))
         d.ksplit = 0 if self.splitk else -1
-        if ostr is None:
-            if out is None:
-                out = self.act(Ho, Wo, Cout)
-            d.Cout = out.Cphys
-            d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1
-            otb = out.tbuf
-        else:  # explicit element strides into `out_tbuf` (o_base, o_sb, o_sy, o_sx, o_sc)
-            d.Cout = Cout
-            d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = ostr
-            otb = out_tbuf
-        self.keep += [d, packed, sc, sh]
+        otb = out.tbuf if ostr is None else out_tbuf     # ostr: explicit element strides into `out_tbuf`
+        self.keep += [packed, sc, sh]
         rtb = residual.tbuf if residual is not None else None
         if residual is not None and ostr is None:
             assert (residual.cstride, residual.coff, residual.H, residual.W) == (out.cstride, out.coff, out.H, out.W), \
                 "residual must share the output layout"
-        fn = self.lib.cp_conv3x3_halo if halo else (self.lib.cp_gemm_rows if gemm else self.lib.cp_conv2d_igemm)
-        if halo2:
-            fn = self.lib.cp_conv2x2_halo
         dref = C.byref(d)
         pw, ps, pt = packed.data_ptr(), sc.data_ptr(), sh.data_ptr()
         xtb = x.tbuf
-        if halo:
-            fam = "conv3x3_halo_s" if wCout <= 80 else ("conv3x3_halo4" if wCout % 256 == 0 else "conv3x3_halo")
+        if route == "s2small":                           # (no residual operand)
+            argb = lambda P: (dref, P(xtb), pw, ps, pt, P(otb))
         else:
-            fam = "gemm_rows" if gemm else "conv_igemm"
-        if halo2:
-            fam = "conv3x3_halo_s"
-        if s2small:
-            fam = "conv3x3_s2_small"
-            self._add(self.lib.cp_conv3x3_s2_small, lambda P: (dref, P(xtb), pw, ps, pt, P(otb)), fam + ":" + wkey, [xtb], [otb])
-        else:
-            self._add(fn, lambda P: (dref, P(xtb), pw, ps, pt, P(rtb) if rtb is not None else None, P(otb)),
-                      fam + ":" + wkey, [xtb, rtb], [otb])
-        fl = 2 * x.B * Ho * Wo * R * S * wCin * wCout
-        self.flops += fl
+            argb = lambda P: (dref, P(xtb), pw, ps, pt, P(rtb) if rtb is not None else None, P(otb))
         oes = 4 if out_f32 else self.es
         nbytes = (x.B * x.H * x.W * wCin * self.es + x.B * Ho * Wo * wCout * oes * (2 if residual is not None else 1)
                   + R * S * wCin * wCout * self.es)          # algorithmic: input + output (+ residual) + weights, unpadded
-        self.conv_log.append((wkey, x.B * Ho * Wo, wCout, R * S * wCin, fl, fam, nbytes))
+        self._mfma(fn, argb, fam, wkey, [xtb, rtb], [otb], x.B * Ho * Wo, wCout, R * S * wCin, 2 * x.B * Ho * Wo * R * S * wCin * wCout, nbytes)
         return out
 
     def would_splitk(self, M, K, Cout):
@@ -433,23 +482,13 @@ class Program:
         Ho, Wo = 2 * x.H, 2 * x.W
         if out is None:
             out = self.act(Ho, Wo, wCout)
-        d = CpConvDesc()
-        d.dtype, d.out_f32 = self.dtype, 0
-        d.B, d.H, d.W = x.B, Ho, Wo
-        d.Cin, d.in_cstride, d.in_coff = x.Cphys, x.cstride, x.coff
-        d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = 3, 3, 1, 1, Ho, Wo
-        d.act, d.slope, d.Cout = act, slope, out.Cphys
-        d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1
-        self.keep += [d, packed, sc, sh]
-        fn = self.lib.cp_conv3x3_halo_up2x
-        dref = C.byref(d)
+        dref = C.byref(self._desc(x, 3, 3, 1, 1, Ho, Wo, act, slope, out, in_hw=(Ho, Wo)))     # d.H, d.W: the conv's own (upsampled) input
+        self.keep += [packed, sc, sh]
         pw, ps, pt = packed.data_ptr(), sc.data_ptr(), sh.data_ptr()
         xtb, otb = x.tbuf, out.tbuf
-        self._add(fn, lambda P: (dref, P(xtb), pw, ps, pt, P(otb)), "conv3x3_halo4:" + wkey, [xtb], [otb])
-        fl = 2 * x.B * Ho * Wo * 9 * wCin * wCout
-        self.flops += fl
         nbytes = x.B * x.H * x.W * wCin * self.es + x.B * Ho * Wo * wCout * self.es + 9 * wCin * wCout * self.es
-        self.conv_log.append((wkey, x.B * Ho * Wo, wCout, 9 * wCin, fl, "conv3x3_halo4", nbytes))
+        self._mfma(self.lib.cp_conv3x3_halo_up2x, lambda P: (dref, P(xtb), pw, ps, pt, P(otb)), "conv3x3_halo4", wkey, [xtb], [otb],
+                   x.B * Ho * Wo, wCout, 9 * wCin, 2 * x.B * Ho * Wo * 9 * wCin * wCout, nbytes)
         return out
 
     def can_conv_halo_seg(self, x: Act, Cout, S):
@@ -473,23 +512,13 @@ class Program:
             return w2.contiguous().to(self.device), seg_b.float().contiguous().to(self.device)
         sw, sb = self.ws.cached(("seg_head", seg_key, self.dtype), head)
         out = self.act(x.H, x.W, wCout)
-        d = CpConvDesc()
-        d.dtype, d.out_f32 = self.dtype, 0
-        d.B, d.H, d.W = x.B, x.H, x.W
-        d.Cin, d.in_cstride, d.in_coff = x.Cphys, x.cstride, x.coff
-        d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = 3, 3, 1, 1, x.H, x.W
-        d.act, d.slope, d.Cout = act, slope, out.Cphys
-        d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1
-        self.keep += [d, packed, sc, sh, sw, sb]
-        fn = self.lib.cp_conv3x3_halo_seg
-        dref = C.byref(d)
+        dref = C.byref(self._desc(x, 3, 3, 1, 1, x.H, x.W, act, slope, out))
+        self.keep += [packed, sc, sh, sw, sb]
         pw, ps, pt, psw, psb = packed.data_ptr(), sc.data_ptr(), sh.data_ptr(), sw.data_ptr(), sb.data_ptr()
         xtb, otb = x.tbuf, out.tbuf
-        self._add(fn, lambda P: (dref, P(xtb), pw, ps, pt, P(otb), psw, psb, S, P(seg_tbuf)), "conv3x3_halo4:" + wkey, [xtb], [otb, seg_tbuf])
-        fl = 2 * x.B * x.H * x.W * 9 * wCin * wCout
-        self.flops += fl
         nbytes = x.B * x.H * x.W * (wCin + wCout) * self.es + 9 * wCin * wCout * self.es
-        self.conv_log.append((wkey, x.B * x.H * x.W, wCout, 9 * wCin, fl, "conv3x3_halo4", nbytes))
+        self._mfma(self.lib.cp_conv3x3_halo_seg, lambda P: (dref, P(xtb), pw, ps, pt, P(otb), psw, psb, S, P(seg_tbuf)), "conv3x3_halo4", wkey,
+                   [xtb], [otb, seg_tbuf], x.B * x.H * x.W, wCout, 9 * wCin, 2 * x.B * x.H * x.W * 9 * wCin * wCout, nbytes)
         return out
 
     def can_fuse_basicblock(self, x: Act, C_):
@@ -503,22 +532,14 @@ class Program:
         a1 = self.ws.affine(k1 + "#0", s1, t1, C_)
         a2 = self.ws.affine(k2 + "#0", s2, t2, C_)
         out = self.act(x.H, x.W, C_)
-        d = CpConvDesc()
-        d.dtype, d.out_f32, d.B, d.H, d.W = self.dtype, 0, x.B, x.H, x.W
-        d.Cin, d.in_cstride, d.in_coff = x.Cphys, x.cstride, x.coff
-        d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = 3, 3, 1, 1, x.H, x.W
-        d.Cout, d.act, d.slope = out.Cphys, ACT_RELU, 0.0
-        d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1
-        self.keep += [d, pw1, pw2, a1, a2]
-        fn = self.lib.cp_basicblock_fused
-        dref = C.byref(d)
+        dref = C.byref(self._desc(x, 3, 3, 1, 1, x.H, x.W, ACT_RELU, 0.0, out))
+        self.keep += [pw1, pw2, a1, a2]
         ptrs = (pw1.data_ptr(), a1[0].data_ptr(), a1[1].data_ptr(), pw2.data_ptr(), a2[0].data_ptr(), a2[1].data_ptr())
         xtb, otb = x.tbuf, out.tbuf
-        self._add(fn, lambda P: (dref, P(xtb)) + ptrs + (P(otb),), "basicblock_fused:" + k1, [xtb], [otb])
         fl = 2 * x.B * x.H * x.W * 9 * C_ * C_
         nb = x.B * x.H * x.W * C_ * self.es
-        self.flops += 2 * fl
-        self.conv_log.append((k1, x.B * x.H * x.W, C_, 9 * C_, 2 * fl, "basicblock_fused", 2 * nb + 2 * 9 * C_ * C_ * self.es))
+        self._mfma(self.lib.cp_basicblock_fused, lambda P: (dref, P(xtb)) + ptrs + (P(otb),), "basicblock_fused", k1, [xtb], [otb],
+                   x.B * x.H * x.W, C_, 9 * C_, 2 * fl, 2 * nb + 2 * 9 * C_ * C_ * self.es)
         return out
 
     def can_fuse_stem(self, size):
@@ -526,27 +547,23 @@ class Program:
 
     def hr_stem(self, img_t, size, k1, w1, s1, t1, k2, w2, s2, t2):
         """timm hrnet stem (conv1-bn1-relu-conv2-bn2-relu) from the NCHW fp32 image in one launch (cp_hr_stem)"""
-        ck = ("stem", k1)
-        if ck not in self.ws.cache:
-            p1 = torch.empty(self.lib.cp_hr_stem_weight_bytes(0), dtype=torch.uint8, device=self.device)
-            p2 = torch.empty(self.lib.cp_hr_stem_weight_bytes(1), dtype=torch.uint8, device=self.device)
-            w1c, w2c = w1.contiguous(), w2.contiguous()
-            self.ws.keep += [w1c, w2c]
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _abi.check(self.lib.cp_pack_hr_stem_weights(st, w1c.data_ptr(), w2c.data_ptr(), p1.data_ptr(), p2.data_ptr()), "cp_pack_hr_stem_weights")
-            self.ws.cache[ck] = (p1, p2)
-        p1, p2 = self.ws.cache[ck]
-        a1, a2 = self.ws.affine(k1 + "#0", s1, t1, 64), self.ws.affine(k2 + "#0", s2, t2, 64)
+        lib, ws = self.lib, self.ws
+
+        def make():                                   # one launch packs both images: conv2's is the call's own, conv1's rides along
+            p1 = torch.empty(lib.cp_hr_stem_weight_bytes(0), dtype=torch.uint8, device=self.device)
+            p2 = ws._packed(lib.cp_hr_stem_weight_bytes(1), w2, lambda st, wp, op: lib.cp_pack_hr_stem_weights(st, ws._hold(w1), wp, p1.data_ptr(), op),
+                            "cp_pack_hr_stem_weights")
+            return p1, p2
+        p1, p2 = ws.cached(("stem", k1), make)
+        a1, a2 = ws.affine(k1 + "#0", s1, t1, 64), ws.affine(k2 + "#0", s2, t2, 64)
         out = self.act(size // 4, size // 4, 64)
         self.keep += [p1, p2, a1, a2]
-        fn = self.lib.cp_hr_stem
         ip = img_t.data_ptr()
         ot = out.tbuf
         args = (p1.data_ptr(), a1[0].data_ptr(), a1[1].data_ptr(), p2.data_ptr(), a2[0].data_ptr(), a2[1].data_ptr())
-        self._add(fn, lambda P: (ip, self.B, size, size) + args + (P(ot),), "hr_stem:" + k1, [], [ot])
-        fl = 2 * self.B * ((size // 2) ** 2 * 64 * 27 + (size // 4) ** 2 * 64 * 576)
-        self.flops += fl
-        self.conv_log.append((k1, self.B * (size // 4) ** 2, 64, 576, fl, "hr_stem", self.B * (3 * size * size * 4 + (size // 4) ** 2 * 64 * 2)))
+        self._mfma(lib.cp_hr_stem, lambda P: (ip, self.B, size, size) + args + (P(ot),), "hr_stem", k1, [], [ot],
+                   self.B * (size // 4) ** 2, 64, 576, 2 * self.B * ((size // 2) ** 2 * 64 * 27 + (size // 4) ** 2 * 64 * 576),
+                   self.B * (3 * size * size * 4 + (size // 4) ** 2 * 64 * 2))
         return out
 
     def can_chain(self, C_, H, W):
@@ -566,28 +583,21 @@ class Program:
         out = self.act(H, W, C_)
         if tail is not None:
             return self._hr_chain_tail(name, srcs, shifts, relu_in, blob, aff, out, C_, H, W, tail)
-        n = len(srcs)
-        arr_p = (C.c_void_p * 4)()
-        arr_s = (C.c_int32 * 4)(*([int(v) for v in shifts] + [0] * (4 - n)))
-        self.keep += [arr_p, arr_s, blob, aff]
-        for s_, sh in zip(srcs, shifts):
-            assert s_.coff == 0 and s_.cstride == s_.Cphys == out.Cphys and (s_.H << sh, s_.W << sh) == (H, W)
-        tbs = [s_.tbuf for s_ in srcs]
-        ot = out.tbuf
-        fn = self.lib.cp_hr_branch_chain
-        bp, ap = blob.data_ptr(), aff.data_ptr()
-
-        def argb(P):
-            for i, t in enumerate(tbs):
-                arr_p[i] = P(t)
-            return (self.B, C_, H, W, n, arr_p, arr_s, 1 if relu_in else 0, bp, ap, P(ot))
-
-        self._add(fn, argb, "hr_chain:" + name, tbs, [ot])
-        fl = 8 * 2 * self.B * H * W * 9 * C_ * C_
-        self.flops += fl
-        nb = self.B * H * W * C_ * self.es
-        self.conv_log.append((name, self.B * H * W, C_, 9 * C_, fl, "hr_chain", (n + 1) * nb + 8 * 9 * C_ * C_ * self.es))
+        self._chain(self.lib.cp_hr_branch_chain, name, srcs, shifts, relu_in, blob, aff, out, C_, H, W)
         return out
+
+    def _chain(self, fn, name, srcs, shifts, relu_in, blob, aff, out, C_, H, W, touts=(), tail=lambda ptrs: (), fl_t=0, nb_t=0):
+        """The launch of a branch chain, plain or with a tail: fn(B, C, H, W, n, sources, shifts, relu_in, blob, affine, out,
+        *tail(pointers of the tail outputs `touts`)).  fl_t / nb_t: the tail convs' flops / bytes, on top of the chain's own
+        eight 3x3 convs, its n source maps, its output and its weights."""
+        n, arr_s, tbs, bind = self._sources(srcs, shifts, out, (H, W))
+        self.keep += [blob, aff]
+        ot, tts = out.tbuf, [o.tbuf for o in touts]
+        bp, ap = blob.data_ptr(), aff.data_ptr()
+        nb = self.B * H * W * C_ * self.es
+        self._mfma(fn, lambda P: (self.B, C_, H, W, n, bind(P), arr_s, 1 if relu_in else 0, bp, ap, P(ot)) + tail([P(t) for t in tts]),
+                   "hr_chain", name, tbs, [ot] + tts, self.B * H * W, C_, 9 * C_, 8 * 2 * self.B * H * W * 9 * C_ * C_ + fl_t,
+                   (n + 1) * nb + 8 * 9 * C_ * C_ * self.es + nb_t)
 
     def can_chain_tails(self, C_, H, W, convs):
         """every first-level fuse conv fed by this (36 / 72 / 144-channel) branch fits its chain launch's tail (cp_hr_branch_chain_tails);
@@ -606,19 +616,15 @@ class Program:
         for i, (wkey, w, scale, shift, k, relu) in enumerate(convs):
             kind = 1 if k == 3 else 0
             Cout = int(w.shape[0])
-            ck = ("chain_tailconv", wkey)
-            if ck not in self.ws.cache:
-                buf = torch.empty(lib.cp_hr_chain_tailconv_weight_bytes(C_, H, W, kind, Cout), dtype=torch.uint8, device=self.device)
-                wc = w.contiguous()
-                sc = scale.to(device=self.device, dtype=torch.float32).contiguous()
-                self.ws.keep += [wc, sc]
-                st = torch.cuda.current_stream(self.device).cuda_stream
-                _abi.check(lib.cp_pack_hr_chain_tailconv_weight(st, wc.data_ptr(), sc.data_ptr(), C_, H, W, kind, Cout, buf.data_ptr()),
-                           "cp_pack_hr_chain_tailconv_weight(%s)" % wkey)
+
+            def make():                               # (runs inside cached(), in this iteration)
+                buf = self.ws._packed(lib.cp_hr_chain_tailconv_weight_bytes(C_, H, W, kind, Cout), w,
+                                      lambda st, wp, op: lib.cp_pack_hr_chain_tailconv_weight(st, wp, self.ws._scale(scale), C_, H, W, kind, Cout, op),
+                                      "cp_pack_hr_chain_tailconv_weight(%s)" % wkey)
                 sh = torch.zeros(_rup(Cout, 16), dtype=torch.float32, device=self.device)
                 sh[:Cout] = shift
-                self.ws.cache[ck] = (buf, sh)
-            buf, sh = self.ws.cache[ck]
+                return buf, sh
+            buf, sh = self.ws.cached(("chain_tailconv", wkey), make)
             o = self.act(H >> kind, W >> kind, Cout)
             assert o.coff == 0 and o.cstride == o.Cphys
             arr[i].packed_w, arr[i].shift = buf.data_ptr(), sh.data_ptr()
@@ -627,77 +633,50 @@ class Program:
             keep += [buf, sh]
             fl_t += 2 * self.B * o.H * o.W * k * k * C_ * Cout
             nb_t += self.B * o.H * o.W * Cout * self.es + k * k * C_ * Cout * self.es
-        n = len(srcs)
-        arr_p = (C.c_void_p * 4)()
-        arr_s = (C.c_int32 * 4)(*([int(v) for v in shifts] + [0] * (4 - n)))
-        self.keep += [arr_p, arr_s, blob, aff, arr] + keep
-        for s_, sh_ in zip(srcs, shifts):
-            assert s_.coff == 0 and s_.cstride == s_.Cphys == out.Cphys and (s_.H << sh_, s_.W << sh_) == (H, W)
-        tbs, ot, tts = [s_.tbuf for s_ in srcs], out.tbuf, [o.tbuf for o in touts]
-        bp, ap = blob.data_ptr(), aff.data_ptr()
+        self.keep += [arr] + keep
 
-        def argb(P):
-            for i, t in enumerate(tbs):
-                arr_p[i] = P(t)
-            for i, t in enumerate(tts):
-                arr[i].out = P(t)
-            return (self.B, C_, H, W, n, arr_p, arr_s, 1 if relu_in else 0, bp, ap, P(ot), len(convs), arr)
+        def tail(ptrs):
+            for i, p in enumerate(ptrs):
+                arr[i].out = p
+            return (len(convs), arr)
 
-        self._add(lib.cp_hr_branch_chain_tails, argb, "hr_chain:" + name, tbs, [ot] + tts)
-        fl = 8 * 2 * self.B * H * W * 9 * C_ * C_ + fl_t
-        self.flops += fl
-        nb = self.B * H * W * C_ * self.es
-        self.conv_log.append((name, self.B * H * W, C_, 9 * C_, fl, "hr_chain", (n + 1) * nb + 8 * 9 * C_ * C_ * self.es + nb_t))
+        self._chain(lib.cp_hr_branch_chain_tails, name, srcs, shifts, relu_in, blob, aff, out, C_, H, W, touts, tail, fl_t, nb_t)
         return out, touts
 
     def _hr_chain_tail(self, name, srcs, shifts, relu_in, blob, aff, out, C_, H, W, tail):
         lib = self.lib
-        ck = ("chain_tail", name)
-        if ck not in self.ws.cache:
-            tb = torch.zeros(lib.cp_hr_chain_tail_weight_bytes(), dtype=torch.uint8, device=self.device)
+
+        def make():       # the convs' images side by side in pieces of 8 output channels; image and shift table zero-filled between them
             tsh = torch.zeros(lib.cp_hr_chain_tail_channels(), dtype=torch.float32, device=self.device)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            piece = 0
-            for wkey, w, scale, shift, relu in tail:
-                Cout = w.shape[0]
-                cph = _rup(Cout, self.E)
-                wc = w.contiguous()
-                sc = scale.to(device=self.device, dtype=torch.float32).contiguous()
-                self.ws.keep += [wc, sc]
-                _abi.check(lib.cp_pack_hr_chain_tail_weight(st, wc.data_ptr(), sc.data_ptr(), Cout, piece, cph, tb.data_ptr()),
-                           "cp_pack_hr_chain_tail_weight(%s)" % wkey)
-                tsh[piece * 8: piece * 8 + Cout] = shift
-                piece += cph // 8
-            self.ws.cache[ck] = (tb, tsh)
-        tb, tsh = self.ws.cache[ck]
+
+            def pieces(st, _, op):
+                piece = 0
+                for wkey, w, scale, shift, relu in tail:
+                    Cout = w.shape[0]
+                    cph = _rup(Cout, self.E)
+                    _abi.check(lib.cp_pack_hr_chain_tail_weight(st, self.ws._hold(w), self.ws._scale(scale), Cout, piece, cph, op),
+                               "cp_pack_hr_chain_tail_weight(%s)" % wkey)
+                    tsh[piece * 8: piece * 8 + Cout] = shift
+                    piece += cph // 8
+                return 0
+            return self.ws._packed(lib.cp_hr_chain_tail_weight_bytes(), None, pieces, "cp_pack_hr_chain_tail_weight", zero=True), tsh
+        tb, tsh = self.ws.cached(("chain_tail", name), make)
         touts = [self.act(H >> 1, W >> 1, w.shape[0]) for _, w, *_ in tail]
         tl = CpChainTail()
         tl.packed_w, tl.shift, tl.nconv = tb.data_ptr(), tsh.data_ptr(), len(tail)
         for i, ((wkey, w, scale, shift, relu), o) in enumerate(zip(tail, touts)):
             assert o.coff == 0 and o.cstride == o.Cphys
             tl.Cout[i], tl.out_cphys[i], tl.relu[i] = w.shape[0], o.Cphys, 1 if relu else 0
-        n = len(srcs)
-        arr_p = (C.c_void_p * 4)()
-        arr_s = (C.c_int32 * 4)(*([int(v) for v in shifts] + [0] * (4 - n)))
-        self.keep += [arr_p, arr_s, blob, aff, tb, tsh, tl]
-        for s_, sh in zip(srcs, shifts):
-            assert s_.coff == 0 and s_.cstride == s_.Cphys == out.Cphys and (s_.H << sh, s_.W << sh) == (H, W)
-        tbs, ot, tts = [s_.tbuf for s_ in srcs], out.tbuf, [o.tbuf for o in touts]
-        bp, ap = blob.data_ptr(), aff.data_ptr()
+        self.keep += [tb, tsh, tl]
 
-        def argb(P):
-            for i, t in enumerate(tbs):
-                arr_p[i] = P(t)
-            for i, t in enumerate(tts):
-                tl.out[i] = P(t)
-            return (self.B, C_, H, W, n, arr_p, arr_s, 1 if relu_in else 0, bp, ap, P(ot), C.byref(tl))
+        def targs(ptrs):
+            for i, p in enumerate(ptrs):
+                tl.out[i] = p
+            return (C.byref(tl),)
 
-        self._add(lib.cp_hr_branch_chain_tail, argb, "hr_chain:" + name, tbs, [ot] + tts)
-        fl = 8 * 2 * self.B * H * W * 9 * C_ * C_ + sum(2 * self.B * (H >> 1) * (W >> 1) * 9 * C_ * w.shape[0] for _, w, *_ in tail)
-        self.flops += fl
-        nb = self.B * H * W * C_ * self.es
-        nbt = sum(self.B * (H >> 1) * (W >> 1) * w.shape[0] * self.es + 9 * C_ * w.shape[0] * self.es for _, w, *_ in tail)
-        self.conv_log.append((name, self.B * H * W, C_, 9 * C_, fl, "hr_chain", (n + 1) * nb + 8 * 9 * C_ * C_ * self.es + nbt))
+        self._chain(lib.cp_hr_branch_chain_tail, name, srcs, shifts, relu_in, blob, aff, out, C_, H, W, touts, targs,
+                    sum(2 * self.B * (H >> 1) * (W >> 1) * 9 * C_ * w.shape[0] for _, w, *_ in tail),
+                    sum(self.B * (H >> 1) * (W >> 1) * w.shape[0] * self.es + 9 * C_ * w.shape[0] * self.es for _, w, *_ in tail))
         return out, touts
 
     def can_fuse_out(self, x: Act, couts=()):
@@ -718,20 +697,16 @@ class Program:
             Cout, Cin = w.shape[0], w.shape[1]
             assert Cin == x.C and w.shape[2] == k
             out = self.act(x.H >> kind, x.W >> kind, Cout)
-            ck = ("fuse_out", wkey)
-            if ck not in self.ws.cache:
-                buf = torch.empty(self.lib.cp_hr_fuse_out_weight_bytes(x.Cphys, out.Cphys, kind), dtype=torch.uint8, device=self.device)
-                wc = w.contiguous()
-                self.ws.keep.append(wc)
-                st = torch.cuda.current_stream(self.device).cuda_stream
-                _abi.check(self.lib.cp_pack_hr_fuse_out_weight(st, wc.data_ptr(), Cout, Cin, x.Cphys, out.Cphys, kind, buf.data_ptr()),
-                           "cp_pack_hr_fuse_out_weight")
-                n = self.lib.cp_hr_fuse_out_affine_floats(out.Cphys)
-                aff = torch.zeros(2, n, dtype=torch.float32, device=self.device)
+
+            def make():                               # (runs inside cached(), in this iteration)
+                buf = self.ws._packed(self.lib.cp_hr_fuse_out_weight_bytes(x.Cphys, out.Cphys, kind), w,
+                                      lambda st, wp, op: self.lib.cp_pack_hr_fuse_out_weight(st, wp, Cout, Cin, x.Cphys, out.Cphys, kind, op),
+                                      "cp_pack_hr_fuse_out_weight")
+                aff = torch.zeros(2, self.lib.cp_hr_fuse_out_affine_floats(out.Cphys), dtype=torch.float32, device=self.device)
                 aff[0, :Cout] = scale
                 aff[1, :Cout] = shift
-                self.ws.cache[ck] = (buf, aff)
-            buf, aff = self.ws.cache[ck]
+                return buf, aff
+            buf, aff = self.ws.cached(("fuse_out", wkey), make)
             keep += [buf, aff]
             arr[i].packed_w, arr[i].affine = buf.data_ptr(), aff.data_ptr()
             arr[i].kind, arr[i].Cout, arr[i].out_cphys, arr[i].relu = kind, Cout, out.Cphys, 1 if relu else 0
@@ -739,7 +714,6 @@ class Program:
             fl += 2 * x.B * out.H * out.W * k * k * Cin * Cout
             nbytes += x.B * out.H * out.W * Cout * self.es + k * k * Cin * Cout * self.es
         self.keep += keep + [arr]
-        fn = self.lib.cp_hr_fuse_out
         xt, ots = x.tbuf, [o.tbuf for o in outs]
 
         def argb(P):
@@ -747,10 +721,8 @@ class Program:
                 arr[i].out = P(t)
             return (P(xt), x.B, x.H, x.W, x.Cphys, len(convs), arr)
 
-        name = convs[0][0]
-        self._add(fn, argb, "hr_fuse_out:" + name, [xt], ots)
-        self.flops += fl
-        self.conv_log.append((name, x.B * x.H * x.W, sum(c[1].shape[0] for c in convs), x.C, fl, "hr_fuse_out", nbytes))
+        self._mfma(self.lib.cp_hr_fuse_out, argb, "hr_fuse_out", convs[0][0], [xt], ots,
+                   x.B * x.H * x.W, sum(c[1].shape[0] for c in convs), x.C, fl, nbytes)
         return outs
 
     def can_fuse_bottleneck(self, x: Act, planes, cout, has_ds):
@@ -770,27 +742,18 @@ class Program:
         af = [self.ws.affine(keys[i] + "#0", affs[i][0], affs[i][1], (64, 64, 256, 256)[i]) for i in range(len(keys))]
         if out is None:
             out = self.act(x.H, x.W, 256)
-        d = CpConvDesc()
-        d.dtype, d.out_f32, d.B, d.H, d.W = self.dtype, 0, x.B, x.H, x.W
-        d.Cin, d.in_cstride, d.in_coff = cin, x.cstride, x.coff
-        d.R, d.S, d.stride, d.pad, d.Ho, d.Wo = 3, 3, 1, 1, x.H, x.W
-        d.Cout, d.act, d.slope = 256, ACT_RELU, 0.0
-        d.o_base, d.o_sb, d.o_sy, d.o_sx, d.o_sc = out.coff, out.H * out.W * out.cstride, out.W * out.cstride, out.cstride, 1
-        self.keep += [d] + pw + af
-        fn = self.lib.cp_bottleneck_fused
-        dref = C.byref(d)
+        dref = C.byref(self._desc(x, 3, 3, 1, 1, x.H, x.W, ACT_RELU, 0.0, out, Cout=256, cin=cin))     # logical channel counts
+        self.keep += pw + af
         ptrs = ()
         for i in range(len(keys)):
             ptrs += (pw[i].data_ptr(), af[i][0].data_ptr(), af[i][1].data_ptr())
         if not has_ds:
             ptrs += (None, None, None)
         xtb, otb = x.tbuf, out.tbuf
-        self._add(fn, lambda P: (dref, P(xtb)) + ptrs + (P(otb),), "bottleneck_fused:" + keys[0], [xtb], [otb])
         npx = x.B * x.H * x.W
         macs = cin * 64 + 9 * 64 * 64 + 64 * 256 + (64 * 256 if has_ds else 0)
-        fl = 2 * npx * macs
-        self.flops += fl
-        self.conv_log.append((keys[0], npx, 256, cin, fl, "bottleneck_fused", npx * (cin + 256) * self.es + macs * self.es))
+        self._mfma(self.lib.cp_bottleneck_fused, lambda P: (dref, P(xtb)) + ptrs + (P(otb),), "bottleneck_fused", keys[0], [xtb], [otb],
+                   npx, 256, cin, 2 * npx * macs, npx * (cin + 256) * self.es + macs * self.es)
         return out
 
     def upsample2x(self, x: Act, out: Act):
@@ -802,22 +765,11 @@ class Program:
         return out
 
     def fuse_sum(self, srcs, shifts, out: Act, relu=True):
-        n = len(srcs)
-        arr_p = (C.c_void_p * 4)()
-        arr_s = (C.c_int32 * 4)(*([int(s) for s in shifts] + [0] * (4 - n)))
-        self.keep += [arr_p, arr_s]
-        fn = self.lib.cp_fuse_sum_act
-        tbs = [s.tbuf for s in srcs]
-        for s in srcs:
-            assert s.coff == 0 and s.cstride == s.Cphys == out.Cphys
+        n, arr_s, tbs, bind = self._sources(srcs, shifts, out)
         ot = out.tbuf
-
-        def argb(P):
-            for i, t in enumerate(tbs):
-                arr_p[i] = P(t)
-            return (self.dtype, n, arr_p, arr_s, P(ot), out.B, out.H, out.W, out.Cphys, 1 if relu else 0, out.cstride, out.coff)
-
-        self._add(fn, argb, "fuse_sum", tbs, [ot])
+        self._add(self.lib.cp_fuse_sum_act,
+                  lambda P: (self.dtype, n, bind(P), arr_s, P(ot), out.B, out.H, out.W, out.Cphys, 1 if relu else 0, out.cstride, out.coff),
+                  "fuse_sum", tbs, [ot])
         return out
 
     def maxpool(self, x: Act):
@@ -831,8 +783,7 @@ class Program:
         gdt = self.gdt
         fn = self.lib.cp_edgeconv_gather_max
         pt, ot = pq.tbuf, out.tbuf
-        ip = idx_t.data_ptr()
-        gp = gids_t.data_ptr() if gids_t is not None else None
+        ip, gp = idx_t.data_ptr(), _ptr(gids_t)
         N = pq.W
         self._add(fn, lambda P: (gdt, P(pt), ip, gp, P(ot), pq.B, N, K, C_, G, out.cstride, out.coff, slope),
                   "edge_gather:%d" % C_, [pt], [ot])
@@ -871,15 +822,11 @@ class Program:
         if EDGE_SCHED:
             idx_t = self.ws.cache[sk]
             self.keep.append(idx_t)
-        ip = idx_t.data_ptr()
-        gp = gids_t.data_ptr() if gids_t is not None else None
         N = x.W
-        a = (buf.data_ptr(), sc.data_ptr(), sh.data_ptr(), ip, gp)
-        self._add(fn, lambda P: (gdt, P(xt), x.cstride, x.coff) + a + (P(ot), out.cstride, out.coff, self.B, N, K, Cin, Co2 // 2, G, slope),
-                  "edge_fused:" + wkey, [xt], [ot])
-        fl = 2 * self.B * N * Cin * Co2
-        self.flops += fl
-        self.conv_log.append((wkey, self.B * N, Co2, Cin, fl, "edge_fused", self.B * N * (Cin + Co2 // 2) * self.es + Co2 * Cin * self.es))
+        a = (buf.data_ptr(), sc.data_ptr(), sh.data_ptr(), idx_t.data_ptr(), _ptr(gids_t))
+        self._mfma(fn, lambda P: (gdt, P(xt), x.cstride, x.coff) + a + (P(ot), out.cstride, out.coff, self.B, N, K, Cin, Co2 // 2, G, slope),
+                   "edge_fused", wkey, [xt], [ot], self.B * N, Co2, Cin, 2 * self.B * N * Cin * Co2,
+                   self.B * N * (Cin + Co2 // 2) * self.es + Co2 * Cin * self.es)
         return out
 
     def can_tile_edgeconv(self, N, K, Cin, Cout, HPAD):
@@ -901,14 +848,11 @@ class Program:
         self.keep += [buf, sc, sh, bq, tiled["halo"], tiled["nbr"]]
         fn = self.lib.cp_edgeconv_tiled_t
         xt, ot = x.tbuf, out.tbuf
-        gp = gids_t.data_ptr() if gids_t is not None else None
-        a = (buf.data_ptr(), bq.data_ptr(), sc.data_ptr(), sh.data_ptr(), tiled["halo"].data_ptr(), tiled["nbr"].data_ptr(), gp)
+        a = (buf.data_ptr(), bq.data_ptr(), sc.data_ptr(), sh.data_ptr(), tiled["halo"].data_ptr(), tiled["nbr"].data_ptr(), _ptr(gids_t))
         HPAD = tiled["HPAD"]
-        self._add(fn, lambda P: (gdt, P(xt), x.cstride, x.coff) + a + (P(ktab), P(ot), out.cstride, out.coff, self.B, N, K, Cin, Co, G, HPAD, slope),
-                  "edge_tiled:" + wkey, [xt], [ot, ktab])
-        fl = 2 * self.B * N * Cin * Co2
-        self.flops += fl
-        self.conv_log.append((wkey, self.B * N, Co2, Cin, fl, "edge_tiled", self.B * N * (Cin + Co) * self.es + Co2 * Cin * self.es))
+        self._mfma(fn, lambda P: (gdt, P(xt), x.cstride, x.coff) + a + (P(ktab), P(ot), out.cstride, out.coff, self.B, N, K, Cin, Co, G, HPAD, slope),
+                   "edge_tiled", wkey, [xt], [ot, ktab], self.B * N, Co2, Cin, 2 * self.B * N * Cin * Co2,
+                   self.B * N * (Cin + Co) * self.es + Co2 * Cin * self.es)
         return out
 
     def can_fuse_query_mlp(self, x: Act, dims):
@@ -940,12 +884,11 @@ class Program:
         if ids is not None:
             fn, a1, o = self.lib.cp_mlp_query_fused_n, a1 + (nout,), o + (ids[0].data_ptr(), ids[1].data_ptr(), None, None)
             writes = [out_tbuf, self.raw(ids[0]), self.raw(ids[1])]
-        self._add(fn, lambda P: (gdt, P(xt), x.cstride, x.coff, self.B, N) + a1 + (P(out_tbuf),) + o, "mlp_fused:" + keys[0], [xt], writes)
         M = self.B * N
-        fl = 2 * M * (256 * 256 + 256 * 64 + 64 * nout)
-        self.flops += fl
         obytes = 4 * nout + (16 if ids is not None else 0)          # fp32 logits (+ two int64 ids) per row
-        self.conv_log.append((keys[0], M, 256 + 64 + nout, 256, fl, "mlp_fused", M * (256 * self.es + obytes) + (256 * 256 + 64 * 256) * self.es))
+        self._mfma(fn, lambda P: (gdt, P(xt), x.cstride, x.coff, self.B, N) + a1 + (P(out_tbuf),) + o, "mlp_fused", keys[0], [xt], writes,
+                   M, 256 + 64 + nout, 256, 2 * M * (256 * 256 + 256 * 64 + 64 * nout),
+                   M * (256 * self.es + obytes) + (256 * 256 + 64 * 256) * self.es)
 
     def code_decode(self, bits_t, rows, r, x64_t, y64_t, N):
         """x / y codes of a packed logit block (rows 1..r, r+1..2r) -> int64 ids (cp_code_decode)"""
@@ -974,12 +917,10 @@ class Program:
             out = self.act(1, N, 256)
         xt, ot = x.tbuf, out.tbuf
         a1 = (pw1.data_ptr(), b1.data_ptr(), float(slope), pw2.data_ptr(), b2.data_ptr(), float(slope))
-        self._add(self.lib.cp_mlp_pair_fused_t, lambda P: (gdt, P(xt), x.cstride, x.coff, Cin, self.B, N) + a1 + (P(ot), out.cstride, out.coff),
-                  "mlp_fused:" + keys[0], [xt], [ot])
         M = self.B * N
-        fl = 2 * M * (Cin * 256 + 256 * 256)
-        self.flops += fl
-        self.conv_log.append((keys[0], M, 512, Cin, fl, "mlp_fused", M * (Cin + 256) * self.es + (Cin * 256 + 256 * 256) * self.es))
+        self._mfma(self.lib.cp_mlp_pair_fused_t, lambda P: (gdt, P(xt), x.cstride, x.coff, Cin, self.B, N) + a1 + (P(ot), out.cstride, out.coff),
+                   "mlp_fused", keys[0], [xt], [ot], M, 512, Cin, 2 * M * (Cin * 256 + 256 * 256),
+                   M * (Cin + 256) * self.es + (Cin * 256 + 256 * 256) * self.es)
         return out
 
     def can_fuse_mlp_pair_gather(self, L: Act, patches: Act, w1, w2, E_ch, k):
@@ -1009,14 +950,11 @@ class Program:
             descs.append(g)                                   # the descriptor must outlive the (possibly deferred) call
             return (gdt, C.byref(g), P(lt), L.cstride, L.coff + 256, Cg, self.B, N) + a1 + (P(ot), out.cstride, out.coff)
         self.keep.append(descs)
-        self._add(self.lib.cp_mlp_pair_fused_gather_t, args, "mlp_fused:" + keys[0],
-                  [pt, lt, self.raw(xid_t), self.raw(yid_t), self.raw(mask_t)], [ot])
         M = self.B * N
-        fl = 2 * M * (Cin * 256 + 256 * 256)
-        self.flops += fl
         # algorithmic HBM bytes: the gathered taps overlap and repeat, so at most the patch map itself is read once
         nby = (min(patches.B * patches.H * patches.W * 64, M * 256) + M * (Cg + 256) + Cin * 256 + 256 * 256) * self.es
-        self.conv_log.append((keys[0], M, 512, Cin, fl, "mlp_fused", nby))
+        self._mfma(self.lib.cp_mlp_pair_fused_gather_t, args, "mlp_fused", keys[0], [pt, lt, self.raw(xid_t), self.raw(yid_t), self.raw(mask_t)], [ot],
+                   M, 512, Cin, 2 * M * (Cin * 256 + 256 * 256), nby)
         return out
 
     def permute_rows(self, x: Act, out: Act, perm_t, gids_t):
@@ -1024,7 +962,7 @@ class Program:
         assert x.coff == 0 and out.coff == 0 and x.cstride == out.cstride and (x.cstride * self.es) % 16 == 0
         fn = self.lib.cp_permute_rows
         xt, ot = x.tbuf, out.tbuf
-        gp = gids_t.data_ptr() if gids_t is not None else None
+        gp = _ptr(gids_t)
         self.keep.append(perm_t)
         self._add(fn, lambda P: (P(xt), P(ot), perm_t.data_ptr(), gp, x.B, x.W, x.cstride * self.es), "permute_rows", [xt], [ot])
         return out
@@ -1032,9 +970,8 @@ class Program:
     def permute_cols(self, in_t, out_t, perm_t, gids_t, R, N, scatter):
         """(B, R, N) caller-owned arrays: scatter: out[b, r, perm[i]] = in[b, r, i]; else out[b, r, i] = in[b, r, perm[i]]"""
         fn = self.lib.cp_permute_cols
-        gp = gids_t.data_ptr() if gids_t is not None else None
         self.keep += [perm_t, in_t, out_t]
-        a = (in_t.data_ptr(), out_t.data_ptr(), perm_t.data_ptr(), gp, self.B, R, N, in_t.element_size(), 1 if scatter else 0)
+        a = (in_t.data_ptr(), out_t.data_ptr(), perm_t.data_ptr(), _ptr(gids_t), self.B, R, N, in_t.element_size(), 1 if scatter else 0)
         self._add(fn, lambda P: a, "permute_cols", [self.raw(in_t)], [self.raw(out_t)])
 
     def can_gather_patch(self, f: Act, N, E_ch, k):
@@ -1043,28 +980,19 @@ class Program:
                 and 8 * N <= (f.H + 1) * (f.W + 1) and f.B * f.H * f.W * f.cstride * 2 < (1 << 31))
 
     def index2feat_conv(self, f: Act, wkey, w, bias, xid_t, yid_t, mask_t, out: Act, N, k):
-        ck = ("patch_gather", wkey)
-        if ck not in self.ws.cache:
-            buf = torch.empty(self.lib.cp_index2feat_conv_weight_bytes(), dtype=torch.uint8, device=self.device)
-            wc = w.contiguous()
-            self.ws.keep.append(wc)
-            st = torch.cuda.current_stream(self.device).cuda_stream
-            _abi.check(self.lib.cp_pack_index2feat_conv_weight(st, wc.data_ptr(), buf.data_ptr()), "cp_pack_index2feat_conv_weight")
-            self.ws.cache[ck] = (buf, bias.contiguous())
-        buf, bs = self.ws.cache[ck]
+        buf, bs = self.ws.cached(("patch_gather", wkey), lambda: (
+            self.ws._packed(self.lib.cp_index2feat_conv_weight_bytes(), w, self.lib.cp_pack_index2feat_conv_weight, "cp_pack_index2feat_conv_weight"),
+            bias.contiguous()))
         self.keep += [buf, bs]
-        fn = self.lib.cp_index2feat_conv_t
         gdt = self.gdt
         ft, ot = f.tbuf, out.tbuf
         a = (buf.data_ptr(), bs.data_ptr(), xid_t.data_ptr(), yid_t.data_ptr(), mask_t.data_ptr())
-        self._add(fn, lambda P: (gdt, P(ft), f.cstride, f.coff) + a + (P(ot), f.B, N, f.H, f.W, k, out.cstride, out.coff),
-                  "patch_gather:" + wkey, [ft, self.raw(xid_t), self.raw(yid_t), self.raw(mask_t)], [ot])
-        fl = 2 * f.B * 4 * N * 64 * 4 * f.C
-        self.flops += fl
         # algorithmic HBM bytes: the gathered 2x2 patches overlap and repeat, so at most the feature map itself is read once
         # (PMC: far less -- only pixels some keypoint points at are touched), + the (B, N, 4*64) output + weights
         nby = (f.B * min(f.H * f.W * f.C, 4 * N * 4 * f.C) + f.B * N * 4 * 64 + 64 * 4 * f.C) * self.es
-        self.conv_log.append((wkey, f.B * 4 * N, 64, 4 * f.C, fl, "patch_gather", nby))
+        self._mfma(self.lib.cp_index2feat_conv_t, lambda P: (gdt, P(ft), f.cstride, f.coff) + a + (P(ot), f.B, N, f.H, f.W, k, out.cstride, out.coff),
+                   "patch_gather", wkey, [ft, self.raw(xid_t), self.raw(yid_t), self.raw(mask_t)], [ot],
+                   f.B * 4 * N, 64, 4 * f.C, 2 * f.B * 4 * N * 64 * 4 * f.C, nby)
         return out
 
     def index2feat(self, patches: Act, xid_t, yid_t, mask_t, out: Act, N, E_ch, k):

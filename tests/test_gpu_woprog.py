@@ -214,6 +214,36 @@ def test_decoder_launches_equal_posenets(lib):
     assert seqs[0] == seqs[1], [(a, b) for a, b in zip(*seqs) if a != b]
 
 
+# the conv_log families (the keys of bench.py's MFMA_KERNELS)
+MFMA_FAMILIES = {"conv_igemm", "conv3x3_halo", "conv3x3_halo4", "conv3x3_halo_s", "conv3x3_s2_small", "gemm_rows", "basicblock_fused",
+                 "bottleneck_fused", "hr_chain", "hr_fuse_out", "edge_fused", "edge_tiled", "hr_stem", "patch_gather", "mlp_fused"}
+
+
+@pytest.mark.parametrize("dtype,selection", [("bf16", "per_crop"), ("fp32", "auto")])
+def test_conv_log_in_step_with_launches(lib, dtype, selection):
+    """What Program._mfma owns, on every program slice: a launch named family:key has the NEXT conv_log row, of that family and key
+    (bench.py walks the two lists in step while it times the launches), no row is left over, and prog.flops is the sum of the
+    logged flops"""
+    from checkerpose_amd.synthetic import build_net
+    B = 2
+    net = build_net(512).to(dev()).set_compute_dtype(dtype)
+    net.set_kernel_selection(selection)
+    with torch.no_grad():
+        net(det_image(B, seed=4).to(dev()), None)
+    progs = net.program_for(B).progs
+    assert progs and all(len(p.conv_log) > 0 for p in progs)
+    for prog in progs:
+        families = MFMA_FAMILIES | {e[5] for e in prog.conv_log}
+        log = iter(prog.conv_log)
+        for _, _, name in prog.calls:
+            fam, _, key = name.partition(":")
+            if fam in families:
+                e = next(log, None)
+                assert e is not None and (e[5], e[0]) == (fam, key), (name, e)
+        assert next(log, None) is None
+        assert prog.flops == sum(e[4] for e in prog.conv_log)
+
+
 # ---- training step against torch-CPU autograd over the oracle in train mode (helpers restated from tests/test_gpu_train_step.py:
 # the EdgeConv arg-max slots and the (Leaky)ReLU branches the device took are teacher-forced into the oracle -- both are
 # discontinuous, and the ~1e-6 forward differences would otherwise route a few near-tie gradients differently)

@@ -1,11 +1,12 @@
 """Canonical text of the launch programs the emitters build, for A/B-ing a host-side refactor of netbuilder.py / engine.py: two trees
 emit the same programs exactly when this tool's output is byte-equal (`python tools/program_dump.py > a.txt` in each, then diff).
 
-Per matrix row (PoseNet / woProg / InitNet x dtype x batch x kernel selection, eval and one training step) and per batch slice:
+Per matrix row (PoseNet / woProg / InitNet x backbone x dtype x batch x kernel selection, eval and one training step) and per batch slice:
 the sched list, workspace_bytes, flops, conv_log, then every call as `<C symbol> <recorder's name> lane=<k>` with its arguments --
 pointers (told from integers by fn.argtypes) as `ws+<offset>` inside the program's workspace and `p<k>` (numbered by first
 appearance) elsewhere, by-reference structs and arrays field by field under the same rules -- and the sha256 of every output
-tensor of one run on det_image(B, seed=100) (training: deterministic mode, outputs + the parameter-gradient arena).
+tensor of one run on det_image(B, seed=100) (training: deterministic mode, outputs + the parameter-gradient arena).  Last, the
+sorted set of C symbols launched over the whole matrix: a recorder none of whose entry points is listed was not compared.
 
   --json FILE      also write {row: sha256 of the row's text}
   --time-build N   instead of the dump: wall time of N program builds at B = 256 (bf16 PoseNet, first forward after invalidate())
@@ -54,7 +55,11 @@ class Canon:
         return repr(float(v)) if ctype is C.c_float or isinstance(v, float) else str(int(v))
 
 
+SYMBOLS = set()          # every C entry point some dumped program launches
+
+
 def dump_program(prog, out):
+    SYMBOLS.update(fn.__name__ for fn, _, _ in prog.calls)
     lane_of = {item[1]: item[2] for item in prog.sched if item[0] == "op"}
     out.append("sched %r" % (prog.sched,))
     out.append("workspace_bytes %d flops %d" % (prog.workspace_bytes, prog.flops))
@@ -149,6 +154,12 @@ def matrix():
     for sel in ("auto", "per_crop"):
         rows.append(("posenet lm N=4096 bf16 B=2 %s" % sel, lambda sel=sel: eval_row(lm_net, "bf16", 2, lm=True, selection=sel)))
     rows.append(("initnet bf16 B=2", lambda: eval_row(lambda: build_net(512, full=False), "bf16", 2)))
+    # the other backbones: maxpool, the unfused basic_block and the fp32 small-Cout halo rule (resnet34), the small HRNet's branches
+    for dt in ("bf16", "fp32"):
+        rows.append(("posenet resnet34 %s B=2" % dt, lambda dt=dt: eval_row(lambda: build_net(512, backbone="resnet34"), dt, 2)))
+    rows.append(("posenet hrnet_w18_small bf16 B=2 per_crop",
+                 lambda: eval_row(lambda: build_net(512, backbone="hrnet_w18_small"), "bf16", 2, selection="per_crop")))
+    rows.append(("posenet bf16 B=96", lambda: eval_row(pose, "bf16", 96)))      # the smallest batch at which auto takes hr_stem and edge_fused
     rows.append(("posenet train fp32 B=2", lambda: train_row(pose, False)))
     rows.append(("woprog train fp32 B=2", lambda: train_row(wop, True)))
     return rows
@@ -185,6 +196,7 @@ def main():
         sys.stdout.write(text)
         sys.stdout.flush()
         digests[name] = hashlib.sha256(text.encode()).hexdigest()
+    print("==== C symbols launched\n" + "\n".join(sorted(SYMBOLS)))
     if a.json:
         with open(a.json, "w") as f:
             json.dump(digests, f, indent=1)
