@@ -10,11 +10,13 @@ their fused / unfused choice) and _out_layer (the eval / train fork of a strided
 emitters is what differs: which lanes run what, and PoseNet's progressive feedback.
 """
 import os
+from typing import NamedTuple, Optional
 
 import torch
 
 from ._abi import ACT_LEAKY, ACT_NONE, ACT_RELU
 from .engine import Act, Program, _rup
+from .trainer import BnGrad, BnLayer
 
 from .model.backbone import HRNET_CFGS     # layer1 = (blocks, planes), stages = ((modules, blocks per branch, branch channels), ...)
 IMG_FEATS_DIMS = {"resnet34": [64, 128, 256, 512], "hrnet_w18": [128, 256, 512, 1024], "hrnet_w18_small": [128, 256, 512, 1024],
@@ -27,6 +29,19 @@ FUSE_OUT_DEEP = os.environ.get("CHECKERPOSE_AMD_FUSE_OUT_DEEP", "1") != "0"   # 
 DECODER_SPLITK = os.environ.get("CHECKERPOSE_AMD_DECODER_SPLITK", "1") != "0"   # A/B: decoder convs as split-K convs at batch 1-4
 HEAD_ON_REFINE_LANE = os.environ.get("CHECKERPOSE_AMD_HEAD_LANE", "1") != "0"   # A/B: InitNet head beside up_net[0]
 FUSE_SAME_LANE = os.environ.get("CHECKERPOSE_AMD_FUSE_SAME_LANE", "1") != "0"   # A/B: a fuse chain's later convs on its source's lane (no second region)
+
+
+class ConvBn(NamedTuple):
+    """conv (k x k, no bias) + BatchNorm (+residual) (+ReLU): one member of NetEmitter.conv_bn_group"""
+    x: Act
+    conv: str
+    bn: str
+    k: int
+    stride: int
+    pad: int
+    relu: bool = True
+    residual: Optional[Act] = None
+    out: Optional[Act] = None
 
 
 class NetEmitter:
@@ -52,74 +67,48 @@ class NetEmitter:
 
     # ---- conv + folded BN (+residual) (+ReLU)
     def conv_bn(self, x, conv, bn, k, stride, pad, relu=True, residual=None, out=None):
-        w = self.W(conv + ".weight")
         if self.tp is not None:
-            return self._conv_bn_train(x, conv, bn, w, k, stride, pad, ACT_RELU if relu else ACT_NONE, residual, out)
+            return self.conv_bn_group([ConvBn(x, conv, bn, k, stride, pad, relu, residual, out)])[0]
+        w = self.W(conv + ".weight")
         s, t = self.ws.bn_fold(bn)
         return self.p.conv(x, conv, w, s, t, k, k, stride, pad, w.shape[0], ACT_RELU if relu else ACT_NONE,
                            residual=residual, out=out)
 
     # ---- train mode: raw conv -> batch statistics -> affine+act, backward pushed on the tape
-    def _bn_train(self, raw, bn, act, residual, out, slope=0.0):
+    def _bn_layer(self, raw, bn, act, residual, out):
+        """the trainer.BnLayer of BatchNorm `bn` behind the raw conv output `raw` (out None: a tensor of its own)"""
         tp = self.tp
-        Cout = raw.C
-        st = tp.bn_stats(raw, Cout, self.W(bn + ".weight"), self.W(bn + ".bias"), self.sd[bn + ".running_mean"],
-                         self.sd[bn + ".running_var"])
+        y = out if out is not None else tp.act(raw.H, raw.W, raw.C)
         self.bn_counters.append(self.sd[bn + ".num_batches_tracked"])
-        y = out if out is not None else tp.act(raw.H, raw.W, Cout)
-        tp.bn_apply(raw, st, residual, y, act, slope)
         if act != ACT_NONE:
             tp.kinks[bn] = y
-        return y, st
+        return BnLayer(raw, self.W(bn + ".weight"), self.W(bn + ".bias"), self.sd[bn + ".running_mean"], self.sd[bn + ".running_var"],
+                       residual, y, act)
 
-    def _conv_bn_train(self, x, conv, bn, w, k, stride, pad, act, residual, out):
-        tp = self.tp
-        Cout = w.shape[0]
-        raw = tp.conv(x, conv, w, tp.const_vec(Cout, True), tp.const_vec(Cout, False), k, k, stride, pad, Cout)
-        y, st = self._bn_train(raw, bn, act, residual, out)
-
-        def bwd():
-            if y.tbuf not in tp.grads:
-                return
-            gy = tp.grad_of(y)
-            gres = tp.grad_of(residual) if residual is not None else None
-            tp.bn_bwd(gy, y, raw, st, act, 0.0, gres, tp.pg_ptr(bn + ".weight"), tp.pg_ptr(bn + ".bias"))
-            tp.conv_backward(conv, w, x, gy, k, k, stride, pad)
-        tp.tape.append(bwd)
-        return y
+    def _bn_train(self, raw, bn, act, residual, out):
+        layer = self._bn_layer(raw, bn, act, residual, out)
+        return layer.out, self.tp.bn_forward([layer])[0]
 
     def conv_bn_group(self, specs):
-        """Training program: conv + train-mode BatchNorm (+residual) (+ReLU) of INDEPENDENT layers -- the convs one launch each, their
-        BatchNorm passes grouped (trainer.bn_train_group / bn_bwd_group: one launch per pass for the whole group).
-        specs: [(x, conv key, bn key, k, stride, pad, relu, residual)] -> [y]"""
+        """Training program: conv + train-mode BatchNorm (+residual) (+ReLU) of INDEPENDENT layers [ConvBn] -> [y] -- the convs one
+        launch each, their BatchNorm passes grouped (trainer.bn_forward / bn_backward: one launch per pass for the whole group)"""
         tp = self.tp
-        members, recs = [], []
-        ws = [self.W(conv + ".weight") for _, conv, *_ in specs]
-        raws = [tp.conv(x, conv, w, tp.const_vec(w.shape[0], True), tp.const_vec(w.shape[0], False), k, k, stride, pad, w.shape[0])
-                for (x, conv, _, k, stride, pad, _, _), w in zip(specs, ws)]
-        for (x, conv, bn, k, stride, pad, relu, residual), w, raw in zip(specs, ws, raws):
-            recs.append((x, conv, bn, w, k, stride, pad, ACT_RELU if relu else ACT_NONE, residual, raw))
-        ys = []
-        for x, conv, bn, w, k, stride, pad, act, residual, raw in recs:
-            y = tp.act(raw.H, raw.W, raw.C)
-            members.append((raw, raw.C, self.W(bn + ".weight"), self.W(bn + ".bias"), self.sd[bn + ".running_mean"],
-                            self.sd[bn + ".running_var"], residual, y, act, 0.0))
-            self.bn_counters.append(self.sd[bn + ".num_batches_tracked"])
-            if act != ACT_NONE:
-                tp.kinks[bn] = y
-            ys.append(y)
-        sts = tp.bn_train_group(members)
+        ws = [self.W(s.conv + ".weight") for s in specs]
+        raws = [tp.conv(s.x, s.conv, w, tp.const_vec(w.shape[0], True), tp.const_vec(w.shape[0], False), s.k, s.k, s.stride, s.pad, w.shape[0])
+                for s, w in zip(specs, ws)]
+        layers = [self._bn_layer(raw, s.bn, ACT_RELU if s.relu else ACT_NONE, s.residual, s.out) for s, raw in zip(specs, raws)]
+        sts = tp.bn_forward(layers)
 
         def bwd():
-            live = [(r, y, st) for r, y, st in zip(recs, ys, sts) if y.tbuf in tp.grads]
+            live = [(s, w, m, st) for s, w, m, st in zip(specs, ws, layers, sts) if m.out.tbuf in tp.grads]
             if not live:
                 return
-            gys = [tp.grad_of(y) for _, y, _ in live]
-            tp.bn_bwd_group([(gy, y, r[9], st, r[7], 0.0, tp.grad_of(r[8]) if r[8] is not None else None,
-                              tp.pg_ptr(r[2] + ".weight"), tp.pg_ptr(r[2] + ".bias")) for gy, (r, y, st) in zip(gys, live)])
-            tp.conv_backward_group([(r[1], r[3], r[0], gy, r[4], r[4], r[5], r[6]) for gy, (r, y, st) in zip(gys, live)])
+            gys = [tp.grad_of(m.out) for _, _, m, _ in live]
+            tp.bn_backward([BnGrad(gy, m.out, m.x, st, m.act, 0.0, tp.grad_of(m.residual) if m.residual is not None else None,
+                                   tp.pg_ptr(s.bn + ".weight"), tp.pg_ptr(s.bn + ".bias")) for gy, (s, _, m, st) in zip(gys, live)])
+            tp.conv_backward_group([(s.conv, w, s.x, gy, s.k, s.k, s.stride, s.pad) for gy, (s, w, _, _) in zip(gys, live)])
         tp.tape.append(bwd)
-        return ys
+        return [m.out for m in layers]
 
     def _hr_module_train(self, pfx, xs, nblocks=4):
         """hr_module for the training program, emitted DEPTH-major: block k / conv c of every branch, then ONE grouped launch per
@@ -129,8 +118,8 @@ class NetEmitter:
         for k in range(nblocks):
             bp = ["%s.branches.%d.%d" % (pfx, j, k) for j in range(nb)]
             assert not any((q + ".downsample.0.weight") in self.sd for q in bp)
-            ys = self.conv_bn_group([(xs[j], bp[j] + ".conv1", bp[j] + ".bn1", 3, 1, 1, True, None) for j in range(nb)])
-            xs = self.conv_bn_group([(ys[j], bp[j] + ".conv2", bp[j] + ".bn2", 3, 1, 1, True, xs[j]) for j in range(nb)])
+            ys = self.conv_bn_group([ConvBn(xs[j], bp[j] + ".conv1", bp[j] + ".bn1", 3, 1, 1) for j in range(nb)])
+            xs = self.conv_bn_group([ConvBn(ys[j], bp[j] + ".conv2", bp[j] + ".bn2", 3, 1, 1, residual=xs[j]) for j in range(nb)])
         terms = [[None] * nb for _ in range(nb)]
         for i in range(nb):
             terms[i][i] = xs[i]
@@ -143,11 +132,11 @@ class NetEmitter:
                 q = "%s.fuse_layers.%d.%d" % (pfx, i, j)
                 if j > i:
                     if level == 0:
-                        specs.append((xs[j], q + ".0", q + ".1", 1, 1, 0, False, None))
+                        specs.append(ConvBn(xs[j], q + ".0", q + ".1", 1, 1, 0, relu=False))
                         who.append((i, j))
                 elif level < i - j:
                     src = xs[j] if level == 0 else cur[(i, j)]
-                    specs.append((src, "%s.%d.0" % (q, level), "%s.%d.1" % (q, level), 3, 2, 1, level != i - j - 1, None))
+                    specs.append(ConvBn(src, "%s.%d.0" % (q, level), "%s.%d.1" % (q, level), 3, 2, 1, relu=level != i - j - 1))
                     who.append((i, j))
             if not specs:
                 break

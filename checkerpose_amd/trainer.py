@@ -13,6 +13,7 @@ torch supplies memory and the autograd hook (model/_runtime.py: _TrainFn) only.
 import ctypes as C
 import os
 import weakref
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -20,10 +21,114 @@ from . import _abi
 from ._abi import (CpWgradReduceItem, CpWgradItem, CpFuseBwdItem, CP_WGRAD_ITEM_3X3_S2_SMALL, CP_WGRAD_ITEM_3X3, CP_WGRAD_ITEM_3X3_SMALL, CP_WGRAD_ITEM_GENERIC_BF16,
                    CP_WGRAD_ITEM_GENERIC_F32, ACT_LEAKY, ACT_NONE, ACT_RELU, CP_BF16, CP_F32, CpPackItem, CpWgradDesc, CpBnItem, BN_GROUP_MAX,
                    CP_BN_ITEM_STATS, CP_BN_ITEM_APPLY, CP_BN_ITEM_BWD_SUMS, CP_BN_ITEM_BWD_APPLY)
-from .engine import Act, Program, WeightStore, _rup
+from .engine import Act, Program, WeightStore, _ptr, _rup
 
 
 ALL_TAPS_KINDS = (CP_WGRAD_ITEM_3X3, CP_WGRAD_ITEM_3X3_SMALL, CP_WGRAD_ITEM_3X3_S2_SMALL)      # one block = all nine taps
+MARKERS = ("__fork__", "__sync__", "__join__", "__mark__", "__wait__")                          # ops that are no launches
+
+
+# ---- train-mode BatchNorm: the records of a layer and the argument tuples of its four passes.  A pass over ONE layer is a launch of its
+# own (cp_bn_*), a pass over several independent layers is a grouped launch (cp_bn_group) whose items cp_bn_item_* fill from the SAME
+# tuple: the C signatures differ only in the leading stream and the trailing CpBnItem*
+class BnState(NamedTuple):
+    """what a train-mode BatchNorm layer's forward keeps: the batch statistics the apply pass writes (the backward reads them), the
+    live parameters and running statistics, the layer's fp64 accumulator slot"""
+    mean: torch.Tensor
+    rstd: torch.Tensor
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    rmean: torch.Tensor
+    rvar: torch.Tensor
+    acc: int
+    momentum: float = 0.1
+    eps: float = 1e-5
+
+
+class BnLayer(NamedTuple):
+    """forward: out = act(BatchNorm(x) + residual) over the batch statistics of the raw conv output x"""
+    x: Act
+    gamma: torch.Tensor
+    beta: torch.Tensor
+    rmean: torch.Tensor
+    rvar: torch.Tensor
+    residual: Optional[Act]
+    out: Act
+    act: int
+    slope: float = 0.0
+    st: Optional[BnState] = None       # filled in by TrainProgram.bn_forward
+
+
+class BnGrad(NamedTuple):
+    """backward, in place on gy: gy <- d loss / d raw ; gres += dz ; dgamma / dbeta written.  raw None (and bn None) = bias-only layer;
+    y is read only behind an activation"""
+    gy: Act
+    y: Optional[Act]
+    raw: Optional[Act]
+    bn: Optional[BnState]
+    act: int
+    slope: float
+    gres: Optional[Act]
+    dgamma: Optional[int]
+    dbeta: Optional[int]
+    acc: int = 0                       # filled in by TrainProgram.bn_backward
+
+
+def _opt(P, a):
+    """the (pointer, channel stride, channel offset) triple of an optional operand"""
+    return (P(a.tbuf), a.cstride, a.coff) if a is not None else (None, 0, 0)
+
+
+def _tbufs(*acts):
+    return [a.tbuf for a in acts if a is not None]
+
+
+def _bn_stats_args(tp, P, m):
+    x = m.x
+    return (tp.dtype, P(x.tbuf), x.B * x.H * x.W, x.C, x.cstride, x.coff, tp._acc_ptr(m.st.acc))
+
+
+def _bn_apply_args(tp, P, m):
+    x, st, out = m.x, m.st, m.out
+    return ((tp.dtype, P(x.tbuf), x.cstride, x.coff, tp._acc_ptr(st.acc), st.gamma.data_ptr(), st.beta.data_ptr(), st.rmean.data_ptr(),
+             st.rvar.data_ptr(), st.momentum, st.eps) + _opt(P, m.residual) +
+            (P(out.tbuf), out.cstride, out.coff, x.B * x.H * x.W, x.C, m.act, m.slope, st.mean.data_ptr(), st.rstd.data_ptr()))
+
+
+def _bn_bwd_head(tp, P, m):
+    gy = m.gy
+    return (tp.dtype, P(gy.tbuf), gy.cstride, gy.coff) + _opt(P, m.y) + _opt(P, m.raw) + (_ptr(m.bn and m.bn.mean), _ptr(m.bn and m.bn.rstd))
+
+
+def _bn_bwd_sums_args(tp, P, m):
+    gy = m.gy
+    return _bn_bwd_head(tp, P, m) + (gy.B * gy.H * gy.W, gy.C, m.act, m.slope, tp._acc_ptr(m.acc))
+
+
+def _bn_bwd_apply_args(tp, P, m):
+    gy = m.gy
+    return (_bn_bwd_head(tp, P, m) + (_ptr(m.bn and m.bn.gamma), tp._acc_ptr(m.acc), gy.B * gy.H * gy.W, gy.C, m.act, m.slope) +
+            _opt(P, gy) + _opt(P, m.gres) + (1, m.dgamma, m.dbeta))
+
+
+class BnPass(NamedTuple):
+    name: str          # recorder name of the single launch; the grouped one is <name>_group:<members>
+    single: str        # C entry point of the pass over one layer
+    fill: str          # C entry point that fills a CpBnItem from the same arguments
+    kind: int          # CP_BN_ITEM_*
+    args: object       # (program, P, record) -> the argument tuple behind the stream
+    reads: object      # record -> TBufs read
+    writes: object     # record -> TBufs written
+
+
+BN_STATS = BnPass("bn_stats", "cp_bn_stats_accumulate", "cp_bn_item_stats", CP_BN_ITEM_STATS, _bn_stats_args,
+                  lambda m: _tbufs(m.x), lambda m: [])
+BN_APPLY = BnPass("bn_apply", "cp_bn_apply", "cp_bn_item_apply", CP_BN_ITEM_APPLY, _bn_apply_args,
+                  lambda m: _tbufs(m.x, m.residual), lambda m: _tbufs(m.out))
+BN_BWD_SUMS = BnPass("bn_bwd_acc", "cp_bn_bwd_accumulate", "cp_bn_item_bwd_sums", CP_BN_ITEM_BWD_SUMS, _bn_bwd_sums_args,
+                     lambda m: _tbufs(m.gy, m.y, m.raw), lambda m: [])
+BN_BWD_APPLY = BnPass("bn_bwd", "cp_bn_bwd_apply", "cp_bn_item_bwd_apply", CP_BN_ITEM_BWD_APPLY, _bn_bwd_apply_args,
+                      lambda m: _tbufs(m.gy, m.y, m.raw, m.gres), lambda m: _tbufs(m.gy, m.gres))
 
 
 class TrainWeightStore(WeightStore):
@@ -36,49 +141,33 @@ class TrainWeightStore(WeightStore):
         self.passthrough = set()
         self.repacks_every_step = True
 
-    def _item(self, rc, item, what):
-        _abi.check(rc, what)
-        self.prog.add_item("packs", item)
+    def _image(self, ck, nbytes, keep, fill, what):
+        """a packed weight image of `nbytes`, made once per cache key `ck`: one "packs" item of the program, filled by
+        fill(image pointer, byref(item)) -> status; `keep`: the tensors the item reads"""
+        def make():
+            out = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self.prog.keep += keep + [out]
+            self.prog.prep_item("packs", lambda ref: fill(out.data_ptr(), ref), what)
+            return out
+        return self.cached(ck, make)
 
     def pack(self, name, w, Cout, Cin, R, S, cin_phys, cout_rows, transposed=0, phase=0, row_map=None):
-        ck = (name, cin_phys, cout_rows, transposed, phase)
-        if ck in self.cache:
-            return self.cache[ck]
-        out = torch.empty(self.lib.cp_packed_weight_bytes(self.dtype, cout_rows, cin_phys, R, S), dtype=torch.uint8, device=self.device)
-        rm = None
-        if row_map is not None:
-            rm = torch.tensor(row_map, dtype=torch.int32, device=self.device)
-        self.prog.keep += [w, rm, out]
-        it = CpPackItem()
-        self._item(self.lib.cp_pack_item_conv(self.dtype, w.data_ptr(), Cout, Cin, R, S, cin_phys, transposed, phase,
-                                              rm.data_ptr() if rm is not None else None, cout_rows, out.data_ptr(), C.byref(it)),
-                   it, "pack:" + name)
-        self.cache[ck] = out
-        return out
+        def fill(op, ref):
+            rm = None
+            if row_map is not None:
+                rm = torch.tensor(row_map, dtype=torch.int32, device=self.device)
+                self.prog.keep.append(rm)
+            return self.lib.cp_pack_item_conv(self.dtype, w.data_ptr(), Cout, Cin, R, S, cin_phys, transposed, phase, _ptr(rm), cout_rows, op, ref)
+        return self._image((name, cin_phys, cout_rows, transposed, phase), self.lib.cp_packed_weight_bytes(self.dtype, cout_rows, cin_phys, R, S),
+                           [w], fill, "pack:" + name)
 
     def pack_halo(self, name, w, Cout, Cin, cin_phys):
-        ck = ("halo", name, cin_phys)
-        if ck in self.cache:
-            return self.cache[ck]
-        out = torch.empty(self.lib.cp_packed_halo_weight_bytes(self.dtype, Cout, cin_phys), dtype=torch.uint8, device=self.device)
-        self.prog.keep += [w, out]
-        it = CpPackItem()
-        self._item(self.lib.cp_pack_item_halo(self.dtype, w.data_ptr(), Cout, Cin, cin_phys, out.data_ptr(), C.byref(it)), it,
-                   "pack_halo:" + name)
-        self.cache[ck] = out
-        return out
+        return self._image(("halo", name, cin_phys), self.lib.cp_packed_halo_weight_bytes(self.dtype, Cout, cin_phys), [w],
+                           lambda op, ref: self.lib.cp_pack_item_halo(self.dtype, w.data_ptr(), Cout, Cin, cin_phys, op, ref), "pack_halo:" + name)
 
     def pack_gemm(self, name, w, Cout, Cin, cin_phys):
-        ck = ("gemm", name, cin_phys)
-        if ck in self.cache:
-            return self.cache[ck]
-        out = torch.empty(self.lib.cp_packed_gemm_weight_bytes(self.dtype, Cout, cin_phys), dtype=torch.uint8, device=self.device)
-        self.prog.keep += [w, out]
-        it = CpPackItem()
-        self._item(self.lib.cp_pack_item_gemm(self.dtype, w.data_ptr(), Cout, Cin, cin_phys, out.data_ptr(), C.byref(it)), it,
-                   "pack_gemm:" + name)
-        self.cache[ck] = out
-        return out
+        return self._image(("gemm", name, cin_phys), self.lib.cp_packed_gemm_weight_bytes(self.dtype, Cout, cin_phys), [w],
+                           lambda op, ref: self.lib.cp_pack_item_gemm(self.dtype, w.data_ptr(), Cout, Cin, cin_phys, op, ref), "pack_gemm:" + name)
 
     def affine(self, name, scale, shift, rows):
         if id(scale) in self.passthrough and id(shift) in self.passthrough:
@@ -105,6 +194,24 @@ def _shared_wgrad_arena(device):
     return arena, stream
 
 
+class PendingWgrad:
+    """a layer's weight gradient waiting for its grouped launch (flush_wgrad_compute fills kind .. wsn in three phases)"""
+    __slots__ = ("lib", "d", "dt", "xt", "dw", "flops", "k3s1", "pix", "cc", "taps", "kind", "work", "target", "need", "blocks", "wsp", "wsn")
+
+    def __init__(self, lib, d, dt, xt, dw, flops):
+        self.lib, self.d, self.dt, self.xt, self.dw, self.flops = lib, d, dt, xt, dw, flops
+        self.k3s1 = d.R == 3 and d.stride == 1
+        self.pix, self.cc, self.taps = d.B * d.Ho * d.Wo, ((d.Cout + 63) // 64) * ((d.Cin + 63) // 64), d.R * d.S
+
+    def item(self, dy, x, ws, ws_bytes, target):
+        """this layer's share of a grouped launch over the operands dy / x, its partial tiles in ws[:ws_bytes], cut into about `target`
+        workgroups -> (CpWgradItem, the CpWgradReduceItem it owes: ws null if it adds with atomics instead)"""
+        ci, ri = CpWgradItem(), CpWgradReduceItem()
+        _abi.check(self.lib.cp_conv2d_wgrad_item(C.byref(self.d), dy, x, self.dw, ws, ws_bytes, target, C.byref(ci), C.byref(ri)),
+                   "cp_conv2d_wgrad_item")
+        return ci, ri
+
+
 class TrainProgram(Program):
     training = True
 
@@ -123,7 +230,7 @@ class TrainProgram(Program):
         # each build their own program, but the partials never outlive the backward that wrote them and backwards on one stream are
         # ordered)
         self.wg_ws, self.wg_stream = _shared_wgrad_arena(device)
-        self._wg_off, self._wg_items, self._wg_keys, self.wg_tabs = 0, [], set(), []
+        self._wg_off, self._wg_items, self._wg_keys = 0, [], set()
         # grouped weight gradients: the partial-sum launches of up to wg_group_n layers wait for each other and go out as ONE launch
         # per kernel kind (cp_wgrad_group), every layer cut into its share of wg_group_blocks workgroups instead of a GPU's worth
         self.wg_group_n = int(os.environ.get("CHECKERPOSE_AMD_WGRAD_GROUP_N", "64"))
@@ -143,7 +250,7 @@ class TrainProgram(Program):
         # weight preparation (packing, data-gradient / EdgeConv views, bias refreshes) reads only parameters: all items of a
         # half are processed by TWO launches at its start (views, then the packs that may consume them) -- cp_pack_batch
         self.items = {("views", 0): [], ("packs", 0): [], ("views", 1): [], ("packs", 1): []}
-        self.item_tabs = {}
+        self.prep_tabs = {}        # (kind, half) -> that launch's table (finalize)
         self.half = 0
         for kind in ("views", "packs"):
             self._add(lib.cp_pack_batch, (lambda k: lambda P: self._batch_args(k, 0))(kind), "prep_%s_fwd" % kind, [], [])
@@ -155,14 +262,21 @@ class TrainProgram(Program):
     # ---- lanes: the FORWARD half keeps the eval program's fork/join markers (the liveness planner keeps a region's tensors alive
     # over the whole region); the backward half is emitted after the last join.  Both halves replay on one ordered stream.
     # Scratch that is shared between launches is per lane (bn_ws).
-    def add_item(self, kind, item):
-        self.items[(kind, self.half)].append(item)
+    def prep_item(self, kind, fill, what):
+        """one item of the current half's `kind` ("views" / "packs") launch, filled by fill(byref(item)) -> status"""
+        it = CpPackItem()
+        _abi.check(fill(C.byref(it)), what)
+        self.items[(kind, self.half)].append(it)
 
     def _batch_args(self, kind, half):
-        tab = self.item_tabs.get((kind, half))
-        if tab is None:
-            return (self.dtype, None, None, 0, 0)
-        return (self.dtype, tab[0].data_ptr(), tab[1].data_ptr(), tab[2], tab[3])
+        return (self.dtype,) + self.prep_tabs.get((kind, half), (None, None, 0, 0))
+
+    def _table(self, items, blocks):
+        """the device tables of a grouped launch over `items` (workgroups per item: `blocks`), kept alive with the program ->
+        (item table pointer, prefix table pointer, number of items, total workgroups)"""
+        raw, prefix, total = _abi.device_table(items, blocks, self.device)
+        self.keep += [raw, prefix]
+        return (raw.data_ptr(), prefix.data_ptr(), len(items), total)
 
     # ---- small helpers
     @property
@@ -196,9 +310,7 @@ class TrainProgram(Program):
 
     def memcpy(self, dst_ptr, src_ptr, nbytes, name="memcpy", prep=False):
         if prep:
-            it = CpPackItem()
-            _abi.check(self.lib.cp_pack_item_copy_f32(src_ptr, dst_ptr, nbytes // 4, C.byref(it)), name)
-            self.add_item("views", it)
+            self.prep_item("views", lambda ref: self.lib.cp_pack_item_copy_f32(src_ptr, dst_ptr, nbytes // 4, ref), name)
         else:
             self._add(self.lib.cp_memcpy_d2d, lambda P: (dst_ptr, src_ptr, nbytes), name, [], [])
 
@@ -239,30 +351,37 @@ class TrainProgram(Program):
     def _acc_ptr(self, off):
         return self.acc_arena.data_ptr() + 8 * off
 
-    def bn_stats(self, x: Act, C_, gamma, beta, rmean, rvar, momentum=0.1, eps=1e-5):
-        bn = dict(mean=self.vec(C_), rstd=self.vec(C_), gamma=gamma, beta=beta, rmean=rmean, rvar=rvar, C=C_, acc=self._acc_slot(C_),
-                  momentum=momentum, eps=eps)
-        self.keep += [gamma, beta, rmean, rvar]
-        xt = x.tbuf
-        M = x.B * x.H * x.W
-        off = bn["acc"]
-        self._add(self.lib.cp_bn_stats_accumulate, lambda P: (self.dtype, P(xt), M, C_, x.cstride, x.coff, self._acc_ptr(off)),
-                  "bn_stats", [xt], [])
-        return bn
+    def _bn_pass(self, p: BnPass, members):
+        """one BatchNorm pass over INDEPENDENT layers (the branches of an HRNet module at equal depth, the fuse convs of a module): one
+        layer is a launch of its own; several go out as ONE launch per BN_GROUP_MAX of them (cp_bn_group: at B = 32 a single pass is a
+        5-13 us launch over 0.3-5 MB, latency not bandwidth), their items built when the workspace is planned (pointers are final then)"""
+        reads, writes = [t for m in members for t in p.reads(m)], [t for m in members for t in p.writes(m)]
+        if len(members) == 1:
+            m = members[0]
+            self._add(getattr(self.lib, p.single), lambda P: p.args(self, P, m), p.name, reads, writes)
+            return
+        fill = getattr(self.lib, p.fill)
+        for lo in range(0, len(members), BN_GROUP_MAX):
+            chunk = members[lo:lo + BN_GROUP_MAX]
 
-    def bn_apply(self, x: Act, bn, residual, out: Act, act, slope=0.0):
-        xt, ot = x.tbuf, out.tbuf
-        rt = residual.tbuf if residual is not None else None
-        M = x.B * x.H * x.W
-        rcs, rco = (residual.cstride, residual.coff) if residual is not None else (0, 0)
-        off = bn["acc"]
-        a1 = (bn["gamma"].data_ptr(), bn["beta"].data_ptr(), bn["rmean"].data_ptr(), bn["rvar"].data_ptr(), bn["momentum"], bn["eps"])
-        mp, rp = bn["mean"].data_ptr(), bn["rstd"].data_ptr()
-        self._add(self.lib.cp_bn_apply,
-                  lambda P: (self.dtype, P(xt), x.cstride, x.coff, self._acc_ptr(off)) + a1 +
-                            (P(rt) if rt is not None else None, rcs, rco, P(ot), out.cstride, out.coff, M, x.C, act, slope, mp, rp),
-                  "bn_apply", [xt, rt], [ot])
-        return out
+            def argb(P, chunk=chunk):
+                items = [CpBnItem() for _ in chunk]
+                for m, it in zip(chunk, items):
+                    _abi.check(fill(*p.args(self, P, m), C.byref(it)), p.fill)
+                return (self.dtype, p.kind) + self._table(items, [it.blocks for it in items]) + (max(int(it.lds_bytes) for it in items),)
+            self._add(self.lib.cp_bn_group, argb, "%s_group:%d" % (p.name, len(chunk)), reads, writes)
+
+    def bn_forward(self, layers):
+        """[BnLayer] of independent layers -> [BnState]: the statistics of all of them, then apply (+residual, +activation)"""
+        members = []
+        for m in layers:
+            C_ = m.x.C
+            st = BnState(self.vec(C_), self.vec(C_), m.gamma, m.beta, m.rmean, m.rvar, self._acc_slot(C_))
+            self.keep += [m.gamma, m.beta, m.rmean, m.rvar]
+            members.append(m._replace(st=st))
+        self._bn_pass(BN_STATS, members)
+        self._bn_pass(BN_APPLY, members)
+        return [m.st for m in members]
 
     def affine_act(self, x: Act, scale, shift, residual, out: Act, act, slope=0.0):
         xt, ot = x.tbuf, out.tbuf
@@ -275,134 +394,15 @@ class TrainProgram(Program):
                              out.cstride, out.coff, M, x.C, act, slope), "affine_act", [xt, rt], [ot])
         return out
 
-    def bn_bwd(self, gy: Act, y: Act, raw: Act, bn, act, slope, gres: Act, dgamma_ptr, dbeta_ptr):
-        """in place on gy: gy <- d loss / d raw ; gres += dz ; dgamma / dbeta written.  raw None = bias-only layer."""
-        gt = gy.tbuf
-        yt = y.tbuf if (y is not None and act != ACT_NONE) else None
-        rt = raw.tbuf if raw is not None else None
-        grt = gres.tbuf if gres is not None else None
-        M = gy.B * gy.H * gy.W
-        C_ = gy.C
-        mean_p = bn["mean"].data_ptr() if bn else None
-        rstd_p = bn["rstd"].data_ptr() if bn else None
-        gam_p = bn["gamma"].data_ptr() if bn else None
-        ycs, yco = (y.cstride, y.coff) if yt is not None else (0, 0)
-        rcs, rco = (raw.cstride, raw.coff) if raw is not None else (0, 0)
-        gcs, gco = (gres.cstride, gres.coff) if gres is not None else (0, 0)
-        off = self._acc_slot(C_)
-        self._add(self.lib.cp_bn_bwd_accumulate,
-                  lambda P: (self.dtype, P(gt), gy.cstride, gy.coff, P(yt) if yt is not None else None, ycs, yco,
-                             P(rt) if rt is not None else None, rcs, rco, mean_p, rstd_p, M, C_, act, slope, self._acc_ptr(off)),
-                  "bn_bwd_acc", [gt, yt, rt], [])
-        self._add(self.lib.cp_bn_bwd_apply,
-                  lambda P: (self.dtype, P(gt), gy.cstride, gy.coff, P(yt) if yt is not None else None, ycs, yco,
-                             P(rt) if rt is not None else None, rcs, rco, mean_p, rstd_p, gam_p, self._acc_ptr(off), M, C_, act, slope,
-                             P(gt), gy.cstride, gy.coff, P(grt) if grt is not None else None, gcs, gco, 1, dgamma_ptr, dbeta_ptr),
-                  "bn_bwd", [gt, yt, rt, grt], [gt, grt])
+    def bn_backward(self, grads):
+        """[BnGrad] of independent layers: the column sums of all of them, then apply"""
+        members = [m._replace(y=m.y if m.act != ACT_NONE else None, acc=self._acc_slot(m.gy.C)) for m in grads]
+        self._bn_pass(BN_BWD_SUMS, members)
+        self._bn_pass(BN_BWD_APPLY, members)
 
-    # ---- grouped BatchNorm passes: the same pass of INDEPENDENT layers (the branches of an HRNet module at equal depth, the fuse
-    # convs of a module) in ONE launch (cp_bn_group): at B = 32 a single pass is a 5-13 us launch over 0.3-5 MB, latency not bandwidth
-    def _bn_group(self, kind, builders, name, reads, writes):
-        """builders: callables P -> CpBnItem, run when the workspace is planned (pointers are final then)"""
-        def argb(P):
-            items = [b(P) for b in builders]
-            raw, prefix, total = _abi.device_table(items, [it.blocks for it in items], self.device)
-            self.keep += [raw, prefix]
-            return (self.dtype, kind, raw.data_ptr(), prefix.data_ptr(), len(items), total, max(int(it.lds_bytes) for it in items))
-        self._add(self.lib.cp_bn_group, argb, name, reads, writes)
-
-    def bn_train_group(self, members):
-        """members: [(raw Act, C, gamma, beta, rmean, rvar, residual Act | None, out Act, act, slope)] of independent layers ->
-        [bn dict]; statistics of all of them in one launch, apply (+residual, +activation) in a second one"""
-        if len(members) == 1:
-            out = []
-            for raw, C_, g, b, rm, rv, res, y, act, slope in members:
-                bn = self.bn_stats(raw, C_, g, b, rm, rv)
-                self.bn_apply(raw, bn, res, y, act, slope)
-                out.append(bn)
-            return out
-        bns, sb, ab, reads_s, reads_a, writes_a = [], [], [], [], [], []
-        lib, dt = self.lib, self.dtype
-        for raw, C_, g, b, rm, rv, res, y, act, slope in members:
-            bn = dict(mean=self.vec(C_), rstd=self.vec(C_), gamma=g, beta=b, rmean=rm, rvar=rv, C=C_, acc=self._acc_slot(C_),
-                      momentum=0.1, eps=1e-5)
-            self.keep += [g, b, rm, rv]
-            bns.append(bn)
-            M = raw.B * raw.H * raw.W
-
-            def stats(P, raw=raw, C_=C_, M=M, off=bn["acc"]):
-                it = CpBnItem()
-                _abi.check(lib.cp_bn_item_stats(dt, P(raw.tbuf), M, C_, raw.cstride, raw.coff, self._acc_ptr(off), C.byref(it)), "cp_bn_item_stats")
-                return it
-
-            def apply_(P, raw=raw, M=M, bn=bn, res=res, y=y, act=act, slope=slope):
-                it = CpBnItem()
-                rp, rcs, rco = (P(res.tbuf), res.cstride, res.coff) if res is not None else (None, 0, 0)
-                _abi.check(lib.cp_bn_item_apply(dt, P(raw.tbuf), raw.cstride, raw.coff, self._acc_ptr(bn["acc"]), bn["gamma"].data_ptr(),
-                                                bn["beta"].data_ptr(), bn["rmean"].data_ptr(), bn["rvar"].data_ptr(), bn["momentum"],
-                                                bn["eps"], rp, rcs, rco, P(y.tbuf), y.cstride, y.coff, M, raw.C, act, slope,
-                                                bn["mean"].data_ptr(), bn["rstd"].data_ptr(), C.byref(it)), "cp_bn_item_apply")
-                return it
-            sb.append(stats)
-            ab.append(apply_)
-            reads_s.append(raw.tbuf)
-            reads_a += [raw.tbuf] + ([res.tbuf] if res is not None else [])
-            writes_a.append(y.tbuf)
-        for lo in range(0, len(members), BN_GROUP_MAX):
-            hi = lo + BN_GROUP_MAX
-            self._bn_group(CP_BN_ITEM_STATS, sb[lo:hi], "bn_stats_group:%d" % len(sb[lo:hi]), reads_s, [])
-        for lo in range(0, len(members), BN_GROUP_MAX):
-            hi = lo + BN_GROUP_MAX
-            self._bn_group(CP_BN_ITEM_APPLY, ab[lo:hi], "bn_apply_group:%d" % len(ab[lo:hi]), reads_a, writes_a)
-        return bns
-
-    def bn_bwd_group(self, members):
-        """members: [(gy, y, raw, bn, act, slope, gres, dgamma_ptr, dbeta_ptr)] as bn_bwd's arguments, independent layers"""
-        if len(members) == 1:
-            for m in members:
-                self.bn_bwd(*m)
-            return
-        lib, dt = self.lib, self.dtype
-        sb, ab, reads_s, reads_a, writes_a = [], [], [], [], []
-        for gy, y, raw, bn, act, slope, gres, dgp, dbp in members:
-            use_y = y is not None and act != ACT_NONE
-            M, C_ = gy.B * gy.H * gy.W, gy.C
-            off = self._acc_slot(C_)
-            mean_p = bn["mean"].data_ptr() if bn else None
-            rstd_p = bn["rstd"].data_ptr() if bn else None
-            gam_p = bn["gamma"].data_ptr() if bn else None
-
-            def ptrs(P, gy=gy, y=y, raw=raw, use_y=use_y):
-                yv = (P(y.tbuf), y.cstride, y.coff) if use_y else (None, 0, 0)
-                xv = (P(raw.tbuf), raw.cstride, raw.coff) if raw is not None else (None, 0, 0)
-                return (dt, P(gy.tbuf), gy.cstride, gy.coff) + yv + xv
-
-            def sums(P, ptrs=ptrs, M=M, C_=C_, act=act, slope=slope, off=off, mean_p=mean_p, rstd_p=rstd_p):
-                it = CpBnItem()
-                _abi.check(lib.cp_bn_item_bwd_sums(*(ptrs(P) + (mean_p, rstd_p, M, C_, act, slope, self._acc_ptr(off), C.byref(it)))),
-                           "cp_bn_item_bwd_sums")
-                return it
-
-            def apply_(P, ptrs=ptrs, gy=gy, gres=gres, M=M, C_=C_, act=act, slope=slope, off=off, mean_p=mean_p, rstd_p=rstd_p,
-                       gam_p=gam_p, dgp=dgp, dbp=dbp):
-                it = CpBnItem()
-                gr = (P(gres.tbuf), gres.cstride, gres.coff) if gres is not None else (None, 0, 0)
-                _abi.check(lib.cp_bn_item_bwd_apply(*(ptrs(P) + (mean_p, rstd_p, gam_p, self._acc_ptr(off), M, C_, act, slope,
-                                                                 P(gy.tbuf), gy.cstride, gy.coff) + gr + (1, dgp, dbp, C.byref(it)))),
-                           "cp_bn_item_bwd_apply")
-                return it
-            sb.append(sums)
-            ab.append(apply_)
-            rd = [gy.tbuf] + ([y.tbuf] if use_y else []) + ([raw.tbuf] if raw is not None else [])
-            reads_s += rd
-            reads_a += rd + ([gres.tbuf] if gres is not None else [])
-            writes_a += [gy.tbuf] + ([gres.tbuf] if gres is not None else [])
-        for lo in range(0, len(members), BN_GROUP_MAX):
-            hi = lo + BN_GROUP_MAX
-            self._bn_group(CP_BN_ITEM_BWD_SUMS, sb[lo:hi], "bn_bwd_acc_group:%d" % len(sb[lo:hi]), reads_s, [])
-        for lo in range(0, len(members), BN_GROUP_MAX):
-            hi = lo + BN_GROUP_MAX
-            self._bn_group(CP_BN_ITEM_BWD_APPLY, ab[lo:hi], "bn_bwd_group:%d" % len(ab[lo:hi]), reads_a, writes_a)
+    def bn_bwd(self, *m):
+        """bn_backward of one layer: the fields of a BnGrad"""
+        self.bn_backward([BnGrad(*m)])
 
     # ---- dense layer backward
     def wgrad(self, dy: Act, x: Act, dw_ptr, Cout, Cin, R, S, stride, pad, Ho=None, Wo=None, base=0, sco=None, sci=None):
@@ -419,8 +419,7 @@ class TrainProgram(Program):
         name = "wgrad:%d->%d k%d s%d %dx%d" % (Cin, Cout, R, stride, x.H, x.W)
         flops = 2 * dy.B * d.Ho * d.Wo * R * S * Cin * Cout                # algorithmic, unpadded
         if flops < self.wg_group_flops:
-            self._wgc_pending.append(dict(d=d, dref=dref, dt=dt, xt=xt, dw=dw_ptr, flops=flops, k3s1=(R == 3 and stride == 1),
-                                          pix=dy.B * d.Ho * d.Wo, cc=((Cout + 63) // 64) * ((Cin + 63) // 64), taps=R * S))
+            self._wgc_pending.append(PendingWgrad(self.lib, d, dt, xt, dw_ptr, flops))
             if len(self._wgc_pending) >= self.wg_group_n:
                 self.flush_wgrad_compute()
             return
@@ -447,70 +446,52 @@ class TrainProgram(Program):
         pend, self._wgc_pending = self._wgc_pending, []
         if not pend:
             return
-        lib, arena, asz = self.lib, self.wg_ws.data_ptr(), self.wg_ws.numel()
+        arena, asz = self.wg_ws.data_ptr(), self.wg_ws.numel()
         for m in pend:                        # kernel kind of every layer (depends on the descriptor only)
-            ci, ri = CpWgradItem(), CpWgradReduceItem()
-            _abi.check(lib.cp_conv2d_wgrad_item(m["dref"], arena, arena, m["dw"], arena, asz, 0, C.byref(ci), C.byref(ri)), "cp_conv2d_wgrad_item")
-            m["kind"] = int(ci.kind)
-            m["work"] = m["pix"] * m["cc"] * (1 if ci.kind in ALL_TAPS_KINDS else m["taps"])
-        kinds = sorted({m["kind"] for m in pend})
+            m.kind = int(m.item(arena, arena, arena, asz, 0)[0].kind)
+            m.work = m.pix * m.cc * (1 if m.kind in ALL_TAPS_KINDS else m.taps)
+        kinds = sorted({m.kind for m in pend})
         for kind in kinds:                    # every layer's share of its launch, and the partial tiles that share needs
-            mem = [m for m in pend if m["kind"] == kind]
-            total = float(sum(m["work"] for m in mem))
+            mem = [m for m in pend if m.kind == kind]
+            total = float(sum(m.work for m in mem))
             for m in mem:
-                m["target"] = max(1, int(round(self.wg_group_blocks[kind] * m["work"] / total)))
-                ci, ri = CpWgradItem(), CpWgradReduceItem()
-                _abi.check(lib.cp_conv2d_wgrad_item(m["dref"], arena, arena, m["dw"], arena, asz, m["target"], C.byref(ci), C.byref(ri)), "cp_conv2d_wgrad_item")
-                m["need"] = (int(ri.S) * int(ri.GY) * int(ri.taps_in_block) * 4096 * 4 + 255) // 256 * 256 if ri.ws else 0
-                m["blocks"] = int(ci.blocks)
-        need_all = sum(m["need"] for m in pend)
+                m.target = max(1, int(round(self.wg_group_blocks[kind] * m.work / total)))
+                ci, ri = m.item(arena, arena, arena, asz, m.target)
+                m.need = (int(ri.S) * int(ri.GY) * int(ri.taps_in_block) * 4096 * 4 + 255) // 256 * 256 if ri.ws else 0
+                m.blocks = int(ci.blocks)
+        need_all = sum(m.need for m in pend)
         if need_all > asz:
             raise RuntimeError("checkerpose_amd: the weight-gradient arena (%d MB, CHECKERPOSE_AMD_WGRAD_ARENA_MB) is smaller than the partial "
                                "tiles of one group of layers (%d MB)" % (asz >> 20, (need_all >> 20) + 1))
         if self._wg_off + need_all > asz:     # the reductions owed so far (their producers are all emitted) free the arena
             self._flush_wgrad_reduce()
-        for kind in kinds:
-            mem = [m for m in pend if m["kind"] == kind]
-            builders = []
+        for kind in kinds:                    # every layer's place in the arena, and the launch of its kind
+            mem = [m for m in pend if m.kind == kind]
             for m in mem:
-                if m["need"]:
-                    m["wsp"], m["wsn"] = arena + self._wg_off, m["need"]
-                    ci, ri = CpWgradItem(), CpWgradReduceItem()
-                    _abi.check(lib.cp_conv2d_wgrad_item(m["dref"], arena, arena, m["dw"], m["wsp"], m["wsn"], m["target"], C.byref(ci), C.byref(ri)),
-                               "cp_conv2d_wgrad_item")
-                    assert ri.ws == m["wsp"] and int(ci.blocks) == m["blocks"]
+                if m.need:
+                    m.wsp, m.wsn = arena + self._wg_off, m.need
+                    ci, ri = m.item(arena, arena, m.wsp, m.wsn, m.target)
+                    assert ri.ws == m.wsp and int(ci.blocks) == m.blocks
                     self._wg_items.append(ri)
-                    self._wg_off += m["need"]
+                    self._wg_off += m.need
                 else:
-                    m["wsp"], m["wsn"] = arena, asz
+                    m.wsp, m.wsn = arena, asz
 
-                def build(P, m=m):
-                    it, spare = CpWgradItem(), CpWgradReduceItem()
-                    _abi.check(lib.cp_conv2d_wgrad_item(m["dref"], P(m["dt"]), P(m["xt"]), m["dw"], m["wsp"], m["wsn"], m["target"], C.byref(it),
-                                                        C.byref(spare)), "cp_conv2d_wgrad_item")
-                    assert int(it.blocks) == m["blocks"] and int(it.kind) == m["kind"]
-                    return it
-                builders.append(build)
-
-            def argb(P, builders=builders, kind=kind):
-                items = [b(P) for b in builders]
-                raw, prefix, total = _abi.device_table(items, [it.blocks for it in items], self.device)
-                self.keep += [raw, prefix]
-                return (kind, raw.data_ptr(), prefix.data_ptr(), len(items), total)
-            k3 = all(m["k3s1"] for m in mem)
-            self._add(lib.cp_wgrad_group, argb, "wgrad_group:%s x%d" % (" k3 s1 " if k3 else "mixed", len(mem)),
-                      [t for m in mem for t in (m["dt"], m["xt"])], [])
-            self.wgrad_flops[len(self.ops) - 1] = sum(m["flops"] for m in mem)
+            def argb(P, mem=mem, kind=kind):
+                items = [m.item(P(m.dt), P(m.xt), m.wsp, m.wsn, m.target)[0] for m in mem]
+                assert all(int(it.blocks) == m.blocks and int(it.kind) == m.kind for it, m in zip(items, mem))
+                return (kind,) + self._table(items, [it.blocks for it in items])
+            k3 = all(m.k3s1 for m in mem)
+            self._add(self.lib.cp_wgrad_group, argb, "wgrad_group:%s x%d" % (" k3 s1 " if k3 else "mixed", len(mem)),
+                      [t for m in mem for t in (m.dt, m.xt)], [])
+            self.wgrad_flops[len(self.ops) - 1] = sum(m.flops for m in mem)
         if len(self._wg_items) >= self.wg_reduce_n:        # settle in a few instalments: the data-parallel step's gradient buckets
             self.flush_wgrad()                              # complete (and start their all-reduce) while the backward goes on
 
     def _flush_wgrad_reduce(self):
         if self._wg_items:
-            items = self._wg_items
-            raw, prefix, acc = _abi.device_table(items, [self.lib.cp_wgrad_reduce_item_blocks(C.byref(it)) for it in items], self.device)
-            self.wg_tabs.append((raw, prefix))
-            n = len(items)
-            self._add(self.lib.cp_wgrad_reduce_batch, lambda P: (raw.data_ptr(), prefix.data_ptr(), n, acc), "wgrad_reduce_batch:%d" % n, [], [])
+            tab = self._table(self._wg_items, [self.lib.cp_wgrad_reduce_item_blocks(C.byref(it)) for it in self._wg_items])
+            self._add(self.lib.cp_wgrad_reduce_batch, lambda P: tab, "wgrad_reduce_batch:%d" % tab[2], [], [])
         self._wg_off, self._wg_items = 0, []
 
     def flush_wgrad(self):
@@ -525,17 +506,12 @@ class TrainProgram(Program):
     def weight_dgrad(self, w, Cout, Cin, R, S):
         wt = self.scratch_f32(Cout * Cin * R * S).view(Cin, Cout, R, S)
         self.keep.append(w)
-        it = CpPackItem()
-        _abi.check(self.lib.cp_pack_item_dgrad_view(w.data_ptr(), Cout, Cin, R, S, wt.data_ptr(), C.byref(it)), "weight_dgrad")
-        self.add_item("views", it)
+        self.prep_item("views", lambda ref: self.lib.cp_pack_item_dgrad_view(w.data_ptr(), Cout, Cin, R, S, wt.data_ptr(), ref), "weight_dgrad")
         return wt
 
     def conv_backward(self, key, w, x: Act, g: Act, R, S, stride, pad):
         """g = d loss / d (raw conv output) in channels-last; accumulates into grad(x), writes the weight gradient."""
-        Cout, Cin = w.shape[0], w.shape[1]
-        self.wgrad(g, x, self.pg_ptr(key + ".weight"), Cout, Cin, R, S, stride, pad)
-        if self.needs_grad(x):
-            self._dgrad(key, w, x, g, R, S, stride, pad)
+        self.conv_backward_group([(key, w, x, g, R, S, stride, pad)])
 
     def conv_backward_group(self, members):
         """conv_backward of INDEPENDENT layers [(key, w, x, g, R, S, stride, pad)]: every weight gradient first, the 3x3 / stride 1
@@ -604,9 +580,7 @@ class TrainProgram(Program):
                                                             int(shift), 1 if relu else 0, 1, C.byref(it), C.byref(nb)), "cp_fuse_sum_act_bwd_item")
                     items.append(it)
                     nbs.append(nb.value)
-                raw, prefix, total = _abi.device_table(items, nbs, self.device)
-                self.keep += [raw, prefix]
-                return (dt, raw.data_ptr(), prefix.data_ptr(), len(items), total)
+                return (dt,) + self._table(items, nbs)
             tbs = [t for gout, out, gsrc, _, _ in mem for t in (gout.tbuf, out.tbuf, gsrc.tbuf)]
             self._add(lib.cp_fuse_sum_act_bwd_group, argb, "fuse_sum_bwd_group:%d" % len(mem), tbs, [m[2].tbuf for m in mem])
 
@@ -629,9 +603,7 @@ class TrainProgram(Program):
     def edge_weight_view(self, w, Co, Ci, mode):
         out = self.scratch_f32(2 * Co * Ci)
         self.keep.append(w)
-        it = CpPackItem()
-        _abi.check(self.lib.cp_pack_item_edge_view(w.data_ptr(), Co, Ci, mode, out.data_ptr(), C.byref(it)), "edge_weight_view")
-        self.add_item("views", it)
+        self.prep_item("views", lambda ref: self.lib.cp_pack_item_edge_view(w.data_ptr(), Co, Ci, mode, out.data_ptr(), ref), "edge_weight_view")
         return out.view(2 * Co, Ci, 1, 1) if mode == 0 else out.view(Ci, 2 * Co, 1, 1)
 
     def edge_train_fwd(self, pq: Act, graph, gamma, beta, rmean, rvar, out: Act, Co, slope, momentum=0.1, eps=1e-5):
@@ -671,8 +643,7 @@ class TrainProgram(Program):
         for key, items in self.items.items():
             if not items:
                 continue
-            raw, prefix, acc = _abi.device_table(items, [(int(it.total) + 255) // 256 for it in items], self.device)
-            self.item_tabs[key] = (raw, prefix, len(items), acc)
+            self.prep_tabs[key] = self._table(items, [(int(it.total) + 255) // 256 for it in items])
         self.acc_arena = torch.zeros(max(self.acc_total, 2), dtype=torch.float64, device=self.device)
         total = sum(t.nbytes for t in self.arena)
         self.grad_arena = torch.empty(max(total, 256), dtype=torch.uint8, device=self.device)
@@ -681,23 +652,15 @@ class TrainProgram(Program):
             t.fixed = self.grad_arena[off:off + t.nbytes]
             off += t.nbytes
         super().finalize()
-        # n_fwd_ops was recorded in units of emitted ops (launches + fork/sync/join markers): convert to launches
-        markers = ("__fork__", "__sync__", "__join__", "__mark__", "__wait__")
-        nmark, before = 0, []
-        for op in self.ops:                     # before[i] = launches among ops[:i]
-            before.append(nmark)
-            nmark += 0 if op[0] in markers else 1
-        before.append(nmark)
-        self.pslot_done_call = {k: before[i] for k, i in self.pslot_done.items()}
-        self.n_fwd_ops = sum(1 for op in self.ops[:self.n_fwd_ops] if op[0] not in markers)
-        ci, flops = 0, {}
-        for i, op in enumerate(self.ops):
-            if op[0] in markers:
-                continue
-            if i in self.wgrad_flops:
-                flops[ci] = self.wgrad_flops[i]
-            ci += 1
-        self.wgrad_flops = flops           # re-keyed by launch (call) index, like everything bench_train reads
+        # op indices (launches + fork / sync / join markers) -> launch (call) indices, like everything bench_train reads
+        call_of, n = [], 0                      # call_of[i] = launches among ops[:i]
+        for op in self.ops:
+            call_of.append(n)
+            n += 0 if op[0] in MARKERS else 1
+        call_of.append(n)
+        self.pslot_done_call = {k: call_of[i] for k, i in self.pslot_done.items()}
+        self.n_fwd_ops = call_of[self.n_fwd_ops]
+        self.wgrad_flops = {call_of[i]: f for i, f in self.wgrad_flops.items()}
         return self
 
     def zero_grad_arena(self):

@@ -433,3 +433,31 @@ def test_deterministic_mode_matches_default_mode_numerically():
     worst = max(float((a[k].float() - b[k].float()).abs().max()) / (1e-6 + float(b[k].float().abs().max())) for k in a
                 if a[k].dtype.is_floating_point)
     assert worst <= 2e-2, worst
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+def test_train_program_bookkeeping_counts_launches(dt):
+    """What TrainProgram.finalize owns after a B = 2 PoseNet step: everything bench_train and the gradient buckets read is in units of
+    LAUNCHES (indices into prog.calls), not of emitted ops (launches + fork / sync / join markers) -- the weight-gradient FLOPs sit on
+    exactly the weight-gradient launches, every parameter's gradient is final inside the backward half, the backward half begins with
+    its weight-preparation launch, and no parameter that received a gradient is missing from the bucket plan's input"""
+    B = 2
+    net = build_net(seed=3).cuda().train()
+    net.set_compute_dtype(dt)
+    with torch.enable_grad():
+        res = net(det_image(B, seed=7).cuda(), None)
+        ts = [t for t in res[:4] if t.requires_grad]
+        torch.autograd.backward(ts, [torch.ones_like(t) for t in ts])
+    torch.cuda.synchronize()
+    pr = list(net._train_programs.values())[-1]
+    prog, pgrad = pr["prog"], pr["pgrad"]
+    wg = {i for i, (fn, _, _) in enumerate(prog.calls) if fn.__name__ in ("cp_conv2d_wgrad_deferred", "cp_wgrad_group")}
+    assert wg and set(prog.wgrad_flops) == wg
+    assert all(v > 0 for v in prog.wgrad_flops.values())
+    assert prog.pslot_done_call and all(prog.n_fwd_ops <= v <= len(prog.calls) for v in prog.pslot_done_call.values())
+    assert prog.calls[prog.n_fwd_ops][2] == "prep_views_bwd"
+    params = dict(net.named_parameters())
+    with_grad = [k for k, off in prog.pslots.items() if bool(pgrad[off:off + params[k].numel()].any())]
+    assert len(with_grad) > 100
+    missing = [k for k in with_grad if k not in prog.pslot_done or k not in prog.pslot_done_call]
+    assert not missing, missing[:5]

@@ -5,11 +5,16 @@ Per matrix row (PoseNet / woProg / InitNet x backbone x dtype x batch x kernel s
 the sched list, workspace_bytes, flops, conv_log, then every call as `<C symbol> <recorder's name> lane=<k>` with its arguments --
 pointers (told from integers by fn.argtypes) as `ws+<offset>` inside the program's workspace and `p<k>` (numbered by first
 appearance) elsewhere, by-reference structs and arrays field by field under the same rules -- and the sha256 of every output
-tensor of one run on det_image(B, seed=100) (training: deterministic mode, outputs + the parameter-gradient arena).  Last, the
-sorted set of C symbols launched over the whole matrix: a recorder none of whose entry points is listed was not compared.
+tensor of one run on det_image(B, seed=100) (training: deterministic mode, outputs + the parameter-gradient arena + every module
+buffer after the step, i.e. the BatchNorm running statistics and counters).  A grouped launch (TABLES) is followed by its item table and
+prefix table, read back from the device: every item field by field, each 64-bit word of an opaque parameter block as `ws+<offset>`,
+`p<k>+<offset>` inside an allocation the program or the module holds, or the integer it is.  Last, the sorted set of C symbols launched
+over the whole matrix: a recorder none of whose entry points is listed was not compared.
 
-  --json FILE      also write {row: sha256 of the row's text}
-  --time-build N   instead of the dump: wall time of N program builds at B = 256 (bf16 PoseNet, first forward after invalidate())
+  --json FILE            also write {row: sha256 of the row's text}
+  --rows TEXT            only the rows whose name contains TEXT
+  --time-build N         instead of the dump: wall time of N program builds at B = 256 (bf16 PoseNet, first forward after invalidate())
+  --time-build-train N   likewise for the training program: bf16 PoseNet, B = 32, first training step after invalidate()
 """
 import argparse
 import ctypes as C
@@ -22,16 +27,17 @@ import time
 import torch
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-from checkerpose_amd import set_deterministic                                # noqa: E402
+from checkerpose_amd import _abi, set_deterministic                          # noqa: E402
 from checkerpose_amd.synthetic import build_net, build_woprog, det_image     # noqa: E402
 
 
 class Canon:
     """pointer naming of one program"""
 
-    def __init__(self, prog):
+    def __init__(self, prog, held=()):
         ws = prog.workspace
         self.lo, self.hi, self.names = ws.data_ptr(), ws.data_ptr() + ws.numel(), {}
+        self.allocs = sorted({(t.data_ptr(), t.data_ptr() + t.numel() * t.element_size()) for t in held if t.numel()})
 
     def ptr(self, v):
         v = getattr(v, "value", v)
@@ -41,11 +47,26 @@ class Canon:
             return "ws+%d" % (v - self.lo)
         return self.names.setdefault(v, "p%d" % len(self.names))
 
+    def word(self, v):
+        """one 64-bit word of an opaque parameter block: a pointer into the workspace or into a held allocation (the outermost one that
+        contains it), else the integer"""
+        v = int(v)
+        if self.lo <= v < self.hi:
+            return "ws+%d" % (v - self.lo)
+        if v in self.names:
+            return self.names[v] + "+0"
+        for lo, hi in self.allocs:
+            if lo <= v < hi:
+                return "%s+%d" % (self.ptr(lo), v - lo)
+        return str(v)
+
     def value(self, v, ctype=None):
         if hasattr(v, "_obj"):                                   # C.byref(x)
             return self.value(v._obj)
         if isinstance(v, C.Structure):
             return "{%s}" % ", ".join("%s=%s" % (n, self.value(getattr(v, n), t)) for n, t in v._fields_)
+        if isinstance(v, C.Array) and v._type_ is C.c_uint64:    # an opaque block (CpBnItem.params, CpWgradItem.params)
+            return "[%s]" % ", ".join(self.word(e) for e in v)
         if isinstance(v, C.Array):
             return "[%s]" % ", ".join(self.value(e, v._type_) for e in v)
         if ctype is C.c_void_p or isinstance(v, C.c_void_p):
@@ -58,17 +79,68 @@ class Canon:
 SYMBOLS = set()          # every C entry point some dumped program launches
 
 
-def dump_program(prog, out):
+# grouped launches: C symbol -> (item type, position of the item-table pointer among the arguments behind the stream; the prefix-table
+# pointer and the item count follow it)
+TABLES = {"cp_bn_group": (_abi.CpBnItem, 2), "cp_wgrad_group": (_abi.CpWgradItem, 1), "cp_wgrad_reduce_batch": (_abi.CpWgradReduceItem, 0),
+          "cp_fuse_sum_act_bwd_group": (_abi.CpFuseBwdItem, 1), "cp_pack_batch": (_abi.CpPackItem, 1)}
+
+
+class _DeviceBytes:
+    def __init__(self, ptr, n):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "|u1", "data": (int(ptr), False), "version": 2}
+
+
+def read_device(ptr, n, device):
+    return torch.as_tensor(_DeviceBytes(ptr, n), device=device).cpu().numpy().tobytes()
+
+
+def tensors_in(x, depth=0):
+    """every tensor reachable from x through lists, tuples and dicts"""
+    if torch.is_tensor(x):
+        return [x]
+    if isinstance(x, dict):
+        x = list(x.values())
+    if isinstance(x, (list, tuple)) and depth < 4:
+        return [t for e in x for t in tensors_in(e, depth + 1)]
+    return []
+
+
+def held_tensors(prog, net):
+    """the allocations opaque words may point into: what the program keeps alive, its arenas, the module's parameters and buffers"""
+    held = tensors_in(list(prog.keep))
+    for name in ("pgrad", "acc_arena", "grad_arena", "wg_ws"):
+        held += tensors_in(getattr(prog, name, None))
+    if net is not None:
+        held += [t for t in net.state_dict(keep_vars=True).values() if t.is_cuda]
+    return held
+
+
+def dump_table(cn, fn, args, out, device):
+    itype, at = TABLES[fn.__name__]
+    raw, prefix, n = (getattr(a, "value", a) for a in args[at:at + 3])
+    if not n:
+        return
+    size = C.sizeof(itype)
+    blob = read_device(raw, n * size, device)
+    for k in range(n):
+        out.append("  item %d %s" % (k, cn.value(itype.from_buffer_copy(blob, k * size))))
+    pre = (C.c_uint32 * (n + 1)).from_buffer_copy(read_device(prefix, 4 * (n + 1), device))
+    out.append("  prefix %s" % (list(pre),))
+
+
+def dump_program(prog, out, net=None):
     SYMBOLS.update(fn.__name__ for fn, _, _ in prog.calls)
     lane_of = {item[1]: item[2] for item in prog.sched if item[0] == "op"}
     out.append("sched %r" % (prog.sched,))
     out.append("workspace_bytes %d flops %d" % (prog.workspace_bytes, prog.flops))
     out.append("conv_log %r" % (list(prog.conv_log),))
-    cn = Canon(prog)
+    cn = Canon(prog, held_tensors(prog, net))
     for i, (fn, args, name) in enumerate(prog.calls):
         types = list(fn.argtypes)[1:]                            # [0]: the stream
         assert len(types) == len(args) - 1, (fn.__name__, len(types), len(args))
         out.append("%s %s lane=%d (%s)" % (fn.__name__, name, lane_of[i], ", ".join(cn.value(a, t) for a, t in zip(args[1:], types))))
+        if fn.__name__ in TABLES:
+            dump_table(cn, fn, args[1:], out, prog.workspace.device)
 
 
 def sha(t):
@@ -109,12 +181,21 @@ def eval_row(make, dtype, B, lm=False, stage=None, selection="auto"):
     return out
 
 
-def train_row(make, lm):
+# the smallest power of two (MB) of CHECKERPOSE_AMD_WGRAD_ARENA_MB at which the fp32 PoseNet training program builds at B = 2 (found on the
+# commit before the trainer refactor: 32 raises "arena is smaller than ..."): the backward runs out of arena and settles in instalments
+SMALL_ARENA_MB = 64
+
+
+def train_row(make, lm, dtype=None, env=None):
     dev = torch.device("cuda:0")
     B, out = 2, []
+    saved = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
     set_deterministic(True)
     try:
         net = make().to(dev).train()
+        if dtype is not None:
+            net.set_compute_dtype(dtype)
         with torch.enable_grad():
             res = call(net, det_image(B, seed=100).to(dev), lm)
             ts = [t for t in tensors_of(res) if t.requires_grad]
@@ -122,11 +203,14 @@ def train_row(make, lm):
         torch.cuda.synchronize()
         pr = list(net._train_programs.values())[-1]              # (no public accessor: program_for lists the eval programs)
         out.append("n_fwd_ops %d" % pr["prog"].n_fwd_ops)
-        dump_program(pr["prog"], out)
+        dump_program(pr["prog"], out, net)
         out += ["out%d %s" % (k, sha(t)) for k, t in enumerate(tensors_of(res))]
         out.append("pgrad %s" % sha(pr["pgrad"]))
+        out += ["buffer %s %s" % (k, sha(t)) for k, t in net.named_buffers()]
     finally:
         set_deterministic(False)
+        for k, v in saved.items():
+            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
     return out
 
 
@@ -162,6 +246,15 @@ def matrix():
     rows.append(("posenet bf16 B=96", lambda: eval_row(pose, "bf16", 96)))      # the smallest batch at which auto takes hr_stem and edge_fused
     rows.append(("posenet train fp32 B=2", lambda: train_row(pose, False)))
     rows.append(("woprog train fp32 B=2", lambda: train_row(wop, True)))
+    # the training recorders' other paths: the bf16 weight-gradient kind and BatchNorm items; max-pool backward and the ungrouped basic
+    # blocks; the small HRNet; every weight gradient launched alone (cp_conv2d_wgrad_deferred); a weight-gradient arena that fills up
+    # in mid-backward (cp_wgrad_reduce_batch in instalments)
+    rows.append(("posenet train bf16 B=2", lambda: train_row(pose, False, "bf16")))
+    rows.append(("posenet resnet34 train fp32 B=2", lambda: train_row(lambda: build_net(512, backbone="resnet34"), False)))
+    rows.append(("posenet hrnet_w18_small train fp32 B=2", lambda: train_row(lambda: build_net(512, backbone="hrnet_w18_small"), False)))
+    rows.append(("posenet train fp32 B=2 wgrad alone", lambda: train_row(pose, False, env={"CHECKERPOSE_AMD_WGRAD_GROUP_GFLOP": "0"})))
+    rows.append(("posenet train fp32 B=2 arena %d MB" % SMALL_ARENA_MB,
+                 lambda: train_row(pose, False, env={"CHECKERPOSE_AMD_WGRAD_ARENA_MB": str(SMALL_ARENA_MB)})))
     return rows
 
 
@@ -183,15 +276,43 @@ def time_build(n):
     print(json.dumps({"program_build_b256_seconds": secs}))
 
 
+def time_build_train(n):
+    dev = torch.device("cuda:0")
+    net = build_net(512).to(dev).train().set_compute_dtype("bf16")
+    img = det_image(32, seed=100).to(dev)
+
+    def step():
+        with torch.enable_grad():
+            ts = [t for t in tensors_of(net(img, None)) if t.requires_grad]
+            torch.autograd.backward(ts, [torch.ones_like(t) for t in ts])
+        torch.cuda.synchronize()
+    step()                                                       # library load, allocator warm-up
+    secs = []
+    for _ in range(n):
+        net.invalidate()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        step()
+        secs.append(time.perf_counter() - t0)
+        assert len(net._train_programs) == 1
+    print(json.dumps({"train_program_build_b32_seconds": secs}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json")
     ap.add_argument("--time-build", type=int, default=0)
+    ap.add_argument("--time-build-train", type=int, default=0)
+    ap.add_argument("--rows", help="only the rows whose name contains this text")
     a = ap.parse_args()
     if a.time_build:
         return time_build(a.time_build)
+    if a.time_build_train:
+        return time_build_train(a.time_build_train)
     digests = {}
     for name, row in matrix():
+        if a.rows and a.rows not in name:
+            continue
         text = "\n".join(["==== " + name] + row()) + "\n"
         sys.stdout.write(text)
         sys.stdout.flush()
