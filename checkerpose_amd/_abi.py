@@ -202,6 +202,9 @@ SIGNATURES = {
     "cp_pnp_refine_lm_record_doubles": (_I, []),
     "cp_pnp_refine_lm_info_doubles": (_I, []),
     "cp_pnp_refine_lm": (_I, [_P, _P, _L, _P, _P, _I, _P, _L, _I, _I, _P, _P, _I, C.c_double, _P, _P, _P, _P]),
+    "cp_pose_rete": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "cp_rete_pass_columns": (_I, []),
+    "cp_rete_pass_counts": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "cp_pnp_gc_scratch_bytes": (C.c_size_t, [_I, _I, _L]),
     "cp_pnp_gc": (_I, [_P, _P, _L, _P, _P, _I, _P, _L, _P, _P, _P, _P, _I, _L, _L, _I, _I, _F, C.c_int32, _I, _I, C.c_uint32, _P, _P, _P, _P]),
     "cp_pose_errors_scratch_bytes": (C.c_size_t, [_I, _I]),

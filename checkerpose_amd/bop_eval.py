@@ -25,7 +25,7 @@ import torch
 
 from . import _abi, metric, scene
 
-ERROR_KINDS = ("add", "adi", "ad", "mssd", "mspd", "proj", "vsd", "cus")
+ERROR_KINDS = ("add", "adi", "ad", "mssd", "mspd", "proj", "vsd", "cus", "re", "te", "rete")
 
 
 def _dev(device):
@@ -238,20 +238,26 @@ def calc_errors(pairs, ests, kind, meshes, obj_index, scene_camera=None, symmetr
       {scene_id: inout.load_scene_camera's dict} or one (3,3) K ("mspd", "proj", "vsd", "cus");  symmetries: as metric.bop_errors';
       depths: {scene_id: {im_id: (H,W) depth in mm}} ("vsd");  delta, taus, sphere_check: metric.vsd_errors';  size: (W, H) of the
       frames ("cus").
-    re / te / rete tables are the caller's (no kernel computes them): pass them to match() as they are.
-    -> float64 CUDA tensor (P, 1), or (P, T) for "vsd", in the pairs' order."""
+    "re", "te", "rete": pose_error.re(R_e, R_g) / .te(t_e, t_g) as eval_calc_errors.py:368-375 calls them (targets.pose_re_te_sym
+    without symmetries: cp_pose_rete): no symmetries and no diameter shortcut, the script applies none to these kinds; meshes is not
+    read.  A table of the caller's own goes to match() as it is.
+    -> float64 CUDA tensor (P, 1), (P, 2) = [re | te] for "rete", or (P, T) for "vsd", in the pairs' order."""
     if kind not in ERROR_KINDS:
         raise ValueError("kind must be among %s, got %r" % (ERROR_KINDS, kind))
     es = pairs.evalset
     dev = _dev(es.device)
     P = int(pairs.pair_est.shape[0])
     if P == 0:
-        return torch.zeros((0, 1 if kind != "vsd" else len(metric.vsd_taus(taus)[0])), dtype=torch.float64, device=dev)
+        return torch.zeros((0, 2 if kind == "rete" else (1 if kind != "vsd" else len(metric.vsd_taus(taus)[0]))), dtype=torch.float64, device=dev)
     src = pairs.est_src[pairs.pair_est]
     Re, te = _poses_of(ests, src, dev)
     tabs = es.on_device()
     gi = torch.from_numpy(pairs.pair_gt).to(dev)
     Rg, tg = tabs["gt_R"].index_select(0, gi), tabs["gt_t"].index_select(0, gi)
+    if kind in ("re", "te", "rete"):
+        from .targets import pose_re_te_sym
+        e_re, e_te = pose_re_te_sym(Re, te, Rg, tg)
+        return torch.stack([e_re, e_te], 1) if kind == "rete" else (e_re if kind == "re" else e_te)[:, None]
     objs = es.gt_obj[pairs.pair_gt]
     for o in np.unique(objs):
         if int(o) not in obj_index:
@@ -558,6 +564,8 @@ def evaluate_results(evalset, ests, meshes, obj_index, scene_camera, im_width, s
     divided by the diameter and MSPD multiplied by 640 / im_width before thresholding (eval_calc_scores.py:246-258), VSD over its ten
     taus x ten thresholds.  Arguments: calc_errors'; "vsd" is scored when `depths` is given.  "cus" among the kinds (needs `size`)
     is scored at its threshold 0.5 (eval_calc_scores.py:43) and reported as "AR_CUS"; it is not part of "AR".
+    "re", "te", "rete" among the kinds are scored at eval_calc_scores.py:44-46's thresholds (5 degrees, 5, and the pair [5, 5]) and
+    reported as "AR_RE" / "AR_TE" / "AR_RETE"; they are not part of "AR" either.
     -> {"AR_VSD", "AR_MSSD", "AR_MSPD": the mean of the overall recall over the kind's columns, "AR": their mean (when all three are
     there), "recall": {kind: (C,) recalls, VSD tau-major}, "scores": {kind: localization_scores' dict}, "valid"}."""
     es = evalset

@@ -221,6 +221,10 @@ def bop_thresholds(kind):
         return np.arange(0.05, 0.51, 0.05)
     if kind == "cus":                                      # eval_calc_scores.py:43
         return np.array([0.5])
+    if kind in ("re", "te"):                               # eval_calc_scores.py:45-46: degrees, centimetres
+        return np.array([5.0])
+    if kind == "rete":                                     # eval_calc_scores.py:44: one two-element threshold [deg, cm]
+        return np.array([[5.0, 5.0]])
     raise ValueError("%r has no default thresholds (BOP'19 scores \"mssd\" and \"mspd\"): pass `thresholds`" % (kind,))
 
 

@@ -386,11 +386,19 @@ class SymmetrySet:
         return cls(torch.from_numpy(np.ascontiguousarray(np.stack(rows, 0))), torch.tensor(off, dtype=torch.int32))
 
     @classmethod
-    def from_models_info(cls, infos, max_sym_disc_step=0.01):
-        """infos: one models_info.json entry (dict) per mesh, in MeshSet order -> misc.get_symmetry_transformations of each"""
+    def from_models_info(cls, infos, max_sym_disc_step=0.01, rotations_as=None):
+        """infos: one models_info.json entry (dict) per mesh, in MeshSet order -> misc.get_symmetry_transformations of each.
+        rotations_as=np.float32 rounds every rotation entry through float32, as the LM loader's `load_lm_obj_sym_info` keeps them
+        (lm_dataset_pytorch.py:552-563), so that targets.pose_re_te_sym meets the candidates test_lm.py meets; the translations and
+        the default (None: float64 as computed) are unchanged."""
         if isinstance(infos, dict):
             raise ValueError("pass a LIST of models_info entries, one per mesh in MeshSet order")
-        return cls.from_transforms([symmetry_transformations(i, max_sym_disc_step) for i in infos])
+        if rotations_as is not None and np.dtype(rotations_as) != np.dtype(np.float32):
+            raise ValueError("rotations_as must be None or np.float32, got %r" % (rotations_as,))
+        ss = cls.from_transforms([symmetry_transformations(i, max_sym_disc_step) for i in infos])
+        if rotations_as is not None:
+            ss.table[:, :9] = ss.table[:, :9].to(torch.float32).to(torch.float64)
+        return ss
 
     @classmethod
     def identity(cls, M):

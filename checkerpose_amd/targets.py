@@ -12,6 +12,8 @@ per crop in Python (`test.py:388-389,432-457`).  Here:
   code_report          network outputs + labels + GT mask crops -> test.py's per-crop code / mask figures and their integer counts
   pose_re_te           bop_toolkit_lib.pose_error.re / te, batched
   evaluate_batch       frames + boxes + GT -> everything test.py scores per crop; summarize_report -> its score lines
+  pose_re_te_sym       re against the closest symmetric ground truth (test_lm.py's get_closest_rot) + te, one launch (cp_pose_rete; row N23)
+  summarize_report_lm  test_lm.py's score file over the 13 LINEMOD objects: rete_pass_counts (cp_rete_pass_counts) + lm_report_text
 
 No CPU fallback: CPU tensors raise, as in `preprocess` / `postprocess`."""
 import numpy as np
@@ -329,13 +331,105 @@ def pose_re_te(R_est, t_est, R_gt, t_gt, return_cos=False):
     return (re, te, cos) if return_cos else (re, te)
 
 
-COLUMNS = ("all", "full", "visib")          # correspondences()' validity columns: RoI bit | also in the full mask | in the visible mask
+def pose_re_te_sym(R_est, t_est, R_gt, t_gt, symmetries=None, mesh_ids=None, return_cos=False, return_index=False, return_closest=False):
+    """`pose_error.re` / `.te` for a batch with the rotation error taken against the closest symmetric ground truth, as test_lm.py
+    takes it (`get_closest_rot`, :33-55, then `pose_error.re(pred_rot, r_GT_sym)`, :309-310), one launch (cp_pose_rete; the rule is at
+    the top of csrc/rete.hip).  The candidates are R_gt itself (index -1), then R_gt . S_k in the set's order; the first one with the
+    smallest re wins; te = |t_gt - t_est| does not look at the symmetries.
+      R_* (P,3,3), t_* (P,3) / (P,3,1): device tensors or host arrays (at least one a device tensor);
+      symmetries: a scene.SymmetrySet, or per-mesh lists of {"R", "t"} as scene.as_symmetries takes them (only "R" is used); None =
+      no symmetries, the plain re / te;  mesh_ids (P,): each pair's set among the M of `symmetries` (None with one set); ids on the
+      host are checked here, ids on the device stay unread (an id outside 0 .. M-1 gives NaN and index -1).
+    -> (re (P,) degrees, te (P,)), then in this order where asked: cos (the winner's `error_cos` before the clamp), index (int32: the
+    winner's place in its set, -1 = R_gt itself), R_gt_sym (P,3,3) = what get_closest_rot returns."""
+    from . import scene as SC
+    dev = _device_of(R_est, t_est, R_gt, t_gt)
+    Re, Rg = _f64(R_est, dev).reshape(-1, 3, 3), _f64(R_gt, dev).reshape(-1, 3, 3)
+    te_, tg = _f64(t_est, dev).reshape(-1, 3), _f64(t_gt, dev).reshape(-1, 3)
+    P = int(Re.shape[0])
+    if Rg.shape[0] != P or te_.shape[0] != P or tg.shape[0] != P:
+        raise ValueError("R_est, t_est, R_gt, t_gt must describe the same number of poses")
+    A, Bp = torch.cat([Re.reshape(P, 9), te_], 1).contiguous(), torch.cat([Rg.reshape(P, 9), tg], 1).contiguous()
+    tab = off = ids = None
+    off_host = ids_host = None
+    M = 0
+    if symmetries is None:
+        if mesh_ids is not None:
+            raise ValueError("mesh_ids without symmetries")
+    else:
+        ss = symmetries if isinstance(symmetries, SC.SymmetrySet) else SC.SymmetrySet.from_transforms(symmetries)
+        M = len(ss)
+        tab, off = ss.on(dev)
+        off_host = np.ascontiguousarray(ss.offsets.numpy(), dtype=np.int32)
+        if mesh_ids is None:
+            if M != 1:
+                raise ValueError("mesh_ids: several symmetry sets need one id per pose")
+        elif torch.is_tensor(mesh_ids) and mesh_ids.is_cuda:
+            ids = mesh_ids.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        else:
+            h = (mesh_ids.numpy() if torch.is_tensor(mesh_ids) else np.asarray(mesh_ids)).astype(np.int64).reshape(-1)
+            if h.shape[0] == P and P and (h.min() < 0 or h.max() >= M):
+                raise ValueError("mesh_ids must lie in 0 .. %d" % (M - 1))
+            ids_host = np.ascontiguousarray(h, dtype=np.int32)
+            ids = torch.from_numpy(ids_host).to(dev)
+        if ids is not None and ids.shape[0] != P:
+            raise ValueError("mesh_ids: one id per pose (%d), got %d" % (P, ids.shape[0]))
+    re, te = torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.float64, device=dev)
+    cos, idx = torch.empty(P, dtype=torch.float64, device=dev), torch.empty(P, dtype=torch.int32, device=dev)
+    if P:
+        _abi.call("cp_pose_rete", dev, A, Bp, P, tab, off, None if off_host is None else off_host.ctypes.data, M, ids,
+                  None if ids_host is None else ids_host.ctypes.data, re, te, cos, idx)
+    out = (re, te) + ((cos,) if return_cos else ()) + ((idx,) if return_index else ())
+    if return_closest:
+        if tab is None:
+            closest = Rg.clone()
+        else:
+            base = off.long()[ids.long()] if ids is not None else torch.zeros(P, dtype=torch.int64, device=dev)
+            S = tab[:, :9].reshape(-1, 3, 3)[(base + idx.long().clamp(min=0)).clamp(max=tab.shape[0] - 1)]
+            closest = torch.where((idx >= 0)[:, None, None], torch.matmul(Rg, S), Rg)
+        out = out + (closest,)
+    return out
+
+
+LM13_OBJ_IDS = (1, 2, 4, 5, 6, 8, 9, 10, 11, 12, 13, 14, 15)      # LINEMOD's 13 objects (3 and 7 are not evaluated)
+LM_SYMMETRIC_OBJ_IDS = (10, 11, 7, 3)
+RETE_COUNTS = ("n", "adx2", "adx5", "adx10", "rete2", "rete5", "re2", "re5", "te2", "te5")
+
+
+def rete_pass_counts(re, te, adx, diameters, slots, n_obj):
+    """The integer pass counts of test_lm.py:306-327 per object slot, one launch (cp_rete_pass_counts): re, te, adx, diameters (P,)
+    float64 and slots (P,) in 0 .. n_obj-1 (device tensors or host arrays, at least one on the device; host slots are checked).
+    -> (n_obj, 10) int32 device tensor, columns RETE_COUNTS; NaN counts as 10000, every `<` is strict."""
+    dev = _device_of(re, te, adx, diameters, slots)
+    r, t, a, d = (_f64(x, dev).reshape(-1) for x in (re, te, adx, diameters))
+    P, n_obj = int(r.shape[0]), int(n_obj)
+    if not 1 <= n_obj <= 256:
+        raise ValueError("n_obj must be in 1 .. 256, got %r" % (n_obj,))
+    slot_host = None
+    if torch.is_tensor(slots) and slots.is_cuda:
+        sl = slots.detach().to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    else:
+        h = (slots.numpy() if torch.is_tensor(slots) else np.asarray(slots)).astype(np.int64).reshape(-1)
+        if h.size and (h.min() < 0 or h.max() >= n_obj):
+            raise ValueError("slots must lie in 0 .. %d" % (n_obj - 1))
+        slot_host = np.ascontiguousarray(h, dtype=np.int32)
+        sl = torch.from_numpy(slot_host).to(dev)
+    if not (t.shape[0] == a.shape[0] == d.shape[0] == sl.shape[0] == P):
+        raise ValueError("re, te, adx, diameters and slots must have one entry per pose")
+    counts = torch.zeros(n_obj, len(RETE_COUNTS), dtype=torch.int32, device=dev)
+    if P == 0:
+        return counts
+    _abi.call("cp_rete_pass_counts", dev, r, t, a, d, sl, None if slot_host is None else slot_host.ctypes.data, P, n_obj, counts)
+    return counts
+
+
+COLUMNS =("all", "full", "visib")          # correspondences()' validity columns: RoI bit | also in the full mask | in the visible mask
 
 
 def evaluate_batch(net, frames, masks_visib, masks_full, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None,
                    kinds=("add", "adi"), img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256, crop_size_gt=64,
                    resize_method="crop_square_resize", discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0,
-                   symmetries=None, depth_test=None, image_ids=None, size=None):
+                   symmetries=None, depth_test=None, image_ids=None, size=None, re_symmetries=None):
     """test.py's loop body for a batch (:279-457), everything it scores per crop, without leaving the device: what
     `postprocess.evaluate_poses` does -- crops, ONE forward, correspondences, EPnP + RANSAC, ADD / ADD-S -- for the three correspondence
     sets the reference scores (all RoI keypoints | inside the predicted full mask | inside the visible mask, :335-368), plus `re` / `te`
@@ -343,6 +437,9 @@ def evaluate_batch(net, frames, masks_visib, masks_full, Bboxes, p3d_xyz, cam_K,
       frames / masks_visib / masks_full / Bboxes (detections; None = no detection) / p3d_xyz / obj_ids / cam_K as in
       make_training_batch(is_train=False); R_gt, t_gt, vertices, mesh_ids, kinds, symmetries, depth_test, image_ids as in
       postprocess.evaluate_poses (kind "vsd" needs depth_test; "cus" / "cou_bb_proj" need size = (W, H)).
+      re_symmetries: None, or what pose_re_te_sym takes as `symmetries` (with mesh_ids choosing each crop's set): then each column's
+      "re" is the error against the closest symmetric ground truth in test_lm.py's order (:309-310, the estimate first) and
+      "re_index" (int32, -1 = the plain ground truth) is added.  None runs what ran before the keyword existed.
     -> dict: "all" / "full" / "visib" -> {"errors": {kind: (B,) f64}, "R", "t", "status", "re", "te"}; "report": code_report's dict;
        "labels": encode_targets' dict; "final_Bboxes": (B,4) int array; "outputs": the network's tuple; "mask_crops": the GT
        (visible, full) uint8 crops (B,S,S)."""
@@ -369,11 +466,16 @@ def evaluate_batch(net, frames, masks_visib, masks_full, Bboxes, p3d_xyz, cam_K,
     for col, name in enumerate(COLUMNS):
         R, t, _, status = post.solve_pnp_ransac(p3_pose, p2d, valid, cam_K, column=col, reproj_threshold=reproj_threshold,
                                                 iterations=iterations, seed=seed)
-        re, te = pose_re_te(R_gt, t_gt, R, t)      # test.py:388-389 passes the ground truth first: trace(R_gt . inv(R_pred))
+        if re_symmetries is None:
+            re, te = pose_re_te(R_gt, t_gt, R, t)      # test.py:388-389 passes the ground truth first: trace(R_gt . inv(R_pred))
+        else:
+            re, te, re_index = pose_re_te_sym(R, t, R_gt, t_gt, symmetries=re_symmetries, mesh_ids=mesh_ids, return_index=True)
         res[name] = {"errors": metric.score_poses(R, t, R_gt, t_gt, cam_K, vertices, mesh_ids=mesh_ids, kinds=kinds, symmetries=symmetries,
                                                 depth_test=depth_test, image_ids=image_ids, size=size),
                      "R": R, "t": t,
                      "status": status, "re": re, "te": te}
+        if re_symmetries is not None:
+            res[name]["re_index"] = re_index
     Rg = R_gt if torch.is_tensor(R_gt) else torch.from_numpy(np.ascontiguousarray(np.asarray(R_gt, dtype=np.float64))).to(frames.device)
     labels = encode_targets(p3d_xyz, cam_K, Rg, t_gt, final, crop_size_gt, obj_ids=obj_ids)
     res["report"] = code_report(out, labels, m_vis, m_full)
@@ -418,3 +520,79 @@ def summarize_report(batches, diameters, symmetric=False):
     rows += tail
     text = "".join("%s %s\n" % (k, np.array2string(v, max_line_width=10 ** 6) if isinstance(v, np.ndarray) else "%.4f" % v) for k, v in rows)
     return dict(rows), text
+
+
+def lm_report_text(counts, figures, adx_type="all"):
+    """The LM report from its integer counts, on the host: test_lm.py:372-419 restated.
+      counts: (n_obj, 10) integers, columns RETE_COUNTS, one row per evaluated object (the 13 of LINEMOD);  figures: dict with the
+      means over all crops of roi_bit_acc, reproj_x_acc, reproj_y_acc, visib_pixel_acc, visib_iou, full_pixel_acc, full_iou (floats)
+      and bit_err_arr (1-d array).
+    Per object the pass rate is count / n (what np.mean of the 0 / 1 flags gives; an object without a sample gives NaN, as np.mean of
+    an empty list does); each reported rate is np.mean over the objects.
+    -> (dict key -> value, the text of the score file's lines in its order and format)"""
+    c = np.asarray(counts, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rates = c[:, 1:] / c[:, :1]
+    mean = {k: float(np.mean(rates[:, i])) for i, k in enumerate(RETE_COUNTS[1:])}
+    rows = [("adx_type", adx_type), ("acc", mean["adx10"])] + [(k, mean[k]) for k in RETE_COUNTS[1:]]
+    rows += [(k, float(figures[k])) for k in ("roi_bit_acc", "reproj_x_acc", "reproj_y_acc")]
+    rows.append(("bit_err_arr", np.asarray(figures["bit_err_arr"])))
+    rows += [(k, float(figures[k])) for k in ("visib_pixel_acc", "visib_iou", "full_pixel_acc", "full_iou")]
+    text = "".join("%s %s\n" % (k, v if isinstance(v, (str, np.ndarray)) else "%.4f" % v) for k, v in rows)
+    out = dict(rows)
+    out["per_object"] = {k: rates[:, i] for i, k in enumerate(RETE_COUNTS[1:])}
+    out["counts"] = np.asarray(counts)
+    return out, text
+
+
+def summarize_report_lm(batches, obj_ids, diameters, symmetric_obj_ids=LM_SYMMETRIC_OBJ_IDS, lm_obj_ids=LM13_OBJ_IDS, adx_type="all"):
+    """test_lm.py's score file (:299-327 per crop, :372-419 the summary) from accumulated `evaluate_batch` results over several objects.
+      batches: a list of evaluate_batch dicts (or one), scored with kinds "add" and / or "adi" as their objects need and -- for the
+      reference's numbers -- with re_symmetries;  obj_ids: each crop's object id over all batches, in order;  diameters: {obj_id:
+      diameter} or one diameter per crop;  symmetric_obj_ids: the objects whose main error is ADI (ADD for the others) -- test_lm.py's
+      `symmetry_ids`;  lm_obj_ids: the objects the means run over, in the report's order;  adx_type: the correspondence column
+      scored, "all" / "full" / "visib" (targets.COLUMNS).
+    The nine pass flags are counted per object on the device (cp_rete_pass_counts: NaN counts as 10000, strict `<`); 13 x 10
+    integers come to the host, where lm_report_text forms the rates and their means; the code / mask figures are the means over all
+    crops, as summarize_report forms them.
+    -> (dict key -> value, the text of the lines test_lm.py:411-419 writes)"""
+    if isinstance(batches, dict):
+        batches = [batches]
+    if adx_type not in COLUMNS:
+        raise ValueError("adx_type must be among %s, got %r" % (COLUMNS, adx_type))
+    ids = (obj_ids.detach().cpu().numpy() if torch.is_tensor(obj_ids) else np.asarray(obj_ids)).astype(np.int64).reshape(-1)
+    n = sum(int(b[adx_type]["re"].shape[0]) for b in batches)
+    if ids.shape[0] != n:
+        raise ValueError("obj_ids: one object id per crop (%d), got %d" % (n, ids.shape[0]))
+    order = [int(o) for o in lm_obj_ids]
+    if len(set(order)) != len(order) or not order:
+        raise ValueError("lm_obj_ids must name each evaluated object once")
+    slot_of = {o: k for k, o in enumerate(order)}
+    stray = sorted(set(ids.tolist()) - set(order))
+    if stray:
+        raise ValueError("obj_ids %r are not among lm_obj_ids" % (stray,))
+    slots = np.array([slot_of[int(o)] for o in ids], dtype=np.int32)
+    if isinstance(diameters, dict):
+        diam = np.array([float(diameters[int(o)]) for o in ids], dtype=np.float64)
+    else:
+        diam = np.asarray(diameters, dtype=np.float64).reshape(-1)
+        if diam.shape[0] != n:
+            raise ValueError("diameters: a dict obj_id -> diameter or one per crop (%d), got %d" % (n, diam.shape[0]))
+    sym = np.isin(ids, np.asarray(list(symmetric_obj_ids), dtype=np.int64))
+    dev = batches[0][adx_type]["re"].device
+    cat = lambda f: torch.cat([f(b).detach().to(device=dev, dtype=torch.float64).reshape(-1) for b in batches])      # noqa: E731
+    for need, kind in ((sym.any(), "adi"), ((~sym).any(), "add")):
+        if need and not all(kind in b[adx_type]["errors"] for b in batches):
+            raise ValueError("batches: the %s objects need kind %r in evaluate_batch's kinds" % ("symmetric" if kind == "adi" else "asymmetric", kind))
+    if sym.all():
+        adx = cat(lambda b: b[adx_type]["errors"]["adi"])
+    elif not sym.any():
+        adx = cat(lambda b: b[adx_type]["errors"]["add"])
+    else:
+        adx = torch.where(torch.from_numpy(sym).to(dev), cat(lambda b: b[adx_type]["errors"]["adi"]), cat(lambda b: b[adx_type]["errors"]["add"]))
+    counts = rete_pass_counts(cat(lambda b: b[adx_type]["re"]), cat(lambda b: b[adx_type]["te"]), adx, torch.from_numpy(diam).to(dev), slots,
+                              len(order)).cpu().numpy()
+    rep = lambda k: torch.cat([b["report"][k].detach().to(torch.float64) for b in batches], 0).cpu().numpy()      # noqa: E731
+    figures = {k: float(np.mean(rep(k))) for k in FIGURES}
+    figures["bit_err_arr"] = np.mean(rep("bit_err_arr"), axis=0)
+    return lm_report_text(counts, figures, adx_type)

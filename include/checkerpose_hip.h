@@ -621,6 +621,35 @@ int cp_pnp_refine_lm(cp_stream_t stream, const float* p3d, long long p3d_bstride
                      const int32_t* status_in, int max_iters, double step_tol, double* pose_out, int32_t* status_out,
                      double* info, double* records);
 
+/* Rotation / translation errors, symmetry-aware (row N23): bop_toolkit_lib.pose_error.re / .te (pose_error.py:187-214) for P pose
+ * pairs, the rotation error optionally against the closest symmetric copy of the second pose (checkerpose/test_lm.py:33-55,
+ * get_closest_rot).  The rule is stated in full at the top of csrc/rete.hip and restated in numpy by tests/rete_stages.py.  One
+ * launch, one wave per pair, fp64 without contraction, no atomics.
+ *   pose_a, pose_b fp64 (P,12) = [R row-major | t] (P == 0 returns without a launch);
+ *   syms fp64 (sumS,12) + s_offsets int32 (M+1) on the device (cp_bop_errors' layout; only the rotation part of a row is read) with
+ *   s_offsets_host, the same M + 1 words in host memory, checked before anything is launched: [0] == 0 and ascending (an empty set
+ *   is allowed); mesh_ids int32 (P) on the device, or NULL with M == 1; mesh_ids_host: the same P words in host memory, or NULL
+ *   (then an id outside [0, M) is met on the device: that pair gets re = cos = NaN, index -1).  syms == NULL: no symmetries, the
+ *   plain re / te (its four companions must be NULL too, M is not read).
+ * Candidates in order: index -1 is R_b itself, then R_b . S_k, k = 0 .. S-1; cos_k = 1 + 0.5 sum((R_a - R_cand) o cof R_cand) /
+ * det R_cand; re_k = degrees(acos(clamp(cos_k, -1, 1))), NaN where cos_k is not finite; the winner is the FIRST candidate with the
+ * smallest re_k (strict <, NaN never replaces, a NaN plain candidate stays).  te = |t_b - t_a|.
+ * Outputs: re fp64 (P) in degrees, te fp64 (P), cos fp64 (P) or NULL (the winner's cos_k before the clamp), index int32 (P) or NULL.
+ * CP_ERR_INVALID: a null pointer, P < 0, M < 1, offsets that do not start at 0 or do not ascend, a host mesh id outside [0, M),
+ * companions of a table that is not given.  CP_ERR_ALIGN: a pointer not aligned to its element. */
+int cp_pose_rete(cp_stream_t stream, const double* pose_a, const double* pose_b, int P, const double* syms, const int32_t* s_offsets,
+                 const int32_t* s_offsets_host, int M, const int32_t* mesh_ids, const int32_t* mesh_ids_host, double* re, double* te,
+                 double* cos_out, int32_t* index);
+/* The pass counts of the reference's LM report (test_lm.py:306-327) per object slot: counts int32 (n_obj, cp_rete_pass_columns() = 10)
+ * = [n, adx < 0.02 d, adx < 0.05 d, adx < 0.1 d, re < 2 & te < 20, re < 5 & te < 50, re < 2, re < 5, te < 20, te < 50], every `<`
+ * strict, a NaN error counted as 10000 first.  re, te, adx, diam fp64 (P), slot int32 (P) on the device; slot_host: the same P words
+ * in host memory, or NULL (then a slot outside [0, n_obj) is skipped on the device).  counts is zeroed first (one hipMemsetAsync),
+ * then one launch: LDS partial sums per workgroup, integer atomics after them -- the result does not depend on the order.
+ * CP_ERR_INVALID: a null pointer, P < 0, n_obj outside 1..256, a host slot outside [0, n_obj). */
+int cp_rete_pass_columns(void);
+int cp_rete_pass_counts(cp_stream_t stream, const double* re, const double* te, const double* adx, const double* diam,
+                        const int32_t* slot, const int32_t* slot_host, int P, int n_obj, int32_t* counts);
+
 /* Pose errors on the device (next-row N5; reference metric.py:8-18 -> bop_toolkit_lib/pose_error.py:147-184, called once per image
  * by test.py:378-427 / test_lm.py:300-321): ADD = mean_i |P_est(p_i) - P_gt(p_i)| and ADD-S / ADI = mean_i min_j |P_gt(p_i) - P_est(p_j)|
  * over an object's mesh vertices, for B poses at once.
