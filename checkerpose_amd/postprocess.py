@@ -357,14 +357,153 @@ def pose_covariance(info, sigma=None):
     return torch.where(ok[:, None, None], cov, torch.full_like(cov, float("nan")))
 
 
-def _check_refine(refine):
-    if refine not in (None, "lm"):
-        raise ValueError("refine must be None or 'lm', got %r" % (refine,))
+ICP_MAX_ITERS, ICP_GRID_MAX, ICP_RECORD, ICP_INFO = 64, 64, 18, 42        # csrc/icp_refine.hip
+_SAMPLE_KEYS = ("rect", "shape", "pixel", "depth", "face", "X", "N", "ok")
+
+
+def _check_grid(grid):
+    grid = int(grid)
+    if not 1 <= grid <= ICP_GRID_MAX:
+        raise ValueError("grid must be in 1..%d, got %r" % (ICP_GRID_MAX, grid))
+    return grid
+
+
+def surface_samples(R, t, cam_K, meshes, size, mesh_ids=None, grid=32):
+    """Stage A of refine_poses_icp (row N24) on its own: ONE raster pass of the P poses of `meshes` (a MeshSet with faces) on a frame of
+    size = (width, height), then per pose a lattice of at most grid x grid pixels over its projected rectangle inside the frame
+    (csrc/icp_refine.hip states the rule).  S = grid * grid slots per pose; slot j * nx + i is lattice pixel (i, j), slots beyond nx * ny
+    are empty.  -> dict of device tensors:
+      rect (P,4) int32 x0 y0 x1 y1 (-1 four times when empty); shape (P,2) int32 nx ny; pixel (P,S,2) int32; depth (P,S) f32:
+      metric.render_depth's value at the pixel; face (P,S) int32: the winning face, -1 = empty slot; X (P,S,3) f64 the model-space
+      point, N (P,S,3) f64 the face's unit normal towards the camera (NaN in empty slots); ok (P,) int32: 0 where the pose was not
+      rendered (a non-finite entry, a vertex at Z <= 0, a mesh id out of range)."""
+    from . import scene
+    grid = _check_grid(grid)
+    dev, poses, P = scene.mesh_poses(R, t, meshes)
+    K, k_stride = scene.camera(cam_K, P, dev, "P")
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, P, dev, meshes.sizes)
+    W, H = scene.frame_size(size)
+    verts, v_off = meshes.on(dev)
+    faces, f_off, _ = meshes.faces_on(dev)
+    S = grid * grid
+    out = dict(rect=torch.empty((P, 4), dtype=torch.int32, device=dev), shape=torch.empty((P, 2), dtype=torch.int32, device=dev),
+               pixel=torch.empty((P, S, 2), dtype=torch.int32, device=dev), depth=torch.empty((P, S), dtype=torch.float32, device=dev),
+               face=torch.empty((P, S), dtype=torch.int32, device=dev), X=torch.empty((P, S, 3), dtype=torch.float64, device=dev),
+               N=torch.empty((P, S, 3), dtype=torch.float64, device=dev), ok=torch.empty((P,), dtype=torch.int32, device=dev))
+    scratch = torch.empty(_abi.load().cp_surface_samples_scratch_bytes(P, vmax), dtype=torch.uint8, device=dev)
+    _abi.call("cp_surface_samples", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, H, W, P, vmax, grid,
+              *[out[k] for k in _SAMPLE_KEYS], scratch)
+    return out
+
+
+def refine_poses_icp(R, t, cam_K, meshes, depth, max_dist, image_ids=None, mesh_ids=None, status=None, grid=32, max_iters=20, step_tol=1e-6,
+                     min_pairs=6, inertia=1e-2, samples=None, return_records=False):
+    """Projective point-to-plane ICP of poses against the sensor's depth image on the device (row N24; opt-in -- the reference does not
+    refine): what a user with an RGB-D frame runs after an RGB-only estimate, whose error is largest along the viewing ray.  The rule
+    is this project's own (csrc/icp_refine.hip states it, tests/icp_stages.py restates it; parity with any ICP library UNPINNED):
+    surface samples of each mesh rendered ONCE at the input pose (surface_samples), re-associated with the depth pixel they project
+    to after every accepted step, point-to-plane residuals with the normals frozen per association, Levenberg-Marquardt with a step
+    bound and an absolute damping term.
+      R (P,3,3), t (P,3,1) / (P,3): the poses to start from (CUDA/HIP tensors); cam_K (3,3) / (P,3,3); meshes: a MeshSet with faces
+      (its diameters give rho = diameter / 2); depth (H,W) / (I,H,W) in the meshes' units with image_ids (P,) when poses share images
+      (as `depth_test` elsewhere); mesh_ids (P,) with several meshes; status (P,) or None: poses whose entry is 0 are left alone.
+      max_dist: a number or a (P,) tensor in the meshes' units, NO default: pairs farther apart than this are dropped (occluders,
+      background) and no step moves the object by more.  Nothing in the project or the reference fixes one; a fraction of the mesh
+      diameter (0.1 - 0.3) is a reasonable start, and it is the caller's choice.
+      grid in 1..64: the lattice per pose; max_iters in 1..64; step_tol > 0; min_pairs >= 6; inertia >= 0: the weight of the absolute
+      damping term inertia * n * diag(rho^2 x 3, 1 x 3) (UNPINNED design default 1e-2; 0 lets a box seen face-on slide along its faces);
+      samples: a surface_samples(...) result for THESE poses, so that several depth hypotheses share one render (grid is then its).
+    A box seen nearly face-on stays weakly constrained in the face's plane: that is point-to-plane's nature, not tuned away.
+    -> (R (P,3,3) f64, t (P,3,1) f64, refine_status (P,) int32, info[, records])
+       refine_status: 1 = an accepted step below step_tol, 2 = max_iters ran out, 3 = lambda passed 1e8 or fewer than min_pairs pairs
+       were left after a step, 0 = pass-through (the input pose, bitwise: status 0 given, a non-finite pose or cam_K, a pose that is not
+       rendered, fewer than min_pairs samples or pairs under the input pose);
+       info: dict of device tensors -- cost0, cost (P,) f64: sums of squared point-to-plane distances at the input / returned pose;
+       n_samples, n0, n (P,) int64: samples, pairs at the input pose, pairs at the returned pose; iters (P,) int64; H (P,6,6) f64: the
+       undamped J^T J at the returned pose over its pairs (rotation then translation); status = refine_status.  Pass-through rows hold
+       NaN in cost0, cost and H.
+       records (return_records=True): (P, max_iters, 18) f64, [lambda, n, c, c', accepted, s, R' (9), t' (3)] per executed iteration,
+       NaN where none ran."""
+    from . import scene
+    max_iters, min_pairs, step_tol, inertia = int(max_iters), int(min_pairs), float(step_tol), float(inertia)
+    if not 1 <= max_iters <= ICP_MAX_ITERS:
+        raise ValueError("max_iters must be in 1..%d for cp_icp_refine, got %r" % (ICP_MAX_ITERS, max_iters))
+    if not 0.0 < step_tol < float("inf"):
+        raise ValueError("step_tol must be a finite number > 0, got %r" % (step_tol,))
+    if min_pairs < 6:
+        raise ValueError("min_pairs must be >= 6, got %r" % (min_pairs,))
+    if not 0.0 <= inertia < float("inf"):
+        raise ValueError("inertia must be a finite number >= 0, got %r" % (inertia,))
+    grid = _check_grid(grid)
+    dev, poses, P = scene.mesh_poses(R, t, meshes)
+    if torch.is_tensor(max_dist):
+        scene.require_cuda("postprocess", max_dist)
+        if max_dist.numel() != P:
+            raise ValueError("max_dist must be a number or a (P,) tensor")
+        md = max_dist.reshape(P).to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        if not 0.0 < float(max_dist) < float("inf"):
+            raise ValueError("max_dist must be a finite number > 0 (in the meshes' units), got %r" % (max_dist,))
+        md = torch.full((P,), float(max_dist), dtype=torch.float64, device=dev)
+    if torch.is_tensor(depth):
+        scene.require_cuda("postprocess", depth)
+    if status is not None and (not torch.is_tensor(status) or tuple(status.shape) != (P,)):
+        raise ValueError("status must be a (P,) tensor or None")
+    if status is not None:
+        scene.require_cuda("postprocess", status)
+    K, k_stride = scene.camera(cam_K, P, dev, "P")
+    ids, _ = scene.mesh_ids_on(mesh_ids, P, dev, meshes.sizes)
+    images, img_ids, n_img = scene.depth_images(depth, image_ids, P, dev)
+    H, W = int(images.shape[1]), int(images.shape[2])
+    if samples is None:
+        samples = surface_samples(R, t, cam_K, meshes, (W, H), mesh_ids=mesh_ids, grid=grid)
+    else:
+        if not isinstance(samples, dict) or any(k not in samples for k in _SAMPLE_KEYS):
+            raise ValueError("samples must be the dict surface_samples returns")
+        scene.require_cuda("postprocess", *[samples[k] for k in _SAMPLE_KEYS])
+        S = int(samples["face"].shape[1]) if samples["face"].dim() == 2 else 0
+        if tuple(samples["face"].shape) != (P, S) or tuple(samples["X"].shape) != (P, S, 3) or tuple(samples["N"].shape) != (P, S, 3) or not 1 <= S <= ICP_GRID_MAX ** 2:
+            raise ValueError("samples do not belong to these %d poses" % P)
+    sX, sN, sF = samples["X"].contiguous(), samples["N"].contiguous(), samples["face"].contiguous()
+    if sX.dtype != torch.float64 or sN.dtype != torch.float64 or sF.dtype != torch.int32:
+        raise ValueError("samples must be the dict surface_samples returns")
+    S = int(sF.shape[1])
+    _, _, diam = meshes.faces_on(dev)
+    st_in = None if status is None else status.to(device=dev, dtype=torch.int32).contiguous()
+    pose = torch.empty(P, 12, dtype=torch.float64, device=dev)
+    rstatus = torch.empty(P, dtype=torch.int32, device=dev)
+    info = torch.empty(P, ICP_INFO, dtype=torch.float64, device=dev)
+    rec = torch.full((P, max_iters, ICP_RECORD), float("nan"), dtype=torch.float64, device=dev) if return_records else None
+    _abi.call("cp_icp_refine", dev, poses, K, k_stride, sX, sN, sF, S, images, img_ids, n_img, H, W, md, diam, len(meshes), ids, st_in,
+              max_iters, step_tol, min_pairs, inertia, P, pose, rstatus, info, rec)
+    out_info = dict(cost0=info[:, 0], cost=info[:, 1], n_samples=info[:, 2].long(), n0=info[:, 3].long(), n=info[:, 4].long(),
+                    iters=info[:, 5].long(), H=info[:, 6:].view(P, 6, 6), status=rstatus)
+    out = (pose[:, :9].view(P, 3, 3), pose[:, 9:].view(P, 3, 1), rstatus, out_info)
+    if return_records:
+        out += (rec,)
+    return out
+
+
+REFINES = (None, "lm", "icp", "lm+icp")
+
+
+def _check_refine(refine, allowed=(None, "lm")):
+    if refine not in allowed:
+        raise ValueError("refine must be %s, got %r" % (" or ".join("None" if a is None else repr(a) for a in allowed), refine))
+
+
+def _check_icp(refine, icp):
+    """estimate_poses' `icp` argument: required with an "icp" refinement, a dict with meshes, depth and max_dist"""
+    if refine in ("icp", "lm+icp"):
+        if not isinstance(icp, dict) or any(k not in icp for k in ("meshes", "depth", "max_dist")):
+            raise ValueError("refine=%r needs icp=dict(meshes=..., depth=..., max_dist=...[, mesh_ids=..., ...])" % (refine,))
+        if "image_ids" in icp or "status" in icp or "samples" in icp:
+            raise ValueError("icp must not name image_ids, status or samples: they are the call's img_index and the solver's status")
 
 
 def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
                    resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0, solver="epnp",
-                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None):
+                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None):
     """The inner loop of the reference's test.py (:198-330) for a whole batch without leaving the GPU: detection boxes on full uint8
     frames -> padded RoI crops (`padding_Bbox` + `get_roi`, bop_dataset_pytorch.py:344-354; preprocess.get_roi_batch) -> network forward
     (uint8 input, normalised on the device) -> correspondences from the crops' final boxes (`get_final_Bbox`; N2) -> EPnP + RANSAC (N4).
@@ -374,11 +513,15 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
       radius_graph(p3d_xyz) with spatial_coherence_weight and prog_max_iters iterations; obj_ids then also name each crop's graph.
       refine None (default): the solver's pose as it is; "lm" (row N22): refine_poses_lm over the solver's inliers at its defaults,
       with either solver -- the returned R, t are then the refined ones, inliers and status still the solver's.
+      "icp" (row N24): refine_poses_icp against the frames' depth, "lm+icp": N22 first, then N24.  Both need icp = a dict with
+      `meshes` (a MeshSet with faces, in the units of p3d_xyz), `depth` ((H,W) / (n_img,H,W)) and `max_dist`, and optionally `mesh_ids`
+      and refine_poses_icp's other keywords; each crop's image is the call's img_index.
     -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32 (0: identity fallback), final boxes (B,4) int array)"""
     from . import preprocess as PP
     if solver not in ("epnp", "gc"):
         raise ValueError("solver must be 'epnp' or 'gc', got %r" % (solver,))
-    _check_refine(refine)
+    _check_refine(refine, REFINES)
+    _check_icp(refine, icp)
     if solver == "gc" and graph is None:
         raise ValueError("solver='gc' needs graph=radius_graph(p3d_xyz)")
     if frames.dim() == 3:
@@ -397,8 +540,11 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
     else:
         R, t, inl, status = solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
                                              iterations=iterations, seed=seed)
-    if refine == "lm":
+    if refine in ("lm", "lm+icp"):
         R, t = refine_poses_lm(p3d_xyz, p2d, inl, cam_K, R, t, status=status)[:2]
+    if refine in ("icp", "lm+icp"):
+        kw = {k: v for k, v in icp.items() if k not in ("meshes", "depth", "max_dist")}
+        R, t = refine_poses_icp(R, t, cam_K, icp["meshes"], icp["depth"], icp["max_dist"], image_ids=img_index, status=status, **kw)[:2]
     return R, t, inl, status, final
 
 

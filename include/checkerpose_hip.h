@@ -621,6 +621,42 @@ int cp_pnp_refine_lm(cp_stream_t stream, const float* p3d, long long p3d_bstride
                      const int32_t* status_in, int max_iters, double step_tol, double* pose_out, int32_t* status_out,
                      double* info, double* records);
 
+/* Projective point-to-plane ICP of poses against a depth image (row N24): the depth refinement of an RGB-only pose.  The reference
+ * does not refine; opt-in, the rule is this project's own (stated in full at the top of csrc/icp_refine.hip, restated in numpy by
+ * tests/icp_stages.py); parity with any ICP library is UNPINNED.
+ * cp_surface_samples (stage A): one raster pass of P poses (poses, cam_K, k_stride, verts .. Vmax, H, W as cp_render_depth), then per
+ *   pose a lattice of at most grid x grid (grid in 1..64) pixels over its vertex rectangle inside the frame; S = grid * grid slots.
+ *   Outputs: rect int32 (P,4) x0 y0 x1 y1 (-1 four times when empty), shape int32 (P,2) nx ny, pixel int32 (P,S,2) (-1 -1 beyond
+ *   nx * ny), depth fp32 (P,S) (cp_render_depth's bits at the pixel, 0 = not covered), face int32 (P,S) (-1 = empty slot), X, N fp64
+ *   (P,S,3) the sample's model-space point and unit face normal towards the camera (NaN in an empty slot), ok int32 (P) (0: not
+ *   rendered).  scratch: cp_surface_samples_scratch_bytes(P, Vmax) bytes, 16-byte aligned.  Four launches, no atomics but the
+ *   scaffold's integer rectangle merge.
+ * cp_icp_refine (stages B and C): ONE launch, one workgroup per pose, fp64 without contraction.
+ *   pose_in fp64 (P,12) = [R row-major | t]; cam_K fp64 with k_stride 0 or 9; X, N, face: cp_surface_samples' outputs with S slots per
+ *   pose (1..4096); depth fp32 (I,H,W) the sensor's images, image_ids int32 (P) or NULL with I == 1; max_dist fp64 (P); diameters fp64
+ *   (M) with mesh_ids int32 (P) or NULL with M == 1 (rho = diameter / 2); status_in int32 (P) or NULL: 0 = leave this pose alone;
+ *   max_iters in 1..64; step_tol > 0, finite; min_pairs >= 6; inertia >= 0, finite.
+ *   Outputs: pose_out fp64 (P,12) (bitwise the last accepted trial, or pose_in; pose_out == pose_in is allowed, a partial overlap is
+ *   refused); status_out int32 (P): 1 step rule, 2 max_iters, 3 lambda > 1e8 or fewer than min_pairs pairs after a step, 0 =
+ *   pass-through; info fp64 (P, cp_icp_refine_info_doubles() = 42) = [c at the input pose, c at the returned pose, samples, pairs at
+ *   the input pose, pairs at the returned pose, iterations, undamped H at the returned pose (36; w then v)] (status 0: NaN but for
+ *   the counts); records fp64 (P, max_iters, cp_icp_refine_record_doubles() = 18) or NULL: per executed iteration [lambda used, n, c,
+ *   c', accepted 0/1, s, R' (9), t' (3)]; slots of iterations that did not run are never written.
+ * CP_ERR_INVALID: a null pointer, the mesh / view / image argument rules of the raster family, a grid, S, max_iters, step_tol,
+ * min_pairs or inertia outside its range, a partial overlap of the poses; CP_ERR_ALIGN; CP_ERR_RANGE: H * W >= 2^31, too many blocks. */
+size_t cp_surface_samples_scratch_bytes(int P, int Vmax);
+int cp_surface_samples(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                       const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                       int H, int W, int P, int Vmax, int grid, int32_t* rect, int32_t* shape, int32_t* pixel, float* depth,
+                       int32_t* face, double* X, double* N, int32_t* ok, void* scratch);
+int cp_icp_refine_record_doubles(void);
+int cp_icp_refine_info_doubles(void);
+int cp_icp_refine(cp_stream_t stream, const double* pose_in, const double* cam_K, int k_stride, const double* X, const double* N,
+                  const int32_t* face, int S, const float* depth, const int32_t* image_ids, int I, int H, int W,
+                  const double* max_dist, const double* diameters, int M, const int32_t* mesh_ids, const int32_t* status_in,
+                  int max_iters, double step_tol, int min_pairs, double inertia, int P, double* pose_out, int32_t* status_out,
+                  double* info, double* records);
+
 /* Rotation / translation errors, symmetry-aware (row N23): bop_toolkit_lib.pose_error.re / .te (pose_error.py:187-214) for P pose
  * pairs, the rotation error optionally against the closest symmetric copy of the second pose (checkerpose/test_lm.py:33-55,
  * get_closest_rot).  The rule is stated in full at the top of csrc/rete.hip and restated in numpy by tests/rete_stages.py.  One
