@@ -208,6 +208,11 @@ SIGNATURES = {
     "cp_icp_refine_info_doubles": (_I, []),
     "cp_icp_refine": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _I, C.c_double, _I, C.c_double, _I,
                            _P, _P, _P, _P]),
+    "cp_lift_correspondences": (_I, [_P, _P, _P, _I, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "cp_pose_depth_ransac_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
+    "cp_pose_depth_record_doubles": (_I, []),
+    "cp_pose_depth_ransac": (_I, [_P, _P, _L, _P, _P, _I, _P, _L, _P, _P, _I, _I, _I, _I, _I, C.c_double, _P, _I, C.c_uint32,
+                                  _P, _P, _P, _P]),
     "cp_pose_rete": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cp_rete_pass_columns": (_I, []),
     "cp_rete_pass_counts": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),

@@ -229,6 +229,67 @@ __device__ void procrustes_rotation(const double* m, double* R) {
   if (det < 0.0) { R[6] = -R[6]; R[7] = -R[7]; R[8] = -R[8]; }
 }
 
+// R = the PROPER rotation nearest m (row-major 3 x 3; absolute orientation of pose_depth.hip, row N25): with m = U S V^T by the same
+// one-sided Jacobi, R = [u1 | u2 | det(V) (u1 x u2)] V^T.  The third direction is always the cross product of the two strongest, so a
+// rank-2 m (three points, coplanar points) and a full-rank one share one formula, det R = +1 by construction, and a reflection flips the
+// WEAKEST direction (procrustes_rotation negates R's third row instead: epnp.cpp's rule, which N4 / N17 / N22 keep).  Returns the rank
+// found, 3 or 2, or 0 -- R unwritten -- when the second singular value is not above 1e-12 of the first (or m is not finite).
+// Every index below is a compile-time constant after unrolling: the matrices stay in registers (no scratch).
+__device__ __forceinline__ int nearest_rotation(const double* m, double* R) {
+  double a[9], v[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) a[i] = m[i];
+  for (int sweep = 0; sweep < 40; ++sweep) {
+    bool rotated = false;
+#pragma unroll
+    for (int pq = 0; pq < 3; ++pq) {
+      const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;   // (0,1), (0,2), (1,2)
+      double al = 0, be = 0, ga = 0;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) { al += a[3 * i + p] * a[3 * i + p]; be += a[3 * i + q] * a[3 * i + q]; ga += a[3 * i + p] * a[3 * i + q]; }
+      if (fabs(ga) <= 1e-16 * sqrt(al * be) || ga == 0.0) continue;
+      rotated = true;
+      const double zeta = (be - al) / (2.0 * ga);
+      const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+      const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double aip = a[3 * i + p], aiq = a[3 * i + q];
+        a[3 * i + p] = c * aip - s * aiq; a[3 * i + q] = s * aip + c * aiq;
+        const double vip = v[3 * i + p], viq = v[3 * i + q];
+        v[3 * i + p] = c * vip - s * viq; v[3 * i + q] = s * vip + c * viq;
+      }
+    }
+    if (!rotated) break;
+  }
+  double sg[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) sg[j] = sqrt(a[j] * a[j] + a[3 + j] * a[3 + j] + a[6 + j] * a[6 + j]);
+#pragma unroll
+  for (int pq = 0; pq < 3; ++pq) {                           // columns by descending sigma: compare-swaps (0,1), (0,2), (1,2)
+    const int p = pq == 2 ? 1 : 0, q = pq == 0 ? 1 : 2;
+    if (sg[q] > sg[p]) {
+      double tmp = sg[p]; sg[p] = sg[q]; sg[q] = tmp;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        tmp = a[3 * i + p]; a[3 * i + p] = a[3 * i + q]; a[3 * i + q] = tmp;
+        tmp = v[3 * i + p]; v[3 * i + p] = v[3 * i + q]; v[3 * i + q] = tmp;
+      }
+    }
+  }
+  if (!(sg[1] > 1e-12 * sg[0])) return 0;
+  const double i0 = 1.0 / sg[0], i1 = 1.0 / sg[1];
+  const double u0[3] = {a[0] * i0, a[3] * i0, a[6] * i0}, u1[3] = {a[1] * i1, a[4] * i1, a[7] * i1};
+  const double dv = v[0] * (v[4] * v[8] - v[5] * v[7]) - v[1] * (v[3] * v[8] - v[5] * v[6]) + v[2] * (v[3] * v[7] - v[4] * v[6]);
+  const double sgn = dv >= 0.0 ? 1.0 : -1.0;
+  const double u2[3] = {sgn * (u0[1] * u1[2] - u0[2] * u1[1]), sgn * (u0[2] * u1[0] - u0[0] * u1[2]), sgn * (u0[0] * u1[1] - u0[1] * u1[0])};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = u0[i] * v[3 * j] + u1[i] * v[3 * j + 1] + u2[i] * v[3 * j + 2];
+  return sg[2] <= 1e-12 * sg[0] ? 2 : 3;
+}
+
 // ---- exactly four valid correspondences: OpenCV's solvePnPRansac runs no RANSAC there (calib3d solvepnp.cpp: model_points ==
 // npoints) but solvePnP with its P3P kernel -- P3P on the first three points, the fourth picks among the up-to-four poses by its
 // reprojection error; all four are reported as inliers.  P3P here: Grunert's quartic in v = s3 / s1 (Haralick et al., IJCV 1994),

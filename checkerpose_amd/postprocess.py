@@ -484,6 +484,109 @@ def refine_poses_icp(R, t, cam_K, meshes, depth, max_dist, image_ids=None, mesh_
     return out
 
 
+DEPTH_POSE_MAX_ITERS, DEPTH_POSE_NMAX, DEPTH_POSE_RECORD, DEPTH_POSE_STEPS = 256, 4096, 14, 4        # csrc/pose_depth.hip
+
+
+def _depth_pose_inputs(who, p2d, valid, cam_K, depth, image_ids, column):
+    """the arguments lift_correspondences and solve_pose_depth share -> (dev, B, N, p2d, valid, K, K stride, images, image ids, I, H, W)"""
+    from . import scene
+    if not torch.is_tensor(p2d) or p2d.dim() != 3 or p2d.shape[2] != 2:
+        raise ValueError("p2d must be a (B,N,2) tensor")
+    B, N, _ = p2d.shape
+    if not 1 <= N <= DEPTH_POSE_NMAX:
+        raise ValueError("p2d: N must be in 1..%d for %s, got %d" % (DEPTH_POSE_NMAX, who, N))
+    if not torch.is_tensor(valid) or tuple(valid.shape) != (B, N, 3) or valid.dtype != torch.uint8 or not 0 <= int(column) < 3:
+        raise ValueError("valid must be the (B,N,3) uint8 tensor of correspondences(), column in 0..2")
+    scene.require_cuda("postprocess", p2d, valid)
+    if torch.is_tensor(depth):
+        scene.require_cuda("postprocess", depth)
+    dev = p2d.device
+    K = torch.as_tensor(cam_K, dtype=torch.float32, device=dev).contiguous()
+    if K.shape[-2:] != (3, 3) or K.dim() not in (2, 3) or (K.dim() == 3 and K.shape[0] != B):
+        raise ValueError("cam_K must be (3,3) / (B,3,3)")
+    images, ids, n_img = scene.depth_images(depth, image_ids, B, dev)
+    return (dev, B, N, p2d.contiguous().float(), valid.contiguous(), K, 9 if K.dim() == 3 else 0, images, ids, n_img,
+            int(images.shape[1]), int(images.shape[2]))
+
+
+def lift_correspondences(p2d, valid, cam_K, depth, image_ids=None, column=0):
+    """Stage A of solve_pose_depth (row N25) on its own: each valid correspondence lifted to a camera-frame point by the sensor's depth
+    under it.  p2d (B,N,2), valid (B,N,3) from correspondences(), column as solve_pnp_ransac; cam_K (3,3) / (B,3,3); depth (H,W) /
+    (I,H,W) in the keypoints' units with image_ids (B,) when crops share images (as `depth_test` elsewhere).  A keypoint with
+    (u, v) = its p2d reads z = depth[floor v, floor u]; it is dropped outside the frame or where z is not finite or <= 0, else
+    Q = ((u - cx) / fx z, (v - cy) / fy z, z): the ray through (u, v) as given, not through the pixel centre.
+    -> (Q (B,N,3) f32, 0 where not lifted; lifted (B,N) bool; n_lifted (B,) int32)"""
+    dev, B, N, p2, va, K, ks, images, ids, n_img, H, W = _depth_pose_inputs("cp_lift_correspondences", p2d, valid, cam_K, depth, image_ids, column)
+    Q = torch.empty(B, N, 3, dtype=torch.float32, device=dev)
+    lifted = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    n_lifted = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:                                            # nothing to launch (an empty tensor has no address to hand over)
+        return Q, lifted.bool(), n_lifted
+    _abi.call("cp_lift_correspondences", dev, p2, va.data_ptr() + int(column), 3, K, ks, images, ids, n_img, H, W, B, N, Q, lifted, n_lifted)
+    return Q, lifted.bool(), n_lifted
+
+
+def solve_pose_depth(p3d_xyz, p2d, valid, cam_K, depth, dist_threshold, image_ids=None, column=0, iterations=150, seed=0,
+                     return_hypotheses=False):
+    """Pose from depth-lifted correspondences on the device (row N25; opt-in -- the reference uses no depth at test time): with the
+    sensor's depth under each correspondence the 2-D -- 3-D problem of solve_pnp_ransac becomes a 3-D -- 3-D one, solved by RANSAC over
+    three-pair absolute orientation and a least-squares fit over the inliers, re-evaluated at most 3 times while the inlier set grows.
+    No mesh, no start pose.  The rule is this project's own (csrc/pose_depth.hip states it, tests/depth_pose_stages.py restates it).
+      p3d_xyz, p2d, valid, column, cam_K, iterations (1..256), seed as solve_pnp_ransac; depth, image_ids as lift_correspondences.
+      dist_threshold: a number or a (B,) tensor in the keypoints' units, NO default: a lifted point farther than this from the posed
+      model point is an outlier (occluders, background, wrong codes).  Nothing in the project or the reference fixes one; the depth
+      noise plus the model-space size of a grid cell is a reasonable start, and it is the caller's choice.
+    -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32: 0 = the identity fallback -- fewer than 3 lifted
+       keypoints, no hypothesis with 3 inliers, or a threshold entry that is not positive and finite)
+    return_hypotheses=True adds a fifth value, the solver's records as a dict of device tensors: hypotheses (B,iterations,14) f64
+    [inlier count or -1, unused, R row-major, t], steps (B,4,14) f64 [the step's inlier count, accepted, R, t after the step], NaN where
+    the solver wrote nothing; Q, lifted (uint8), n_lifted: stage A's outputs."""
+    iterations = int(iterations)
+    if not 0 < iterations <= DEPTH_POSE_MAX_ITERS:        # no silent clamp
+        raise ValueError("iterations must be in 1..%d for cp_pose_depth_ransac, got %r" % (DEPTH_POSE_MAX_ITERS, iterations))
+    dev, B, N, p2, va, K, ks, images, ids, n_img, H, W = _depth_pose_inputs("cp_pose_depth_ransac", p2d, valid, cam_K, depth, image_ids, column)
+    thr_b, thr = None, 0.0
+    if torch.is_tensor(dist_threshold):
+        if not dist_threshold.is_cuda:
+            raise RuntimeError("checkerpose_amd.postprocess: CUDA/HIP tensors required (no CPU fallback)")
+        if dist_threshold.numel() != B:
+            raise ValueError("dist_threshold must be a number or a (B,) tensor")
+        thr_b = dist_threshold.reshape(B).to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        if dist_threshold is None or not 0.0 < float(dist_threshold) < float("inf"):
+            raise ValueError("dist_threshold must be a finite number > 0 (in the keypoints' units), got %r" % (dist_threshold,))
+        thr = float(dist_threshold)
+    p3 = torch.as_tensor(p3d_xyz, dtype=torch.float32, device=dev).contiguous()
+    if p3.shape[-2:] != (N, 3) or p3.dim() not in (2, 3) or (p3.dim() == 3 and p3.shape[0] != B):
+        raise ValueError("p3d_xyz must be (N,3) / (B,N,3)")
+    pose = torch.empty(B, 12, dtype=torch.float64, device=dev)
+    inl = torch.empty(B, N, dtype=torch.uint8, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev)
+    if B == 0:                                            # nothing to launch
+        out = (pose[:, :9].view(0, 3, 3), pose[:, 9:].view(0, 3, 1), inl.bool(), status)
+        if return_hypotheses:
+            out += (dict(hypotheses=pose.new_empty(0, iterations, DEPTH_POSE_RECORD), steps=pose.new_empty(0, DEPTH_POSE_STEPS, DEPTH_POSE_RECORD),
+                         Q=p2.new_empty(0, N, 3), n_lifted=status.new_empty(0), lifted=inl.new_empty(0, N)),)
+        return out
+    nbytes = _abi.load().cp_pose_depth_ransac_scratch_bytes(B, N, iterations)
+    o_steps = B * iterations * DEPTH_POSE_RECORD
+    o_q = o_steps + B * DEPTH_POSE_STEPS * DEPTH_POSE_RECORD
+    scratch = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    if return_hypotheses:
+        scratch[:o_q] = float("nan")
+    _abi.call("cp_pose_depth_ransac", dev, p3, 3 * N if p3.dim() == 3 else 0, p2, va.data_ptr() + int(column), 3, K, ks, images, ids, n_img,
+              H, W, B, N, thr, thr_b, iterations, int(seed) & 0xFFFFFFFF, pose, inl, status, scratch)
+    out = (pose[:, :9].view(B, 3, 3), pose[:, 9:].view(B, 3, 1), inl.bool(), status)
+    if return_hypotheses:
+        raw = scratch.view(torch.uint8)
+        b_q, b_n = o_q * 8, o_q * 8 + B * N * 12
+        out += (dict(hypotheses=scratch[:o_steps].view(B, iterations, DEPTH_POSE_RECORD),
+                     steps=scratch[o_steps:o_q].view(B, DEPTH_POSE_STEPS, DEPTH_POSE_RECORD),
+                     Q=raw[b_q:b_n].view(torch.float32).view(B, N, 3), n_lifted=raw[b_n:b_n + 4 * B].view(torch.int32),
+                     lifted=raw[b_n + 4 * B:b_n + 4 * B + B * N].view(B, N)),)
+    return out
+
+
 REFINES = (None, "lm", "icp", "lm+icp")
 
 
@@ -503,7 +606,8 @@ def _check_icp(refine, icp):
 
 def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
                    resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0, solver="epnp",
-                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None):
+                   graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None, depth=None,
+                   dist_threshold=None):
     """The inner loop of the reference's test.py (:198-330) for a whole batch without leaving the GPU: detection boxes on full uint8
     frames -> padded RoI crops (`padding_Bbox` + `get_roi`, bop_dataset_pytorch.py:344-354; preprocess.get_roi_batch) -> network forward
     (uint8 input, normalised on the device) -> correspondences from the crops' final boxes (`get_final_Bbox`; N2) -> EPnP + RANSAC (N4).
@@ -511,6 +615,9 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
       p3d_xyz (N,3) / (B,N,3) model keypoints in original units; cam_K (3,3) / (B,3,3); obj_ids for the LM shared estimator.
       solver "epnp" (default): solve_pnp_ransac; "gc": solve_pnp_gc (row N17, the `--use_progressivex` path) over `graph` =
       radius_graph(p3d_xyz) with spatial_coherence_weight and prog_max_iters iterations; obj_ids then also name each crop's graph.
+      "depth" (row N25): solve_pose_depth over the correspondences lifted by `depth` ((H,W) / (n_img,H,W), in the units of p3d_xyz) with
+      `dist_threshold` (no default) and `iterations`; each crop's image is the call's img_index.  Both keywords are required with
+      "depth" and refused with the other solvers; reproj_threshold plays no part.
       refine None (default): the solver's pose as it is; "lm" (row N22): refine_poses_lm over the solver's inliers at its defaults,
       with either solver -- the returned R, t are then the refined ones, inliers and status still the solver's.
       "icp" (row N24): refine_poses_icp against the frames' depth, "lm+icp": N22 first, then N24.  Both need icp = a dict with
@@ -518,8 +625,12 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
       and refine_poses_icp's other keywords; each crop's image is the call's img_index.
     -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32 (0: identity fallback), final boxes (B,4) int array)"""
     from . import preprocess as PP
-    if solver not in ("epnp", "gc"):
-        raise ValueError("solver must be 'epnp' or 'gc', got %r" % (solver,))
+    if solver not in ("epnp", "gc", "depth"):
+        raise ValueError("solver must be 'epnp', 'gc' or 'depth', got %r" % (solver,))
+    if solver == "depth" and (depth is None or dist_threshold is None):
+        raise ValueError("solver='depth' needs depth=... (the frames' depth images) and dist_threshold=... (no default)")
+    if solver != "depth" and (depth is not None or dist_threshold is not None):
+        raise ValueError("depth and dist_threshold belong to solver='depth', got solver=%r" % (solver,))
     _check_refine(refine, REFINES)
     _check_icp(refine, icp)
     if solver == "gc" and graph is None:
@@ -537,6 +648,9 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
         R, t, inl, status = solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=obj_ids if graph.M > 1 else None,
                                          column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
                                          spatial_coherence_weight=spatial_coherence_weight, iterations=prog_max_iters, seed=seed)
+    elif solver == "depth":
+        R, t, inl, status = solve_pose_depth(p3d_xyz, p2d, valid, cam_K, depth, dist_threshold, image_ids=img_index,
+                                             column=1 if check_seg else 0, iterations=iterations, seed=seed)
     else:
         R, t, inl, status = solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
                                              iterations=iterations, seed=seed)

@@ -657,6 +657,41 @@ int cp_icp_refine(cp_stream_t stream, const double* pose_in, const double* cam_K
                   int max_iters, double step_tol, int min_pairs, double inertia, int P, double* pose_out, int32_t* status_out,
                   double* info, double* records);
 
+/* Pose from depth-lifted correspondences (row N25): RANSAC over three-pair absolute orientation with a local optimisation, for an
+ * RGB-D frame resident on the device.  The reference uses no depth at test time; opt-in, the rule is this project's own (stated in
+ * full at the top of csrc/pose_depth.hip, restated in numpy by tests/depth_pose_stages.py); parity with any library is UNPINNED.
+ *   p3d, p3d_bstride, p2d, valid, valid_stride, cam_K (fp32), K_bstride, B, N, seed, pose, inliers, status as cp_pnp_ransac
+ *   (N <= 4096; B == 0 returns without a launch); depth fp32 (I,H,W) the sensor's images in the keypoints' units; image_ids int32 (B)
+ *   names each crop's image, NULL = image 0 for all when I == 1, image b for crop b when I == B (anything else is refused); an id
+ *   outside 0..I-1 lifts nothing.
+ * cp_lift_correspondences (stage A; one memset and one launch): a valid keypoint with (u, v) = its p2d reads z = depth[image, floor v,
+ *   floor u]; it is dropped outside the frame or when z is not finite or <= 0, else Q = ((u - cx) / fx z, (v - cy) / fy z, z) in fp64,
+ *   rounded once.  Q fp32 (B,N,3) (0 where dropped), lifted uint8 (B,N), n_lifted int32 (B).
+ * cp_pose_depth_ransac (stage A into the scratch, then ONE launch, one workgroup per crop, fp64 without contraction): over the n
+ *   lifted keypoints, hypotheses from 3 distinct positions (the hash sampler of cp_pnp_ransac with m = 3) in rounds of 64 with OpenCV's
+ *   stopping rule between them (sample size 3); a sample whose model points are collinear (|e1 x e2|^2 <= 1e-12 (max squared edge)^2) or
+ *   whose cross-covariance has rank < 2 is degenerate; inliers: |R X + t - Q|^2 <= threshold^2; the winner has the most inliers (>= 3),
+ *   first on ties; then the least-squares pose over its inliers, re-evaluated at most 3 times while the inlier set grows.  n < 3, no
+ *   winner, or a per-crop threshold that is not positive and finite: the identity with status 0 and no inliers.
+ *   dist_thresholds fp64 (B) on the device or NULL = dist_threshold (a number, positive and finite) for all; iterations in 1..256.
+ *   scratch: cp_pose_depth_ransac_scratch_bytes(B, N, iterations) bytes (0 = bad arguments), 8-byte aligned; what the call leaves is
+ *   part of the interface, at byte offsets: 0: hypothesis records, cp_pose_depth_record_doubles() = 14 doubles at (b * iterations + h)
+ *   * 14 = [count or -1, unused and never written, R row-major, t] (pose only when count >= 0; records of rounds the stopping rule cut
+ *   off, and of crops that fell back before the rounds, unwritten); B*iterations*14*8: 4 step records of 14 doubles per crop = [the
+ *   step's inlier count, accepted 0/1, R, t of the state after the step] (step 0: the first fit; unwritten where none ran); then Q fp32
+ *   (B,N,3), n_lifted int32 (B), lifted uint8 (B,N): stage A's outputs.
+ * CP_ERR_INVALID: a null pointer, a size, stride, iteration count or threshold outside its range, several images without ids;
+ * CP_ERR_ALIGN; CP_ERR_RANGE: H * W >= 2^31, B >= 2^24. */
+int cp_lift_correspondences(cp_stream_t stream, const float* p2d, const uint8_t* valid, int valid_stride, const float* cam_K,
+                            long long K_bstride, const float* depth, const int32_t* image_ids, int I, int H, int W, int B, int N,
+                            float* Q, uint8_t* lifted, int32_t* n_lifted);
+size_t cp_pose_depth_ransac_scratch_bytes(int B, int N, int iterations);
+int cp_pose_depth_record_doubles(void);
+int cp_pose_depth_ransac(cp_stream_t stream, const float* p3d, long long p3d_bstride, const float* p2d, const uint8_t* valid,
+                         int valid_stride, const float* cam_K, long long K_bstride, const float* depth, const int32_t* image_ids,
+                         int I, int H, int W, int B, int N, double dist_threshold, const double* dist_thresholds, int iterations,
+                         uint32_t seed, double* pose, uint8_t* inliers, int32_t* status, void* scratch);
+
 /* Rotation / translation errors, symmetry-aware (row N23): bop_toolkit_lib.pose_error.re / .te (pose_error.py:187-214) for P pose
  * pairs, the rotation error optionally against the closest symmetric copy of the second pose (checkerpose/test_lm.py:33-55,
  * get_closest_rot).  The rule is stated in full at the top of csrc/rete.hip and restated in numpy by tests/rete_stages.py.  One
