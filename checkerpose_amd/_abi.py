@@ -213,6 +213,9 @@ SIGNATURES = {
     "cp_pose_depth_record_doubles": (_I, []),
     "cp_pose_depth_ransac": (_I, [_P, _P, _L, _P, _P, _I, _P, _L, _P, _P, _I, _I, _I, _I, _I, C.c_double, _P, _I, C.c_uint32,
                                   _P, _P, _P, _P]),
+    "cp_verify_poses_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_verify_poses": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P, C.c_double, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_select_poses": (_I, [_P, _P, _P, _I, _I, _P]),
     "cp_pose_rete": (_I, [_P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cp_rete_pass_columns": (_I, []),
     "cp_rete_pass_counts": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P]),

@@ -587,6 +587,102 @@ def solve_pose_depth(p3d_xyz, p2d, valid, cam_K, depth, dist_threshold, image_id
     return out
 
 
+VERIFY_MAX_PIXELS, VERIFY_CMAX = 1 << 24, 64        # csrc/pose_verify.hip
+VERIFY_COUNTS = ("n_model", "n_missing", "n_match", "n_occluded", "n_through", "sum_q")
+VERIFY_LABELS = ("none", "match", "occluded", "through", "missing")        # the label map's values 0..4
+
+
+def verify_poses(R, t, cam_K, meshes, depth, tau, image_ids=None, mesh_ids=None, status=None, occlusion_weight=1.0, return_labels=False):
+    """Hypothesis verification of poses against the sensor's depth image on the device (row N26; opt-in -- the reference does not
+    verify): each pose is rendered and compared pixel by pixel with what the sensor saw, inside one tile kernel -- no depth frame is
+    stored.  The rule is this project's own (csrc/pose_verify.hip states it, tests/verify_stages.py restates it).  With D the pose's
+    render (metric.render_depth's bits) and S the sensor's depth, every pixel with D > 0 is a model pixel and is
+      missing (S not finite or <= 0) | match (|S - D| <= tau) | occluded (S - D < -tau: something in front of the model) |
+      through (S - D > tau: the sensor saw past the model's surface);
+    a match also adds q = min(63, int(64 |S - D| / tau)) to sum_q (fp32).  fit = n_match - sum_q / 64,
+    den = n_match + n_through + occlusion_weight n_occluded, score = fit / den in [0, 1]: a per-pose confidence that comes from the pose.
+      R (P,3,3), t (P,3,1) / (P,3): CUDA/HIP tensors; cam_K (3,3) / (P,3,3); meshes: a MeshSet with faces; depth (H,W) / (I,H,W) in the
+      meshes' units with image_ids (P,) when poses share images (as `depth_test` elsewhere; H W <= 2^24); mesh_ids (P,) with several
+      meshes; status (P,) or None: a pose whose entry is 0 (the solvers' identity fallback) is no candidate.
+      tau: a number or a (P,) tensor in the meshes' units, NO default: the depth tolerance.  Nothing in the project or the reference
+      fixes one; the sensor's noise plus the pose error still to be accepted is a reasonable start (BOP's VSD uses 20 mm), and it is the
+      caller's choice.  occlusion_weight in [0, 1] (default 1: every measured model pixel that does not support the pose counts against
+      it; lower it where occluders are expected).
+    -> (score (P,) f64, info[, labels (P,H,W) uint8: 0 none, 1 match, 2 occluded, 3 through, 4 missing])
+       info: dict of device tensors -- n_model, n_missing, n_match, n_occluded, n_through, sum_q (P,) int32; ok (P,) bool; fit, den (P,)
+       f64.  score is NaN with ok False when den == 0 or the pose is not counted (all counts 0): a non-finite pose or cam_K, a vertex at
+       Z <= 0, an image or mesh id out of range, status 0, a tau entry that as float32 is not positive and finite.  Every output is a
+       function of integer sums: bitwise the same for a pose alone or in a batch, with or without labels."""
+    from . import scene
+    occlusion_weight = float(occlusion_weight)
+    if not 0.0 <= occlusion_weight <= 1.0:
+        raise ValueError("occlusion_weight must be in [0, 1], got %r" % (occlusion_weight,))
+    if not torch.is_tensor(tau) and (tau is None or not 0.0 < float(tau) < float("inf")):
+        raise ValueError("tau must be a finite number > 0 (in the meshes' units), got %r" % (tau,))
+    dev, poses, P = scene.mesh_poses(R, t, meshes)
+    if torch.is_tensor(tau):
+        scene.require_cuda("postprocess", tau)
+        if tau.numel() != P:
+            raise ValueError("tau must be a number or a (P,) tensor")
+        tau_d = tau.reshape(P).to(device=dev, dtype=torch.float64).contiguous()
+    else:
+        tau_d = torch.full((P,), float(tau), dtype=torch.float64, device=dev)
+    if torch.is_tensor(depth):
+        scene.require_cuda("postprocess", depth)
+    if status is not None and (not torch.is_tensor(status) or tuple(status.shape) != (P,)):
+        raise ValueError("status must be a (P,) tensor or None")
+    if status is not None:
+        scene.require_cuda("postprocess", status)
+    K, k_stride = scene.camera(cam_K, P, dev, "P")
+    ids, (vmax,) = scene.mesh_ids_on(mesh_ids, P, dev, meshes.sizes)
+    images, img_ids, n_img = scene.depth_images(depth, image_ids, P, dev)
+    H, W = int(images.shape[1]), int(images.shape[2])
+    if H * W > VERIFY_MAX_PIXELS:
+        raise ValueError("depth: H * W must be <= 2^24 for cp_verify_poses (its sums are int32), got %d x %d" % (H, W))
+    verts, v_off = meshes.on(dev)
+    faces, f_off, _ = meshes.faces_on(dev)
+    st_in = None if status is None else status.to(device=dev, dtype=torch.int32).contiguous()
+    counts = torch.empty((P, len(VERIFY_COUNTS)), dtype=torch.int32, device=dev)
+    score, fit, den = (torch.empty((P,), dtype=torch.float64, device=dev) for _ in range(3))
+    ok = torch.empty((P,), dtype=torch.uint8, device=dev)
+    labels = torch.empty((P, H, W), dtype=torch.uint8, device=dev) if return_labels else None
+    scratch = torch.empty(_abi.load().cp_verify_poses_scratch_bytes(P, vmax), dtype=torch.uint8, device=dev)
+    _abi.call("cp_verify_poses", dev, poses, K, k_stride, verts, v_off, faces, f_off, len(meshes), ids, images, img_ids, n_img, H, W, tau_d,
+              st_in, occlusion_weight, P, vmax, counts, score, fit, den, ok, labels, scratch)
+    info = {k: counts[:, i] for i, k in enumerate(VERIFY_COUNTS)}
+    info.update(ok=ok.bool(), fit=fit, den=den)
+    return (score, info, labels) if return_labels else (score, info)
+
+
+def select_poses(score, ok=None, R=None, t=None):
+    """The choice among C candidate poses of each of B crops on the device (row N26): score (C,B) as verify_poses gives it for poses laid
+    out candidate-major, ok (C,B) bool / uint8 or None (then every score that is not NaN is eligible).  Per crop the eligible candidate
+    with the largest score wins, the smallest candidate index on equal scores, candidate 0 when none is eligible.  C <= 64.
+    -> choice (B,) int32, or (choice, R_sel (B,3,3), t_sel (B,3,1)) when R (C,B,3,3) and t (C,B,3,1) are given: plain indexing, the
+       chosen candidate's bits."""
+    from . import scene
+    if not torch.is_tensor(score) or score.dim() != 2 or not 1 <= score.shape[0] <= VERIFY_CMAX:
+        raise ValueError("score must be a (C,B) tensor with C in 1..%d" % VERIFY_CMAX)
+    C_, B = int(score.shape[0]), int(score.shape[1])
+    if ok is not None and (not torch.is_tensor(ok) or tuple(ok.shape) != (C_, B) or ok.dtype not in (torch.bool, torch.uint8)):
+        raise ValueError("ok must be a (C,B) bool or uint8 tensor or None")
+    if (R is None) != (t is None):
+        raise ValueError("give both R (C,B,3,3) and t (C,B,3,1), or neither")
+    if R is not None and (not torch.is_tensor(R) or not torch.is_tensor(t) or tuple(R.shape) != (C_, B, 3, 3) or tuple(t.shape) != (C_, B, 3, 1)):
+        raise ValueError("R must be (C,B,3,3) and t (C,B,3,1) tensors")
+    scene.require_cuda("postprocess", score, *[x for x in (ok, R, t) if x is not None])
+    dev = score.device
+    sc = score.to(torch.float64).contiguous()
+    okb = None if ok is None else ok.to(dev).contiguous().view(torch.uint8)
+    choice = torch.empty((B,), dtype=torch.int32, device=dev)
+    if B:                                                 # (an empty tensor has no address to hand over)
+        _abi.call("cp_select_poses", dev, sc, okb, C_, B, choice)
+    if R is None:
+        return choice
+    idx, cols = choice.long(), torch.arange(B, device=dev)
+    return choice, R[idx, cols], t[idx, cols]
+
+
 REFINES = (None, "lm", "icp", "lm+icp")
 
 
@@ -602,6 +698,17 @@ def _check_icp(refine, icp):
             raise ValueError("refine=%r needs icp=dict(meshes=..., depth=..., max_dist=...[, mesh_ids=..., ...])" % (refine,))
         if "image_ids" in icp or "status" in icp or "samples" in icp:
             raise ValueError("icp must not name image_ids, status or samples: they are the call's img_index and the solver's status")
+
+
+def _check_verify(verify):
+    """estimate_poses_verified's `verify` argument: a dict with meshes, depth and tau (optionally mesh_ids and occlusion_weight)"""
+    if not isinstance(verify, dict) or any(k not in verify for k in ("meshes", "depth", "tau")):
+        raise ValueError("verify must be dict(meshes=..., depth=..., tau=...[, mesh_ids=..., occlusion_weight=...])")
+    if "image_ids" in verify or "status" in verify:
+        raise ValueError("verify must not name image_ids or status: they are the call's img_index and the solver's status")
+    extra = [k for k in verify if k not in ("meshes", "depth", "tau", "mesh_ids", "occlusion_weight")]
+    if extra:
+        raise ValueError("verify: unknown key(s) %r" % (extra,))
 
 
 def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
@@ -623,7 +730,19 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
       "icp" (row N24): refine_poses_icp against the frames' depth, "lm+icp": N22 first, then N24.  Both need icp = a dict with
       `meshes` (a MeshSet with faces, in the units of p3d_xyz), `depth` ((H,W) / (n_img,H,W)) and `max_dist`, and optionally `mesh_ids`
       and refine_poses_icp's other keywords; each crop's image is the call's img_index.
+      The last stage's pose is returned as it is; estimate_poses_verified (row N26) runs the same stages and keeps per crop the stage's
+      pose that the frames' depth supports best.
     -> (R (B,3,3) f64, t (B,3,1) f64, inliers (B,N) bool, status (B,) int32 (0: identity fallback), final boxes (B,4) int array)"""
+    stages, inl, status, final = _estimate_stages(**locals())        # (the first statement: locals() holds the arguments alone)
+    return stages[-1][1], stages[-1][2], inl, status, final
+
+
+def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
+                     resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0,
+                     solver="epnp", graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None, depth=None,
+                     dist_threshold=None):
+    """estimate_poses' arguments -> (stages: [(name, R, t)] after the solver, "lm" and "icp" as far as `refine` runs them, inliers, status,
+    final boxes)"""
     from . import preprocess as PP
     if solver not in ("epnp", "gc", "depth"):
         raise ValueError("solver must be 'epnp', 'gc' or 'depth', got %r" % (solver,))
@@ -654,12 +773,59 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
     else:
         R, t, inl, status = solve_pnp_ransac(p3d_xyz, p2d, valid, cam_K, column=1 if check_seg else 0, reproj_threshold=reproj_threshold,
                                              iterations=iterations, seed=seed)
+    stages = [("solver", R, t)]
     if refine in ("lm", "lm+icp"):
         R, t = refine_poses_lm(p3d_xyz, p2d, inl, cam_K, R, t, status=status)[:2]
+        stages.append(("lm", R, t))
     if refine in ("icp", "lm+icp"):
         kw = {k: v for k, v in icp.items() if k not in ("meshes", "depth", "max_dist")}
         R, t = refine_poses_icp(R, t, cam_K, icp["meshes"], icp["depth"], icp["max_dist"], image_ids=img_index, status=status, **kw)[:2]
-    return R, t, inl, status, final
+        stages.append(("icp", R, t))
+    return stages, inl, status, final
+
+
+def estimate_poses_verified(net, frames, Bboxes, p3d_xyz, cam_K, verify, return_verify=False, **estimate_kwargs):
+    """estimate_poses with hypothesis verification (row N26): the same call (estimate_kwargs are estimate_poses' keywords), but instead
+    of the last stage's pose unconditionally, the poses after each stage the call runs -- the solver's, then after "lm", then after
+    "icp": 1, 2 or 3 candidates per crop -- are scored by ONE verify_poses call against the frames' depth and ONE select_poses keeps per
+    crop the one the sensor supports.
+      verify: a dict with `meshes` (a MeshSet with faces, in the units of p3d_xyz), `depth` ((H,W) / (n_img,H,W)), `tau` (no default) and
+      optionally `mesh_ids` and `occlusion_weight`; each crop's image is the call's img_index and a crop with solver status 0 is no
+      candidate, so `image_ids` and `status` are refused.
+    -> (R, t, inliers, status, final boxes) as estimate_poses: R, t the chosen candidates' (their bits), inliers and status still the
+       solver's; return_verify=True appends a dict: score (C,B), choice (B,) int32, stages (a tuple of "solver" / "lm" / "icp") and info
+       (verify_poses' dict over the C * B poses, candidate-major)."""
+    _check_verify(verify)
+    stages, inl, status, final = _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, **estimate_kwargs)
+    R, t, report = _verify_stages(stages, cam_K, estimate_kwargs.get("img_index"), status, verify)
+    return (R, t, inl, status, final, report) if return_verify else (R, t, inl, status, final)
+
+
+def _verify_stages(stages, cam_K, img_index, status, verify):
+    """estimate_poses_verified's verification: the stages' poses candidate-major through ONE verify_poses and ONE select_poses
+    -> (R, t of the chosen candidates, the report of return_verify)"""
+    C_, B = len(stages), int(stages[0][1].shape[0])
+    Rc = torch.stack([r.reshape(B, 3, 3) for _, r, _ in stages])
+    tc = torch.stack([x.reshape(B, 3, 1) for _, _, x in stages])
+
+    def per_candidate(x):                                 # a per-crop (B,) argument -> (C * B,), candidate-major
+        if x is None:
+            return None
+        return x.reshape(-1).repeat(C_) if torch.is_tensor(x) else np.tile(np.asarray(x).reshape(-1), C_)
+
+    K = cam_K if torch.is_tensor(cam_K) else np.asarray(cam_K)
+    if K.ndim == 3:
+        K = K.repeat(C_, 1, 1) if torch.is_tensor(K) else np.tile(K, (C_, 1, 1))
+    depth, tau = verify["depth"], verify["tau"]
+    if img_index is None and B > 1 and getattr(depth, "ndim", 0) == 3 and len(depth) == B:
+        img_index = np.arange(B)                          # the default rule (image b for crop b), said before the crops are stacked
+    score, info = verify_poses(Rc.reshape(C_ * B, 3, 3), tc.reshape(C_ * B, 3, 1), K, verify["meshes"], depth,
+                               per_candidate(tau) if torch.is_tensor(tau) else tau, image_ids=per_candidate(img_index),
+                               mesh_ids=per_candidate(verify.get("mesh_ids")), status=per_candidate(status),
+                               occlusion_weight=verify.get("occlusion_weight", 1.0))
+    score = score.view(C_, B)
+    choice, R, t = select_poses(score, info["ok"].view(C_, B), Rc, tc)
+    return R, t, dict(score=score, choice=choice, stages=tuple(n for n, _, _ in stages), info=info)
 
 
 def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, mesh_ids=None, kinds=("add", "adi"), symmetries=None,
@@ -674,9 +840,17 @@ def evaluate_poses(net, frames, Bboxes, p3d_xyz, cam_K, R_gt, t_gt, vertices, me
       kind "vsd" (metric.vsd_errors at its defaults) needs `depth_test` (H,W) / (I,H,W) in the units of `vertices`, a MeshSet with
       faces, and `image_ids` (B,) when poses share images; its errors are (B, T), one column per tau.
       kinds "cus" / "cou_bb_proj" (metric.mask_errors, no sphere shortcut) need `size` = (W, H) of the frame and a MeshSet with faces.
+      A `verify` keyword (row N26) routes the call through estimate_poses_verified: the scored poses are then the chosen ones;
+      `return_verify` is refused: this call's return has no place for the report -- call estimate_poses_verified itself for it.
     -> (errors: dict kind -> (B,) f64 CUDA tensor, R, t, inliers, status, final boxes)"""
     from . import metric
-    R, t, inl, status, final = estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, **estimate_kwargs)
+    if "return_verify" in estimate_kwargs:
+        raise ValueError("evaluate_poses does not return the verification's report (return_verify): call estimate_poses_verified for it")
+    verify = estimate_kwargs.pop("verify", None)
+    if verify is None:
+        R, t, inl, status, final = estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, **estimate_kwargs)
+    else:
+        R, t, inl, status, final = estimate_poses_verified(net, frames, Bboxes, p3d_xyz, cam_K, verify, **estimate_kwargs)
     errors = metric.score_poses(R, t, R_gt, t_gt, cam_K, vertices, mesh_ids=mesh_ids, kinds=kinds, symmetries=symmetries,
                                 depth_test=depth_test, image_ids=image_ids, size=size)
     return errors, R, t, inl, status, final

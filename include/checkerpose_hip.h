@@ -692,6 +692,32 @@ int cp_pose_depth_ransac(cp_stream_t stream, const float* p3d, long long p3d_bst
                          int I, int H, int W, int B, int N, double dist_threshold, const double* dist_thresholds, int iterations,
                          uint32_t seed, double* pose, uint8_t* inliers, int32_t* status, void* scratch);
 
+/* Hypothesis verification of poses against a depth image, and the choice among candidates (row N26).  The reference does not verify;
+ * opt-in, the rule is this project's own (stated in full at the top of csrc/pose_verify.hip, restated in numpy by
+ * tests/verify_stages.py).
+ * cp_verify_poses: P poses (poses, cam_K, k_stride, verts .. Vmax, H, W as cp_render_depth; depth, image_ids, I as cp_gt_info) are
+ *   rendered tile by tile -- no depth frame is stored -- and every model pixel (render D > 0) is classified against the sensor depth S
+ *   with the pose's tolerance tau (fp64 (P) on the device, converted to fp32 once): missing (S not finite or <= 0), match
+ *   (|S - D| <= tau, which also adds q = min(63, (int)(64 (|S - D| / tau))) to sum_q), occluded (S - D < -tau), through (S - D > tau).
+ *   status int32 (P) or NULL: a pose whose entry is 0 is not a candidate.  occlusion_weight in [0, 1].
+ *   Outputs: counts int32 (P,6) = n_model n_missing n_match n_occluded n_through sum_q; fit = n_match - sum_q / 64, den = n_match +
+ *   n_through + occlusion_weight n_occluded, score = fit / den, all fp64 (P); ok uint8 (P).  score is NaN with ok = 0 when den == 0 or
+ *   the pose is not counted (all six counts 0): a non-finite pose or cam_K, a vertex at Z <= 0, an image or mesh id out of range,
+ *   status 0, a tau that as fp32 is not positive and finite.  labels uint8 (P,H,W) or NULL: 0 none, 1 match, 2 occluded, 3 through,
+ *   4 missing.  scratch: cp_verify_poses_scratch_bytes(P, Vmax) bytes (0 = bad arguments), 16-byte aligned.  Four launches; every
+ *   output is a function of integer sums: bitwise the same alone or in a batch, with or without labels.
+ * cp_select_poses: score fp64 (C,B) candidate-major, ok uint8 (C,B) or NULL (then every score that is not NaN is eligible), C in 1..64
+ *   -> choice int32 (B): the eligible candidate with the largest score, the smallest index on equal scores, 0 when none is eligible.
+ * CP_ERR_INVALID: a null pointer, the mesh / view / image argument rules of the raster family, an occlusion_weight outside [0, 1], C
+ * or B outside its range; CP_ERR_ALIGN; CP_ERR_RANGE: H * W > 2^24 (the sums are int32), too many blocks, C * B >= 2^31. */
+size_t cp_verify_poses_scratch_bytes(int P, int Vmax);
+int cp_verify_poses(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                    const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                    const float* depth, const int32_t* image_ids, int I, int H, int W, const double* tau, const int32_t* status,
+                    double occlusion_weight, int P, int Vmax, int32_t* counts, double* score, double* fit, double* den, uint8_t* ok,
+                    uint8_t* labels, void* scratch);
+int cp_select_poses(cp_stream_t stream, const double* score, const uint8_t* ok, int C, int B, int32_t* choice);
+
 /* Rotation / translation errors, symmetry-aware (row N23): bop_toolkit_lib.pose_error.re / .te (pose_error.py:187-214) for P pose
  * pairs, the rotation error optionally against the closest symmetric copy of the second pose (checkerpose/test_lm.py:33-55,
  * get_closest_rot).  The rule is stated in full at the top of csrc/rete.hip and restated in numpy by tests/rete_stages.py.  One
