@@ -4,6 +4,8 @@ bop_toolkit's scripts/calc_gt_coco.py, scripts/eval_bop22_coco.py and bop_toolki
 COCOeval.evaluate / accumulate / summarize as the script drives them, for masks and boxes that are resident on the device:
 
   annotate_masks(...)       area, box and (optionally) the column-major RLE of N masks
+  unpack_masks(...)         PackedMasks back to dense uint8 masks, for callers who want a picture
+  segmentation_results(...) row N27: the network's seg logits + the crops' boxes -> the BOP'22 result dicts (postprocess.paste_masks_rle)
   calc_gt_coco(...)         the `images` / `annotations` lists of scene_gt_coco.json (ids, skips, ignore flags, RLE dicts)
   mask_ious / box_ious      IoU of listed (detection, ground truth) pairs, float64
   CocoSet                   the ground truth of an evaluation, built from arrays
@@ -80,6 +82,16 @@ def pack_masks(masks, device=None):
     return PackedMasks(bits, area, box, H, W)
 
 
+def unpack_masks(packed):
+    """cp_coco_unpack, pack_masks' inverse: PackedMasks -> (N,H,W) uint8 CUDA tensor of 0 / 1"""
+    N, dev = len(packed), packed.device
+    scene.require_cuda("coco_eval", packed.bits)
+    out = torch.empty((N, packed.H, packed.W), dtype=torch.uint8, device=dev)
+    if N:
+        _abi.call("cp_coco_unpack", dev, packed.bits, N, packed.H, packed.W, out)
+    return out
+
+
 def rle_encode(packed):
     """pycoco_utils.binary_mask_to_rle of every packed mask -> (counts int32 (total,), offsets int64 (N + 1,)) on the device: mask n's
     run lengths are counts[offsets[n]:offsets[n + 1]]"""
@@ -108,12 +120,48 @@ def annotate_masks(masks, return_rle=False, device=None):
     the host list of RLE dicts."""
     p = pack_masks(masks, device)
     box = p.box
-    wh = box[:, 2:] - box[:, :2] + 1
-    bbox = torch.where((p.area > 0)[:, None], torch.cat([box[:, :2], wh], 1), torch.full_like(box, -1))
-    out = {"area": p.area, "box": box, "bbox": bbox, "packed": p}
+    out = {"area": p.area, "box": box, "bbox": _xywh(p.area, box), "packed": p}
     if return_rle:
         out["rle_counts"], out["rle_offsets"] = rle_encode(p)
         out["rle"] = rle_dicts(out["rle_counts"], out["rle_offsets"], p.H, p.W)
+    return out
+
+
+def _xywh(area, box):
+    """pycoco_utils.bbox_from_binary_mask's x y w h from xmin ymin xmax ymax (w = xmax - xmin + 1); all -1 for an empty mask"""
+    wh = box[:, 2:] - box[:, :2] + 1
+    return torch.where((area > 0)[:, None], torch.cat([box[:, :2], wh], 1), torch.full_like(box, -1))
+
+
+def segmentation_results(seg, Bboxes, frame_size, scene_id, image_id, category_id, score, time=None, resize_method="crop_square_resize",
+                         channel=0):
+    """The BOP'22 segmentation results of one forward (row N27): the network's `seg` logits (B,C,Sh,Sw) and the crops' padded boxes ->
+    the host list of result dicts that check_coco_results / eval_bop22_coco / save_coco_results read: scene_id, image_id, category_id,
+    score, bbox [x, y, w, h] of the pasted mask, segmentation {"counts", "size": [H, W]} and, when given, time.  Built from
+    postprocess.paste_masks_rle (its arguments): no dense mask exists on either side.  scene_id, image_id, category_id, score, time:
+    a value for all detections or one per detection.  A detection whose mask is empty is KEPT, with bbox [-1, -1, -1, -1]
+    (annotate_masks' convention): dropping it would change the false-positive count."""
+    from . import postprocess
+    counts, offsets, area, box = postprocess.paste_masks_rle(seg, Bboxes, frame_size, resize_method, channel)
+    B = int(area.shape[0])
+    H, W = (int(v) for v in frame_size)
+    rles = rle_dicts(counts, offsets, H, W)
+    bbox = _xywh(area, box).cpu().numpy()
+
+    def per_det(v, name):
+        a = np.asarray(v.detach().cpu() if torch.is_tensor(v) else v).reshape(-1)
+        if a.shape[0] not in (1, B):
+            raise ValueError("%s must be one value or one per detection (%d), got %d" % (name, B, a.shape[0]))
+        return np.broadcast_to(a, (B,))
+    cols = [per_det(v, k) for k, v in (("scene_id", scene_id), ("image_id", image_id), ("category_id", category_id), ("score", score))]
+    times = None if time is None else per_det(time, "time")
+    out = []
+    for b in range(B):
+        row = {"scene_id": int(cols[0][b]), "image_id": int(cols[1][b]), "category_id": int(cols[2][b]), "score": float(cols[3][b]),
+               "bbox": [int(v) for v in bbox[b]], "segmentation": rles[b]}
+        if times is not None:
+            row["time"] = float(times[b])
+        out.append(row)
     return out
 
 

@@ -6,6 +6,7 @@
 //                       word x >> 5; a wave ballot over 64 pixels of a row yields two words; bits past W are zero), the pixel count and
 //                       [xmin ymin xmax ymax] (-1s for an empty mask).  The ballot is wave-uniform: no shuffle is needed within a
 //                       wave, the waves meet in LDS.
+//   cp_coco_unpack      the inverse for callers who want a picture: bit rows -> uint8 0 / 1 (N,H,W), a thread per pixel (row N27).
 //   cp_coco_rle_count / cp_coco_rle_write
 //                       pycoco_utils.binary_mask_to_rle: run lengths of the mask ravelled column-major (i = x H + y; runs go on across
 //                       the column boundary; a leading 0 when pixel 0 is set).  A workgroup per mask; every thread owns a contiguous
@@ -81,24 +82,17 @@ __global__ __launch_bounds__(CE_PACK_THREADS) void coco_pack_kernel(const uint8_
   }
 }
 
-// ---- rle
-// inclusive scan over the workgroup of (sum of c, max of l); -> this thread's inclusive values, the exclusive ones in ec / el
-__device__ __forceinline__ void ce_scan(int& c, int& l, int& ec, int& el, int (*s)[2]) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int oc = __shfl_up(c, d, 64), ol = __shfl_up(l, d, 64);
-    if (lane >= d) { c += oc; l = max(l, ol); }
-  }
-  ec = __shfl_up(c, 1, 64); el = __shfl_up(l, 1, 64);
-  if (lane == 0) { ec = 0; el = -1; }
-  if (lane == 63) { s[wave][0] = c; s[wave][1] = l; }
-  __syncthreads();
-  int pc = 0, pl = -1;
-  for (int w = 0; w < wave; ++w) { pc += s[w][0]; pl = max(pl, s[w][1]); }
-  c += pc; l = max(l, pl); ec += pc; el = max(el, pl);
+// ---- unpack: cp_coco_pack's inverse for the bits, a thread per pixel
+__global__ __launch_bounds__(CE_THREADS) void coco_unpack_kernel(const uint32_t* __restrict__ bits, uint8_t* __restrict__ masks, int H, int W,
+                                                                 int WW, size_t total) {
+  const size_t i = (size_t)blockIdx.x * CE_THREADS + threadIdx.x;     // over N * H * W
+  if (i >= total) return;
+  const size_t row = i / W;                                          // n * H + y
+  const int x = (int)(i - row * W);
+  masks[i] = (uint8_t)((bits[row * WW + (x >> 5)] >> (x & 31)) & 1u);
 }
 
+// ---- rle
 template <bool WRITE>
 __global__ __launch_bounds__(CE_RLE_THREADS) void coco_rle_kernel(const uint32_t* __restrict__ bits, int H, int W, int WW,
                                                                   const int64_t* __restrict__ off, int32_t* __restrict__ n_runs,
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(CE_RLE_THREADS) void coco_rle_kernel(const uint32_t
     }
   }
   int ec, el;
-  ce_scan(cnt, last, ec, el, s_scan);                                // cnt / last are inclusive now
+  cp_scan_sum_max(cnt, last, ec, el, s_scan);                                // cnt / last are inclusive now
   const int lead = bit(0, 0);
   if (!WRITE) {
     if (tid == CE_RLE_THREADS - 1) n_runs[mi] = cnt + lead;
@@ -388,6 +382,17 @@ extern "C" int cp_coco_pack(cp_stream_t stream, const uint8_t* masks, int N, int
   if (cp_misaligned(bits, 3) || cp_misaligned(area, 3) || cp_misaligned(box, 3)) return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) - 4096 || N >= (1 << 24)) return CP_ERR_RANGE;
   CP_LAUNCH(coco_pack_kernel, dim3((unsigned)N), dim3(CE_PACK_THREADS), 0, (hipStream_t)stream, masks, bits, area, box, H, W, (W + 31) / 32);
+  return cp_check_launch();
+}
+
+extern "C" int cp_coco_unpack(cp_stream_t stream, const uint32_t* bits, int N, int H, int W, uint8_t* masks) {
+  if (!bits || !masks) return CP_ERR_INVALID;
+  if (N < 1 || H < 1 || W < 1) return CP_ERR_INVALID;
+  if (cp_misaligned(bits, 3)) return CP_ERR_ALIGN;
+  if ((long long)H * W >= (1LL << 31) - 4096 || N >= (1 << 24)) return CP_ERR_RANGE;
+  const size_t total = (size_t)N * H * W, blocks = (total + CE_THREADS - 1) / CE_THREADS;
+  if (blocks >= ((size_t)1 << 31)) return CP_ERR_RANGE;
+  CP_LAUNCH(coco_unpack_kernel, dim3((unsigned)blocks), dim3(CE_THREADS), 0, (hipStream_t)stream, bits, masks, H, W, (W + 31) / 32, total);
   return cp_check_launch();
 }
 

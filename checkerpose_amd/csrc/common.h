@@ -163,6 +163,28 @@ template <> struct Vec16<F16Tag> {            // pack() saturates under cp_f16_s
   static __device__ __forceinline__ u32x4 pack(const float* f) { return cp_pack8<true>(f); }
 };
 
+// the reference's `torch.sigmoid(z) > 0.5` in fp32 as the pinned test on the logit (graph_ops.hip's bit decode states the measurement;
+// CP_SIGMOID_HALF_Z0_BITS in the header): NaN, -0.0 and +0.0 fail it
+__device__ __forceinline__ bool cp_sigmoid_gt_half(float z) { return z > __uint_as_float(CP_SIGMOID_HALF_Z0_BITS); }
+
+// inclusive scan over the workgroup (blockDim.x a multiple of 64, s: a row per wave) of (sum of c, max of l); -> this thread's inclusive
+// values, the exclusive ones in ec / el.  The run placement of coco_eval.hip's and paste_masks.hip's RLE kernels.
+__device__ __forceinline__ void cp_scan_sum_max(int& c, int& l, int& ec, int& el, int (*s)[2]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int oc = __shfl_up(c, d, 64), ol = __shfl_up(l, d, 64);
+    if (lane >= d) { c += oc; l = max(l, ol); }
+  }
+  ec = __shfl_up(c, 1, 64); el = __shfl_up(l, 1, 64);
+  if (lane == 0) { ec = 0; el = -1; }
+  if (lane == 63) { s[wave][0] = c; s[wave][1] = l; }
+  __syncthreads();
+  int pc = 0, pl = -1;
+  for (int w = 0; w < wave; ++w) { pc += s[w][0]; pl = max(pl, s[w][1]); }
+  c += pc; l = max(l, pl); ec += pc; el = max(el, pl);
+}
+
 // align_corners source coordinate of output index o (scale s = (n - 1) / (2 n - 1)): left neighbour, step to the right one, the
 // right one's weight.  `contract(off)`: hipcc's default -ffp-contract=fast may fuse s * o - i0 into one fma in one kernel and
 // not in another (__fmul_rn / __fsub_rn are plain * and - in HIP); with the pragma every kernel derives the same weights.

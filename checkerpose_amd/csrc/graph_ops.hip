@@ -174,8 +174,7 @@ extern "C" int cp_index2feat_gather(cp_stream_t stream, int dtype, const void* p
 // The reference thresholds `torch.sigmoid(z) > 0.5` in fp32, and fp32 sigmoid rounds to exactly 0.5 for every
 // 0 <= z <= CP_SIGMOID_HALF_Z0 (1.5 * 2^-24, bits 0x33C00000): measured on torch 2.10 CPU (scalar, AVX2 and AVX-512 paths)
 // through the reference's own from_mask_prob_to_mask (tests/golden/make_golden_r2.py sigmoid, fixture sigmoid_threshold.npz).
-// Index work is bit exact, so the decision is z > Z0, not z > 0.
-__device__ __forceinline__ bool cp_sigmoid_gt_half(float z) { return z > __uint_as_float(CP_SIGMOID_HALF_Z0_BITS); }
+// Index work is bit exact, so the decision is z > Z0, not z > 0 (cp_sigmoid_gt_half, common.h: paste_masks.hip shares it).
 __global__ void bits_decode_kernel(const float* __restrict__ bits, int stage, float* __restrict__ mask,
                                    int32_t* __restrict__ x_id, int32_t* __restrict__ y_id, int64_t* __restrict__ x64,
                                    int64_t* __restrict__ y64, int N, size_t total) {

@@ -6,6 +6,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from .paste import estimate_poses_masks, paste_masks, paste_masks_rle      # noqa: F401  (row N27: checkerpose_amd/paste.py)
 
 
 def correspondences(outputs, roi_xy_ori=None, discard_bd_pixel=0, Bboxes=None):
@@ -740,9 +741,9 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
 def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
                      resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0,
                      solver="epnp", graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None, depth=None,
-                     dist_threshold=None):
+                     dist_threshold=None, keep=None):
     """estimate_poses' arguments -> (stages: [(name, R, t)] after the solver, "lm" and "icp" as far as `refine` runs them, inliers, status,
-    final boxes)"""
+    final boxes).  keep: a dict that receives the forward's `seg` logits and the `padded` boxes of the crops (estimate_poses_masks)"""
     from . import preprocess as PP
     if solver not in ("epnp", "gc", "depth"):
         raise ValueError("solver must be 'epnp', 'gc' or 'depth', got %r" % (solver,))
@@ -762,6 +763,8 @@ def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_id
     final = np.array([[0, 0, 0, 0] if b is None else PP.get_final_Bbox(b, resize_method, W, H) for b in padded], dtype=np.int32)
     with torch.no_grad():
         out = net(crops, None) if obj_ids is None else net(crops, None, obj_ids)
+    if keep is not None:
+        keep["seg"], keep["padded"] = out[3], padded
     p2d, valid, _ = correspondences(out, discard_bd_pixel=discard_bd_pixel, Bboxes=final)
     if solver == "gc":
         R, t, inl, status = solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=obj_ids if graph.M > 1 else None,

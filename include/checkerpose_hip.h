@@ -1597,6 +1597,33 @@ int cp_coco_accumulate(cp_stream_t stream, const int32_t* dt_match, const uint8_
                        int ND, int NGT, const int32_t* max_dets, const double* rec_thrs, double* precision, double* recall);
 
 /* ---------------------------------------------------------------------------------------------
+ * Predicted masks pasted into the frame on the device (row N27; csrc/paste_masks.hip).  The reference never pastes a mask; the rule
+ * is this project's own, the integer inverse of the crop window of cp_crop_resize_u8, stated in full at the top of the kernel file
+ * and restated in numpy by tests/paste_stages.py: frame pixel (y, x) of mask b is set iff rw, rh > 0, max(x1, 0) <= x < min(x2, W,
+ * x1 + rw) (y alike) and seg[((2 (y - y1) + 1) Sh) / (2 rh), ((2 (x - x1) + 1) Sw) / (2 rw)] > CP_SIGMOID_HALF_Z0 (integer division).
+ *
+ * seg: crop 0's plane of the wanted channel, fp32 logits, Sh x Sw contiguous; seg_bstride: floats between two crops' planes (2 Sh Sw
+ *   for the module's (B,2,Sh,Sw) tensor; >= 0).  windows: int32 (B,6) x1 y1 x2 y2 roi_w roi_h on the device, as cp_crop_resize_u8's.
+ * cp_paste_masks: -> exactly what cp_coco_pack leaves for the dense pasted masks: bits (B,H,WW), area (B), box (B,4) xmin ymin xmax
+ *   ymax (-1s for an empty mask).  Every word is written.  One launch, a workgroup per mask.
+ * cp_paste_rle_count / cp_paste_rle_write: -> exactly cp_coco_rle_count / cp_coco_rle_write of those bits, without the bits: n_runs
+ *   (B) together with area and box; then, with offsets int64 (B + 1) = 0 and the cumulative sums, counts int32 (total).  A mask whose
+ *   offsets do not fit the buffer is not written.  Work proportional to the window.
+ * cp_coco_unpack: cp_coco_pack's inverse, bits (N,H,WW) -> masks uint8 (N,H,W) of 0 / 1.
+ * No atomics, no scratch, nothing allocates or synchronises; bit-identical for a mask alone or at any batch position.
+ * CP_ERR_INVALID: a null pointer, B < 1, seg_bstride < 0, Sh or Sw outside 1..128, H or W outside 1..4096 (cp_coco_unpack: N, H or
+ *   W < 1), total < 1; CP_ERR_ALIGN: a pointer not aligned to its element; CP_ERR_RANGE: H * W >= 2^31 - 512, B >= 2^24
+ *   (cp_coco_unpack: cp_coco_pack's limits, 2^31 workgroups or more).
+ * ------------------------------------------------------------------------------------------- */
+int cp_paste_masks(cp_stream_t stream, const float* seg, long long seg_bstride, int Sh, int Sw, const int32_t* windows, int B, int H,
+                   int W, uint32_t* bits, int32_t* area, int32_t* box);
+int cp_paste_rle_count(cp_stream_t stream, const float* seg, long long seg_bstride, int Sh, int Sw, const int32_t* windows, int B, int H,
+                       int W, int32_t* n_runs, int32_t* area, int32_t* box);
+int cp_paste_rle_write(cp_stream_t stream, const float* seg, long long seg_bstride, int Sh, int Sw, const int32_t* windows, int B, int H,
+                       int W, const int64_t* offsets, int32_t* counts, long long total);
+int cp_coco_unpack(cp_stream_t stream, const uint32_t* bits, int N, int H, int W, uint8_t* masks);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph helpers: capture the launch sequence of one forward (everything above is capture-safe:
  * no allocation, no synchronisation) and replay it with one call.
  * ------------------------------------------------------------------------------------------- */
