@@ -718,6 +718,32 @@ int cp_verify_poses(cp_stream_t stream, const double* poses, const double* cam_K
                     uint8_t* labels, void* scratch);
 int cp_select_poses(cp_stream_t stream, const double* score, const uint8_t* ok, int C, int B, int32_t* choice);
 
+/* Hypothesis verification of poses against predicted masks (row N28): row N26 for RGB-only data.  The reference does not verify;
+ * opt-in, the rule is this project's own (stated in full at the top of csrc/pose_verify_mask.hip, restated in numpy by
+ * tests/verify_mask_stages.py).  The choice among candidates is cp_select_poses.
+ * cp_verify_poses_mask: P poses (poses, cam_K, k_stride, verts .. Vmax as cp_render_depth) are rendered tile by tile over the masks'
+ *   W x H frame -- no depth frame and no dense mask is stored -- and every model pixel (render D > 0) is tested against its mask's bit.
+ *   full_bits int32 (NM,H,WW), WW = ceil(W / 32), with full_area int32 (NM): the full (amodal) masks as cp_coco_pack / cp_paste_masks
+ *   leave them (pixel x = bit x & 31 of word x >> 5); vis_bits / vis_area: the visible masks in the same layout, both or both NULL;
+ *   mask_ids int32 (P) or NULL (then NM == P and pose p reads mask p); status int32 (P) or NULL: a pose whose entry is 0 is not a candidate.
+ *   Outputs: counts int32 (P,5) = n_model (D > 0) n_inter (model and full) n_vis_in (model and visible; 0 without) n_mask
+ *   (full_area[m], read) n_vis (vis_area[m], read; 0 without); box int32 (P,4) = xmin ymin xmax ymax of the model pixels, -1s when
+ *   n_model == 0; iou = n_inter / (n_model + n_mask - n_inter), cover = n_vis_in / n_vis, score = iou, all fp64 (P); ok uint8 (P).
+ *   score and iou are NaN with ok = 0 when the union is 0 or the pose is not counted (its three sums 0, its box -1s): a non-finite pose
+ *   or cam_K, a vertex at Z <= 0, a mesh id out of range, a mask id outside 0..NM-1 (n_mask = n_vis = 0 then), status 0.  cover is NaN
+ *   when n_vis == 0, without the visible masks, or when the pose is not counted.  labels uint8 (P,H,W) or NULL: model | full << 1 |
+ *   visible << 2 per pixel; a pose that is not counted still gets its mask bits.  scratch: cp_verify_poses_mask_scratch_bytes(P, Vmax)
+ *   bytes (0 = bad arguments), 16-byte aligned.  Four launches; every output is a function of integer sums: bitwise the same alone or
+ *   in a batch, with or without labels.
+ * CP_ERR_INVALID: a null pointer, the mesh / view argument rules of the raster family, NM <= 0, no mask_ids although NM != P, one of
+ * vis_bits / vis_area without the other; CP_ERR_ALIGN; CP_ERR_RANGE: H * W > 2^24 (the sums are int32), too many blocks. */
+size_t cp_verify_poses_mask_scratch_bytes(int P, int Vmax);
+int cp_verify_poses_mask(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                         const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                         const int32_t* full_bits, const int32_t* full_area, const int32_t* vis_bits, const int32_t* vis_area,
+                         const int32_t* mask_ids, int NM, int H, int W, const int32_t* status, int P, int Vmax, int32_t* counts,
+                         int32_t* box, double* score, double* iou, double* cover, uint8_t* ok, uint8_t* labels, void* scratch);
+
 /* Rotation / translation errors, symmetry-aware (row N23): bop_toolkit_lib.pose_error.re / .te (pose_error.py:187-214) for P pose
  * pairs, the rotation error optionally against the closest symmetric copy of the second pose (checkerpose/test_lm.py:33-55,
  * get_closest_rot).  The rule is stated in full at the top of csrc/rete.hip and restated in numpy by tests/rete_stages.py.  One
