@@ -263,6 +263,8 @@ SIGNATURES = {
     "cp_paste_rle_count": (_I, [_P, _P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _P]),
     "cp_paste_rle_write": (_I, [_P, _P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _L]),
     "cp_coco_unpack": (_I, [_P, _P, _I, _I, _I, _P]),
+    "cp_coco_rle_unpack_scratch_bytes": (C.c_size_t, [_L]),
+    "cp_coco_rle_unpack": (_I, [_P, _P, _P, _I, _I, _I, _L, _P, _P, _P, _P, _P]),
     "cp_mask_errors_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_mask_errors": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_mask_overlap": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),

@@ -5,6 +5,8 @@ COCOeval.evaluate / accumulate / summarize as the script drives them, for masks 
 
   annotate_masks(...)       area, box and (optionally) the column-major RLE of N masks
   unpack_masks(...)         PackedMasks back to dense uint8 masks, for callers who want a picture
+  rle_unpack / rle_stats    row N29 (csrc/rle_unpack.hip): run lists on the device -> PackedMasks / area, box and status alone
+  rle_flatten / pack_rles   RLE dicts (lists or compressed strings: rle_from_string / rle_to_string) -> run lists -> PackedMasks
   segmentation_results(...) row N27: the network's seg logits + the crops' boxes -> the BOP'22 result dicts (postprocess.paste_masks_rle)
   calc_gt_coco(...)         the `images` / `annotations` lists of scene_gt_coco.json (ids, skips, ignore flags, RLE dicts)
   mask_ious / box_ious      IoU of listed (detection, ground truth) pairs, float64
@@ -106,10 +108,142 @@ def rle_encode(packed):
     return counts, offsets
 
 
-def rle_dicts(counts, offsets, H, W):
-    """the device RLE as pycoco_utils' dicts: [{"counts": [...], "size": [H, W]}, ...] (host)"""
+def rle_dicts(counts, offsets, H, W, compress=False):
+    """the device RLE as pycoco_utils' dicts: [{"counts": [...], "size": [H, W]}, ...] (host); with compress the counts are
+    pycocotools' compressed strings (rle_to_string), as cocoapi writers emit them"""
     c, o = counts.cpu().numpy(), offsets.cpu().numpy()
-    return [{"counts": [int(v) for v in c[o[n]:o[n + 1]]], "size": [int(H), int(W)]} for n in range(len(o) - 1)]
+    enc = rle_to_string if compress else (lambda run: [int(v) for v in run])
+    return [{"counts": enc(c[o[n]:o[n + 1]]), "size": [int(H), int(W)]} for n in range(len(o) - 1)]
+
+
+RLE_STATUS = {1: "a negative count", 2: "the counts sum to more than H * W", 3: "the offsets do not fit the counts"}
+
+
+def _rle_args(counts, offsets, H, W):
+    scene.require_cuda("coco_eval", counts, offsets)
+    if counts.dtype != torch.int32 or offsets.dtype != torch.int64 or counts.dim() != 1 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("counts must be int32 (total,) and offsets int64 (N + 1,), as rle_encode makes them")
+    if counts.device != offsets.device:
+        raise ValueError("counts are on %s, offsets on %s" % (counts.device, offsets.device))
+    H, W = int(H), int(W)
+    if H < 1 or W < 1:
+        raise ValueError("the frame must be at least 1 x 1, got %d x %d" % (H, W))
+    return counts.contiguous(), offsets.contiguous(), int(offsets.numel()) - 1, H, W
+
+
+def _rle_unpack(counts, offsets, H, W, with_bits):
+    counts, offsets, N, H, W = _rle_args(counts, offsets, H, W)
+    dev = counts.device
+    bits = torch.empty((N, H, (W + 31) // 32), dtype=torch.int32, device=dev) if with_bits else None
+    area = torch.empty((N,), dtype=torch.int32, device=dev)
+    box = torch.empty((N, 4), dtype=torch.int32, device=dev)
+    status = torch.empty((N,), dtype=torch.int32, device=dev)
+    if N:
+        total = int(counts.numel())
+        ends = torch.empty((total,), dtype=torch.int32, device=dev)      # cp_coco_rle_unpack_scratch_bytes(total) = 4 * total
+        nz = lambda t: t if t.numel() else None      # noqa: E731
+        _abi.call("cp_coco_rle_unpack", dev, nz(counts), offsets, N, H, W, total, nz(ends), bits, area, box, status)
+    return bits, area, box, status, H, W
+
+
+def _check_rle_status(status, H, W, first=0):
+    """ValueError naming the first mask with a nonzero status (one host read of N integers); `first`: the index of mask 0 in the
+    caller's list"""
+    st = status.cpu().numpy()
+    bad = np.nonzero(st)[0]
+    if len(bad):
+        raise ValueError("mask %d: RLE counts do not fit %dx%d (%s)" % (first + bad[0], H, W, RLE_STATUS.get(int(st[bad[0]]), "?")))
+
+
+def rle_unpack(counts, offsets, H, W, check=True, return_status=False):
+    """cp_coco_rle_unpack, rle_encode's inverse and pycoco_utils.rle_to_binary_mask on the device: counts int32 (total,), offsets int64
+    (N + 1,) CUDA tensors (rle_encode's / postprocess.paste_masks_rle's layout) of H x W masks -> PackedMasks; no dense mask exists on
+    either side.  Zero-length runs are taken anywhere, a list that sums to less than H * W leaves the rest background.  A mask whose
+    list holds a negative count (status 1), sums to more than H * W (2) or whose offsets do not fit the counts (3) comes out empty;
+    with check (one host read of N integers) the first such mask raises ValueError instead.  With return_status -> (PackedMasks,
+    status int32 (N,))."""
+    bits, area, box, status, H, W = _rle_unpack(counts, offsets, H, W, True)
+    if check:
+        _check_rle_status(status, H, W)
+    packed = PackedMasks(bits, area, box, H, W)
+    return (packed, status) if return_status else packed
+
+
+def rle_stats(counts, offsets, H, W):
+    """area int32 (N,), box int32 (N,4) xmin ymin xmax ymax and status int32 (N,) of device run lists, from the runs alone (the same
+    entry point without its bits launch): the annotation info of an RLE without decoding it.  A mask with a nonzero status (see
+    rle_unpack) has area 0 and a box of -1s."""
+    _, area, box, status, _, _ = _rle_unpack(counts, offsets, H, W, False)
+    return area, box, status
+
+
+def rle_from_string(s):
+    """pycocotools' rleFrString: the compressed `counts` string of an RLE -> its run lengths (list of int; host).  Each character
+    minus 48 carries 5 payload bits, least significant group first; bit 0x20 says that more follow; on a value's last character bit
+    0x10 extends the sign.  From the fourth value on a value is stored as its difference against the value two places back."""
+    if isinstance(s, str):
+        s = s.encode("ascii")
+    counts, p, n = [], 0, len(s)
+    while p < n:
+        x, k, more = 0, 0, True
+        while more:
+            if p >= n:
+                raise ValueError("the compressed RLE string ends inside a value")
+            c = s[p] - 48
+            if not 0 <= c < 64:
+                raise ValueError("character %r is not part of a compressed RLE string" % (chr(s[p]),))
+            x |= (c & 0x1f) << (5 * k)
+            more = bool(c & 0x20)
+            p += 1
+            k += 1
+            if not more and (c & 0x10):
+                x |= -1 << (5 * k)
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+def rle_to_string(counts):
+    """pycocotools' rleToString, rle_from_string's inverse: run lengths -> the compressed `counts` string (str; host)"""
+    counts = [int(v) for v in counts]
+    out = []
+    for i, x in enumerate(counts):
+        if i > 2:
+            x -= counts[i - 2]
+        more = True
+        while more:
+            c = x & 0x1f
+            x >>= 5
+            more = (x != -1) if (c & 0x10) else (x != 0)
+            if more:
+                c |= 0x20
+            out.append(c + 48)
+    return bytes(out).decode("ascii")
+
+
+def rle_flatten(rles):
+    """a list of RLE dicts of one size -> (counts int32 (total,), offsets int64 (N + 1,), (H, W)) numpy arrays in rle_encode's layout
+    (host).  A `counts` that is a str or bytes is a compressed string (rle_from_string).  Negative counts pass (the decoder names
+    them); counts outside int32 raise ValueError."""
+    if not rles:
+        return np.zeros(0, np.int32), np.zeros(1, np.int64), (1, 1)
+    H, W = (int(v) for v in rles[0]["size"])
+    runs = []
+    for rle in rles:
+        if [int(v) for v in rle["size"]] != [H, W]:
+            raise ValueError("every RLE must have size %r, got %r" % ([H, W], rle["size"]))
+        c = rle["counts"]
+        try:
+            a = np.asarray(rle_from_string(c) if isinstance(c, (str, bytes)) else c, np.int64).reshape(-1)
+        except OverflowError:
+            a = None
+        if a is None or (a.size and (a.max() > 2 ** 31 - 1 or a.min() < -2 ** 31)):
+            raise ValueError("RLE counts do not fit int32")
+        runs.append(a)
+    offsets = np.zeros(len(runs) + 1, np.int64)
+    np.cumsum([len(a) for a in runs], out=offsets[1:])
+    return np.concatenate(runs).astype(np.int32), offsets, (H, W)
 
 
 def annotate_masks(masks, return_rle=False, device=None):
@@ -467,9 +601,21 @@ def concat_packed(parts):
 
 
 def pack_rles(rles, device, chunk=512):
-    """RLE dicts -> PackedMasks, `chunk` masks at a time: decoded on the host, uploaded and packed, so that neither side ever holds
-    more than `chunk` frames as bytes"""
-    return concat_packed([pack_masks(rle_decode(rles[i:i + chunk]), device) for i in range(0, len(rles), chunk)])
+    """RLE dicts (counts as lists or as pycocotools' compressed strings) -> PackedMasks, `chunk` masks per call: the run lists are
+    flattened on the host (rle_flatten), go up in one small upload -- a few KB per mask where the dense mask has H * W bytes -- and are
+    decoded on the device (rle_unpack); no dense mask exists on either side.  The same bits, area and box as
+    pack_masks(rle_decode(rles)); counts that do not fit the frame raise ValueError as there."""
+    dev = torch.device(device)
+    scene.require_cuda("coco_eval", device=dev)
+    parts = []
+    for i in range(0, len(rles), chunk):
+        counts, offsets, (H, W) = rle_flatten(rles[i:i + chunk])
+        head = offsets.nbytes
+        up = torch.from_numpy(np.concatenate([offsets.view(np.uint8), counts.view(np.uint8)])).to(dev)      # offsets first: 8-byte aligned
+        packed, status = rle_unpack(up[head:].view(torch.int32), up[:head].view(torch.int64), H, W, check=False, return_status=True)
+        _check_rle_status(status, H, W, first=i)
+        parts.append(packed)
+    return concat_packed(parts)
 
 
 def merge_scenes(scene_coco_anns, coco_results, targets, ann_type="segm"):
@@ -518,7 +664,8 @@ def eval_bop22_coco(scene_coco_anns, coco_results, targets, ann_type="segm", bbo
     """scripts/eval_bop22_coco.py's loop body on dicts -> the content of scores_bop22_coco_<ann_type>.json: the twelve scores and
     average_time_per_image.  scene_coco_anns: {scene_id: scene_gt_coco dict} in the split's scene order; scene_coco_anns_modal: the
     scene_gt_coco_modal dicts, which the script reads instead when ann_type is 'bbox' and bbox_type is 'modal' (required then).  RLE
-    masks (ground truth and results) are decoded on the host 512 at a time, packed and scored on the device."""
+    masks (ground truth and results; counts as lists or as pycocotools' compressed strings, which loadRes accepts too) go up as run
+    lists 512 masks at a time and are decoded and scored on the device (pack_rles, row N29): no dense mask on either side."""
     if bbox_type not in ("amodal", "modal"):
         raise ValueError("%s is not a valid bounding box type" % (bbox_type,))
     if ann_type == "bbox" and bbox_type == "modal":

@@ -1650,6 +1650,27 @@ int cp_paste_rle_write(cp_stream_t stream, const float* seg, long long seg_bstri
 int cp_coco_unpack(cp_stream_t stream, const uint32_t* bits, int N, int H, int W, uint8_t* masks);
 
 /* ---------------------------------------------------------------------------------------------
+ * COCO RLE masks decoded on the device (row N29; csrc/rle_unpack.hip; reference pycoco_utils.rle_to_binary_mask).  The inverse of
+ * cp_coco_rle_count / cp_coco_rle_write without a dense mask: counts int32 (total) and offsets int64 (N + 1), both on the device, in
+ * cp_coco_rle_write's layout -> what cp_coco_pack leaves for the decoded masks.  The rule is stated at the top of the kernel file and
+ * restated in numpy by tests/rle_stages.py: with E_j the inclusive ends of mask n's run lengths (64-bit sums), pixel i = x H + y is set
+ * iff k = #{ j : E_j <= i } is odd and below the mask's run count; area = the sum of the odd-indexed counts; the box from the runs.
+ *
+ * cp_coco_rle_unpack: -> bits (N,H,WW), every word written (NULL: area, box and status only, one launch), area (N), box (N,4) xmin
+ *   ymin xmax ymax (-1s for an empty mask), status (N): 0 ok; 3 the mask's offsets do not fit [0, total] (no count is read); else 1 a
+ *   negative count; else 2 the counts sum to more than H W.  A mask with a nonzero status gets all-zero bits, area 0, a box of -1s.
+ *   ends_scratch: cp_coco_rle_unpack_scratch_bytes(total) bytes, uninitialised (the inclusive ends, int32).  The stretches of two
+ *   masks must not overlap.  Nothing allocates or synchronises; integer arithmetic only, no atomics; bit-identical for a mask alone
+ *   or at any batch position.
+ * CP_ERR_INVALID: a null pointer (counts and ends_scratch may be NULL when total == 0; bits may be NULL), N, H or W < 1, total < 0;
+ *   CP_ERR_ALIGN: a pointer not aligned to its element; CP_ERR_RANGE: H * W >= 2^31 - 4096, N >= 2^24, total >= 2^31, 2^31
+ *   workgroups or more.
+ * ------------------------------------------------------------------------------------------- */
+size_t cp_coco_rle_unpack_scratch_bytes(long long total);
+int cp_coco_rle_unpack(cp_stream_t stream, const int32_t* counts, const int64_t* offsets, int N, int H, int W, long long total,
+                       int32_t* ends_scratch, uint32_t* bits, int32_t* area, int32_t* box, int32_t* status);
+
+/* ---------------------------------------------------------------------------------------------
  * hipGraph helpers: capture the launch sequence of one forward (everything above is capture-safe:
  * no allocation, no synchronisation) and replay it with one call.
  * ------------------------------------------------------------------------------------------- */
