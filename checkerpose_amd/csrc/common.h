@@ -188,12 +188,33 @@ __device__ __forceinline__ void cp_scan_sum_max(int& c, int& l, int& ec, int& el
 // align_corners source coordinate of output index o (scale s = (n - 1) / (2 n - 1)): left neighbour, step to the right one, the
 // right one's weight.  `contract(off)`: hipcc's default -ffp-contract=fast may fuse s * o - i0 into one fma in one kernel and
 // not in another (__fmul_rn / __fsub_rn are plain * and - in HIP); with the pragma every kernel derives the same weights.
+// Rule: up to CP_UP_F32_MAX_N inputs on the axis the coordinate is ATen's float32 product s * o (the networks' maps are 8 .. 64
+// wide).  That product is off by up to about n * 2^-23 of a pixel (1.5e-5 at n = 128, 1e-3 at n = 16400), so a longer axis takes the
+// exact coordinate instead: i0 = floor(o (n - 1) / (2 n - 1)), l1 = the remainder over 2 n - 1, stepped from the float32 guess.
+#define CP_UP_F32_MAX_N 128
+__device__ __forceinline__ void cp_up_coord_exact(int o, int n, int& i0, float& l1) {      // i0: the float32 guess on entry
+#pragma clang fp contract(off)
+  const long long den = 2LL * n - 1;
+  long long r = (long long)o * (n - 1) - (long long)i0 * den;
+  while (r < 0) { --i0; r += den; }
+  while (r >= den) { ++i0; r -= den; }
+  l1 = (float)r / (float)den;
+}
+// LONG = false: the instantiation for maps with no long axis (every launch of the networks): the float32 form alone, no test of n.
+// The host picks LONG = true when either axis has more than CP_UP_F32_MAX_N inputs; each axis then follows the rule by its own n.
+template <bool LONG = true>
 __device__ __forceinline__ void cp_up_coord(float s, int o, int n, int& i0, int& step, float& l1) {
 #pragma clang fp contract(off)
   const float f = s * (float)o;
   i0 = (int)f;
-  step = i0 < n - 1 ? 1 : 0;
-  l1 = f - (float)i0;
+  if constexpr (LONG) {
+    l1 = f - (float)i0;
+    if (n > CP_UP_F32_MAX_N) cp_up_coord_exact(o, n, i0, l1);
+    step = i0 < n - 1 ? 1 : 0;
+  } else {
+    step = i0 < n - 1 ? 1 : 0;
+    l1 = f - (float)i0;
+  }
 }
 __device__ __forceinline__ float cp_one_minus(float l1) {
 #pragma clang fp contract(off)

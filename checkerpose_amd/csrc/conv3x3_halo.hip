@@ -273,7 +273,7 @@ __global__ __launch_bounds__(256) void conv3x3_halo_kernel(const HaloParams p) {
 // Conv2d(256 -> 2) + bias on the last decoder map, NCHW fp32 out) rides in the epilogue -- every lane dots the 16 activated,
 // storage-rounded channels of its pixel with the head's weights, the four lane groups of a pixel meet by shuffle, the four
 // waves (64 channels each) through LDS: the 537 MB re-read of the map by a separate launch disappears.
-template <typename Tag, bool HAS_RES, bool UP = false, bool SEG = false>
+template <typename Tag, bool HAS_RES, bool UP = false, bool SEG = false, bool UPLONG = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const HaloParams p) {
   constexpr int E = Tag::E;
   constexpr int KCH = 4 * E;
@@ -332,8 +332,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const HaloParams 
   float m_lx[3], m_ly[3];
   if constexpr (UP) {
     int sy0, sx0, st_; float fr_;                              // source tile origin = left / top neighbour of the first in-image halo pixel
-    cp_up_coord(p.up_sy, y0 > 0 ? y0 - 1 : 0, p.Hs, sy0, st_, fr_);
-    cp_up_coord(p.up_sx, x0 > 0 ? x0 - 1 : 0, p.Ws, sx0, st_, fr_);
+    cp_up_coord<UPLONG>(p.up_sy, y0 > 0 ? y0 - 1 : 0, p.Hs, sy0, st_, fr_);
+    cp_up_coord<UPLONG>(p.up_sx, x0 > 0 ? x0 - 1 : 0, p.Ws, sx0, st_, fr_);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
       const int i = tid + 256 * k;
@@ -351,8 +351,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const HaloParams 
       const int gy = y0 - 1 + py, gx = x0 - 1 + px;
       const bool ok = (hp < HPH * HPW) & ((unsigned)gy < (unsigned)p.H) & ((unsigned)gx < (unsigned)p.W);
       int iy0, ix0, my, mx;
-      cp_up_coord(p.up_sy, gy, p.Hs, iy0, my, m_ly[k]);
-      cp_up_coord(p.up_sx, gx, p.Ws, ix0, mx, m_lx[k]);
+      cp_up_coord<UPLONG>(p.up_sy, gy, p.Hs, iy0, my, m_ly[k]);
+      cp_up_coord<UPLONG>(p.up_sx, gx, p.Ws, ix0, mx, m_lx[k]);
       m_off[k] = ok ? (uint32_t)((((iy0 - sy0) * USRW + (ix0 - sx0)) * 4 + pq) * 16) | (uint32_t)(mx | (my << 1) | 4) : 0u;
     }
   }
@@ -1377,7 +1377,10 @@ extern "C" int cp_conv3x3_halo_up2x(cp_stream_t stream, const CpConvDesc* d, con
   p.w_bytes = (uint32_t)wb;
   p.o_base = d->o_base; p.o_sb = d->o_sb; p.o_sy = d->o_sy; p.o_sx = d->o_sx;
   const unsigned grid4 = (unsigned)(((tt + 7) / 8) * 8 * p.NB);
-  if (d->dtype == CP_F32) CP_LAUNCH((conv3x3_halo4_kernel<F32Tag, false, true, false>), dim3(grid4), dim3(256), 2 * HBUF + 2 * USBUF, (hipStream_t)stream, p);
+  if (p.Hs > CP_UP_F32_MAX_N || p.Ws > CP_UP_F32_MAX_N) {      // a long source axis: the exact coordinate, as in the stand-alone kernel
+    if (d->dtype == CP_F32) CP_LAUNCH((conv3x3_halo4_kernel<F32Tag, false, true, false, true>), dim3(grid4), dim3(256), 2 * HBUF + 2 * USBUF, (hipStream_t)stream, p);
+    else CP_LAUNCH((conv3x3_halo4_kernel<BF16Tag, false, true, false, true>), dim3(grid4), dim3(256), 2 * HBUF + 2 * USBUF, (hipStream_t)stream, p);
+  } else if (d->dtype == CP_F32) CP_LAUNCH((conv3x3_halo4_kernel<F32Tag, false, true, false>), dim3(grid4), dim3(256), 2 * HBUF + 2 * USBUF, (hipStream_t)stream, p);
   else CP_LAUNCH((conv3x3_halo4_kernel<BF16Tag, false, true, false>), dim3(grid4), dim3(256), 2 * HBUF + 2 * USBUF, (hipStream_t)stream, p);
   return cp_check_launch();
 }

@@ -5,9 +5,11 @@
 // ---- nn.UpsamplingBilinear2d(scale_factor=2)  (pipeline.py:199; == F.interpolate(align_corners=True)).
 // ATen (UpSample.h, align_corners): scale = (in-1)/(out-1); src = scale*dst; i0 = floor(src); i1 = i0 + (i0 < in-1);
 // l1 = src - i0; l0 = 1 - l1;  out = l0h*(l0w*x00 + l1w*x01) + l1h*(l0w*x10 + l1w*x11)   -- all in fp32.
+// Rule (cp_up_coord): the coordinate is ATen's float32 scale*dst up to 128 inputs on the axis and the exact quotient beyond, where the
+// float32 product would leave the exact map by in * 2^-23 pixels; in == 1 has scale 0 and both outputs copy the one input.
 // grid.y = one output row (b, oy): the row weights / source rows are block-uniform and the only per-thread index split is
 // (ox, channel group) -- a shift when the group count is a power of two (the decoder's 256 / 512 channels).
-template <typename Tag>
+template <typename Tag, bool LONG>
 __global__ void upsample2x_bilinear_kernel(const void* __restrict__ in, void* __restrict__ out, int H, int W, int CG, int cg_shift,
                                            int in_cs, int in_coff, int out_cs, int out_coff, float sy, float sx, unsigned rows) {
   // one thread = one 16-byte channel group of TWO horizontally adjacent output pixels (2 j, 2 j + 1): their source columns
@@ -22,15 +24,15 @@ __global__ void upsample2x_bilinear_kernel(const void* __restrict__ in, void* __
   const int oy = (int)(row % (unsigned)(2 * H));
   const size_t b = row / (unsigned)(2 * H);
   int y0, ystep; float ly1;
-  cp_up_coord(sy, oy, H, y0, ystep, ly1);
+  cp_up_coord<LONG>(sy, oy, H, y0, ystep, ly1);
   const int y1 = y0 + ystep;
   const float ly0 = cp_one_minus(ly1);
   const u32x4* src = (const u32x4*)in;
   const size_t r0 = ((b * H + y0) * W) * in_cs + in_coff + (size_t)g * E, r1 = ((b * H + y1) * W) * in_cs + in_coff + (size_t)g * E;
   const int oxa = 2 * j, oxb = 2 * j + 1;
   int xa0, xb0, xas, xbs; float lxa1, lxb1;
-  cp_up_coord(sx, oxa, W, xa0, xas, lxa1);
-  cp_up_coord(sx, oxb, W, xb0, xbs, lxb1);
+  cp_up_coord<LONG>(sx, oxa, W, xa0, xas, lxa1);
+  cp_up_coord<LONG>(sx, oxb, W, xb0, xbs, lxb1);
   const int xa1 = xa0 + xas, xb1 = xb0 + xbs;
   // distinct source columns: xa0 <= xb0 <= xa0 + 1, so {xa0, xa1, xb1} covers all four (xb0 is xa0 or xa1)
   u32x4 t0 = src[(r0 + (size_t)xa0 * in_cs) / E], t1 = src[(r0 + (size_t)xa1 * in_cs) / E], t2 = src[(r0 + (size_t)xb1 * in_cs) / E];
@@ -62,7 +64,7 @@ extern "C" int cp_upsample2x_bilinear_ac(cp_stream_t stream, int dtype, const vo
   if (dtype != CP_F32 && dtype != CP_BF16) return CP_ERR_INVALID;
   const int E = cp_chan_align(dtype);
   if (C % E || in_cstride % E || in_coff % E || out_cstride % E || out_coff % E) return CP_ERR_ALIGN;
-  if (in_coff + C > in_cstride || out_coff + C > out_cstride) return CP_ERR_INVALID;
+  if (in_coff < 0 || out_coff < 0 || in_coff + C > in_cstride || out_coff + C > out_cstride) return CP_ERR_INVALID;
   if (!cp_aligned16(in) || !cp_aligned16(out)) return CP_ERR_ALIGN;
   const float sy = H > 1 ? (float)(H - 1) / (float)(2 * H - 1) : 0.f;
   const float sx = W > 1 ? (float)(W - 1) / (float)(2 * W - 1) : 0.f;
@@ -74,12 +76,13 @@ extern "C" int cp_upsample2x_bilinear_ac(cp_stream_t stream, int dtype, const vo
   const unsigned gy = rows > 65535 ? 65535u : (unsigned)rows, gz = (unsigned)((rows + gy - 1) / gy);
   if (gz > 65535) return CP_ERR_RANGE;
   const dim3 grid((unsigned)((W * CG + 255) / 256), gy, gz);
-  if (dtype == CP_F32)
-    CP_LAUNCH(upsample2x_bilinear_kernel<F32Tag>, grid, dim3(256), 0, (hipStream_t)stream, in, out, H, W,
-                       CG, cg_shift, in_cstride, in_coff, out_cstride, out_coff, sy, sx, (unsigned)rows);
-  else
-    CP_LAUNCH(upsample2x_bilinear_kernel<BF16Tag>, grid, dim3(256), 0, (hipStream_t)stream, in, out, H, W,
-                       CG, cg_shift, in_cstride, in_coff, out_cstride, out_coff, sy, sx, (unsigned)rows);
+  const bool lng = H > CP_UP_F32_MAX_N || W > CP_UP_F32_MAX_N;      // a long axis: the instantiation with the exact coordinate
+#define CP_UP_LAUNCH(TAG, LONG)                                                                                              \
+  CP_LAUNCH((upsample2x_bilinear_kernel<TAG, LONG>), grid, dim3(256), 0, (hipStream_t)stream, in, out, H, W, CG, cg_shift, \
+            in_cstride, in_coff, out_cstride, out_coff, sy, sx, (unsigned)rows)
+  if (dtype == CP_F32) { if (lng) CP_UP_LAUNCH(F32Tag, true); else CP_UP_LAUNCH(F32Tag, false); }
+  else { if (lng) CP_UP_LAUNCH(BF16Tag, true); else CP_UP_LAUNCH(BF16Tag, false); }
+#undef CP_UP_LAUNCH
   return cp_check_launch();
 }
 

@@ -120,7 +120,8 @@ __global__ void nhwc_to_nchw_kernel(const void* __restrict__ in, float* __restri
 
 extern "C" int cp_nhwc_to_nchw_f32(cp_stream_t stream, int dtype, const void* in, float* out, int B, int C, int H,
                                    int W, int in_cstride, int in_coff) {
-  if (!in || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || in_coff + C > in_cstride) return CP_ERR_INVALID;
+  if (!in || !out || B <= 0 || C <= 0 || H <= 0 || W <= 0 || in_coff < 0 || in_coff + C > in_cstride) return CP_ERR_INVALID;
+  if (B > 65535 || (C + 31) / 32 > 65535) return CP_ERR_RANGE;      // grid.z = B, grid.y = channel tiles
   dim3 grid((H * W + 31) / 32, (C + 31) / 32, B), block(32, 8);
   if (dtype == CP_F32)
     CP_LAUNCH(nhwc_to_nchw_kernel<F32Tag>, grid, block, 0, (hipStream_t)stream, in, out, C, H * W, in_cstride, in_coff);

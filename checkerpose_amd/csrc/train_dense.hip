@@ -328,7 +328,7 @@ int cp_bn_finalize_launch(hipStream_t st, const double* partial, int nblk, int C
 
 static int check_cl(int dtype, const void* p, int cs, int coff, int Cphys) {
   const int E = cp_chan_align(dtype);
-  if (!p) return CP_ERR_INVALID;
+  if (!p || coff < 0) return CP_ERR_INVALID;      // a negative offset would address memory before the buffer
   if (cs % E || coff % E || coff + Cphys > cs || !cp_aligned16(p)) return CP_ERR_ALIGN;
   return CP_OK;
 }
@@ -528,7 +528,8 @@ extern "C" int cp_bn_train_bwd(cp_stream_t stream, int dtype, const void* dy, in
 // ------------------------------------------------------------------------------------------------ resampling backward
 // Adjoint of cp_upsample2x_bilinear_ac in gather form (deterministic): input pixel (y,x) collects every output pixel
 // whose 2x2 footprint touches it, with the forward's own fp32 weights.
-template <typename Tag>
+// LONG (host: an axis with more than CP_UP_F32_MAX_N inputs): the forward's exact coordinate on such an axis (cp_up_coord)
+template <typename Tag, bool LONG>
 __global__ void upsample2x_bwd_kernel(const void* __restrict__ dout, void* __restrict__ din, int H, int W, int CG, int o_cs,
                                       int o_coff, int i_cs, int i_coff, float sy, float sx, int accumulate, size_t total) {
   constexpr int E = Tag::E;
@@ -543,19 +544,27 @@ __global__ void upsample2x_bwd_kernel(const void* __restrict__ dout, void* __res
   float acc[E];
 #pragma unroll
   for (int j = 0; j < E; ++j) acc[j] = 0.f;
-  // candidate outputs: src = s*o in (y-1, y+1)  ->  o in ((y-1)/s, (y+1)/s); scan a safe integer window
-  const int oy_lo = max(0, (int)floorf((y - 1) / fmaxf(sy, 1e-20f)) - 1), oy_hi = min(2 * H - 1, (int)ceilf((y + 1) / fmaxf(sy, 1e-20f)) + 1);
-  const int ox_lo = max(0, (int)floorf((x - 1) / fmaxf(sx, 1e-20f)) - 1), ox_hi = min(2 * W - 1, (int)ceilf((x + 1) / fmaxf(sx, 1e-20f)) + 1);
+  // candidate outputs: floor(s*o) in {y-1, y}  ->  o in [(y-1)/s, (y+1)/s) with 1/s = 2 + 1/(n-1) in (2, 3], i.e. o in
+  // [2y-2, 2y+4]; one more on each side for the rounding of s*o.  Integers only: n == 1 (s == 0, every output maps to
+  // source 0) clamps to the whole axis [0, 1].  The loop body decides membership, the window only has to contain it.
+  const int oy_lo = max(0, 2 * y - 3), oy_hi = min(2 * H - 1, 2 * y + 5);
+  const int ox_lo = max(0, 2 * x - 3), ox_hi = min(2 * W - 1, 2 * x + 5);
   for (int oy = oy_lo; oy <= oy_hi; ++oy) {
     const float fy = sy * oy;
-    const int y0 = (int)fy, y1 = y0 + (y0 < H - 1);
-    const float ly1 = fy - y0, ly0 = 1.f - ly1;
+    int y0 = (int)fy;
+    float ly1 = fy - y0;
+    if constexpr (LONG) { if (H > CP_UP_F32_MAX_N) cp_up_coord_exact(oy, H, y0, ly1); }
+    const int y1 = y0 + (y0 < H - 1);
+    const float ly0 = 1.f - ly1;
     const float wy = (y0 == y ? ly0 : 0.f) + (y1 == y ? ly1 : 0.f);
     if (y0 != y && y1 != y) continue;
     for (int ox = ox_lo; ox <= ox_hi; ++ox) {
       const float fx = sx * ox;
-      const int x0 = (int)fx, x1 = x0 + (x0 < W - 1);
-      const float lx1 = fx - x0, lx0 = 1.f - lx1;
+      int x0 = (int)fx;
+      float lx1 = fx - x0;
+      if constexpr (LONG) { if (W > CP_UP_F32_MAX_N) cp_up_coord_exact(ox, W, x0, lx1); }
+      const int x1 = x0 + (x0 < W - 1);
+      const float lx0 = 1.f - lx1;
       const float wx = (x0 == x ? lx0 : 0.f) + (x1 == x ? lx1 : 0.f);
       if (x0 != x && x1 != x) continue;
       float d[E];
@@ -588,12 +597,13 @@ extern "C" int cp_upsample2x_bilinear_ac_bwd(cp_stream_t stream, int dtype, cons
   const int CG = C / E;
   const size_t total = (size_t)B * H * W * CG;
   const unsigned blocks = (unsigned)((total + 255) / 256);
-  if (dtype == CP_F32)
-    CP_LAUNCH(upsample2x_bwd_kernel<F32Tag>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, din, H, W, CG, out_cstride,
-              out_coff, in_cstride, in_coff, sy, sx, accumulate, total);
-  else
-    CP_LAUNCH(upsample2x_bwd_kernel<BF16Tag>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, din, H, W, CG, out_cstride,
-              out_coff, in_cstride, in_coff, sy, sx, accumulate, total);
+  const bool lng = H > CP_UP_F32_MAX_N || W > CP_UP_F32_MAX_N;
+#define CP_UPB_LAUNCH(TAG, LONG)                                                                                                  \
+  CP_LAUNCH((upsample2x_bwd_kernel<TAG, LONG>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dout, din, H, W, CG, out_cstride, \
+            out_coff, in_cstride, in_coff, sy, sx, accumulate, total)
+  if (dtype == CP_F32) { if (lng) CP_UPB_LAUNCH(F32Tag, true); else CP_UPB_LAUNCH(F32Tag, false); }
+  else { if (lng) CP_UPB_LAUNCH(BF16Tag, true); else CP_UPB_LAUNCH(BF16Tag, false); }
+#undef CP_UPB_LAUNCH
   return cp_check_launch();
 }
 

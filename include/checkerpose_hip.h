@@ -43,7 +43,7 @@ enum {
   CP_ERR_INVALID = -1,   /* bad argument / unsupported shape */
   CP_ERR_HIP = -2,       /* a HIP runtime call failed (launch error, bad pointer, ...) */
   CP_ERR_ALIGN = -3,     /* pointer or stride not aligned as the kernel requires */
-  CP_ERR_RANGE = -4      /* buffer too large for 32-bit buffer addressing (>= 2 GiB) */
+  CP_ERR_RANGE = -4      /* buffer too large for 32-bit buffer addressing (>= 2 GiB), or a size beyond a launch-grid dimension */
 };
 
 int cp_version(void);
@@ -285,7 +285,11 @@ int cp_mlp_pair_fused_gather_t(cp_stream_t stream, int dtype, const CpI2fGather*
                                const float* bias2, float slope2, void* out, int out_cstride, int out_coff);
 
 /* nn.UpsamplingBilinear2d(scale_factor=2) == interpolate(align_corners=True), pipeline.py:199.
- * Reads channels [in_coff, in_coff+C) of (B,H,W,in_cstride), writes [out_coff, ..) of (B,2H,2W,out_cstride). */
+ * Reads channels [in_coff, in_coff+C) of (B,H,W,in_cstride), writes [out_coff, ..) of (B,2H,2W,out_cstride).
+ * H == 1 / W == 1 are legal (scale 0: both outputs of the axis copy the one input).  The source coordinate is ATen's float32
+ * scale * dst on an axis of up to 128 inputs and the exact quotient on a longer one (the float32 product is off by about
+ * n * 2^-23 of a pixel); cp_conv3x3_halo_up2x and the backward follow the same rule.  CP_ERR_INVALID: a channel slice outside
+ * [0, cstride), negative offsets included. */
 int cp_upsample2x_bilinear_ac(cp_stream_t stream, int dtype, const void* in, void* out, int B, int H, int W,
                               int C, int in_cstride, int in_coff, int out_cstride, int out_coff);
 
@@ -1457,7 +1461,8 @@ int cp_edgeconv_train_bwd(cp_stream_t stream, int dtype, const void* pq, const i
  * mode 1: (C, 2C') with out[c][c'] = W1[c'][c], out[c][C'+c'] = W2[c'][c] (data-gradient of the node GEMM over D). */
 int cp_edge_weight_view(cp_stream_t stream, const float* w, int Cout, int Cin, int mode, float* out);
 
-/* Backward of cp_upsample2x_bilinear_ac (gather form, deterministic) and of ONE source of cp_fuse_sum_act
+/* Backward of cp_upsample2x_bilinear_ac (gather form, deterministic; H == 1 / W == 1: the sum of both output rows / columns;
+ * CP_ERR_INVALID for a negative out_coff / in_coff) and of ONE source of cp_fuse_sum_act
  * (dsrc (+)= sum over the 2^shift x 2^shift block of dout * [out > 0]). */
 int cp_upsample2x_bilinear_ac_bwd(cp_stream_t stream, int dtype, const void* dout, void* din, int B, int H, int W, int C,
                                   int out_cstride, int out_coff, int in_cstride, int in_coff, int accumulate);
@@ -1515,7 +1520,9 @@ int cp_pack_batch(cp_stream_t stream, int dtype, const CpPackItem* items_dev, co
                   uint32_t total_blocks);
 
 /* layout plumbing at the boundary: NCHW fp32 image -> channels-last `dtype` (C padded with zeros to
- * Cphys), and channels-last slice -> NCHW fp32 (for `return_img_feats`, init.py:123-124). */
+ * Cphys), and channels-last slice -> NCHW fp32 (for `return_img_feats`, init.py:123-124).
+ * cp_nhwc_to_nchw_f32: CP_ERR_INVALID for in_coff < 0 or in_coff + C > in_cstride; CP_ERR_RANGE for B > 65535 or more than
+ * 65535 channel tiles of 32 (both are grid dimensions). */
 int cp_nchw_to_nhwc(cp_stream_t stream, int dtype, const float* in, void* out, int B, int C, int H, int W,
                     int Cphys);
 int cp_nhwc_to_nchw_f32(cp_stream_t stream, int dtype, const void* in, float* out, int B, int C, int H, int W,

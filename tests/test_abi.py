@@ -272,6 +272,12 @@ def test_training_entry_points_validate_before_launch(lib):
     assert lib.cp_upsample2x_bilinear_ac_bwd(None, 0, A, A, 1, 4, 4, 18, 20, 0, 20, 0, 0) == -3
     assert lib.cp_fuse_sum_act_bwd(None, 0, A, None, A, 1, 4, 4, 16, 1, 1, 0) == -1                    # relu mask without `out`
     assert lib.cp_maxpool3x3s2_bwd(None, 0, A, A, A, 1, 7, 8, 16, 0) == -1
+    assert lib.cp_upsample2x_bilinear_ac(None, 0, A, A, 1, 4, 4, 16, 32, -4, 32, 0) == -1              # negative input channel offset
+    assert lib.cp_upsample2x_bilinear_ac(None, 0, A, A, 1, 4, 4, 16, 32, 0, 32, -4) == -1              # negative output channel offset
+    assert lib.cp_upsample2x_bilinear_ac_bwd(None, 0, A, A, 1, 4, 4, 16, 32, -4, 32, 0, 0) == -1       # ... and in the backward (dout)
+    assert lib.cp_upsample2x_bilinear_ac_bwd(None, 0, A, A, 1, 4, 4, 16, 32, 0, 32, -4, 0) == -1       # (din)
+    assert lib.cp_nhwc_to_nchw_f32(None, 0, A, A, 1, 16, 4, 4, 32, -4) == -1                           # negative input channel offset
+    assert lib.cp_nhwc_to_nchw_f32(None, 0, A, A, 65536, 16, 4, 4, 16, 0) == -4                        # batch beyond gridDim.z
     assert lib.cp_memset_zero(None, A + 4, 64) == -3 and lib.cp_memset_zero(None, None, 64) == -1
     assert lib.cp_memcpy_d2d(None, None, A, 16) == -1
     assert lib.cp_strided_to_nhwc(None, 0, A, 1, 0, 1, 1, 1, A, 1, 4, 3, 4) == -1                      # src dtype neither fp32 nor dtype

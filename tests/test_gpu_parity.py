@@ -335,6 +335,7 @@ UP_CASES = [  # (B, Cin, cin_total, coff, Hs, Ws, Cout, act): low-resolution sou
     (2, 40, 40, 0, 4, 8, 512, ACT_LEAKY),        # one tile per crop, two 256-channel blocks, partial chunk
     (1, 256, 256, 0, 32, 32, 256, ACT_RELU),     # decoder shape class (many tiles per crop, interior tiles)
     (1, 32, 32, 0, 5, 9, 256, ACT_NONE),         # odd source size
+    (1, 32, 32, 0, 130, 3, 256, ACT_NONE),       # more than 128 source rows: the exact source coordinate of cp_up_coord
 ]
 
 
