@@ -44,11 +44,12 @@
 // Stage A is the scaffold's three kernels (pose, vertex, 32 x 32 tile with vs_raster_tile<true>; the tile kernel stores only the
 // lattice pixels' (depth, face) into the pose's slots) and a finish pass that turns them into pixel, X, N.  Stages B and C are ONE
 // launch, one 256-thread workgroup per pose, like pnp_refine.hip: a thread takes slots tid, tid + 256, ... in ascending order,
-// pnp_core.h's block_sum joins the 21 + 6 + 1 + 1 sums (H, g, c, n) in a fixed order, no atomics.  Thread 0 does the Cholesky and
-// Rodrigues (L, y, d in LDS) and publishes the trial through LDS; all threads then evaluate c'.  The pairs are NOT kept between the
-// passes: stage B is recomputed from the state pose (deterministic; 52 bytes per slot and one depth gather, all in L2 after the first
-// pass), which keeps the kernel free of per-thread arrays and of scratch.  Every branch on accept / stop is taken on block_sum results
-// or LDS words that all threads hold identically; every loop is bounded by max_iters or the slot count; no workgroup waits for another.
+// pnp_core.h's block_sum joins the 21 + 6 + 1 + 1 sums (H, g, c, n) in a fixed order, no atomics.  Thread 0 damps H, does the Cholesky
+// and Rodrigues (pnp_core.h's lm_solve_step; L in LDS), applies the step bound and publishes the trial through LDS; all threads then
+// evaluate c'.  The pairs are NOT kept between the passes: stage B is recomputed from the state pose (deterministic; 52 bytes per slot
+// and one depth gather, all in L2 after the first pass), which keeps the kernel free of per-thread arrays and of scratch.  Every
+// branch on accept / stop is taken on block_sum results or LDS words that all threads hold identically; every loop is bounded by
+// max_iters or the slot count; no workgroup waits for another.
 #include "pnp_core.h"
 #include "vsd_raster.h"
 
@@ -284,79 +285,10 @@ __device__ __forceinline__ void icp_accumulate(const IcpView& s, int tid, const 
   }
 }
 
-// thread 0: (H + lambda diag H + inertia n diag(rho^2 x 3, 1 x 3)) d = -g by Cholesky, then the trial pose.  out[0..5] d, [6..14] R',
-// [15..17] t', [18] s.  -> 0: no Cholesky factor (NaN in out); 1: a trial pose; 2: a trial pose beyond the step bound.
-// L (6 x 6), y and d live in LDS: indexed by loop variables, they would otherwise go to scratch
-__device__ __forceinline__ int icp_trial(const double* Hs, const double* R, const double* t, double lambda, double damp, double rho, double max_dist,
-                                         double (*L)[6], double* y, double* d, double* out) {
-  int e = 0;
-#pragma unroll
-  for (int p = 0; p < 6; ++p)
-#pragma unroll
-    for (int q = p; q < 6; ++q) { L[q][p] = Hs[e]; ++e; }                     // lower triangle of H
-  for (int p = 0; p < 6; ++p) L[p][p] = (L[p][p] + lambda * L[p][p]) + damp * (p < 3 ? rho * rho : 1.0);
-  bool pd = true;
-  for (int j = 0; j < 6 && pd; ++j) {
-    double s = L[j][j];
-    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-    if (!(s > 0.0) || !isfinite(s)) { pd = false; break; }
-    const double ljj = sqrt(s);
-    L[j][j] = ljj;
-    for (int i = j + 1; i < 6; ++i) {
-      double v = L[i][j];
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v / ljj;
-    }
-  }
-  if (pd) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] = -Hs[21 + i];
-    for (int i = 0; i < 6; ++i) {
-      double v = y[i];
-      for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-      y[i] = v / L[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-      double v = y[i];
-      for (int k = i + 1; k < 6; ++k) v -= L[k][i] * d[k];
-      d[i] = v / L[i][i];
-    }
-    for (int i = 0; i < 6; ++i) pd = pd && isfinite(d[i]);
-  }
-  if (!pd) {
-    for (int i = 0; i < 19; ++i) out[i] = NAN;
-    return 0;
-  }
-  const double th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-  double ca, cb;                                                              // exp([w]x) = I + ca [w]x + cb [w]x^2
-  if (th2 < 1e-16) {
-    ca = 1.0 - th2 / 6.0; cb = 0.5 - th2 / 24.0;
-  } else {
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    ca = sin(th) / th; cb = 2.0 * sh * sh / th2;
-  }
-  const double W[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
-  double E[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double w2 = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-      E[3 * i + j] = (i == j ? 1.0 : 0.0) + ca * W[3 * i + j] + cb * w2;
-    }
-  for (int i = 0; i < 6; ++i) out[i] = d[i];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) out[6 + 3 * i + j] = E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j] + E[3 * i + 2] * R[6 + j];
-  for (int i = 0; i < 3; ++i) out[15 + i] = t[i] + d[3 + i];
-  const double tn = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-  const double sw = fmax(fmax(fabs(d[0]), fabs(d[1])), fabs(d[2])), sv = fmax(fmax(fabs(d[3]), fabs(d[4])), fabs(d[5])) / tn;
-  out[18] = sv > sw || sv != sv ? sv : sw;
-  const double vn = sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]);
-  return (vn > max_dist || sqrt(th2) * rho > max_dist) ? 2 : 1;
-}
-
 __global__ __launch_bounds__(PNP_THREADS) void icp_refine_kernel(const IcpParams p) {
   __shared__ double sred[4 * ICP_SUMS];
   __shared__ double s_H[ICP_SUMS];                                            // the state's H (21), g (6), c, n: written and read by thread 0
-  __shared__ double s_L[6][6], s_y[6], s_d[6], s_trial[19];
+  __shared__ double s_L[6][6], s_trial[19];
   __shared__ int s_kind;
   const int b = blockIdx.x, tid = threadIdx.x;
   const double* K = p.K + (size_t)p.k_stride * b;
@@ -392,7 +324,19 @@ __global__ __launch_bounds__(PNP_THREADS) void icp_refine_kernel(const IcpParams
     pass = n0 < (double)p.min_pairs;
   }
   for (int it = 0; it < p.max_iters && !pass; ++it) {
-    if (tid == 0) s_kind = icp_trial(s_H, R, t, lambda, p.inertia * n, rho, s.max_dist, s_L, s_y, s_d, s_trial);
+    // thread 0: (H + lambda diag H + inertia n diag(rho^2 x 3, 1 x 3)) d = -g -> kind 0: no Cholesky factor (NaN in s_trial); 1: a trial
+    // pose; 2: a trial pose beyond the step bound
+    if (tid == 0) {
+      const double damp = p.inertia * n;
+      lm_load_lower(s_H, s_L);
+      for (int q = 0; q < 6; ++q) s_L[q][q] = (s_L[q][q] + lambda * s_L[q][q]) + damp * (q < 3 ? rho * rho : 1.0);
+      double y[6], d[6];
+      int kind = lm_solve_step(s_L, s_H + 21, R, t, y, d, s_trial) ? 1 : 0;
+      if (kind && (sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5]) > s.max_dist ||
+                   sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]) * rho > s.max_dist))
+        kind = 2;
+      s_kind = kind;
+    }
     __syncthreads();
     const int kind = s_kind;
     double Rn[9], tn[3];
@@ -492,17 +436,13 @@ extern "C" int cp_icp_refine(cp_stream_t stream, const double* pose_in, const do
   if (!pose_in || !X || !N || !face || !depth || !max_dist || !diameters || !pose_out || !status_out || !info) return CP_ERR_INVALID;
   if (vs_view_invalid(cam_K, k_stride, H, W, P) || vs_images_invalid(image_ids, I) || M <= 0 || (!mesh_ids && M != 1)) return CP_ERR_INVALID;
   if (S < 1 || S > PNP_NMAX || max_iters < 1 || max_iters > ICP_MAX_ITERS || min_pairs < 6) return CP_ERR_INVALID;
-  if (!(step_tol > 0.0) || !(step_tol <= 1.7976931348623157e308) || !(inertia >= 0.0) || !(inertia <= 1.7976931348623157e308))
-    return CP_ERR_INVALID;                                                    // positive and finite; not negative and finite
+  if (!cp_finite_positive(step_tol) || !(inertia >= 0.0) || !(inertia <= 1.7976931348623157e308)) return CP_ERR_INVALID;      // inertia: not negative and finite
   if (cp_misaligned(pose_in, 7) || vs_view_misaligned(cam_K) || cp_misaligned(X, 7) || cp_misaligned(N, 7) || cp_misaligned(face, 3) ||
       cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3) || cp_misaligned(max_dist, 7) || cp_misaligned(diameters, 7) ||
       cp_misaligned(mesh_ids, 3) || cp_misaligned(status_in, 3) || cp_misaligned(pose_out, 7) || cp_misaligned(status_out, 3) ||
       cp_misaligned(info, 7) || cp_misaligned(records, 7))
     return CP_ERR_ALIGN;
-  {                                          // in place (pose_out == pose_in) is fine: a workgroup reads its 12 doubles before it writes them
-    const uintptr_t a = (uintptr_t)pose_in, o = (uintptr_t)pose_out, len = (uintptr_t)P * 12 * sizeof(double);
-    if (a != o && a < o + len && o < a + len) return CP_ERR_INVALID;
-  }
+  if (cp_pose_alias_invalid(pose_in, pose_out, P)) return CP_ERR_INVALID;
   if ((long long)H * W >= (1LL << 31) || P >= (1 << 24)) return CP_ERR_RANGE;
   IcpParams p;
   p.pose_in = pose_in; p.K = cam_K; p.X = X; p.N = N; p.face = face; p.depth = depth; p.image_ids = image_ids; p.max_dist = max_dist;

@@ -21,8 +21,9 @@ namespace {
 
 struct PnpParams {
   const float* p3d; const float* p2d; const uint8_t* valid; const float* K;
-  double* pose; uint8_t* inliers; int32_t* status; int32_t* scratch;
-  long long p3d_bs, K_bs;
+  double* pose; uint8_t* inliers; int32_t* status;
+  int32_t* unused;             // (no reader.  Without it the arguments are laid out and fetched differently: 16 more SGPR spills in the
+  long long p3d_bs, K_bs;      //  selection kernel, or with the strides last ~1 % on a B = 32 call)
   int B, N, valid_stride, iters, round;
   float thr;
   uint32_t seed;
@@ -48,13 +49,12 @@ __global__ __launch_bounds__(64) void pnp_hypotheses_kernel(const PnpParams p, d
   if (p.round > 0 && hypotheses_run(hyp + (size_t)b * p.iters * PNP_HYP, nv, 5, p.iters, p.round) <= 64 * p.round)
     return;                                                  // the rule was satisfied by the earlier rounds: whole workgroup, uniform
   if (h >= p.iters) return;
-  Points P;                                                  // straight from global memory: the scoring loop reads the SAME point on
-  P.p3d = p.p3d + (size_t)b * p.p3d_bs;                      // every lane (one cache line per wave), the solve only its 5 samples
-  P.p2d = p.p2d + (size_t)b * p.N * 2;
-  const float* K = p.K + (size_t)b * p.K_bs;
-  P.fu = K[0]; P.fv = K[4]; P.uc = K[2]; P.vc = K[5];
+  // straight from global memory: the scoring loop reads the SAME point on every lane (one cache line per wave), the solve only its 5 samples
+  const Points P = crop_points(p.p3d + (size_t)b * p.p3d_bs, p.p2d + (size_t)b * p.N * 2, p.K + (size_t)b * p.K_bs);
   const double thr2 = (double)p.thr * (double)p.thr;
   const int m = 5;
+  // pnp_core.h's sample_distinct, mapped through vidx (ascending, so comparing mapped values is comparing positions), kept as its own
+  // loop: with the positions in registers the five-point solve below unrolls differently and every hypothesis moves in its last bits
   int32_t sel[5];
   int got = 0;
   uint32_t tries = 0;
@@ -121,17 +121,13 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_select_refit_kernel(const Pnp
   double* pose = p.pose + (size_t)b * 12;
   auto identity = [&]() {                                    // the reference's fallback: identity pose, no inliers
     if (tid == 0) {
-      for (int i = 0; i < 9; ++i) pose[i] = (i % 4 == 0) ? 1.0 : 0.0;
-      pose[9] = pose[10] = pose[11] = 0.0;
+      write_identity_pose(pose);
       p.status[b] = 0;
     }
   };
   if (nv < 4) { identity(); return; }
   const int m = 5;
-  Points P;
-  P.p3d = s3; P.p2d = s2;
-  const float* K = p.K + (size_t)b * p.K_bs;
-  P.fu = K[0]; P.fv = K[4]; P.uc = K[2]; P.vc = K[5];
+  const Points P = crop_points(s3, s2, p.K + (size_t)b * p.K_bs);
   if (nv == 4) {                                             // OpenCV: no RANSAC, P3P + the fourth point; all four are inliers
     if (tid == 0) {
       float pw4[12], uv4[8];
@@ -147,8 +143,7 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_select_refit_kernel(const Pnp
         for (int i = 0; i < 4; ++i) p.inliers[(size_t)b * p.N + vidx[i]] = 1;
         p.status[b] = 1;
       } else {
-        for (int i = 0; i < 9; ++i) pose[i] = (i % 4 == 0) ? 1.0 : 0.0;
-        pose[9] = pose[10] = pose[11] = 0.0;
+        write_identity_pose(pose);
         p.status[b] = 0;
       }
     }
@@ -184,7 +179,9 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_select_refit_kernel(const Pnp
   const int n = block_compact<PNP_THREADS>([&](int i) { return flag[i]; }, p.N, iidx, wsum, tid);
   Points S = P;
   S.idx = iidx; S.n = n;
-  // ---- final EPnP over the n inliers, loops over the points shared by the 256 threads, the small dense algebra on thread 0
+  // ---- final EPnP over the n inliers, loops over the points shared by the 256 threads, the small dense algebra on thread 0: the
+  // statements of pnp_core.h's epnp_block_refit, kept in the kernel.  Behind a call (a function, forced inline or not, or a lambda) the
+  // compiler optimises them before it inlines them, and the poses of 26 of the 32 committed cases move in their last bits
   double acc[27];
   for (int k = 0; k < 3; ++k) acc[k] = 0.0;
   for (int i = tid; i < n; i += PNP_THREADS) { const float* pw = s3 + 3 * iidx[i]; acc[0] += pw[0]; acc[1] += pw[1]; acc[2] += pw[2]; }
@@ -309,11 +306,10 @@ extern "C" int cp_pnp_ransac(cp_stream_t stream, const float* p3d, long long p3d
   if (!p3d || !p2d || !valid || !cam_K || !pose || !inliers || !status || !scratch) return CP_ERR_INVALID;
   if (B <= 0 || N <= 0 || N > PNP_NMAX || valid_stride <= 0 || iterations <= 0 || iterations > PNP_MAX_ITERS || !(reproj_threshold > 0.f))
     return CP_ERR_INVALID;
-  if (p3d_bstride != 0 && p3d_bstride < 3LL * N) return CP_ERR_INVALID;
-  if (K_bstride != 0 && K_bstride < 9) return CP_ERR_INVALID;
-  if (((uintptr_t)pose & 7) || ((uintptr_t)scratch & 7) || ((uintptr_t)status & 3)) return CP_ERR_ALIGN;
+  if (cp_p3d_stride_invalid(p3d_bstride, N) || cp_K_stride_invalid(K_bstride)) return CP_ERR_INVALID;
+  if (cp_misaligned(pose, 7) || cp_misaligned(scratch, 7) || cp_misaligned(status, 3)) return CP_ERR_ALIGN;
   PnpParams p;
-  p.p3d = p3d; p.p2d = p2d; p.valid = valid; p.K = cam_K; p.pose = pose; p.inliers = inliers; p.status = status; p.scratch = nullptr;
+  p.p3d = p3d; p.p2d = p2d; p.valid = valid; p.K = cam_K; p.pose = pose; p.inliers = inliers; p.status = status; p.unused = nullptr;
   p.p3d_bs = p3d_bstride; p.K_bs = K_bstride; p.B = B; p.N = N; p.valid_stride = valid_stride; p.iters = iterations; p.thr = reproj_threshold;
   p.seed = seed;
   const size_t lds1 = (size_t)2 * 144 * 64 * 8 + (size_t)N * 2 + 16, lds2 = (size_t)N * (5 * 4 + 8 + 1) + 16;

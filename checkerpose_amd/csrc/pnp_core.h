@@ -1,10 +1,38 @@
-// Device functions that the pose solvers share (pnp.hip: EPnP + RANSAC, row N4; pnp_gc.hip: graph-cut RANSAC, row N17): the counter-based
-// hash of the samplers, cyclic Jacobi, P3P on four correspondences, the pieces of EPnP, the block-wide compaction and sum, and OpenCV's
-// stopping rule.  All fp64; included inside each file's own translation unit (everything here has internal linkage).
+// Every step that more than one pose solver performs (pnp.hip: EPnP + RANSAC, row N4; pnp_gc.hip: graph-cut RANSAC, row N17;
+// pnp_refine.hip: Levenberg-Marquardt, row N22; icp_refine.hip: projective ICP, row N24; pose_depth.hip: depth-lifted RANSAC, row N25).
+// All fp64; included inside each file's own translation unit (everything here has internal linkage).
+//   hash32, sample_distinct                       the counter-based hash of the samplers; M distinct positions in [0, n) from it
+//   jacobi_eig*, solve_normal                     cyclic Jacobi (private, LDS-strided, 12 lanes of a wave); small normal equations
+//   procrustes_rotation, nearest_rotation         rotation from a 3 x 3 cross-covariance (epnp.cpp's rule; the proper nearest one)
+//   quartic_real_roots, solve_four_points         P3P on four correspondences
+//   Points, crop_points, Frame, epnp_*, m_rows    the correspondences of one EPnP call and the pieces of EPnP on one thread
+//   reproj_sq, is_inlier, reproj_mean             the squared reprojection error of one correspondence; the inlier test; the mean error
+//   write_identity_pose                           the fallback pose
+//   block_compact, block_sum                      ascending compaction and fixed-order sums over a 256-thread workgroup
+//   needed_iters, hypotheses_run                  OpenCV's stopping rule over rounds of 64 hypotheses
+//   EpnpRefitLds, epnp_block_refit                the final EPnP over an inlier set, shared by the 256 threads of a workgroup (pnp.hip
+//                                                 keeps the same statements inside its kernel and says why)
+//   lm_load_lower, lm_solve_step                  a Levenberg-Marquardt trial step behind the caller's own damping
+//   cp_finite_positive, cp_p3d_stride_invalid, cp_K_stride_invalid, cp_pose_alias_invalid      (host) the entry points' shared rules
+// CONTRACTION.  pnp_refine.hip and icp_refine.hip include this file BEFORE their `#pragma clang fp contract(off)`, pnp.hip and pnp_gc.hip
+// compile it with the default (contraction on), pose_depth.hip with contraction off.  The rules of rows N22 / N24 are stated without
+// contraction, so lm_load_lower and lm_solve_step carry the pragma as the first statement of their bodies; the EPnP pieces,
+// epnp_block_refit included, were pinned with contraction on and must NOT gain one.
 #pragma once
 #include "common.h"
 
 namespace {
+
+// ---- host: argument rules that the solvers' entry points share, as predicates (the entry points keep the order and the error class)
+__host__ __device__ inline bool cp_finite_positive(double x) { return x > 0.0 && x <= 1.7976931348623157e308; }
+// a batch stride of 0 shares one array among the crops; otherwise a crop's (N, 3) points / 3 x 3 camera must fit into it
+inline bool cp_p3d_stride_invalid(long long p3d_bstride, int N) { return p3d_bstride != 0 && p3d_bstride < 3LL * N; }
+inline bool cp_K_stride_invalid(long long K_bstride) { return K_bstride != 0 && K_bstride < 9; }
+// (count, 12) poses: in place (pose_out == pose_in) is fine, a workgroup reads its 12 doubles before it writes them; a partial overlap is not
+inline bool cp_pose_alias_invalid(const double* pose_in, const double* pose_out, int count) {
+  const uintptr_t a = (uintptr_t)pose_in, o = (uintptr_t)pose_out, len = (uintptr_t)count * 12 * sizeof(double);
+  return a != o && a < o + len && o < a + len;
+}
 
 __device__ __forceinline__ uint32_t hash32(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   uint32_t h = a * 0x9E3779B1u + 0x7F4A7C15u;
@@ -18,6 +46,30 @@ __device__ __forceinline__ uint32_t hash32(uint32_t a, uint32_t b, uint32_t c, u
     h ^= h >> 16;
   }
   return h;
+}
+
+// M distinct positions in [0, n), n >= M: draw k = hash32(seed, crop, hyp, try) % n, duplicates redrawn (oracle/pnp_oracle.py:
+// sample_indices).  false only when 2^20 tries did not suffice (never met in practice: it bounds the loop).  pos is written through
+// constant indices, so that it can stay in registers
+template <int M>
+__device__ __forceinline__ bool sample_distinct(uint32_t seed, uint32_t crop, uint32_t hyp, int n, int* pos) {
+#pragma unroll
+  for (int k = 0; k < M; ++k) pos[k] = 0;
+  int got = 0;
+  uint32_t tries = 0;
+  while (got < M && tries < (1u << 20)) {
+    const int r = (int)(hash32(seed, crop, hyp, tries++) % (uint32_t)n);
+    bool dup = false;
+#pragma unroll
+    for (int k = 0; k < M; ++k) dup = dup || (k < got && pos[k] == r);
+    if (!dup) {
+#pragma unroll
+      for (int k = 0; k < M; ++k)
+        if (k == got) pos[k] = r;
+      ++got;
+    }
+  }
+  return got == M;
 }
 
 // cyclic Jacobi on a symmetric n x n matrix (row-major a, destroyed: eigenvalues end on its diagonal); eigenvectors = columns of v
@@ -430,6 +482,19 @@ struct Points {            // the correspondences of one EPnP call: idx[0 .. n) 
   const float* p3d; const float* p2d; const int32_t* idx; int n;
   double fu, fv, uc, vc;
 };
+// a crop's arrays and its camera (K row-major 3 x 3); idx and n are the caller's
+__device__ __forceinline__ Points crop_points(const float* p3d, const float* p2d, const float* K) {
+  Points P;
+  P.p3d = p3d; P.p2d = p2d; P.idx = nullptr; P.n = 0;
+  P.fu = K[0]; P.fv = K[4]; P.uc = K[2]; P.vc = K[5];
+  return P;
+}
+
+// the reference's fallback: the identity pose (the caller sets no inliers and the status)
+__device__ __forceinline__ void write_identity_pose(double* pose) {
+  for (int i = 0; i < 9; ++i) pose[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  pose[9] = pose[10] = pose[11] = 0.0;
+}
 
 struct Frame { double cw[4][3]; double ci[9]; };            // control points, inverse of [cw1 - cw0 | cw2 - cw0 | cw3 - cw0]
 
@@ -648,22 +713,22 @@ __device__ bool epnp_finish(const Points& P, const Frame& f, double* MtM, double
   return found;
 }
 
-__device__ __forceinline__ bool is_inlier(const Points& P, const double* R, const double* t, int k, double thr2) {
+// the squared reprojection error of correspondence k (an index into the crop's arrays) under (R, t)
+__device__ __forceinline__ double reproj_sq(const Points& P, const double* R, const double* t, int k) {
   const float* pw = P.p3d + 3 * (size_t)k;
   const double X = R[0] * pw[0] + R[1] * pw[1] + R[2] * pw[2] + t[0], Y = R[3] * pw[0] + R[4] * pw[1] + R[5] * pw[2] + t[1];
   const double iz = 1.0 / (R[6] * pw[0] + R[7] * pw[1] + R[8] * pw[2] + t[2]);
   const double du = P.uc + P.fu * X * iz - P.p2d[2 * (size_t)k], dv = P.vc + P.fv * Y * iz - P.p2d[2 * (size_t)k + 1];
-  return du * du + dv * dv <= thr2;
+  return du * du + dv * dv;
+}
+__device__ __forceinline__ bool is_inlier(const Points& P, const double* R, const double* t, int k, double thr2) {
+  return reproj_sq(P, R, t, k) <= thr2;
 }
 
-
-// ---- shared staging: this crop's correspondences in LDS (every later pass reads them dozens of times), valid indices compacted in
-// ascending order by a block-wide scan.  T = threads of the calling workgroup (a multiple of 64).
-struct CropLds { float* p3d; float* p2d; int32_t* vidx; int* nv; int* wsum; };
-
+// ascending compaction of the points whose flag is set, by a block-wide scan: chunks of T points, wave ballots + a scan over the waves'
+// counts.  T = threads of the calling workgroup (a multiple of 64).
 template <int T, typename IdxT, typename F>
 __device__ __forceinline__ int block_compact(F flag_of_point, int N, IdxT* out, int* wsum, int tid) {
-  // ascending compaction of the points whose flag is set: chunks of T points, wave ballots + a scan over the waves' counts
   int base = 0;
   const int lane = tid & 63, wave = tid >> 6;
   for (int c0 = 0; c0 < N; c0 += T) {
@@ -723,6 +788,206 @@ __device__ __forceinline__ void block_sum(double* v, double* sred, int tid) {   
 #pragma unroll
   for (int k = 0; k < NV; ++k) v[k] = sred[k] + sred[NV + k] + sred[2 * NV + k] + sred[3 * NV + k];
   __syncthreads();
+}
+
+struct EpnpRefitLds {
+  double sred[4 * 27];
+  double mtm[144], evec[144];
+  double cc[3][4][3], Rt[3][12], pose[12];
+  Frame frame;
+  int ok, kok[3];
+};
+
+// EPnP over the n points S.idx[0 .. n) shared by the 256 threads of a workgroup: every loop over the points is split among the threads
+// and joined by block reductions (centroid, scatter matrix, the 78 entries of M^T M, the candidates' centroids / cross-covariances /
+// errors), the 12 x 12 Jacobi runs on 12 lanes of wave 0, the rest of the small dense algebra (betas, Gauss-Newton, 3 x 3 SVD) on
+// single threads.  -> true + L.pose on every thread; false: a degenerate point set
+__device__ bool epnp_block_refit(const Points& S, EpnpRefitLds& L, int tid) {
+  const int n = S.n;
+  const int32_t* iidx = S.idx;
+  const float* s3 = S.p3d;
+  const float* s2 = S.p2d;
+  double acc[27];
+  for (int k = 0; k < 3; ++k) acc[k] = 0.0;
+  for (int i = tid; i < n; i += PNP_THREADS) { const float* pw = s3 + 3 * iidx[i]; acc[0] += pw[0]; acc[1] += pw[1]; acc[2] += pw[2]; }
+  block_sum<3>(acc, L.sred, tid);
+  const double pw0[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
+  for (int k = 0; k < 6; ++k) acc[k] = 0.0;
+  for (int i = tid; i < n; i += PNP_THREADS) {
+    const float* pw = s3 + 3 * iidx[i];
+    const double d0 = pw[0] - pw0[0], d1 = pw[1] - pw0[1], d2 = pw[2] - pw0[2];
+    acc[0] += d0 * d0; acc[1] += d0 * d1; acc[2] += d0 * d2; acc[3] += d1 * d1; acc[4] += d1 * d2; acc[5] += d2 * d2;
+  }
+  block_sum<6>(acc, L.sred, tid);
+  if (tid == 0) {
+    const double Sm[9] = {acc[0], acc[1], acc[2], acc[1], acc[3], acc[4], acc[2], acc[4], acc[5]};
+    L.ok = epnp_frame_from(pw0, Sm, n, L.frame) ? 1 : 0;
+  }
+  __syncthreads();
+  bool ok = L.ok != 0;
+  if (ok && tid < 78) {                                      // entry (a, c), a <= c, of M^T M per thread
+    int a = 0, rem = tid;
+    while (rem >= 12 - a) { rem -= 12 - a; ++a; }
+    const int c = a + rem;
+    double e = 0.0;
+    for (int i = 0; i < n; ++i) {
+      double r0[12], r1[12];
+      m_rows(S, L.frame, i, r0, r1);
+      e += r0[a] * r0[c] + r1[a] * r1[c];
+    }
+    L.mtm[a * 12 + c] = e;
+    L.mtm[c * 12 + a] = e;
+  }
+  __syncthreads();
+  if (ok && tid < 64) jacobi_eig12_wave(L.mtm, L.evec, tid);
+  __syncthreads();
+  if (ok && tid == 0) {
+    double v[4][12], cc[3][4][3];
+    bool kok[3];
+    epnp_betas(S, L.frame, L.mtm, L.evec, -1, v, cc, kok);
+    for (int k = 0; k < 3; ++k) {
+      L.kok[k] = kok[k] ? 1 : 0;
+      for (int j = 0; j < 4; ++j)
+        for (int c = 0; c < 3; ++c) L.cc[k][j][c] = cc[k][j][c];
+    }
+  }
+  __syncthreads();
+  if (ok) {
+    auto pc_of = [&](int k, int i, double* pc) {
+      double al[4];
+      alphas_of(L.frame, s3 + 3 * iidx[i], al);
+      for (int c = 0; c < 3; ++c) pc[c] = al[0] * L.cc[k][0][c] + al[1] * L.cc[k][1][c] + al[2] * L.cc[k][2][c] + al[3] * L.cc[k][3][c];
+    };
+    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += PNP_THREADS)
+      for (int k = 0; k < 3; ++k) { double pc[3]; pc_of(k, i, pc); acc[3 * k] += pc[0]; acc[3 * k + 1] += pc[1]; acc[3 * k + 2] += pc[2]; }
+    block_sum<9>(acc, L.sred, tid);
+    double pc0[3][3];
+    for (int k = 0; k < 3; ++k)
+      for (int c = 0; c < 3; ++c) pc0[k][c] = acc[3 * k + c] / n;
+    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += PNP_THREADS) {
+      const float* pw = s3 + 3 * iidx[i];
+      for (int k = 0; k < 3; ++k) {
+        double pc[3];
+        pc_of(k, i, pc);
+        for (int a = 0; a < 3; ++a)
+          for (int c = 0; c < 3; ++c) acc[9 * k + 3 * a + c] += (pc[a] - pc0[k][a]) * (pw[c] - pw0[c]);
+      }
+    }
+    block_sum<27>(acc, L.sred, tid);
+    if (tid < 3 && L.kok[tid]) {                             // absolute orientation of candidate `tid`
+      double R[9], t[3];
+      procrustes_rotation(acc + 9 * tid, R);
+      for (int a = 0; a < 3; ++a) t[a] = pc0[tid][a] - (R[3 * a] * pw0[0] + R[3 * a + 1] * pw0[1] + R[3 * a + 2] * pw0[2]);
+      for (int i = 0; i < 9; ++i) L.Rt[tid][i] = R[i];
+      for (int i = 0; i < 3; ++i) L.Rt[tid][9 + i] = t[i];
+    }
+    __syncthreads();
+    for (int k = 0; k < 3; ++k) acc[k] = 0.0;
+    for (int i = tid; i < n; i += PNP_THREADS) {
+      const int kk = iidx[i];
+      const float* pw = s3 + 3 * kk;
+      for (int k = 0; k < 3; ++k) {
+        if (!L.kok[k]) continue;
+        const double* R = L.Rt[k];
+        const double X = R[0] * pw[0] + R[1] * pw[1] + R[2] * pw[2] + R[9], Y = R[3] * pw[0] + R[4] * pw[1] + R[5] * pw[2] + R[10];
+        const double iz = 1.0 / (R[6] * pw[0] + R[7] * pw[1] + R[8] * pw[2] + R[11]);
+        const double du = S.uc + S.fu * X * iz - s2[2 * kk], dv = S.vc + S.fv * Y * iz - s2[2 * kk + 1];
+        acc[k] += sqrt(du * du + dv * dv);
+      }
+    }
+    block_sum<3>(acc, L.sred, tid);
+    if (tid == 0) {
+      int pick = -1;
+      double be = INFINITY;
+      for (int k = 0; k < 3; ++k)
+        if (L.kok[k] && isfinite(acc[k]) && acc[k] < be) { be = acc[k]; pick = k; }
+      if (pick >= 0) {
+        for (int i = 0; i < 12; ++i) L.pose[i] = L.Rt[pick][i];
+      } else ok = false;
+      L.ok = ok ? 1 : 0;
+    }
+    __syncthreads();
+    ok = L.ok != 0;
+  }
+  __syncthreads();
+  return ok;
+}
+
+// ---- a Levenberg-Marquardt trial step over the 6-vector d = (w, v): R' = exp([w]x) R, t' = t + v.  One thread.  L (6 x 6) lives in
+// LDS: indexed by loop variables, it would otherwise go to scratch.  y and d are the caller's, in LDS or thread-local (their loops
+// unroll, so local ones stay in registers).  The caller damps L's diagonal between the two calls.
+// the lower triangle of H from its upper triangle stored row by row (21 sums)
+__device__ __forceinline__ void lm_load_lower(const double* Hs, double (*L)[6]) {
+#pragma clang fp contract(off)
+  int e = 0;
+#pragma unroll
+  for (int p = 0; p < 6; ++p)
+#pragma unroll
+    for (int q = p; q < 6; ++q) { L[q][p] = Hs[e]; ++e; }
+}
+
+// L d = -g by Cholesky (L: the damped lower triangle, destroyed; y: work space), then the trial pose.  d[6]: the step, also for the
+// caller's own tests of it; out[0..5] d, [6..14] R', [15..17] t', [18] s = max(|w|_inf, |v|_inf / |t|).  false (NaN in out, d not to be
+// read) where the matrix is not positive definite or d is not finite
+__device__ __forceinline__ bool lm_solve_step(double (*L)[6], const double* g, const double* R, const double* t, double* y, double* d, double* out) {
+#pragma clang fp contract(off)
+  bool pd = true;
+  for (int j = 0; j < 6 && pd; ++j) {
+    double s = L[j][j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    if (!(s > 0.0) || !isfinite(s)) { pd = false; break; }
+    const double ljj = sqrt(s);
+    L[j][j] = ljj;
+    for (int i = j + 1; i < 6; ++i) {
+      double v = L[i][j];
+      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+      L[i][j] = v / ljj;
+    }
+  }
+  if (pd) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) y[i] = -g[i];
+    for (int i = 0; i < 6; ++i) {
+      double v = y[i];
+      for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+      y[i] = v / L[i][i];
+    }
+    for (int i = 5; i >= 0; --i) {
+      double v = y[i];
+      for (int k = i + 1; k < 6; ++k) v -= L[k][i] * d[k];
+      d[i] = v / L[i][i];
+    }
+    for (int i = 0; i < 6; ++i) pd = pd && isfinite(d[i]);
+  }
+  if (!pd) {
+    for (int i = 0; i < 19; ++i) out[i] = NAN;
+    return false;
+  }
+  const double th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+  double ca, cb;                                                              // exp([w]x) = I + ca [w]x + cb [w]x^2
+  if (th2 < 1e-16) {
+    ca = 1.0 - th2 / 6.0; cb = 0.5 - th2 / 24.0;
+  } else {
+    const double th = sqrt(th2), sh = sin(0.5 * th);
+    ca = sin(th) / th; cb = 2.0 * sh * sh / th2;
+  }
+  const double W[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
+  double E[9];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) {
+      const double w2 = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
+      E[3 * i + j] = (i == j ? 1.0 : 0.0) + ca * W[3 * i + j] + cb * w2;
+    }
+  for (int i = 0; i < 6; ++i) out[i] = d[i];
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) out[6 + 3 * i + j] = E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j] + E[3 * i + 2] * R[6 + j];
+  for (int i = 0; i < 3; ++i) out[15 + i] = t[i] + d[3 + i];
+  const double tn = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+  const double sw = fmax(fmax(fabs(d[0]), fabs(d[1])), fabs(d[2])), sv = fmax(fmax(fabs(d[3]), fabs(d[4])), fabs(d[5])) / tn;
+  out[18] = sv > sw || sv != sv ? sv : sw;
+  return true;
 }
 
 }  // namespace

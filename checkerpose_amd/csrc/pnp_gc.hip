@@ -8,8 +8,8 @@
 //                           sequence, solve_four_points (P3P on three, the fourth picks the root), count + MSAC score -> a 14-double
 //                           record; between rounds OpenCV's stopping rule (needed_iters, m = 4) on the counts
 //   gc_select_lo_kernel     one 256-thread workgroup per crop: winner = first record with the largest score among those with count >= 4;
-//                           then at most GC_LO_MAX refits: L_k = label(P_k) (below), Q_k = EPnP over L_k (the block-wide refit of
-//                           pnp_select_refit_kernel), accepted while score(Q_k) > score(P_k)
+//                           then at most GC_LO_MAX refits: L_k = label(P_k) (below), Q_k = EPnP over L_k (pnp_core.h's
+//                           epnp_block_refit), accepted while score(Q_k) > score(P_k)
 //   graphcut_label_kernel   the labelling alone on caller-given capacities (what the tests compare with an exact max-flow)
 // The labelling: capacities are integers with Q = 2^16: s->i = Q, i->t = cin_i, i<->j = w per direction on every graph edge between two
 // valid points.  The inlier set is the MINIMAL source side of a minimum cut (the nodes reachable from s in the residual graph of a
@@ -249,14 +249,6 @@ struct GcParams {
   uint32_t seed;
 };
 
-__device__ __forceinline__ double reproj_sq(const Points& P, const double* R, const double* t, int k) {
-  const float* pw = P.p3d + 3 * (size_t)k;
-  const double X = R[0] * pw[0] + R[1] * pw[1] + R[2] * pw[2] + t[0], Y = R[3] * pw[0] + R[4] * pw[1] + R[5] * pw[2] + t[1];
-  const double iz = 1.0 / (R[6] * pw[0] + R[7] * pw[1] + R[8] * pw[2] + t[2]);
-  const double du = P.uc + P.fu * X * iz - P.p2d[2 * (size_t)k], dv = P.vc + P.fv * Y * iz - P.p2d[2 * (size_t)k + 1];
-  return du * du + dv * dv;
-}
-
 // one launch per round of 64 hypotheses, grid B, one wave per workgroup, a hypothesis per lane
 __global__ __launch_bounds__(64) void gc_hypotheses_kernel(const GcParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -271,28 +263,17 @@ __global__ __launch_bounds__(64) void gc_hypotheses_kernel(const GcParams p) {
   double* hb = p.hyp + (size_t)b * p.iters * PNP_HYP;
   if (p.round > 0 && hypotheses_run(hb, nv, 4, p.iters, p.round) <= 64 * p.round) return;      // whole workgroup, uniform
   if (h >= p.iters) return;
-  Points P;
-  P.p3d = p.p3d + (size_t)b * p.p3d_bs;
-  P.p2d = p.p2d + (size_t)b * p.N * 2;
-  const float* K = p.K + (size_t)b * p.K_bs;
-  P.fu = K[0]; P.fv = K[4]; P.uc = K[2]; P.vc = K[5];
+  const Points P = crop_points(p.p3d + (size_t)b * p.p3d_bs, p.p2d + (size_t)b * p.N * 2, p.K + (size_t)b * p.K_bs);
   const double thr2 = (double)p.thr * (double)p.thr;
-  int32_t sel[4];
-  int got = 0;
-  uint32_t tries = 0;
-  while (got < 4 && tries < (1u << 20)) {                     // (nv >= 4 distinct values: the bound is never met in practice)
-    const int r = (int)(hash32(p.seed, (uint32_t)b, (uint32_t)h, tries++) % (uint32_t)nv);
-    bool dup = false;
-    for (int k = 0; k < got; ++k) dup = dup || sel[k] == (int32_t)vidx[r];
-    if (!dup) sel[got++] = (int32_t)vidx[r];
-  }
+  int pos[4];
   double R[9], t[3];
-  bool ok = got == 4;
+  bool ok = sample_distinct<4>(p.seed, (uint32_t)b, (uint32_t)h, nv, pos);
   if (ok) {
     float pw4[12], uv4[8];
     for (int i = 0; i < 4; ++i) {
-      for (int c = 0; c < 3; ++c) pw4[3 * i + c] = P.p3d[3 * (size_t)sel[i] + c];
-      uv4[2 * i] = P.p2d[2 * (size_t)sel[i]]; uv4[2 * i + 1] = P.p2d[2 * (size_t)sel[i] + 1];
+      const size_t k = (size_t)vidx[pos[i]];
+      for (int c = 0; c < 3; ++c) pw4[3 * i + c] = P.p3d[3 * k + c];
+      uv4[2 * i] = P.p2d[2 * k]; uv4[2 * i + 1] = P.p2d[2 * k + 1];
     }
     ok = solve_four_points(pw4, uv4, P.fu, P.fv, P.uc, P.vc, R, t);
   }
@@ -312,129 +293,6 @@ __global__ __launch_bounds__(64) void gc_hypotheses_kernel(const GcParams p) {
   rec[0] = (double)cnt;
 }
 
-struct GcRefitLds {
-  double sred[4 * 27];
-  double mtm[144], evec[144];
-  double cc[3][4][3], Rt[3][12], pose[12];
-  Frame frame;
-  int ok, kok[3];
-};
-
-// EPnP over the n points S.idx[0 .. n) shared by the 256 threads: the refit of pnp_select_refit_kernel (loops over the points shared,
-// block reductions, the small dense algebra on single threads).  -> true + L.pose on every thread
-__device__ bool gc_block_refit(const Points& S, GcRefitLds& L, int tid) {
-  const int n = S.n;
-  const int32_t* iidx = S.idx;
-  const float* s3 = S.p3d;
-  const float* s2 = S.p2d;
-  double acc[27];
-  for (int k = 0; k < 3; ++k) acc[k] = 0.0;
-  for (int i = tid; i < n; i += PNP_THREADS) { const float* pw = s3 + 3 * iidx[i]; acc[0] += pw[0]; acc[1] += pw[1]; acc[2] += pw[2]; }
-  block_sum<3>(acc, L.sred, tid);
-  const double pw0[3] = {acc[0] / n, acc[1] / n, acc[2] / n};
-  for (int k = 0; k < 6; ++k) acc[k] = 0.0;
-  for (int i = tid; i < n; i += PNP_THREADS) {
-    const float* pw = s3 + 3 * iidx[i];
-    const double d0 = pw[0] - pw0[0], d1 = pw[1] - pw0[1], d2 = pw[2] - pw0[2];
-    acc[0] += d0 * d0; acc[1] += d0 * d1; acc[2] += d0 * d2; acc[3] += d1 * d1; acc[4] += d1 * d2; acc[5] += d2 * d2;
-  }
-  block_sum<6>(acc, L.sred, tid);
-  if (tid == 0) {
-    const double Sm[9] = {acc[0], acc[1], acc[2], acc[1], acc[3], acc[4], acc[2], acc[4], acc[5]};
-    L.ok = epnp_frame_from(pw0, Sm, n, L.frame) ? 1 : 0;
-  }
-  __syncthreads();
-  bool ok = L.ok != 0;
-  if (ok && tid < 78) {                                      // entry (a, c), a <= c, of M^T M per thread
-    int a = 0, rem = tid;
-    while (rem >= 12 - a) { rem -= 12 - a; ++a; }
-    const int c = a + rem;
-    double e = 0.0;
-    for (int i = 0; i < n; ++i) {
-      double r0[12], r1[12];
-      m_rows(S, L.frame, i, r0, r1);
-      e += r0[a] * r0[c] + r1[a] * r1[c];
-    }
-    L.mtm[a * 12 + c] = e;
-    L.mtm[c * 12 + a] = e;
-  }
-  __syncthreads();
-  if (ok && tid < 64) jacobi_eig12_wave(L.mtm, L.evec, tid);
-  __syncthreads();
-  if (ok && tid == 0) {
-    double v[4][12], cc[3][4][3];
-    bool kok[3];
-    epnp_betas(S, L.frame, L.mtm, L.evec, -1, v, cc, kok);
-    for (int k = 0; k < 3; ++k) {
-      L.kok[k] = kok[k] ? 1 : 0;
-      for (int j = 0; j < 4; ++j)
-        for (int c = 0; c < 3; ++c) L.cc[k][j][c] = cc[k][j][c];
-    }
-  }
-  __syncthreads();
-  if (ok) {
-    auto pc_of = [&](int k, int i, double* pc) {
-      double al[4];
-      alphas_of(L.frame, s3 + 3 * iidx[i], al);
-      for (int c = 0; c < 3; ++c) pc[c] = al[0] * L.cc[k][0][c] + al[1] * L.cc[k][1][c] + al[2] * L.cc[k][2][c] + al[3] * L.cc[k][3][c];
-    };
-    for (int k = 0; k < 9; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n; i += PNP_THREADS)
-      for (int k = 0; k < 3; ++k) { double pc[3]; pc_of(k, i, pc); acc[3 * k] += pc[0]; acc[3 * k + 1] += pc[1]; acc[3 * k + 2] += pc[2]; }
-    block_sum<9>(acc, L.sred, tid);
-    double pc0[3][3];
-    for (int k = 0; k < 3; ++k)
-      for (int c = 0; c < 3; ++c) pc0[k][c] = acc[3 * k + c] / n;
-    for (int k = 0; k < 27; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n; i += PNP_THREADS) {
-      const float* pw = s3 + 3 * iidx[i];
-      for (int k = 0; k < 3; ++k) {
-        double pc[3];
-        pc_of(k, i, pc);
-        for (int a = 0; a < 3; ++a)
-          for (int c = 0; c < 3; ++c) acc[9 * k + 3 * a + c] += (pc[a] - pc0[k][a]) * (pw[c] - pw0[c]);
-      }
-    }
-    block_sum<27>(acc, L.sred, tid);
-    if (tid < 3 && L.kok[tid]) {                             // absolute orientation of candidate `tid`
-      double R[9], t[3];
-      procrustes_rotation(acc + 9 * tid, R);
-      for (int a = 0; a < 3; ++a) t[a] = pc0[tid][a] - (R[3 * a] * pw0[0] + R[3 * a + 1] * pw0[1] + R[3 * a + 2] * pw0[2]);
-      for (int i = 0; i < 9; ++i) L.Rt[tid][i] = R[i];
-      for (int i = 0; i < 3; ++i) L.Rt[tid][9 + i] = t[i];
-    }
-    __syncthreads();
-    for (int k = 0; k < 3; ++k) acc[k] = 0.0;
-    for (int i = tid; i < n; i += PNP_THREADS) {
-      const int kk = iidx[i];
-      const float* pw = s3 + 3 * kk;
-      for (int k = 0; k < 3; ++k) {
-        if (!L.kok[k]) continue;
-        const double* R = L.Rt[k];
-        const double X = R[0] * pw[0] + R[1] * pw[1] + R[2] * pw[2] + R[9], Y = R[3] * pw[0] + R[4] * pw[1] + R[5] * pw[2] + R[10];
-        const double iz = 1.0 / (R[6] * pw[0] + R[7] * pw[1] + R[8] * pw[2] + R[11]);
-        const double du = S.uc + S.fu * X * iz - s2[2 * kk], dv = S.vc + S.fv * Y * iz - s2[2 * kk + 1];
-        acc[k] += sqrt(du * du + dv * dv);
-      }
-    }
-    block_sum<3>(acc, L.sred, tid);
-    if (tid == 0) {
-      int pick = -1;
-      double be = INFINITY;
-      for (int k = 0; k < 3; ++k)
-        if (L.kok[k] && isfinite(acc[k]) && acc[k] < be) { be = acc[k]; pick = k; }
-      if (pick >= 0) {
-        for (int i = 0; i < 12; ++i) L.pose[i] = L.Rt[pick][i];
-      } else ok = false;
-      L.ok = ok ? 1 : 0;
-    }
-    __syncthreads();
-    ok = L.ok != 0;
-  }
-  __syncthreads();
-  return ok;
-}
-
 __global__ __launch_bounds__(GC_THREADS) void gc_select_lo_kernel(const GcParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int N = p.N;
@@ -444,7 +302,7 @@ __global__ __launch_bounds__(GC_THREADS) void gc_select_lo_kernel(const GcParams
   int32_t* const iidx = vidx + N;
   s.lab = (uint8_t*)(iidx + N);
   bool* const flag = (bool*)(s.lab + N);
-  __shared__ GcRefitLds rl;
+  __shared__ EpnpRefitLds rl;
   __shared__ unsigned long long red[1];
   __shared__ int ctl[2], wsum[GC_THREADS / 64], s_best;
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -455,18 +313,13 @@ __global__ __launch_bounds__(GC_THREADS) void gc_select_lo_kernel(const GcParams
   double* pose = p.pose + (size_t)b * 12;
   auto identity = [&](int st) {                              // the reference's fallback: identity pose, no inliers
     if (tid == 0) {
-      for (int i = 0; i < 9; ++i) pose[i] = (i % 4 == 0) ? 1.0 : 0.0;
-      pose[9] = pose[10] = pose[11] = 0.0;
+      write_identity_pose(pose);
       p.status[b] = st;
     }
   };
   if (nv < p.min_inliers) { identity(0); return; }
-  Points P;
-  P.p3d = p.p3d + (size_t)b * p.p3d_bs;
-  P.p2d = p.p2d + (size_t)b * N * 2;
-  P.idx = iidx; P.n = 0;
-  const float* K = p.K + (size_t)b * p.K_bs;
-  P.fu = K[0]; P.fv = K[4]; P.uc = K[2]; P.vc = K[5];
+  Points P = crop_points(p.p3d + (size_t)b * p.p3d_bs, p.p2d + (size_t)b * N * 2, p.K + (size_t)b * p.K_bs);
+  P.idx = iidx;
   const double thr2 = (double)p.thr * (double)p.thr;
   const double* hb = p.hyp + (size_t)b * p.iters * PNP_HYP;
   if (tid == 0) {                                            // the largest score among the records with count >= 4, first on ties
@@ -527,7 +380,7 @@ __global__ __launch_bounds__(GC_THREADS) void gc_select_lo_kernel(const GcParams
     if (!have || k == GC_LO_MAX) break;
     Points S = P;
     S.n = nl;
-    const bool ok = gc_block_refit(S, rl, tid);
+    const bool ok = epnp_block_refit(S, rl, tid);
     if (tid == 0) rec[15] = ok ? 1.0 : 0.0;
     if (!ok) break;
     double Qk[12];
@@ -572,7 +425,7 @@ GcScratch gc_scratch(int B, int N, long long max_edges) {
 extern "C" int cp_radius_graph_count(cp_stream_t stream, const float* pts, int M, int N, double radius, int32_t* offsets, int32_t* totals) {
   if (!pts || !offsets || !totals) return CP_ERR_INVALID;
   if (M <= 0 || N <= 0 || N > GC_NMAX || !(radius >= 0.0) || !(radius < 1e150)) return CP_ERR_INVALID;
-  if (((uintptr_t)pts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)totals & 3)) return CP_ERR_ALIGN;
+  if (cp_misaligned(pts, 3) || cp_misaligned(offsets, 3) || cp_misaligned(totals, 3)) return CP_ERR_ALIGN;
   CP_LAUNCH(radius_graph_count_kernel, dim3((unsigned)M), dim3(GC_THREADS), (size_t)N * 4, (hipStream_t)stream, pts, N, radius * radius, offsets, totals);
   return cp_check_launch();
 }
@@ -582,7 +435,7 @@ extern "C" int cp_radius_graph_fill(cp_stream_t stream, const float* pts, int M,
   if (!pts || !offsets || !base || !indices) return CP_ERR_INVALID;
   if (M <= 0 || N <= 0 || N > GC_NMAX || !(radius >= 0.0) || !(radius < 1e150)) return CP_ERR_INVALID;
   if (n_indices < 0 || n_indices > (long long)M * GC_MAX_EDGES) return CP_ERR_INVALID;
-  if (((uintptr_t)pts & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)base & 7)) return CP_ERR_ALIGN;
+  if (cp_misaligned(pts, 3) || cp_misaligned(offsets, 3) || cp_misaligned(indices, 3) || cp_misaligned(base, 7)) return CP_ERR_ALIGN;
   CP_LAUNCH(radius_graph_fill_kernel, dim3((unsigned)M), dim3(GC_THREADS), 0, (hipStream_t)stream, pts, N, radius * radius, offsets,
             (const long long*)base, indices, n_indices);
   return cp_check_launch();
@@ -594,8 +447,8 @@ extern "C" int cp_graphcut_label(cp_stream_t stream, const int32_t* cin, const i
   if (!cin || !offsets || !indices || !labels || !flow_value || !status || !scratch) return CP_ERR_INVALID;
   if (B <= 0 || N <= 0 || N > GC_NMAX || n_edges < 0 || n_edges > GC_MAX_EDGES || w < 0 || w > GC_WMAX) return CP_ERR_INVALID;
   if (scratch_bytes < (size_t)B * (size_t)(n_edges > 0 ? n_edges : 1) * sizeof(int32_t)) return CP_ERR_INVALID;
-  if (((uintptr_t)cin & 3) || ((uintptr_t)offsets & 3) || ((uintptr_t)indices & 3) || ((uintptr_t)status & 3) || ((uintptr_t)sweeps & 3) ||
-      ((uintptr_t)scratch & 3) || ((uintptr_t)flow_value & 7))
+  if (cp_misaligned(cin, 3) || cp_misaligned(offsets, 3) || cp_misaligned(indices, 3) || cp_misaligned(status, 3) || cp_misaligned(sweeps, 3) ||
+      cp_misaligned(scratch, 3) || cp_misaligned(flow_value, 7))
     return CP_ERR_ALIGN;
   static CpDeviceOnce once;
   const int dev = cp_current_device();
@@ -621,10 +474,9 @@ extern "C" int cp_pnp_gc(cp_stream_t stream, const float* p3d, long long p3d_bst
   if (M <= 0 || (M > 1 && !graph_ids) || max_edges < 0 || max_edges > GC_MAX_EDGES || n_indices < 0 || n_indices > (long long)M * GC_MAX_EDGES ||
       w < 0 || w > GC_WMAX || min_inliers < 4)
     return CP_ERR_INVALID;
-  if (p3d_bstride != 0 && p3d_bstride < 3LL * N) return CP_ERR_INVALID;
-  if (K_bstride != 0 && K_bstride < 9) return CP_ERR_INVALID;
-  if (((uintptr_t)pose & 7) || ((uintptr_t)scratch & 7) || ((uintptr_t)g_base & 7) || ((uintptr_t)status & 3) || ((uintptr_t)g_offsets & 3) ||
-      ((uintptr_t)g_indices & 3) || ((uintptr_t)graph_ids & 3))
+  if (cp_p3d_stride_invalid(p3d_bstride, N) || cp_K_stride_invalid(K_bstride)) return CP_ERR_INVALID;
+  if (cp_misaligned(pose, 7) || cp_misaligned(scratch, 7) || cp_misaligned(g_base, 7) || cp_misaligned(status, 3) || cp_misaligned(g_offsets, 3) ||
+      cp_misaligned(g_indices, 3) || cp_misaligned(graph_ids, 3))
     return CP_ERR_ALIGN;
   const GcScratch sc = gc_scratch(B, N, max_edges);
   unsigned char* base = (unsigned char*)scratch;

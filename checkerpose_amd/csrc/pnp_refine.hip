@@ -25,9 +25,10 @@
 // ONE launch, one 256-thread workgroup per crop.  The selected indices are compacted once (block_compact); the points are read
 // from global memory through them (20 bytes per point: after the first pass they sit in L2).  A thread accumulates the 21 + 6 + 1
 // sums (upper triangle of H, g, c) over its points i = tid, tid + 256, ... in ascending order; the 256 partial sums meet in
-// pnp_core.h's block_sum (shuffle tree inside a wave, then wave 0 + 1 + 2 + 3): a fixed order, no atomics.  Thread 0 does the 6 x 6
-// Cholesky and Rodrigues and publishes the trial pose through LDS; all threads then evaluate the trial's sums in ONE pass (H', g'
-// and c' together: an accepted trial needs no second pass, a rejected one wasted 27 multiply-adds per point) and a second block_sum.
+// pnp_core.h's block_sum (shuffle tree inside a wave, then wave 0 + 1 + 2 + 3): a fixed order, no atomics.  Thread 0 damps H, does the
+// 6 x 6 Cholesky and Rodrigues (pnp_core.h's lm_solve_step) and publishes the trial pose through LDS; all threads then evaluate the
+// trial's sums in ONE pass (H', g' and c' together: an accepted trial needs no second pass, a rejected one wasted 27 multiply-adds per
+// point) and a second block_sum.
 // Every branch on accept / stop is taken on values every thread holds identically (LDS words or block_sum results): uniform over
 // the workgroup.  Every loop is bounded by max_iters; no workgroup waits for another.
 #include "pnp_core.h"
@@ -77,74 +78,6 @@ __device__ __forceinline__ void lm_accumulate(const float* __restrict__ g3, cons
   }
 }
 
-// thread 0: (H + lambda diag H) d = -g by Cholesky, then the trial pose.  out[0..5] d, [6..14] R', [15..17] t', [18] s; false (and
-// NaN in out) where the matrix is not positive definite.  L (6 x 6), y and d live in LDS: indexed by loop variables, they would
-// otherwise go to scratch
-__device__ __forceinline__ bool lm_trial(const double* Hs, const double* R, const double* t, double lambda, double (*L)[6], double* y, double* d,
-                                         double* out) {
-  int e = 0;
-#pragma unroll
-  for (int p = 0; p < 6; ++p)
-#pragma unroll
-    for (int q = p; q < 6; ++q) { L[q][p] = Hs[e]; ++e; }                     // lower triangle of H
-  for (int p = 0; p < 6; ++p) L[p][p] = L[p][p] + lambda * L[p][p];
-  bool pd = true;
-  for (int j = 0; j < 6 && pd; ++j) {
-    double s = L[j][j];
-    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-    if (!(s > 0.0) || !isfinite(s)) { pd = false; break; }
-    const double ljj = sqrt(s);
-    L[j][j] = ljj;
-    for (int i = j + 1; i < 6; ++i) {
-      double v = L[i][j];
-      for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-      L[i][j] = v / ljj;
-    }
-  }
-  if (pd) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) y[i] = -Hs[21 + i];
-    for (int i = 0; i < 6; ++i) {
-      double v = y[i];
-      for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-      y[i] = v / L[i][i];
-    }
-    for (int i = 5; i >= 0; --i) {
-      double v = y[i];
-      for (int k = i + 1; k < 6; ++k) v -= L[k][i] * d[k];
-      d[i] = v / L[i][i];
-    }
-    for (int i = 0; i < 6; ++i) pd = pd && isfinite(d[i]);
-  }
-  if (!pd) {
-    for (int i = 0; i < 19; ++i) out[i] = NAN;
-    return false;
-  }
-  const double th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
-  double ca, cb;                                                              // exp([w]x) = I + ca [w]x + cb [w]x^2
-  if (th2 < 1e-16) {
-    ca = 1.0 - th2 / 6.0; cb = 0.5 - th2 / 24.0;
-  } else {
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    ca = sin(th) / th; cb = 2.0 * sh * sh / th2;
-  }
-  const double W[9] = {0.0, -d[2], d[1], d[2], 0.0, -d[0], -d[1], d[0], 0.0};
-  double E[9];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) {
-      const double w2 = W[3 * i] * W[j] + W[3 * i + 1] * W[3 + j] + W[3 * i + 2] * W[6 + j];
-      E[3 * i + j] = (i == j ? 1.0 : 0.0) + ca * W[3 * i + j] + cb * w2;
-    }
-  for (int i = 0; i < 6; ++i) out[i] = d[i];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) out[6 + 3 * i + j] = E[3 * i] * R[j] + E[3 * i + 1] * R[3 + j] + E[3 * i + 2] * R[6 + j];
-  for (int i = 0; i < 3; ++i) out[15 + i] = t[i] + d[3 + i];
-  const double tn = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-  const double sw = fmax(fmax(fabs(d[0]), fabs(d[1])), fabs(d[2])), sv = fmax(fmax(fabs(d[3]), fabs(d[4])), fabs(d[5])) / tn;
-  out[18] = sv > sw || sv != sv ? sv : sw;
-  return true;
-}
-
 __global__ __launch_bounds__(PNP_THREADS) void pnp_refine_lm_kernel(const LmParams p) {
   __shared__ int32_t vidx[PNP_NMAX];
   __shared__ double sred[4 * LM_SUMS];
@@ -182,7 +115,11 @@ __global__ __launch_bounds__(PNP_THREADS) void pnp_refine_lm_kernel(const LmPara
         if (!isfinite(g2[2 * k]) || !isfinite(g2[2 * k + 1])) bad += 1.0;
       }
     } else {
-      if (tid == 0) s_pd = lm_trial(s_H, R, t, lambda, s_L, s_y, s_d, s_trial) ? 1 : 0;
+      if (tid == 0) {                                                         // (H + lambda diag H) d = -g, then the trial pose
+        lm_load_lower(s_H, s_L);
+        for (int q = 0; q < 6; ++q) s_L[q][q] = s_L[q][q] + lambda * s_L[q][q];
+        s_pd = lm_solve_step(s_L, s_H + 21, R, t, s_y, s_d, s_trial) ? 1 : 0;
+      }
       __syncthreads();
       pd = s_pd != 0;
       for (int i = 0; i < 9; ++i) Rn[i] = s_trial[6 + i];
@@ -255,16 +192,11 @@ extern "C" int cp_pnp_refine_lm(cp_stream_t stream, const float* p3d, long long 
                                 double* info, double* records) {
   if (!p3d || !p2d || !mask || !cam_K || !pose_in || !pose_out || !status_out || !info) return CP_ERR_INVALID;
   if (B < 0 || N <= 0 || N > PNP_NMAX || mask_stride <= 0 || max_iters < 1 || max_iters > LM_MAX_ITERS) return CP_ERR_INVALID;
-  if (!(step_tol > 0.0) || !(step_tol <= 1.7976931348623157e308)) return CP_ERR_INVALID;      // positive and finite
-  if (p3d_bstride != 0 && p3d_bstride < 3LL * N) return CP_ERR_INVALID;
-  if (K_bstride != 0 && K_bstride < 9) return CP_ERR_INVALID;
-  if (((uintptr_t)pose_in & 7) || ((uintptr_t)pose_out & 7) || ((uintptr_t)info & 7) || ((uintptr_t)records & 7) ||
-      ((uintptr_t)status_out & 3) || ((uintptr_t)status_in & 3))
+  if (!cp_finite_positive(step_tol) || cp_p3d_stride_invalid(p3d_bstride, N) || cp_K_stride_invalid(K_bstride)) return CP_ERR_INVALID;
+  if (cp_misaligned(pose_in, 7) || cp_misaligned(pose_out, 7) || cp_misaligned(info, 7) || cp_misaligned(records, 7) ||
+      cp_misaligned(status_out, 3) || cp_misaligned(status_in, 3))
     return CP_ERR_ALIGN;
-  {                                          // in place (pose_out == pose_in) is fine: a workgroup reads its 12 doubles before it writes them
-    const uintptr_t a = (uintptr_t)pose_in, o = (uintptr_t)pose_out, len = (uintptr_t)B * 12 * sizeof(double);
-    if (a != o && a < o + len && o < a + len) return CP_ERR_INVALID;
-  }
+  if (cp_pose_alias_invalid(pose_in, pose_out, B)) return CP_ERR_INVALID;
   if (B == 0) return CP_OK;
   LmParams p;
   p.p3d = p3d; p.p2d = p2d; p.mask = mask; p.K = cam_K; p.pose_in = pose_in; p.status_in = status_in;

@@ -166,13 +166,12 @@ __global__ __launch_bounds__(PNP_THREADS) void pose_depth_ransac_kernel(const Pd
   double* pose = p.pose + (size_t)b * 12;
   auto identity = [&]() {                                      // the reference's fallback: identity pose, no inliers
     if (tid == 0) {
-      for (int i = 0; i < 9; ++i) pose[i] = (i % 4 == 0) ? 1.0 : 0.0;
-      pose[9] = pose[10] = pose[11] = 0.0;
+      write_identity_pose(pose);
       p.status[b] = 0;
     }
   };
   const double thr = p.thr_b ? p.thr_b[b] : p.thr;
-  if (n < 3 || !(thr > 0.0) || !(thr <= 1.7976931348623157e308)) { identity(); return; }
+  if (n < 3 || !cp_finite_positive(thr)) { identity(); return; }
   const double thr2 = thr * thr;
   // ---- stage B
   const int lane = tid & 63, part = tid >> 6;
@@ -181,16 +180,9 @@ __global__ __launch_bounds__(PNP_THREADS) void pose_depth_ransac_kernel(const Pd
     if (tid < 64) {
       bool ok = false;
       if (h < p.iters) {
-        int s0 = 0, s1 = 0, s2 = 0, got = 0;
-        uint32_t tries = 0;
-        while (got < 3) {
-          const int d = (int)(hash32(p.seed, (uint32_t)b, (uint32_t)h, tries++) % (uint32_t)n);
-          if (got == 0) { s0 = d; got = 1; }
-          else if (got == 1) { if (d != s0) { s1 = d; got = 2; } }
-          else if (d != s0 && d != s1) { s2 = d; got = 3; }
-        }
+        int pos[3];
         double P[12];
-        ok = pd_minimal(sX, sQ, s0, s1, s2, P);
+        ok = sample_distinct<3>(p.seed, (uint32_t)b, (uint32_t)h, n, pos) && pd_minimal(sX, sQ, pos[0], pos[1], pos[2], P);
         if (ok)
 #pragma unroll
           for (int i = 0; i < 12; ++i) s_pose[lane][i] = P[i];
@@ -317,7 +309,7 @@ inline int pd_common_invalid(const float* p2d, const uint8_t* valid, int valid_s
                              const int32_t* image_ids, int I, int H, int W, int B, int N) {
   if (!p2d || !valid || !cam_K || !depth) return CP_ERR_INVALID;
   if (B < 0 || N <= 0 || N > PNP_NMAX || valid_stride <= 0 || H <= 0 || W <= 0 || I <= 0) return CP_ERR_INVALID;
-  if (K_bstride != 0 && K_bstride < 9) return CP_ERR_INVALID;
+  if (cp_K_stride_invalid(K_bstride)) return CP_ERR_INVALID;
   if (!image_ids && I != 1 && I != B && B != 0) return CP_ERR_INVALID;
   if (cp_misaligned(p2d, 3) || cp_misaligned(cam_K, 3) || cp_misaligned(depth, 3) || cp_misaligned(image_ids, 3)) return CP_ERR_ALIGN;
   if ((long long)H * W >= (1LL << 31) || B >= (1 << 24)) return CP_ERR_RANGE;
@@ -375,8 +367,7 @@ extern "C" int cp_pose_depth_ransac(cp_stream_t stream, const float* p3d, long l
   const int rc = pd_common_invalid(p2d, valid, valid_stride, cam_K, K_bstride, depth, image_ids, I, H, W, B, N);
   if (rc == CP_ERR_INVALID) return rc;
   if (iterations <= 0 || iterations > PNP_MAX_ITERS) return CP_ERR_INVALID;
-  if (!dist_thresholds && (!(dist_threshold > 0.0) || !(dist_threshold <= 1.7976931348623157e308))) return CP_ERR_INVALID;      // positive and finite
-  if (p3d_bstride != 0 && p3d_bstride < 3LL * N) return CP_ERR_INVALID;
+  if ((!dist_thresholds && !cp_finite_positive(dist_threshold)) || cp_p3d_stride_invalid(p3d_bstride, N)) return CP_ERR_INVALID;
   if (rc != CP_OK) return rc;
   if (cp_misaligned(p3d, 3) || cp_misaligned(pose, 7) || cp_misaligned(scratch, 7) || cp_misaligned(status, 3) || cp_misaligned(dist_thresholds, 7))
     return CP_ERR_ALIGN;

@@ -2,8 +2,8 @@
 
 The rule is this project's own: the restatement below IS its definition for the tests.  It follows the kernel's arithmetic operation
 for operation (fp64, no contraction): the lift, the sampler, the degeneracy test, the minimal solver, nearest_rotation, the inlier
-test.  The sums of a fit take a `sums` function: device_sum restates the kernel's order (thread t adds keypoints t, t + 256, ..., then
-block_sum's tree), permuted_sum another order -- the difference between the two is the summation-order difference that check_case
+test.  The sums of a fit take a `sums` function: device_sum is lm_stages.kernel_sum, the kernel's order (thread t adds keypoints t, t + 256, ...,
+then block_sum's tree), permuted_sum another order -- the difference between the two is the summation-order difference that check_case
 measures per case and compares poses against (margin = 16 x).
 
 check_case replays a device run from its records: every decision (a degenerate sample, an inlier, a round that runs, the winner, a
@@ -16,6 +16,8 @@ import math
 import os
 
 import numpy as np
+
+from tests.lm_stages import kernel_sum
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "checkerpose_amd", "data")
 SIZE = (96, 80)                                     # (W, H)
@@ -180,21 +182,7 @@ def minimal_pose(X3, Q3, order=(0, 1, 2)):
     return _pose_from(H, x, q)
 
 
-def device_sum(vals):
-    """vals (n, k): row j belongs to thread j % 256, which adds its rows in ascending order from 0.0; then block_sum (pnp_core.h): per
-    wave the shfl_down tree (offsets 32 .. 1), then ((w0 + w1) + w2) + w3"""
-    n, k = vals.shape
-    rows = -(-n // THREADS)
-    pad = np.zeros((rows * THREADS, k), np.float64)
-    pad[:n] = vals
-    pad = pad.reshape(rows, THREADS, k)
-    acc = np.zeros((THREADS, k), np.float64)
-    for r in range(rows):
-        acc = acc + pad[r]
-    w = acc.reshape(4, 64, k).copy()
-    for o in (32, 16, 8, 4, 2, 1):
-        w[:, :o] = w[:, :o] + w[:, o:2 * o]
-    return ((w[0, 0] + w[1, 0]) + w[2, 0]) + w[3, 0]
+device_sum = kernel_sum      # vals (n, k): row j belongs to thread j % 256; block_sum's order (pnp_core.h)
 
 
 def permuted_sum(vals):

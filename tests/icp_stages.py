@@ -254,67 +254,19 @@ def trial_cost(a, X, Rn, tn, sums=numpy_sum, N=None, tamper=()):
 
 
 def trial(sums, R, t, lam, damp, rho, max_dist):
-    """csrc/icp_refine.hip:icp_trial in Python floats -> (kind 0 no factor | 1 a trial | 2 beyond the step bound, d, R', t', s)"""
-    nan = float("nan")
-    Lm = [[0.0] * 6 for _ in range(6)]
-    e = 0
-    for p_ in range(6):
-        for q in range(p_, 6):
-            Lm[q][p_] = float(sums[e])
-            e += 1
+    """the trial step of csrc/icp_refine.hip: H + lambda diag H + damp diag(rho^2 x 3, 1 x 3) on its own diagonal, lm_stages.solve_step,
+    then the step bound -> (kind 0 no factor | 1 a trial | 2 beyond the step bound, d, R', t', s)"""
+    Lm = L.load_lower(sums)
     for p_ in range(6):
         Lm[p_][p_] = (Lm[p_][p_] + lam * Lm[p_][p_]) + damp * (rho * rho if p_ < 3 else 1.0)
-    pd = True
-    for j in range(6):
-        s = Lm[j][j]
-        for k in range(j):
-            s -= Lm[j][k] * Lm[j][k]
-        if not (s > 0.0) or not math.isfinite(s):
-            pd = False
-            break
-        ljj = math.sqrt(s)
-        Lm[j][j] = ljj
-        for i in range(j + 1, 6):
-            v = Lm[i][j]
-            for k in range(j):
-                v -= Lm[i][k] * Lm[j][k]
-            Lm[i][j] = v / ljj
-    d = [nan] * 6
-    if pd:
-        y = [0.0] * 6
-        for i in range(6):
-            v = -float(sums[21 + i])
-            for k in range(i):
-                v -= Lm[i][k] * y[k]
-            y[i] = v / Lm[i][i]
-        for i in range(5, -1, -1):
-            v = y[i]
-            for k in range(i + 1, 6):
-                v -= Lm[k][i] * d[k]
-            d[i] = v / Lm[i][i]
-        pd = all(math.isfinite(x) for x in d)
+    pd, d, Rn, tn, s = L.solve_step(Lm, sums[21:27], R, t)
     if not pd:
-        return 0, np.full(6, nan), np.full((3, 3), nan), np.full(3, nan), nan
-    th2 = d[0] * d[0] + d[1] * d[1] + d[2] * d[2]
-    if th2 < 1e-16:
-        ca, cb = 1.0 - th2 / 6.0, 0.5 - th2 / 24.0
-    else:
-        th = math.sqrt(th2)
-        sh = math.sin(0.5 * th)
-        ca, cb = math.sin(th) / th, 2.0 * sh * sh / th2
-    W = [[0.0, -d[2], d[1]], [d[2], 0.0, -d[0]], [-d[1], d[0], 0.0]]
-    E = [[(1.0 if i == j else 0.0) + ca * W[i][j] + cb * (W[i][0] * W[0][j] + W[i][1] * W[1][j] + W[i][2] * W[2][j]) for j in range(3)] for i in range(3)]
-    Rn = np.array([[E[i][0] * float(R[0, j]) + E[i][1] * float(R[1, j]) + E[i][2] * float(R[2, j]) for j in range(3)] for i in range(3)])
-    tn = np.array([float(t[i]) + d[3 + i] for i in range(3)])
-    t0, t1, t2 = float(t[0]), float(t[1]), float(t[2])
-    tnorm = math.sqrt(t0 * t0 + t1 * t1 + t2 * t2)
-    sw = max(abs(d[0]), abs(d[1]), abs(d[2]))
-    with np.errstate(all="ignore"):
-        sv = float(np.float64(max(abs(d[3]), abs(d[4]), abs(d[5]))) / np.float64(tnorm))
-    s = sv if (sv > sw or sv != sv) else sw
-    vn = math.sqrt(d[3] * d[3] + d[4] * d[4] + d[5] * d[5])
+        return 0, d, Rn, tn, s
+    d0, d1, d2, d3, d4, d5 = (float(x) for x in d)
+    th2 = d0 * d0 + d1 * d1 + d2 * d2
+    vn = math.sqrt(d3 * d3 + d4 * d4 + d5 * d5)
     kind = 2 if (vn > max_dist or math.sqrt(th2) * rho > max_dist) else 1
-    return kind, np.array(d), Rn, tn, s
+    return kind, d, Rn, tn, s
 
 
 def unpack_H(sums):

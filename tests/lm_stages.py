@@ -134,17 +134,21 @@ def unpack_H(sums):
     return H
 
 
-def trial(sums, R, t, lam):
-    """csrc/pnp_refine.hip:lm_trial in Python floats: -> (pd, d (6), R' (3,3), t' (3), s); NaN everywhere when there is no Cholesky factor"""
-    nan = float("nan")
+def load_lower(sums):
+    """csrc/pnp_core.h:lm_load_lower: the 21 upper-triangle sums -> the lower triangle of H as 6 x 6 Python floats"""
     L = [[0.0] * 6 for _ in range(6)]
     e = 0
     for p_ in range(6):
         for q in range(p_, 6):
             L[q][p_] = float(sums[e])
             e += 1
-    for p_ in range(6):
-        L[p_][p_] = L[p_][p_] + lam * L[p_][p_]
+    return L
+
+
+def solve_step(L, g, R, t):
+    """csrc/pnp_core.h:lm_solve_step in Python floats, from the damped lower triangle L (destroyed) and g (6): Cholesky, the two solves,
+    Rodrigues -> (pd, d (6), R' (3,3), t' (3), s); NaN everywhere when there is no Cholesky factor"""
+    nan = float("nan")
     pd = True
     for j in range(6):
         s = L[j][j]
@@ -164,7 +168,7 @@ def trial(sums, R, t, lam):
     if pd:
         y = [0.0] * 6
         for i in range(6):
-            v = -float(sums[21 + i])
+            v = -float(g[i])
             for k in range(i):
                 v -= L[i][k] * y[k]
             y[i] = v / L[i][i]
@@ -194,6 +198,14 @@ def trial(sums, R, t, lam):
         sv = float(np.float64(max(abs(d[3]), abs(d[4]), abs(d[5]))) / np.float64(tnorm))
     s = sv if (sv > sw or sv != sv) else sw
     return True, np.array(d), Rn, tn, s
+
+
+def trial(sums, R, t, lam):
+    """the trial step of csrc/pnp_refine.hip: H + lambda diag H on its own diagonal, then solve_step"""
+    L = load_lower(sums)
+    for p_ in range(6):
+        L[p_][p_] = L[p_][p_] + lam * L[p_][p_]
+    return solve_step(L, sums[21:27], R, t)
 
 
 def evaluate(X, p, K, R, t, sums=numpy_sum):
