@@ -748,6 +748,43 @@ int cp_verify_poses_mask(cp_stream_t stream, const double* poses, const double* 
                          const int32_t* mask_ids, int NM, int H, int W, const int32_t* status, int P, int Vmax, int32_t* counts,
                          int32_t* box, double* score, double* iou, double* cover, uint8_t* ok, uint8_t* labels, void* scratch);
 
+/* Silhouette refinement of poses against predicted masks (row N30): row N24 for RGB-only data.  The reference does not refine; opt-in,
+ * the rule is this project's own (stated in full at the top of csrc/mask_refine.hip, restated in numpy by tests/mask_refine_stages.py).
+ * cp_mask_extents: bits int32 (NM,H,WW), WW = ceil(W / 32), as cp_coco_pack / cp_paste_masks leave them -> row int32 (NM,H,2) = (first,
+ *   last) set column of every row, col int32 (NM,W,2) = (first, last) set row of every column, (-1, -1) where there is none; bits at
+ *   columns >= W are ignored.  One launch, integer only, no atomics.
+ * cp_contour_samples (stage A): one raster pass of P poses (poses, cam_K, k_stride, verts .. Vmax, H, W as cp_render_depth), then per
+ *   pose the first / last covered pixel of at most grid lattice rows and the topmost / bottommost of at most grid lattice columns (row
+ *   N24's lattice, grid in 1..64); S = 4 grid slots: 2 j (+ 1) for lattice row j, 2 grid + 2 i (+ 1) for lattice column i.
+ *   Outputs: rect int32 (P,4), shape int32 (P,2) as cp_surface_samples; pixel int32 (P,S,2) (-1 -1 = empty slot: no covered pixel on the
+ *   line, or the pixel lies on the frame's border), depth fp32 (P,S) (cp_render_depth's bits at the pixel, 0 in an empty slot), X fp64
+ *   (P,S,3) the sample's model-space point (NaN in an empty slot), ok int32 (P) (0: not rendered).  scratch:
+ *   cp_contour_samples_scratch_bytes(P, Vmax, grid) bytes (0 = bad arguments), 16-byte aligned.  Four launches; 64-bit integer atomic
+ *   min / max merge the extremes across tiles, nothing else.
+ * cp_mask_refine (stages B and C): ONE launch, one workgroup per pose, fp64 without contraction.
+ *   pose_in fp64 (P,12) = [R row-major | t]; cam_K fp64 with k_stride 0 or 9; X, pixel, ok, grid: cp_contour_samples' outputs for THESE
+ *   poses; row, col: cp_mask_extents' outputs over NM masks of the H x W frame; mask_ids int32 (P) or NULL (then NM == P and pose p reads
+ *   mask p; an id outside 0..NM-1 passes the pose through); max_dist fp64 (P), pixels; status_in int32 (P) or NULL: 0 = leave this pose
+ *   alone; dof 0 = translation only (R is returned bitwise), 1 = rotation and translation; max_iters in 1..64; step_tol > 0, finite;
+ *   min_pairs >= 6.
+ *   Outputs: pose_out, status_out, info (cp_mask_refine_info_doubles() = 42), records (cp_mask_refine_record_doubles() = 18 per
+ *   iteration, or NULL) as cp_icp_refine's.
+ * CP_ERR_INVALID: a null pointer, the mesh / view argument rules of the raster family, NM <= 0, no mask_ids although NM != P, a grid,
+ * dof, max_iters, step_tol or min_pairs outside its range, a partial overlap of the poses; CP_ERR_ALIGN; CP_ERR_RANGE: H * W >= 2^31,
+ * too many blocks. */
+int cp_mask_extents(cp_stream_t stream, const int32_t* bits, int NM, int H, int W, int32_t* row, int32_t* col);
+size_t cp_contour_samples_scratch_bytes(int P, int Vmax, int grid);
+int cp_contour_samples(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                       const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                       int H, int W, int P, int Vmax, int grid, int32_t* rect, int32_t* shape, int32_t* pixel, float* depth,
+                       double* X, int32_t* ok, void* scratch);
+int cp_mask_refine_record_doubles(void);
+int cp_mask_refine_info_doubles(void);
+int cp_mask_refine(cp_stream_t stream, const double* pose_in, const double* cam_K, int k_stride, const double* X, const int32_t* pixel,
+                   const int32_t* ok, int grid, const int32_t* row, const int32_t* col, const int32_t* mask_ids, int NM, int H, int W,
+                   const double* max_dist, const int32_t* status_in, int dof, int max_iters, double step_tol, int min_pairs, int P,
+                   double* pose_out, int32_t* status_out, double* info, double* records);
+
 /* Rotation / translation errors, symmetry-aware (row N23): bop_toolkit_lib.pose_error.re / .te (pose_error.py:187-214) for P pose
  * pairs, the rotation error optionally against the closest symmetric copy of the second pose (checkerpose/test_lm.py:33-55,
  * get_closest_rot).  The rule is stated in full at the top of csrc/rete.hip and restated in numpy by tests/rete_stages.py.  One
