@@ -402,6 +402,7 @@ extern "C" int cp_edgeconv_train_bwd(cp_stream_t stream, int dtype, const void* 
   if (!rev_ptr || !rev_edge || !out || !kstar || !gout || !mean || !rstd || !dpq || !workspace) return CP_ERR_INVALID;
   const int E = cp_chan_align(dtype);
   if (out_cstride % E || out_coff % E || gout_cstride % E || gout_coff % E || C % 16) return CP_ERR_ALIGN;
+  if (out_coff + C > out_cstride || gout_coff + C > gout_cstride) return CP_ERR_ALIGN;      // the slices lie inside their rows
   if (!cp_aligned16(out) || !cp_aligned16(gout) || !cp_aligned16(dpq)) return CP_ERR_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int tpk = C / E, KPB = 256 / tpk;

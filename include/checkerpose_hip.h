@@ -1483,7 +1483,8 @@ int cp_bn_group(cp_stream_t stream, int dtype, int kind, const CpBnItem* items_d
  * affine); kstar (B,N,C) uint8 receives the arg-max neighbour slot; scale/shift/mean/rstd: C floats each.
  * Backward writes dpq (B,N,2C) `dtype` = [dP - dQ | dQ], the operand of the node GEMM's weight- and data-gradient
  * (cp_edge_weight_view mode 1), plus dgamma / dbeta.  rev_ptr (G,N+1), rev_edge (G,N*K): reverse adjacency as for
- * cp_edgeconv_gather_max_bwd.  workspace: cp_edge_train_workspace_bytes(B, C).  C % 16 == 0. */
+ * cp_edgeconv_gather_max_bwd.  workspace: cp_edge_train_workspace_bytes(B, C).  C % 16 == 0.  out / gout may be channel
+ * slices of wider buffers: both calls refuse (CP_ERR_ALIGN) a slice that overruns its row (coff + C > cstride). */
 size_t cp_edge_train_workspace_bytes(int B, int C);
 int cp_edgeconv_train_fwd(cp_stream_t stream, int dtype, const void* pq, const int32_t* idx, const int32_t* graph_ids,
                           const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,

@@ -484,6 +484,11 @@ def test_edgeconv_train_full_layer_real_graph(lib, dtype):
 def test_bn_two_launch_forms(lib, dtype, case):
     """cp_bn_stats_accumulate + cp_bn_apply / cp_bn_bwd_accumulate + cp_bn_bwd_apply (fp64 atomics, no finalize launch)
     against torch autograd -- the forms the training program uses"""
+    _bn_two_launch(lib, dtype, case)
+
+
+def _bn_two_launch(lib, dtype, case):
+    """the body of test_bn_two_launch_forms: runs the four launches, asserts them against torch autograd and returns what they wrote"""
     B, Cc, H, W, act, has_res = case
     M = B * H * W
     x = rnd(det_tensor("b2_x%s" % (case,), (B, Cc, H, W)) * 1.5 + 0.3, dtype).requires_grad_(True)
@@ -530,6 +535,7 @@ def test_bn_two_launch_forms(lib, dtype, case):
     close(db.cpu() / grads[2].abs().max().item(), grads[2] / grads[2].abs().max().item(), tol)
     if has_res:
         close(from_cl(dres, Cc), grads[3], tol)
+    return [t.clone() for t in (yc, dyc, mean, rstd, rm_d, rv_d, dg, db, acc)] + ([dres] if has_res else [])
 
 
 @pytest.mark.parametrize("dtype", [CP_F32, CP_BF16])
@@ -801,3 +807,78 @@ def test_pack_batch_matches_single_launch_packers(lib, dtype):
     for k, (a, b) in enumerate(expect):
         assert torch.equal(a, b), "item %d (kind %d) differs from its single-launch packer" % (k, items[k].kind)
     assert es in (2, 4)
+
+
+# ---- deterministic mode (cp_set_deterministic): the same comparisons as above on the fixed-order forms
+def _deterministic(on):
+    import checkerpose_amd
+    was = checkerpose_amd.is_deterministic()
+    checkerpose_amd.set_deterministic(on)
+    return was
+
+
+WGRAD_DET_CASES = [
+    (2, 18, 16, 24, 36, 3, 1, 1),      # 18-channel small layers: below atomics_max, so the default mode never takes them through the workspace
+    (2, 18, 16, 16, 18, 3, 2, 1),
+    (5, 18, 8, 8, 18, 3, 1, 1),
+    (2, 144, 8, 8, 18, 1, 1, 0),       # fuse 1x1
+    (1, 16, 40, 40, 10, 7, 2, 3),      # 7x7 stem
+    (2, 72, 64, 64, 144, 3, 1, 1),     # all-taps 3x3
+    (16, 32, 32, 32, 32, 3, 1, 1),     # many pixel slices
+]
+
+
+@pytest.mark.parametrize("dtype", [CP_F32, CP_BF16])
+@pytest.mark.parametrize("case", WGRAD_DET_CASES)
+def test_wgrad_deterministic_vs_torch_autograd(lib, dtype, case):
+    """cp_conv2d_wgrad_ws in deterministic mode: every layer, however small, goes through partial tiles in the workspace and the
+    fixed-order reduce launch (the default mode adds small layers with atomics even when it is given a workspace) -- against the same
+    torch-autograd reference and TOLT as test_wgrad_vs_torch_autograd; two calls bit-identical; without a workspace the call is refused.
+    measured (MI355X): max |err| / (max |ref| + |ref|) 2.3e-7 .. 9.3e-7 in fp32, 7.2e-8 .. 4.0e-7 in bf16."""
+    assert case in WGRAD_CASES
+    B, Cin, H, W, Cout, k, stride, pad = case
+    x = rnd(det_tensor("wx%s" % (case,), (B, Cin, H, W)), dtype)
+    w = det_tensor("ww%s" % (case,), (Cout, Cin, k, k), 0.1).requires_grad_(True)
+    with torch.enable_grad():
+        y = F.conv2d(x, w, None, stride, pad)
+    dy = rnd(det_tensor("wd%s" % (case,), tuple(y.shape)), dtype)
+    (ref,) = torch.autograd.grad(y, w, dy)
+    dyc, xc = to_cl(dy, dtype), to_cl(x, dtype)
+    was = _deterministic(True)
+    try:
+        got = _wgrad(lib, dtype, dyc, xc, Cout, Cin, k, k, stride, pad, 0, 0, True)
+        again = _wgrad(lib, dtype, dyc, xc, Cout, Cin, k, k, stride, pad, 0, 0, True)
+        with pytest.raises(RuntimeError, match=r"code -1\)"):                # CP_ERR_INVALID: no atomics in this mode (wgrad.hip)
+            _wgrad(lib, dtype, dyc, xc, Cout, Cin, k, k, stride, pad, 0, 0, False)
+    finally:
+        _deterministic(was)
+    scale = ref.abs().max().item()
+    err = ((got.double() - ref.double()).abs() / (scale + ref.double().abs())).max().item()
+    print("wgrad deterministic %s %s: max rel err %.2e" % ("bf16" if dtype == CP_BF16 else "fp32", case, err))
+    close(got / scale, ref / scale, TOLT[dtype])
+    assert torch.equal(got, again)
+
+
+@pytest.mark.parametrize("dtype", [CP_F32, CP_BF16])
+@pytest.mark.parametrize("case", [(2, 18, 16, 16, ACT_RELU, True), (3, 64, 8, 8, ACT_LEAKY, False), (2, 36, 32, 32, ACT_RELU, False),
+                                  (3, 18, 40, 40, ACT_RELU, True)])
+def test_bn_two_launch_forms_deterministic(lib, dtype, case):
+    """the two-launch BatchNorm forms in deterministic mode (64 accumulator sets, at most 64 blocks, each block alone in its set, the
+    consumers add the sets in index order): the assertions of test_bn_two_launch_forms against torch autograd, with the accumulators
+    sized by cp_bn_acc_doubles AFTER the mode is set (the size depends on it), and two runs bit-identical down to the fp64 sums.
+    The last shape has 4800 rows: the default plan would cut it into 75 blocks, so the 64-block cap is in force (75 rows per block,
+    ragged against the rows-per-pass of a block)."""
+    B, Cc, H, W, _, _ = case
+    if H == 40:
+        assert B * H * W // 64 > 64
+    acc_default = lib.cp_bn_acc_doubles(Cc)
+    was = _deterministic(True)
+    try:
+        assert lib.cp_bn_acc_doubles(Cc) == 64 * 2 * rup(Cc, 16) and lib.cp_bn_acc_doubles(Cc) > acc_default
+        a = _bn_two_launch(lib, dtype, case)
+        b = _bn_two_launch(lib, dtype, case)
+    finally:
+        _deterministic(was)
+    assert len(a) == len(b)
+    for u, v in zip(a, b):
+        assert torch.equal(u, v)
