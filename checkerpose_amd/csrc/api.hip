@@ -31,7 +31,7 @@
 //        cp_graph_capture_set_deps and cp_graph_capture_tail removed (opt-in launch paths that lost their A/B measurements);
 // 0.2.4: cp_set_deterministic, cp_status_*; 0.2.3: cp_kernel_log (0.2.2: cp_graph_capture_set_deps / _tail; 0.2.1:
 // cp_pack_hr_chain_weight takes the folded-BN scale)
-extern "C" int cp_version(void) { return 240; }
+extern "C" int cp_version(void) { return 241; }
 
 // process-wide mode switch of the TRAINING entry points (include/checkerpose_hip.h): every accumulation in a fixed order
 std::atomic<int> g_cp_deterministic{0};

@@ -748,6 +748,39 @@ int cp_verify_poses_mask(cp_stream_t stream, const double* poses, const double* 
                          const int32_t* mask_ids, int NM, int H, int W, const int32_t* status, int P, int Vmax, int32_t* counts,
                          int32_t* box, double* score, double* iou, double* cover, uint8_t* ok, uint8_t* labels, void* scratch);
 
+/* The poses of an image verified together against the visible masks (row N31): row N28 with occlusion between the estimates.  The
+ * reference does not verify; opt-in, the rule is this project's own (stated in full at the top of csrc/scene_verify_mask.hip, restated
+ * in numpy by tests/scene_verify_stages.py).  The choice among candidates is cp_select_poses.
+ * cp_verify_scene_mask: P poses (poses, cam_K, k_stride, verts .. Vmax as cp_render_depth; cam_K per POSE with k_stride 9) are rendered
+ *   tile by tile, depth only, over the masks' W x H frame; pose p belongs to image image_ids[p] (0 .. I-1), int32 (P) on the device.
+ *   Its slot is its rank among the poses of its image in the order given (-1 for an image id out of range); at most 32 poses per image
+ *   take part.  The counted poses of an image give the composite ren = the smallest positive depth (cp_render_scene's), and a model pixel
+ *   (D > 0) of pose p is PREDICTED VISIBLE where cp_render_scene's 'bop19' test holds with ren as the sensor depth: f32(dist_p) -
+ *   f32(dist_ren) <= f32(delta), both distances under pose p's cam_K.  full_bits / full_area, vis_bits / vis_area: the full and the
+ *   visible masks as in cp_verify_poses_mask, BOTH required; mask_ids int32 (P) or NULL (then NM == P); status int32 (P) or NULL.
+ *   A pose is not counted -- it occludes nothing, its sums are 0, its boxes -1s, ok = 0, its quotients NaN -- with a non-finite pose or
+ *   cam_K, a vertex at Z <= 0, a mesh, mask or image id out of range, status 0, or a slot >= 32.
+ *   Outputs: counts int32 (P,8) = n_model n_pvis (predicted visible) n_inter (model and full) n_vis_in (model and visible) n_pvis_in
+ *   (pvis and visible) n_mask (full_area[m], read) n_vis (vis_area[m], read) n_hidden_seen (n_vis_in - n_pvis_in); boxes int32 (P,2,4) =
+ *   xmin ymin xmax ymax of the model pixels and of the predicted-visible pixels, -1s without any; slot int32 (P); fp64 (P): iou =
+ *   n_inter / (n_model + n_mask - n_inter) and cover = n_vis_in / n_vis (cp_verify_poses_mask's bits and NaNs), iou_vis = n_pvis_in /
+ *   (n_pvis + n_vis - n_pvis_in), visib_fract = n_pvis / n_model (NaN when n_model == 0), score = iou_vis; ok uint8 (P): 0 with
+ *   iou_vis = score = NaN when that union is 0 or the pose is not counted.  plane_full, plane_visib int32 (I,H,W), both or both NULL:
+ *   bit s is set where the pose at slot s has a model / a predicted-visible pixel (cp_render_scene's planes).  scratch:
+ *   cp_verify_scene_mask_scratch_bytes(P, Vmax, I) bytes (0 = bad arguments), 16-byte aligned.  Five launches; every output is a
+ *   function of integer sums and per-pixel values: bitwise the same for an image alone or in a batch, with or without the planes.
+ * CP_ERR_INVALID: a null pointer, the mesh / view argument rules of the raster family, NM <= 0, no mask_ids although NM != P, I <= 0,
+ * one plane without the other, a delta that is negative, not finite or no float32; CP_ERR_ALIGN; CP_ERR_RANGE: H * W > 2^24 (the sums
+ * are int32), too many blocks. */
+size_t cp_verify_scene_mask_scratch_bytes(int P, int Vmax, int I);
+int cp_verify_scene_mask(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                         const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                         const int32_t* full_bits, const int32_t* full_area, const int32_t* vis_bits, const int32_t* vis_area,
+                         const int32_t* mask_ids, int NM, int H, int W, const int32_t* image_ids, int I, const int32_t* status,
+                         double delta, int P, int Vmax, int32_t* counts, int32_t* boxes, int32_t* slot, double* score, double* iou,
+                         double* cover, double* iou_vis, double* visib_fract, uint8_t* ok, int32_t* plane_full, int32_t* plane_visib,
+                         void* scratch);
+
 /* Silhouette refinement of poses against predicted masks (row N30): row N24 for RGB-only data.  The reference does not refine; opt-in,
  * the rule is this project's own (stated in full at the top of csrc/mask_refine.hip, restated in numpy by tests/mask_refine_stages.py).
  * cp_mask_extents: bits int32 (NM,H,WW), WW = ceil(W / 32), as cp_coco_pack / cp_paste_masks leave them -> row int32 (NM,H,2) = (first,
