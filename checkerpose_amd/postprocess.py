@@ -10,6 +10,7 @@ from .paste import estimate_poses_masks, paste_masks, paste_masks_rle      # noq
 from .verify_mask import estimate_poses_mask_verified, verify_poses_mask   # noqa: F401  (row N28: checkerpose_amd/verify_mask.py)
 from .verify_scene import estimate_poses_scene_verified, verify_scene_mask   # noqa: F401  (row N31: checkerpose_amd/verify_scene.py)
 from .refine_mask import contour_samples, estimate_poses_mask_refined, mask_extents, refine_poses_mask   # noqa: F401  (row N30: checkerpose_amd/refine_mask.py)
+from .refine_weighted import code_confidence, estimate_poses_weighted, refine_poses_lm_weighted   # noqa: F401  (row N32: checkerpose_amd/refine_weighted.py)
 
 
 def correspondences(outputs, roi_xy_ori=None, discard_bd_pixel=0, Bboxes=None):
@@ -746,7 +747,8 @@ def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_id
                      solver="epnp", graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None, depth=None,
                      dist_threshold=None, keep=None):
     """estimate_poses' arguments -> (stages: [(name, R, t)] after the solver, "lm" and "icp" as far as `refine` runs them, inliers, status,
-    final boxes).  keep: a dict that receives the forward's `seg` logits and the `padded` boxes of the crops (estimate_poses_masks)"""
+    final boxes).  keep: a dict that receives the forward's `seg` logits and the `padded` boxes of the crops (estimate_poses_masks), and the
+    forward's whole `outputs`, `p2d` and `valid` of correspondences (estimate_poses_weighted)"""
     from . import preprocess as PP
     if solver not in ("epnp", "gc", "depth"):
         raise ValueError("solver must be 'epnp', 'gc' or 'depth', got %r" % (solver,))
@@ -769,6 +771,8 @@ def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_id
     if keep is not None:
         keep["seg"], keep["padded"] = out[3], padded
     p2d, valid, _ = correspondences(out, discard_bd_pixel=discard_bd_pixel, Bboxes=final)
+    if keep is not None:
+        keep["outputs"], keep["p2d"], keep["valid"] = out, p2d, valid
     if solver == "gc":
         R, t, inl, status = solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=obj_ids if graph.M > 1 else None,
                                          column=1 if check_seg else 0, reproj_threshold=reproj_threshold,

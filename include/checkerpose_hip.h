@@ -625,6 +625,37 @@ int cp_pnp_refine_lm(cp_stream_t stream, const float* p3d, long long p3d_bstride
                      const int32_t* status_in, int max_iters, double step_tol, double* pose_out, int32_t* status_out,
                      double* info, double* records);
 
+/* Per-keypoint, per-axis pixel variance of the decoded code from the code logits' confidences (row N32; opt-in, the rule is this
+ * project's own: stated in full at the top of csrc/code_confidence.hip, restated in numpy by tests/wlm_stages.py).
+ *   bits (B, rows, N) fp32 as cp_code_decode reads it: row 0 the RoI bit, rows 1..r the x bits MSB first, rows 1+r..2r the y bits,
+ *   1 <= r <= 30, rows >= 1 + 2r; final_bbox (B,4) int32 (x, y, w, h) as cp_correspondences_bbox reads it; the code grid (Hc, Wc);
+ *   floor_cells2 > 0, finite: the variance floor in cells^2 (1/12 = uniform quantisation to one cell).
+ * Per bit with logit z: e = exp(-|z|), q = e / ((1 + e)(1 + e)) = p (1 - p); per axis v = sum_j 4^(r-1-j) q_j (j = 0 the MSB, summed
+ * ascending): the variance of the code under independent Bernoulli bits.  sigma2 fp64 (B,N,2) = [(w / Wc)^2 (floor + v_x),
+ * (h / Hc)^2 (floor + v_y)] in pixels^2, fp64 without contraction; 0 on an axis whose box side is 0; NaN where a logit is NaN.
+ * One launch, one lane per (crop, keypoint); B == 0 returns without a launch.  Whether a trained network's logits are calibrated
+ * enough for v to be a variance in fact is UNPINNED. */
+int cp_code_confidence(cp_stream_t stream, const float* bits, int rows, int r, const int32_t* final_bbox, int B, int N, int Hc, int Wc,
+                       double floor_cells2, double* sigma2);
+
+/* Weighted robust Levenberg-Marquardt polish of solved poses (row N32): cp_pnp_refine_lm with a per-point, per-axis scale on the
+ * residuals and a Huber loss (stated in full at the top of csrc/pnp_refine_w.hip, restated in numpy by tests/wlm_stages.py).
+ * Arguments, refusals, statuses, records (17 doubles) and the returned pose as cp_pnp_refine_lm, plus
+ *   scale fp32 (B,N,2) = 1 / sigma per axis (e.g. rsqrt of cp_code_confidence's sigma2): whitened components u = scale * r, Jacobian
+ *   rows scaled alike, the scale applied before any product (a scale of exactly 1 changes no operand); a NULL scale is refused;
+ *   huber_delta > 0 in whitened units, +inf allowed (the unrobust fit), NaN or <= 0 refused: per scalar component
+ *   rho(u) = u^2 if |u| <= delta else 2 delta |u| - delta^2, weight omega = 1 or delta / |u|; cost c = sum rho; H = sum omega j j^T,
+ *   g = sum omega u j (half the gradient of c); accept iff c' < c on this cost.
+ * Status 0 (pass-through, pose_out BITWISE pose_in) under cp_pnp_refine_lm's conditions, plus a selected point whose scale is not
+ * finite or <= 0.  info fp64 (B, cp_pnp_refine_wlm_info_doubles() = 42): cp_pnp_refine_lm's 40 (H = the whitened, omega-weighted
+ * matrix at the returned pose: its inverse is the covariance), then the number of components with |u| > delta at the input pose,
+ * then at the returned pose. */
+int cp_pnp_refine_wlm_info_doubles(void);
+int cp_pnp_refine_wlm(cp_stream_t stream, const float* p3d, long long p3d_bstride, const float* p2d, const uint8_t* mask,
+                      int mask_stride, const float* scale, const float* cam_K, long long K_bstride, int B, int N, const double* pose_in,
+                      const int32_t* status_in, double huber_delta, int max_iters, double step_tol, double* pose_out,
+                      int32_t* status_out, double* info, double* records);
+
 /* Projective point-to-plane ICP of poses against a depth image (row N24): the depth refinement of an RGB-only pose.  The reference
  * does not refine; opt-in, the rule is this project's own (stated in full at the top of csrc/icp_refine.hip, restated in numpy by
  * tests/icp_stages.py); parity with any ICP library is UNPINNED.
