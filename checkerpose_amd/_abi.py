@@ -205,6 +205,9 @@ SIGNATURES = {
     "cp_code_confidence": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, C.c_double, _P]),
     "cp_pnp_refine_wlm_info_doubles": (_I, []),
     "cp_pnp_refine_wlm": (_I, [_P, _P, _L, _P, _P, _I, _P, _P, _L, _I, _I, _P, _P, C.c_double, _I, C.c_double, _P, _P, _P, _P]),
+    "cp_rank_correspondences": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "cp_pnp_conf_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_pnp_conf": (_I, [_P, _P, _L, _P, _P, _I, _P, _P, _L, _I, _I, C.c_double, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cp_surface_samples_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_surface_samples": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cp_icp_refine_record_doubles": (_I, []),

@@ -11,6 +11,7 @@ from .verify_mask import estimate_poses_mask_verified, verify_poses_mask   # noq
 from .verify_scene import estimate_poses_scene_verified, verify_scene_mask   # noqa: F401  (row N31: checkerpose_amd/verify_scene.py)
 from .refine_mask import contour_samples, estimate_poses_mask_refined, mask_extents, refine_poses_mask   # noqa: F401  (row N30: checkerpose_amd/refine_mask.py)
 from .refine_weighted import code_confidence, estimate_poses_weighted, refine_poses_lm_weighted   # noqa: F401  (row N32: checkerpose_amd/refine_weighted.py)
+from .solve_conf import estimate_poses_conf, rank_correspondences, solve_pnp_conf   # noqa: F401  (row N33: checkerpose_amd/solve_conf.py)
 
 
 def correspondences(outputs, roi_xy_ori=None, discard_bd_pixel=0, Bboxes=None):
@@ -742,6 +743,27 @@ def estimate_poses(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=
     return stages[-1][1], stages[-1][2], inl, status, final
 
 
+def _forward_correspondences(net, frames, Bboxes, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
+                             resize_method="crop_square_resize", discard_bd_pixel=0, keep=None):
+    """_estimate_stages up to and including correspondences -- crops, ONE forward, the final boxes -- without a solver run
+    (estimate_poses_conf brings its own).  keep: as _estimate_stages fills it.  -> (p2d, valid, final boxes)"""
+    from . import preprocess as PP
+    if frames.dim() == 3:
+        frames = frames.unsqueeze(0)
+    H, W = int(frames.shape[1]), int(frames.shape[2])
+    padded = [None if b is None else PP.padding_Bbox(b, padding_ratio) for b in Bboxes]
+    crops = PP.get_roi_batch(frames, padded, crop_size, PP.INTER_LINEAR, resize_method, img_index=img_index)
+    final = np.array([[0, 0, 0, 0] if b is None else PP.get_final_Bbox(b, resize_method, W, H) for b in padded], dtype=np.int32)
+    with torch.no_grad():
+        out = net(crops, None) if obj_ids is None else net(crops, None, obj_ids)
+    if keep is not None:
+        keep["seg"], keep["padded"] = out[3], padded
+    p2d, valid, _ = correspondences(out, discard_bd_pixel=discard_bd_pixel, Bboxes=final)
+    if keep is not None:
+        keep["outputs"], keep["p2d"], keep["valid"] = out, p2d, valid
+    return p2d, valid, final
+
+
 def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_ids=None, padding_ratio=1.5, crop_size=256,
                      resize_method="crop_square_resize", check_seg=False, discard_bd_pixel=0, reproj_threshold=2.0, iterations=150, seed=0,
                      solver="epnp", graph=None, spatial_coherence_weight=0.1, prog_max_iters=400, refine=None, icp=None, depth=None,
@@ -760,19 +782,8 @@ def _estimate_stages(net, frames, Bboxes, p3d_xyz, cam_K, img_index=None, obj_id
     _check_icp(refine, icp)
     if solver == "gc" and graph is None:
         raise ValueError("solver='gc' needs graph=radius_graph(p3d_xyz)")
-    if frames.dim() == 3:
-        frames = frames.unsqueeze(0)
-    H, W = int(frames.shape[1]), int(frames.shape[2])
-    padded = [None if b is None else PP.padding_Bbox(b, padding_ratio) for b in Bboxes]
-    crops = PP.get_roi_batch(frames, padded, crop_size, PP.INTER_LINEAR, resize_method, img_index=img_index)
-    final = np.array([[0, 0, 0, 0] if b is None else PP.get_final_Bbox(b, resize_method, W, H) for b in padded], dtype=np.int32)
-    with torch.no_grad():
-        out = net(crops, None) if obj_ids is None else net(crops, None, obj_ids)
-    if keep is not None:
-        keep["seg"], keep["padded"] = out[3], padded
-    p2d, valid, _ = correspondences(out, discard_bd_pixel=discard_bd_pixel, Bboxes=final)
-    if keep is not None:
-        keep["outputs"], keep["p2d"], keep["valid"] = out, p2d, valid
+    p2d, valid, final = _forward_correspondences(net, frames, Bboxes, img_index, obj_ids, padding_ratio, crop_size, resize_method,
+                                                 discard_bd_pixel, keep)
     if solver == "gc":
         R, t, inl, status = solve_pnp_gc(p3d_xyz, p2d, valid, cam_K, graph, graph_ids=obj_ids if graph.M > 1 else None,
                                          column=1 if check_seg else 0, reproj_threshold=reproj_threshold,

@@ -656,6 +656,29 @@ int cp_pnp_refine_wlm(cp_stream_t stream, const float* p3d, long long p3d_bstrid
                       const int32_t* status_in, double huber_delta, int max_iters, double step_tol, double* pose_out,
                       int32_t* status_out, double* info, double* records);
 
+/* Confidence-guided pose solver (row N33): cp_pnp_ransac fed with cp_code_confidence's variances -- the correspondences ranked by
+ * variance, 5-point samples drawn PROSAC-style from a pool that grows down the ranking, inliers gated on the whitened residual.  Opt-in,
+ * the rule is this project's own (stated in full at the top of csrc/pnp_conf.hip, restated in numpy by tests/cpnp_stages.py).
+ * cp_rank_correspondences: sigma2 fp64 (B,N,2) pixels^2 (x, y), 8-byte aligned; valid / valid_stride as cp_pnp_ransac.  A valid keypoint
+ *   is ranked iff both variances are finite and > 0; key = sigma2_x + sigma2_y (one fp64 add); order int32 (B,N) = the ranked keypoints
+ *   by ascending key, ties by ascending index, -1 beyond n_ranked[b]; n_dropped[b] = the valid keypoints that are not ranked.  One
+ *   launch, one workgroup per crop (bitonic sort in LDS), N <= 4096; B == 0 returns without a launch.
+ * cp_pnp_conf: p3d .. N, iterations, seed, pose, inliers, status as cp_pnp_ransac (the same refusals), plus sigma2 as above,
+ *   chi2_threshold finite and > 0 (refused otherwise; 5.99 / 9.21 = the 95 % / 99 % quantiles of chi^2 with 2 degrees of freedom),
+ *   guided (0: every sample drawn from all ranked points), and the ranking's three outputs, which the call fills first (required).
+ *   Hypothesis h draws its sample from the first n_h of the ranking, n_h = the smallest n in [5, nv] with
+ *   C(n,5) * iterations >= (h + 1) * C(nv,5) in exact integers (nv = n_ranked); keypoint i is an inlier iff
+ *   du^2 / sigma2_x + dv^2 / sigma2_y <= chi2_threshold (fp64, no contraction); dropped keypoints are never sampled and never inliers.
+ *   Rounds, stopping rule, winner, unweighted EPnP refit over the winner's inliers, P3P at nv == 4, identity below: as cp_pnp_ransac.
+ * scratch: cp_pnp_conf_scratch_bytes(B, N) bytes, 8-byte aligned: cp_pnp_ransac's records, [1] = n_h (written with every record). */
+int cp_rank_correspondences(cp_stream_t stream, const double* sigma2, const uint8_t* valid, int valid_stride, int B, int N,
+                            int32_t* order, int32_t* n_ranked, int32_t* n_dropped);
+size_t cp_pnp_conf_scratch_bytes(int B, int N);
+int cp_pnp_conf(cp_stream_t stream, const float* p3d, long long p3d_bstride, const float* p2d, const uint8_t* valid, int valid_stride,
+                const double* sigma2, const float* cam_K, long long K_bstride, int B, int N, double chi2_threshold, int iterations,
+                uint32_t seed, int guided, double* pose, uint8_t* inliers, int32_t* status, int32_t* order, int32_t* n_ranked,
+                int32_t* n_dropped, void* scratch);
+
 /* Projective point-to-plane ICP of poses against a depth image (row N24): the depth refinement of an RGB-only pose.  The reference
  * does not refine; opt-in, the rule is this project's own (stated in full at the top of csrc/icp_refine.hip, restated in numpy by
  * tests/icp_stages.py); parity with any ICP library is UNPINNED.
