@@ -208,6 +208,12 @@ SIGNATURES = {
     "cp_rank_correspondences": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cp_pnp_conf_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_pnp_conf": (_I, [_P, _P, _L, _P, _P, _I, _P, _P, _L, _I, _I, C.c_double, _I, C.c_uint32, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_code_reliability_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_code_reliability": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
+    "cp_fit_code_scale_info_doubles": (_I, []),
+    "cp_fit_code_scale_scratch_bytes": (C.c_size_t, [_I]),
+    "cp_fit_code_scale": (_I, [_P, _P, _L, _I, _I, _P, _P, _P, _I, _P, _I, _I, _I, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P]),
+    "cp_sigma2_consistency": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cp_surface_samples_scratch_bytes": (C.c_size_t, [_I, _I]),
     "cp_surface_samples": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cp_icp_refine_record_doubles": (_I, []),

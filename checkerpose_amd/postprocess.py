@@ -12,6 +12,7 @@ from .verify_scene import estimate_poses_scene_verified, verify_scene_mask   # n
 from .refine_mask import contour_samples, estimate_poses_mask_refined, mask_extents, refine_poses_mask   # noqa: F401  (row N30: checkerpose_amd/refine_mask.py)
 from .refine_weighted import code_confidence, estimate_poses_weighted, refine_poses_lm_weighted   # noqa: F401  (row N32: checkerpose_amd/refine_weighted.py)
 from .solve_conf import estimate_poses_conf, rank_correspondences, solve_pnp_conf   # noqa: F401  (row N33: checkerpose_amd/solve_conf.py)
+from .calibrate import CalibratedNet, add_reliability, collect_logits, fit_code_scale, reliability, reliability_figures, sigma2_consistency   # noqa: F401  (row N34: checkerpose_amd/calibrate.py)
 
 
 def correspondences(outputs, roi_xy_ori=None, discard_bd_pixel=0, Bboxes=None):

@@ -679,6 +679,52 @@ int cp_pnp_conf(cp_stream_t stream, const float* p3d, long long p3d_bstride, con
                 uint32_t seed, int guided, double* pose, uint8_t* inliers, int32_t* status, int32_t* order, int32_t* n_ranked,
                 int32_t* n_dropped, void* scratch);
 
+/* Calibration of the code logits (row N34): the instrument behind rows N32 / N33, which read the logits as probabilities.  Opt-in, the
+ * rule is this project's own (stated in full at the top of csrc/calibrate.hip -- the order of every floating sum included -- and
+ * restated in numpy by tests/calib_stages.py).  fp64 without contraction, no global atomics: integer outputs do not depend on the launch
+ * shape, two calls agree bitwise.
+ * Shared arguments: bits (B, rows, N) fp32 logits with `bits_bstride` elements between crops (>= rows * N), row 0 the RoI bit, rows
+ *   1..r the x bits MSB first, rows 1+r..2r the y bits, 1 <= r <= 30, rows >= 1 + 2r (K = 1 + 2r rows are read); gt_roi (B,1,N), gt_x /
+ *   gt_y (B,gt_bits,N) fp32 with gt_bits >= r: cp_encode_targets' labels (set iff > 0.5).  Row 0 counts every (b, n), the x / y rows only
+ *   where the GT RoI bit is set; a NaN logit is counted in n_nan alone.  B == 0 returns CP_OK without a launch (outputs untouched).
+ * cp_code_reliability: scale_host (K) fp64 in HOST memory, each finite and > 0: t = (double)z * scale[k]; edges_host (M - 1) fp64 in HOST
+ *   memory, no NaN, strictly ascending, in LOGIT space, 1 <= M <= 64 (NULL allowed at M == 1): bin = the number of edges <= t.
+ *   p = sigmoid(t) and nll in the overflow-free forms of the kernel file.  Outputs on the device, 8-byte aligned:
+ *   ints int64 (K, 2M + 3) = [count per bin | positives per bin | n | n_nan | n_right = samples with (z > 0) == y], sums fp64 (K, M + 4) = [sum_p per bin | nll | brier |
+ *   g = sum (p - y) z | h = sum p (1 - p) z^2].  scratch: cp_code_reliability_scratch_bytes(r, M) bytes, 8-byte aligned (0 = bad
+ *   arguments).  Two launches: 1024 workgroups over contiguous slices of (b, n), then one workgroup that adds their records in order.
+ * cp_fit_code_scale: group_of_row_host (K) int32 in HOST memory, values in [0, n_groups), 1 <= n_groups <= K: every group minimises its
+ *   rows' summed nll over one shared s by the bracketed Newton iteration of the kernel file: s = 1, bracket [s_min, s_max] with
+ *   0 < s_min <= 1 <= s_max finite and s_min < s_max, step_tol finite > 0, 1 <= max_iters <= CP_CALIB_MAX_ITERS evaluations, then one
+ *   more at the returned s.  1 + 2 (max_iters + 1) launches are enqueued at once, nothing synchronises; a stopped group is frozen.
+ *   scale fp64 (K): the row's group's s; info fp64 (n_groups, cp_fit_code_scale_info_doubles() = 12): s, lo, hi, status (CP_CALIB_*),
+ *   evaluations, nll_before (at s = 1), nll_after (at the returned s), n, then four internal words.  scratch:
+ *   cp_fit_code_scale_scratch_bytes(r) bytes, 8-byte aligned.
+ * cp_sigma2_consistency: p2d fp32 (B,N,2); proj_xy fp64 (B,N,2) (cp_encode_targets); sigma2 fp64 (B,N,2) (cp_code_confidence); valid /
+ *   valid_stride as cp_pnp_conf; gt_roi (B,1,N); edges_host (E) fp64 in HOST memory, no NaN, strictly ascending, chi-square units,
+ *   0 <= E <= 63.  Point n counts iff valid, GT RoI set and both variances finite and > 0.  d2 = du^2 / sigma2_x + dv^2 / sigma2_y with
+ *   du = (double)p2d_x - proj_x; bin = the number of edges <= d2.  counts int32 (B, E + 1); n_counted_dropped int32 (B,2); sums fp64
+ *   (B,3) = sum d2, sum du / sqrt(sigma2_x), sum dv / sqrt(sigma2_y).  One launch, one workgroup per crop: a crop's outputs do not
+ *   depend on the batch it is in. */
+#define CP_CALIB_OK 0
+#define CP_CALIB_CAPPED_HIGH 1      /* the bracket collapsed onto s_max and g(s_max) < 0: every sign is right */
+#define CP_CALIB_CAPPED_LOW 2       /* ... onto s_min and g(s_min) > 0 */
+#define CP_CALIB_EMPTY 3            /* no counted sample: s stays 1 */
+#define CP_CALIB_NOT_CONVERGED 4    /* max_iters evaluations without a step <= step_tol * s: s = the evaluated point of the lowest nll */
+#define CP_CALIB_MAX_ITERS 256
+size_t cp_code_reliability_scratch_bytes(int r, int M);
+int cp_code_reliability(cp_stream_t stream, const float* bits, long long bits_bstride, int rows, int r, const float* gt_roi,
+                        const float* gt_x, const float* gt_y, int gt_bits, const double* scale_host, const double* edges_host, int M,
+                        int B, int N, long long* ints, double* sums, void* scratch);
+int cp_fit_code_scale_info_doubles(void);
+size_t cp_fit_code_scale_scratch_bytes(int r);
+int cp_fit_code_scale(cp_stream_t stream, const float* bits, long long bits_bstride, int rows, int r, const float* gt_roi,
+                      const float* gt_x, const float* gt_y, int gt_bits, const int32_t* group_of_row_host, int n_groups, int B, int N,
+                      double s_min, double s_max, double step_tol, int max_iters, double* scale, double* info, void* scratch);
+int cp_sigma2_consistency(cp_stream_t stream, const float* p2d, const double* proj_xy, const double* sigma2, const uint8_t* valid,
+                          int valid_stride, const float* gt_roi, const double* edges_host, int E, int B, int N, int32_t* counts,
+                          int32_t* n_counted_dropped, double* sums);
+
 /* Projective point-to-plane ICP of poses against a depth image (row N24): the depth refinement of an RGB-only pose.  The reference
  * does not refine; opt-in, the rule is this project's own (stated in full at the top of csrc/icp_refine.hip, restated in numpy by
  * tests/icp_stages.py); parity with any ICP library is UNPINNED.
