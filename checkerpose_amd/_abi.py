@@ -233,6 +233,11 @@ SIGNATURES = {
     "cp_verify_scene_mask_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_verify_scene_mask": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, C.c_double, _I, _I, _P, _P, _P,
                                   _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_verify_poses_photo_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "cp_verify_poses_photo": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_double, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I,
+                                   _P, _P, _P, _P, _P, _P, _P, _P]),
+    "cp_verify_poses_photo_tex": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, C.c_double, _I, _P, _P, _I, _I, _I, _I, _P, _P, _I, _P, _I, _I, _I,
+                                       _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I]),
     "cp_mask_extents": (_I, [_P, _P, _I, _I, _I, _P, _P]),
     "cp_contour_samples_scratch_bytes": (C.c_size_t, [_I, _I, _I]),
     "cp_contour_samples": (_I, [_P, _P, _P, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P]),

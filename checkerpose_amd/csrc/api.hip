@@ -5,6 +5,7 @@
 
 #include "common.h"
 
+// 0.2.45: cp_verify_poses_photo, cp_verify_poses_photo_tex, cp_verify_poses_photo_scratch_bytes;
 // 0.2.44: cp_code_reliability, cp_code_reliability_scratch_bytes, cp_fit_code_scale, cp_fit_code_scale_scratch_bytes,
 //         cp_fit_code_scale_info_doubles, cp_sigma2_consistency;
 // 0.2.43: cp_rank_correspondences, cp_pnp_conf, cp_pnp_conf_scratch_bytes;
@@ -35,7 +36,7 @@
 //        cp_graph_capture_set_deps and cp_graph_capture_tail removed (opt-in launch paths that lost their A/B measurements);
 // 0.2.4: cp_set_deterministic, cp_status_*; 0.2.3: cp_kernel_log (0.2.2: cp_graph_capture_set_deps / _tail; 0.2.1:
 // cp_pack_hr_chain_weight takes the folded-BN scale)
-extern "C" int cp_version(void) { return 244; }
+extern "C" int cp_version(void) { return 245; }
 
 // process-wide mode switch of the TRAINING entry points (include/checkerpose_hip.h): every accumulation in a fixed order
 std::atomic<int> g_cp_deterministic{0};

@@ -9,6 +9,7 @@ from . import _abi
 from .paste import estimate_poses_masks, paste_masks, paste_masks_rle      # noqa: F401  (row N27: checkerpose_amd/paste.py)
 from .verify_mask import estimate_poses_mask_verified, verify_poses_mask   # noqa: F401  (row N28: checkerpose_amd/verify_mask.py)
 from .verify_scene import estimate_poses_scene_verified, verify_scene_mask   # noqa: F401  (row N31: checkerpose_amd/verify_scene.py)
+from .verify_photo import estimate_poses_photo_verified, verify_poses_photo   # noqa: F401  (row N35: checkerpose_amd/verify_photo.py)
 from .refine_mask import contour_samples, estimate_poses_mask_refined, mask_extents, refine_poses_mask   # noqa: F401  (row N30: checkerpose_amd/refine_mask.py)
 from .refine_weighted import code_confidence, estimate_poses_weighted, refine_poses_lm_weighted   # noqa: F401  (row N32: checkerpose_amd/refine_weighted.py)
 from .solve_conf import estimate_poses_conf, rank_correspondences, solve_pnp_conf   # noqa: F401  (row N33: checkerpose_amd/solve_conf.py)

@@ -881,6 +881,43 @@ int cp_verify_scene_mask(cp_stream_t stream, const double* poses, const double* 
                          double* cover, double* iou_vis, double* visib_fract, uint8_t* ok, int32_t* plane_full, int32_t* plane_visib,
                          void* scratch);
 
+/* Hypothesis verification of poses against the photograph (row N35): the colour term beside rows N26 / N28 / N31, which see geometry
+ * only.  The reference does not verify; opt-in, RGB-only, the rule is this project's own (stated in full at the top of
+ * csrc/pose_verify_photo.hip, restated in numpy by tests/photo_stages.py).  The choice among candidates is cp_select_poses.
+ * cp_verify_poses_photo: P poses (poses, cam_K, k_stride, verts .. mesh_ids, colors, normals, surf_color, light_pos, ambient_weight,
+ *   shading as cp_render_rgb) are rendered and shaded tile by tile over the frames' W x H grid -- cp_render_rgb's colour and depth bits
+ *   at ssaa 1; no frame, render or dense mask is stored -- and correlated with frame image_ids[p] (int32 (P) or NULL: then I == 1) of
+ *   frames uint8 (I,H,W,3), RGB, or B G R with bgr != 0.  Luma Y = (77 R + 150 G + 29 B + 128) >> 8 of both; the pixel set is D > 0,
+ *   intersected with bit (y, x) of visible mask row mask_ids[p] when vis_bits int32 (NM,H,WW), WW = ceil(W / 32) (cp_coco_pack's /
+ *   cp_paste_masks' layout) is given (mask_ids int32 (P) or NULL: then NM == P; without vis_bits NM == 0 and mask_ids NULL).
+ *   status int32 (P) or NULL: a pose whose entry is 0 is not a candidate.  min_pixels >= 2, no default.
+ *   Outputs: counts int32 (P,2) = n_model (D > 0) n (the pixel set); sums int64 (P,5) = Sa Sb Saa Sbb Sab (a: the render's luma, b: the
+ *   frame's); fp64 (P): with cov = n Sab - Sa Sb, va = n Saa - Sa^2, vb = n Sbb - Sb^2 exact in int64, ncc = cov / sqrt(va * vb),
+ *   score = ncc, gain = cov / va, offset = (Sb - gain Sa) / n; ok uint8 (P): 0 with the four NaN when va == 0, vb == 0, n < min_pixels
+ *   or the pose is not counted (zero sums): a non-finite pose or cam_K, a singular R, a vertex at Z <= 0, a mesh, image or mask id out
+ *   of range, status 0.  scratch: cp_verify_poses_photo_scratch_bytes(P, Vmax) bytes (0 = bad arguments), 16-byte aligned.  Four
+ *   launches; integer atomics only; every output is a function of integer sums: bitwise the same alone or in a batch.
+ * cp_verify_poses_photo_tex: the same plus cp_render_rgb_tex's five texture arguments (all NULL: the plain call).
+ * CP_ERR_INVALID: a null pointer, the mesh / view / image / shading / texture argument rules of cp_render_rgb_tex, min_pixels < 2,
+ * NM <= 0 with masks, no mask_ids although NM != P, NM or mask_ids without masks; CP_ERR_ALIGN; CP_ERR_RANGE: H * W > 2^22 (a tile's
+ * sums are int32, a pose's products int64), too many blocks. */
+size_t cp_verify_poses_photo_scratch_bytes(int P, int Vmax);
+int cp_verify_poses_photo(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                          const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                          const float* colors, const float* normals, const double* surf_color, const double* light_pos,
+                          double ambient_weight, int shading, const uint8_t* frames, const int32_t* image_ids, int I, int H, int W,
+                          int bgr, const int32_t* vis_bits, const int32_t* mask_ids, int NM, const int32_t* status, int min_pixels,
+                          int P, int Vmax, int32_t* counts, int64_t* sums, double* ncc, double* score, double* gain, double* offset,
+                          uint8_t* ok, void* scratch);
+int cp_verify_poses_photo_tex(cp_stream_t stream, const double* poses, const double* cam_K, int k_stride, const float* verts,
+                              const int32_t* v_offsets, const int32_t* faces, const int32_t* f_offsets, int M, const int32_t* mesh_ids,
+                              const float* colors, const float* normals, const double* surf_color, const double* light_pos,
+                              double ambient_weight, int shading, const uint8_t* frames, const int32_t* image_ids, int I, int H, int W,
+                              int bgr, const int32_t* vis_bits, const int32_t* mask_ids, int NM, const int32_t* status, int min_pixels,
+                              int P, int Vmax, int32_t* counts, int64_t* sums, double* ncc, double* score, double* gain,
+                              double* offset, uint8_t* ok, void* scratch, const float* uv, const uint32_t* texels,
+                              const int32_t* tex_off, const int32_t* tex_dims, int filter);
+
 /* Silhouette refinement of poses against predicted masks (row N30): row N24 for RGB-only data.  The reference does not refine; opt-in,
  * the rule is this project's own (stated in full at the top of csrc/mask_refine.hip, restated in numpy by tests/mask_refine_stages.py).
  * cp_mask_extents: bits int32 (NM,H,WW), WW = ceil(W / 32), as cp_coco_pack / cp_paste_masks leave them -> row int32 (NM,H,2) = (first,
